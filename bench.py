@@ -2,7 +2,7 @@
 """bench.py -- Msamples/s of the hot path (processJob) on N MI355X, one process per GPU.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload dragon|dragons16|cornell|box] [--spp S] [--mesh-n M]
-                    [--scaling weak|strong] [--size PIXELS]
+                    [--scaling weak|strong] [--size PIXELS] [--dump-outputs DIR]
 
 Metric (BASELINE.json / reference benchmark/main.cpp:20,30): Msamples/s = image_width * image_height * spp / wall seconds
 of processJob with min_sample_count == max_sample_count == spp; one sample = one camera path with all its bounces and
@@ -198,7 +198,32 @@ def parse_args(argv=None):
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="CPU baseline budget (0 = skip)")
     ap.add_argument("--seed", type=int, default=1234)
     ap.add_argument("--frame-out", default=None, help="rank 0 writes the last gathered frame here as .npy (tests)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes what the last timed step computed (the frame processJob returns) under DIR as float32 .npy, at most 64 MB "
+                         "(a larger frame: a fixed, seeded sample of its pixels), so that two builds can be compared output for output")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64_000_000  # all files together, headers included
+
+
+def dump_outputs(directory, image):
+    """image.npy: the (height, width, 4) float32 RGBA frame.  A frame over DUMP_LIMIT_BYTES is written as image_sample.npy, the rows of the
+    same pixels every run (numpy generator seeded with 0, sorted row-major indices), with those indices in image_sample_index.npy
+    (float64, exact for every index below 2^53)."""
+    os.makedirs(directory, exist_ok=True)
+    image = np.ascontiguousarray(image, dtype=np.float32)
+    if image.nbytes + 4096 <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(directory, "image.npy"), image)
+        return
+    flat = image.reshape(-1, image.shape[-1])
+    n = (DUMP_LIMIT_BYTES - 2 * 4096) // (flat.shape[1] * 4 + 8)
+    index = np.sort(np.random.default_rng(0).choice(len(flat), size=n, replace=False))
+    np.save(os.path.join(directory, "image_sample.npy"), flat[index])
+    np.save(os.path.join(directory, "image_sample_index.npy"), index.astype(np.float64))
 
 
 # ---- starting the ranks ---------------------------------------------------------------------------------------------------------------
@@ -387,6 +412,8 @@ def run_rank(args):
     if rank == 0:
         if args.frame_out:
             np.save(args.frame_out, job.image.detach().cpu().numpy())
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, job.image.detach().cpu().numpy())
         total_samples = float(width) * height * args.spp * args.steps
         value = total_samples / elapsed / 1e6
         out = {

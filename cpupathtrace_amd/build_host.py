@@ -34,10 +34,12 @@ def build(force=False):
 
 
 def compile_program(source_files, out_path, extra_includes=(), extra_flags=()):
-    """Compile a C++ program against the PathTrace API (used by the tests for their C++ test programs)."""
+    """Compile a C++ program against the PathTrace API (used by the tests for their C++ test programs).  The program finds the
+    libraries relative to its own location, so programs built under oracle/_ref/ keep working when the tree is built or run elsewhere."""
     build()
+    rpath = "$ORIGIN/" + os.path.relpath(HERE, os.path.dirname(os.path.abspath(out_path)))
     cmd = ["g++"] + CXXFLAGS + ["-I" + i for i in extra_includes] + list(extra_flags) + ["-o", out_path] + list(source_files) + \
-        ["-L" + HERE, "-lPathTrace", "-lpathtrace_hip", "-lz", "-pthread", "-Wl,-rpath," + HERE]
+        ["-L" + HERE, "-lPathTrace", "-lpathtrace_hip", "-lz", "-pthread", "-Wl,-rpath," + rpath]
     subprocess.run(cmd, check=True)
     return out_path
 

@@ -67,12 +67,35 @@ def test_bench_under_the_launcher(tmp_path):
         port = s.getsockname()[1]
     frame = str(tmp_path / "frame.npy")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-                        BENCH, "--gpus", "2", "--size", "64", "--spp", "1", "--steps", "2", "--warmup", "0", "--scaling", "strong", "--frame-out", frame],
+                        BENCH, "--gpus", "2", "--size", "64", "--spp", "1", "--steps", "2", "--warmup", "0", "--scaling", "strong", "--frame-out", frame,
+                        "--dump-outputs", str(tmp_path / "dump")],
                        env=_env(), capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
     _check(lines[0], frame, 2, 64, "strong")
+    out = json.loads(lines[0])
+    assert out["steps"] == 2 and out["ms_per_step"] > 0
+    assert os.listdir(str(tmp_path / "dump")) == ["image.npy"]
+    assert np.array_equal(np.load(str(tmp_path / "dump" / "image.npy")), _expected(64, 64, 1234)), "--dump-outputs holds the gathered frame"
+
+
+def test_dump_outputs_samples_a_large_frame(tmp_path):
+    """A frame over the 64 MB budget is dumped as the same seeded sample of its pixels every time, with the sample's pixel indices."""
+    import bench
+    side = 2100
+    image = _expected(side, side, 1234)
+    for name in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / name), image)
+    files = sorted(os.listdir(str(tmp_path / "a")))
+    assert files == ["image_sample.npy", "image_sample_index.npy"]
+    assert sum(os.path.getsize(str(tmp_path / "a" / f)) for f in files) <= bench.DUMP_LIMIT_BYTES
+    for f in files:
+        assert open(str(tmp_path / "a" / f), "rb").read() == open(str(tmp_path / "b" / f), "rb").read()
+    index = np.load(str(tmp_path / "a" / "image_sample_index.npy"))
+    sample = np.load(str(tmp_path / "a" / "image_sample.npy"))
+    assert index.dtype == np.float64 and sample.dtype == np.float32 and len(np.unique(index)) == len(index) == len(sample)
+    assert np.array_equal(sample, image.reshape(-1, 4)[index.astype(np.int64)])
 
 
 def test_a_dead_rank_voids_the_run():

@@ -17,8 +17,15 @@ REF_OUT = os.path.join(ROOT, "oracle", "_ref")
 GPU_TESTS = "RenderTest,SceneTest,PostProcessingTest"  # tests of the reference's suite that render, query a Scene or post-process a frame (all on the GPU)
 
 
+def _lib_env(**extra):
+    """The environment for a program linked against libPathTrace.so: the loader is pointed at this tree's libraries, whichever
+    directory or link the program itself lies in (its runpath is relative to its own location, which a link or a copy moves)."""
+    path = [build_host.HERE] + [p for p in os.environ.get("LD_LIBRARY_PATH", "").split(os.pathsep) if p]
+    return dict(os.environ, LD_LIBRARY_PATH=os.pathsep.join(path), **extra)
+
+
 def _run(exe, skip=None):
-    env = dict(os.environ)
+    env = _lib_env()
     if skip:
         env["PT_TEST_SKIP"] = skip
     return subprocess.run([exe], env=env, capture_output=True, text=True, timeout=600)
@@ -86,7 +93,7 @@ def test_reference_benchmark_on_gpu(tmp_path):
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import write_standin_obj
     assert write_standin_obj.write(str(tmp_path / "assets" / "xyzrgb_dragon.obj"), 300) == 179400
-    r = subprocess.run([exe, "--benchmark_min_time=0.3"], cwd=str(tmp_path), capture_output=True, text=True, timeout=600)
+    r = subprocess.run([exe, "--benchmark_min_time=0.3"], cwd=str(tmp_path), env=_lib_env(), capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout + r.stderr
     rates = dict(re.findall(r"^(renderScene\w+)/real_time.*items_per_second_per_iteration=([0-9.e+]+)", r.stdout, re.M))
     assert set(rates) == {"renderSceneBox", "renderSceneDragonBox"}, r.stdout
@@ -159,7 +166,7 @@ def test_reference_demo_on_gpu(tmp_path):
     import write_standin_obj
     assert write_standin_obj.write(str(tmp_path / "assets" / "xyzrgb_dragon.obj"), 300) == 179400
     out_png = str(tmp_path / "out" / "demo.png")
-    r = subprocess.run([exe, out_png], cwd=str(tmp_path), env=dict(os.environ, PATHTRACE_SEED="1234"), capture_output=True, text=True, timeout=900)
+    r = subprocess.run([exe, out_png], cwd=str(tmp_path), env=_lib_env(PATHTRACE_SEED="1234"), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     assert "100.00% (64 / 64 tiles)" in r.stdout, r.stdout[-500:]
     width, height, channels, rows = _decode_png(out_png)
@@ -170,5 +177,5 @@ def test_reference_demo_on_gpu(tmp_path):
     assert lit > 0.5 * 256 * 256, "most of the frame is inside the box"
     # the same program again with the same seed: the frame is reproducible bit for bit
     out2 = str(tmp_path / "out" / "demo2.png")
-    r2 = subprocess.run([exe, out2], cwd=str(tmp_path), env=dict(os.environ, PATHTRACE_SEED="1234"), capture_output=True, text=True, timeout=900)
+    r2 = subprocess.run([exe, out2], cwd=str(tmp_path), env=_lib_env(PATHTRACE_SEED="1234"), capture_output=True, text=True, timeout=900)
     assert r2.returncode == 0 and open(out2, "rb").read() == open(out_png, "rb").read()
