@@ -330,7 +330,9 @@ PT_D Ray bsdf_propagate(const Material &m, V3 ray_d, V3 pos, V3 normal, float ep
         float fac = __builtin_sqrtf(1.0f - r2);
         float cos_theta = ptm::powf_glibc(r2, 0.5f);
         float phi = 2.0f * PT_PI_F * r1;
-        V3 local_dir = v3(fac * ptm::cosf_glibc(phi), fac * ptm::sinf_glibc(phi), cos_theta);
+        float sin_phi, cos_phi;
+        ptm::sincosf_glibc(phi, &sin_phi, &cos_phi);
+        V3 local_dir = v3(fac * cos_phi, fac * sin_phi, cos_theta);
         float p = (1.0f + 1) * cos_theta / (2.0f * PT_PI_F);
         V3 dir = local_to_global(local_dir, normal);
         out.o = pos + dir * epsilon;
@@ -435,8 +437,10 @@ PT_D Ray camera_shoot(const PtDevCamera &cam, float x, float y, float pixel_widt
         // CircularApertureSampler, camera.cpp:7-19
         float r = __builtin_sqrtf(rng_uniform01(rng));
         float theta = 2.0f * PT_PI_F * rng_uniform01(rng);
-        float sx = r * ptm::cosf_glibc(theta);
-        float sy = r * ptm::sinf_glibc(theta);
+        float sin_theta, cos_theta;
+        ptm::sincosf_glibc(theta, &sin_theta, &cos_theta);
+        float sx = r * cos_theta;
+        float sy = r * sin_theta;
         aperture_offset_x = sx * cam.aperture_width_half;
         aperture_offset_y = sy * cam.aperture_height_half;
     }

@@ -120,6 +120,28 @@ PT_HD float cosf_glibc(float y) {
     return sincos_eval(x * s, x * x, (n & 2) != 0, n ^ 1);
 }
 
+// sinf_glibc(y) and cosf_glibc(y) with one range reduction, as glibc's sincosf shares it (bit-identical to the two calls)
+PT_HD void sincosf_glibc(float y, float *sinp, float *cosp) {
+    double x = y;
+    if(abstop12(y) < abstop12(0x1.921FB6p-1f)) {
+        double s = x * x;
+        if(abstop12(y) < abstop12(0x1p-12f)) {
+            *sinp = y;
+            *cosp = 1.0f;
+            return;
+        }
+        *sinp = sincos_eval(x, s, 0, 0);
+        *cosp = sincos_eval(x, s, 0, 1);
+        return;
+    }
+    int n;
+    x = sincos_reduce(x, &n);
+    const double s = sincos_sign(n), xs = x * s, x2 = x * x;
+    const int negcos = (n & 2) != 0;
+    *sinp = sincos_eval(xs, x2, negcos, n);
+    *cosp = sincos_eval(xs, x2, negcos, n ^ 1);
+}
+
 // ---- powf ----------------------------------------------------------------------------------------------------------
 
 PT_HD double powf_log2(uint32_t ix) {

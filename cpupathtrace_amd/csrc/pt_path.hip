@@ -501,6 +501,7 @@ template<bool WIDE>
 PT_D void shade_row(const PtDevScene &sc, const PtDevCamera &cam, const PtDevOptions &opt, const PtSlots &S, const PtStreams &T, const PtLocalQueue &Q,
                     WaveCtx &ctx, uint32_t row, uint32_t ls_in, uint32_t lane, size_t slot_base, size_t queue_base, typename SlotWord<WIDE>::lds_ptr word_l, lds_u2_ptr hit_l,
                     float4 *__restrict__ image, PtDevCounters *counters, const ShadeTables &tb, uint32_t &n_samples, uint32_t &n_vertices) {
+    // (n_samples, n_vertices: the wavefront's counts, the same in every lane)
     // the lane's slot of the wave: lane `lane` of row `row`, or -- in a compacted pass (see the kernel) -- the slot the list names; PT_NO_SLOT = none
     const bool have_slot = ls_in != PT_NO_SLOT;
     const uint32_t ls = have_slot ? ls_in : 0u;
@@ -597,6 +598,7 @@ PT_D void shade_row(const PtDevScene &sc, const PtDevCamera &cam, const PtDevOpt
         }
     }
     const bool alive = ready;
+    uint32_t lane_samples = 0; // samples this lane completes here (0, 1 or 2): added to the wavefront's count at the end
 
     // ---- phase A: consume the results of the rays that came back -----------------------------------------------------------------------
     uint64_t rng = 0;
@@ -666,7 +668,7 @@ PT_D void shade_row(const PtDevScene &sc, const PtDevCamera &cam, const PtDevOpt
                 out.a = 1.0f;
                 (void)estimator_add(e, S.cand + p * PT_MAX_CANDIDATES, opt, out);
                 e.pixel_sample++;
-                n_samples++;
+                lane_samples++;
                 S.est[p] = e;
                 flags &= ~(PT_F_OVERLAP | PT_F_COLLECTED | PT_F_SAFE);
                 if(estimator_safe_to_overlap(e, opt)) {
@@ -689,7 +691,7 @@ PT_D void shade_row(const PtDevScene &sc, const PtDevCamera &cam, const PtDevOpt
                     accepted = estimator_add(e, cand, opt, out);
                 }
                 e.pixel_sample++;
-                n_samples++;
+                lane_samples++;
                 if(accepted || e.pixel_sample >= opt.max_sample_count) {
                     // pixel finished (worker.cpp:263-319)
                     const C4 value = estimator_finish(e, cand, opt, accepted);
@@ -813,7 +815,6 @@ PT_D void shade_row(const PtDevScene &sc, const PtDevCamera &cam, const PtDevOpt
     if(shade_vertex) {
         path_length++;
         flags |= PT_F_COLLECTED;
-        n_vertices++;
         pos = ro + rd * hit_t;
         uint32_t material_index;
         n = object_normal(sc, hit_ref, pos, material_index);
@@ -981,6 +982,9 @@ PT_D void shade_row(const PtDevScene &sc, const PtDevCamera &cam, const PtDevOpt
             S.path_length[p] = path_length;
         }
     }
+    // (wavefront totals: per-lane counters would be two more registers live across every pass)
+    n_samples += (uint32_t)__popcll(__ballot(lane_samples & 1u)) + 2u * (uint32_t)__popcll(__ballot((lane_samples & 2u) != 0u));
+    n_vertices += (uint32_t)__popcll(__ballot(shade_vertex));
 }
 
 // ---- the kernel -------------------------------------------------------------------------------------------------------------------------
@@ -1021,7 +1025,9 @@ __global__ __launch_bounds__(256, PT_PATH_WAVES) void pt_path_kernel(const PtPat
     // emitter and material tables (PT_LDS_TABLE_BYTES) | start step of every lane's walk | (small scenes) the whole tree and all triangle records
     const int tid = threadIdx.x;
     const uint32_t lane = (uint32_t)tid & 63u;
-    const uint32_t wave_in_block = (uint32_t)tid >> 6;
+    // (read from the first lane: the compiler does not know that tid >> 6 is the same in every lane, and would keep the wavefront's
+    // number and everything computed from it -- the slot, ring and LDS bases -- in vector registers that the shading pass spills)
+    const uint32_t wave_in_block = __builtin_amdgcn_readfirstlane((uint32_t)tid >> 6);
     const uint32_t wave = blockIdx.x * 4u + wave_in_block;
     const uint32_t n_slots = (uint32_t)rows * 64u;
     unsigned char *at = lds_raw;
@@ -1215,8 +1221,12 @@ __global__ __launch_bounds__(256, PT_PATH_WAVES) void pt_path_kernel(const PtPat
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
             __builtin_amdgcn_s_waitcnt(0);
             {
-                const uint32_t *sv = walk_save + (size_t)wave * 64 + lane;
-                const size_t st = save_stride;
+                // (the save area's address is read again: addresses kept from the stores above would live across the pass, 17 pairs of
+                // registers that the pass has no room for)
+                asm volatile("" : "+s"(pass_offset));
+                const PtPathArgs *R = (const PtPathArgs *)(args_c4)((const char __attribute__((address_space(4))) *)A4 + pass_offset);
+                const uint32_t *sv = R->walk_save + (size_t)wave * 64 + lane;
+                const size_t st = R->save_stride;
                 w.o = v3(__uint_as_float(sv[0 * st]), __uint_as_float(sv[1 * st]), __uint_as_float(sv[2 * st]));
                 w.d = v3(__uint_as_float(sv[3 * st]), __uint_as_float(sv[4 * st]), __uint_as_float(sv[5 * st]));
                 w.inv = slab_inverse(w.d);
@@ -1363,10 +1373,8 @@ __global__ __launch_bounds__(256, PT_PATH_WAVES) void pt_path_kernel(const PtPat
 
     // Work counters: every wave owns one 64-byte slot (plain stores; atomics on a shared line from every wave serialise at the memory side)
     for(int off = 32; off > 0; off >>= 1) {
-        n_rays += __shfl_down(n_rays, off); // (n_nodes and n_leaves are counted for the whole wavefront: Tracer::step)
+        n_rays += __shfl_down(n_rays, off); // (n_nodes, n_leaves, n_samples and n_vertices are counted for the whole wavefront)
         n_shadow += __shfl_down(n_shadow, off);
-        n_samples += __shfl_down(n_samples, off);
-        n_vertices += __shfl_down(n_vertices, off);
     }
     if(lane == 0) {
         unsigned long long *slot = A->wave_counters + 8 * (size_t)wave;

@@ -252,9 +252,12 @@ PT_D bool sample_emissive(const PtDevScene &sc, const Tables &tb, V3 pos, uint64
         const float radius2 = radius * radius;
         const float theta = 2.0f * PT_PI_F * rng_uniform01(rng);
         const float phi = ptm::acosf_glibc(1.0f - 2.0f * rng_uniform01(rng));
-        const float x = ptm::sinf_glibc(phi) * ptm::cosf_glibc(theta);
-        const float y = ptm::sinf_glibc(phi) * ptm::sinf_glibc(theta);
-        const float z = ptm::cosf_glibc(phi);
+        float sin_theta, cos_theta, sin_phi, cos_phi;
+        ptm::sincosf_glibc(theta, &sin_theta, &cos_theta);
+        ptm::sincosf_glibc(phi, &sin_phi, &cos_phi);
+        const float x = sin_phi * cos_theta;
+        const float y = sin_phi * sin_theta;
+        const float z = cos_phi;
         surface_pos = origin + v3(x, y, z) * radius;
         surface_p = 1.0f / (4.0f * PT_PI_F * radius2);
         surface_cull = false;
