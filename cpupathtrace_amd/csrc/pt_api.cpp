@@ -168,12 +168,10 @@ struct pt_scene {
     PtPathConfig path_cfg{};
     int path_blocks_per_cu = 0;
     uint32_t path_slots = 0, path_waves = 0, path_cap = 0;
-    DevBuf<uint32_t> sl_stream, sl_nee_mask, pull_counter, tile_left;
-    DevBuf<int4> sl_rect, st_rect;
-    DevBuf<int32_t> sl_cursor, sl_path_length;
-    DevBuf<uint64_t> sl_rng, st_rng;
-    DevBuf<F4> sl_ray_o, sl_ray_d, sl_spectrum, sl_out, sl_nee, lq_ray_o, lq_ray_d;
-    DevBuf<double> sl_divisor, sl_bounce_pd;
+    DevBuf<uint32_t> sl_nee_mask, pull_counter, tile_left;
+    DevBuf<int4> st_rect;
+    DevBuf<uint64_t> st_rng;
+    DevBuf<F4> sl_state, sl_nee, lq_ray_o, lq_ray_d;
     DevBuf<PtEstimator> sl_est;
     DevBuf<PtCandidate> sl_cand;
     DevBuf<uint2> path_spill, closest_out;
@@ -420,17 +418,11 @@ int ensure_path_workspace(pt_scene *s, uint32_t n, PtPathConfig *out_cfg, const 
     cfg.grid = static_cast<int>(grid);
     cfg.rows = static_cast<int>(rows);
     cfg.slots_per_wave = static_cast<int>(slots_per_wave);
-    PT_HIP(s->sl_stream.ensure(total));
-    PT_HIP(s->sl_rect.ensure(total));
-    PT_HIP(s->sl_cursor.ensure(total));
-    PT_HIP(s->sl_rng.ensure(total));
-    PT_HIP(s->sl_ray_o.ensure(total));
-    PT_HIP(s->sl_ray_d.ensure(total));
-    PT_HIP(s->sl_spectrum.ensure(total));
-    PT_HIP(s->sl_out.ensure(total));
-    PT_HIP(s->sl_divisor.ensure(total));
-    PT_HIP(s->sl_bounce_pd.ensure(total));
-    PT_HIP(s->sl_path_length.ensure(total));
+    // (the kernel addresses the slot state with 32-bit byte offsets)
+    if(static_cast<unsigned long long>(total) * PT_SLOT_PLANES * sizeof(F4) > 0xffffffffULL) {
+        return fail(PT_ERR_UNSUPPORTED, "path kernel: " + std::to_string(total) + " slots do not fit the 4 GiB the slot state may occupy");
+    }
+    PT_HIP(s->sl_state.ensure(static_cast<size_t>(total) * PT_SLOT_PLANES));
     PT_HIP(s->sl_nee.ensure(static_cast<size_t>(total) * std::max<uint32_t>(rays_per_slot - 1U, 1U)));
     PT_HIP(s->sl_nee_mask.ensure(total));
     PT_HIP(s->sl_cost.ensure(total));
@@ -504,17 +496,7 @@ int run_path(pt_scene *s, const PtDevCamera &cam, const PtDevOptions &opt, PtStr
     }
     PtSlots S{};
     S.total = s->path_slots;
-    S.stream = s->sl_stream.ptr;
-    S.rect = s->sl_rect.ptr;
-    S.cursor = s->sl_cursor.ptr;
-    S.rng = s->sl_rng.ptr;
-    S.ray_o = reinterpret_cast<float4 *>(s->sl_ray_o.ptr);
-    S.ray_d = reinterpret_cast<float4 *>(s->sl_ray_d.ptr);
-    S.spectrum = reinterpret_cast<float4 *>(s->sl_spectrum.ptr);
-    S.out = reinterpret_cast<float4 *>(s->sl_out.ptr);
-    S.divisor = s->sl_divisor.ptr;
-    S.bounce_pd = s->sl_bounce_pd.ptr;
-    S.path_length = s->sl_path_length.ptr;
+    S.state = reinterpret_cast<float4 *>(s->sl_state.ptr);
     S.nee = reinterpret_cast<float4 *>(s->sl_nee.ptr);
     S.nee_mask = s->sl_nee_mask.ptr;
     S.cost = s->sl_cost.ptr;

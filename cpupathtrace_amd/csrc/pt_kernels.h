@@ -32,21 +32,20 @@
 #define PT_MAX_ROWS 8      /* rows of 64 slots per wavefront */
 #define PT_F_STREAM 128u   /* the slot holds a stream (flag bit, next to PT_F_*) */
 
-// Path state of the slots (structure of arrays).  Slot index = (global wave index * rows + row) * 64 + lane, so that every access of a
-// shading pass over one row is one coalesced run of 64 elements.
+// Path state of the slots: PT_SLOT_PLANES planes of 16-byte records, plane k of slot p at state[k * total + p].  Slot index = (global wave
+// index * rows + row) * 64 + lane, so that every access of a shading pass over one row is one coalesced run of 64 records: one
+// dwordx4 load or store per plane, addressed as the scalar `state` plus a 32-bit byte offset (the host keeps the whole state below 4 GiB).
+#define PT_PLANE_RAY_O 0    /* current ray origin xyz; w = contribution_unweighted (worker.cpp:38) */
+#define PT_PLANE_RAY_D 1    /* current ray direction xyz; w = bits of path_length (worker.cpp:43) */
+#define PT_PLANE_PD 2       /* (sample_divisor, sample_bounce_pd) as two doubles (worker.cpp:39-40) */
+#define PT_PLANE_ENGINE 3   /* xorshift state of the stream's engine (x, y), index of the current pixel inside the rectangle (z), stream index (w) */
+#define PT_PLANE_SPECTRUM 4 /* sample_spectrum (worker.cpp:41) */
+#define PT_PLANE_OUT 5      /* out_spectrum (worker.cpp:42) */
+#define PT_PLANE_RECT 6     /* the stream's WorkItem rectangle (written when the slot takes the stream) */
+#define PT_SLOT_PLANES 7
 struct PtSlots {
-    uint32_t total;        // slots of the whole grid (stride of the `nee` planes)
-    uint32_t *stream;      // stream index held by the slot
-    int4 *rect;            // its WorkItem rectangle
-    int32_t *cursor;       // index of the current pixel inside the rectangle (row-major)
-    uint64_t *rng;         // xorshift state of the stream's engine
-    float4 *ray_o;         // current ray origin; w = contribution_unweighted (worker.cpp:38)
-    float4 *ray_d;         // current ray direction
-    float4 *spectrum;      // sample_spectrum (worker.cpp:41)
-    float4 *out;           // out_spectrum (worker.cpp:42)
-    double *divisor;       // sample_divisor (worker.cpp:39)
-    double *bounce_pd;     // sample_bounce_pd (worker.cpp:40)
-    int32_t *path_length;  // worker.cpp:43
+    uint32_t total;        // slots of the whole grid (stride of the planes and of the `nee` planes)
+    float4 *state;         // [PT_SLOT_PLANES][total]
     float4 *nee;           // [light samples per vertex][total] weighed_spectrum of the pending shadow rays (worker.cpp:97)
     uint32_t *nee_mask;    // which of them wait for their shadow ray (or needed none): bit per light sample
     uint32_t *cost;        // wave steps the stream's rays spent in traversal so far (only when PtStreams::cost is wanted)

@@ -210,7 +210,10 @@ struct Tracer {
         // this time), so pruning at the threshold skipped the emitter in cases where the reference tested it and found t < threshold.
         // The walk still ends at the first hit below the threshold (the closest hit can only be nearer).
         w.set_t_max(FLT_MAX);
-        const u2v sentinel = {PT_REF_NONE, __float_as_uint(-1.0f)};
+        // (the sentinel pair is made where it is stored: as a constant it was hoisted out of the path kernel's loops and kept in scratch)
+        uint32_t sent_ref, sent_t;
+        asm volatile("v_mov_b32 %0, -1\n\tv_mov_b32 %1, -1.0" : "=v"(sent_ref), "=v"(sent_t)); // PT_REF_NONE, bits of -1.0f
+        const u2v sentinel = {sent_ref, sent_t};
         stack_l[0] = sentinel;
         w.sp = 1;
         w.occluded = false;
@@ -485,6 +488,13 @@ struct ShadeTables {
     bool emis_in_lds, materials_in_lds;
 };
 
+// Plane k of slot p (PtSlots): the scalar base plus a 32-bit byte offset, which becomes the saddr + voffset form of the load or store --
+// no 64-bit address per plane lives in vector registers.
+template<typename V>
+PT_D V *slot_plane(const PtSlots &S, uint32_t k, uint32_t p) {
+    return reinterpret_cast<V *>(reinterpret_cast<char *>(S.state) + (k * S.total + p) * (uint32_t)sizeof(float4));
+}
+
 // One shading pass over row `row` of the wave's slots: the state machine of one stream per lane.
 //   * a slot without a stream takes the next one from the global counter (or dies when there is none left);
 //   * a slot whose rays have all come back first adds the unoccluded light samples of its previous vertex to out_spectrum in the
@@ -499,13 +509,13 @@ struct ShadeTables {
 // give every lane its position; rays of one kind from neighbouring pixels end up in neighbouring lanes of the traversal).
 template<bool WIDE>
 PT_D void shade_row(const PtDevScene &sc, const PtDevCamera &cam, const PtDevOptions &opt, const PtSlots &S, const PtStreams &T, const PtLocalQueue &Q,
-                    WaveCtx &ctx, uint32_t row, uint32_t ls_in, uint32_t lane, size_t slot_base, size_t queue_base, typename SlotWord<WIDE>::lds_ptr word_l, lds_u2_ptr hit_l,
+                    WaveCtx &ctx, uint32_t row, uint32_t ls_in, uint32_t lane, uint32_t slot_base, size_t queue_base, typename SlotWord<WIDE>::lds_ptr word_l, lds_u2_ptr hit_l,
                     float4 *__restrict__ image, PtDevCounters *counters, const ShadeTables &tb, uint32_t &n_samples, uint32_t &n_vertices) {
     // (n_samples, n_vertices: the wavefront's counts, the same in every lane)
     // the lane's slot of the wave: lane `lane` of row `row`, or -- in a compacted pass (see the kernel) -- the slot the list names; PT_NO_SLOT = none
     const bool have_slot = ls_in != PT_NO_SLOT;
     const uint32_t ls = have_slot ? ls_in : 0u;
-    const size_t p = slot_base + ls;     // slot of the grid
+    const uint32_t p = slot_base + ls;   // slot of the grid
     const unsigned long long lt = (1ULL << lane) - 1ULL;
     const uint32_t n_light_samples = sc.n_lights + sc.n_object_samples;
     typedef SlotWord<WIDE> SW;
@@ -580,10 +590,8 @@ PT_D void shade_row(const PtDevScene &sc, const PtDevCamera &cam, const PtDevOpt
                 else {
                     tile_stream(T, mine, rc, r, tile);
                 }
-                S.stream[p] = mine;
-                S.rect[p] = rc;
-                S.rng[p] = r;
-                S.cursor[p] = 0;
+                *slot_plane<int4>(S, PT_PLANE_RECT, p) = rc;
+                *slot_plane<uint4>(S, PT_PLANE_ENGINE, p) = make_uint4((uint32_t)r, (uint32_t)(r >> 32), 0u, mine);
                 if(T.cost != nullptr) {
                     __hip_atomic_store(&S.cost[p], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 }
@@ -613,17 +621,20 @@ PT_D void shade_row(const PtDevScene &sc, const PtDevCamera &cam, const PtDevOpt
     uint32_t hit_ref = PT_REF_NONE;
     int4 rect = make_int4(0, 0, 0, 0);
     int32_t cursor = 0;
+    uint32_t stream = 0;
     bool stream_finished = false;
 
     if(alive) {
-        rng = S.rng[p];
-        rect = S.rect[p];
-        cursor = S.cursor[p];
+        const uint4 engine = *slot_plane<uint4>(S, PT_PLANE_ENGINE, p);
+        rng = (uint64_t)engine.x | ((uint64_t)engine.y << 32);
+        cursor = (int32_t)engine.z;
+        stream = engine.w;
+        rect = *slot_plane<int4>(S, PT_PLANE_RECT, p);
         if(flags & PT_F_IN_FLIGHT) {
             // Everything the slot may need is requested here, in one batch (one memory round trip instead of one per use): the path
             // state, and -- a single word, to bring the line into the caches -- the shading record of the triangle that was hit, which
             // is the one access of this pass that usually comes from HBM.
-            const float4 out4 = S.out[p];
+            const float4 out4 = *slot_plane<float4>(S, PT_PLANE_OUT, p);
             uint32_t mask = SW::waiting(word, S, p);
             // the first two light samples (most scenes have no more) are fetched with the batch, the others one by one below
             const uint32_t lit = mask & vis_bits;
@@ -634,9 +645,9 @@ PT_D void shade_row(const PtDevScene &sc, const PtDevCamera &cam, const PtDevOpt
             if(lit & 2u) {
                 nee1 = S.nee[S.total + p];
             }
-            const float4 o4 = S.ray_o[p], d4 = S.ray_d[p], spectrum4 = S.spectrum[p];
-            const double divisor_in = S.divisor[p], bounce_pd_in = S.bounce_pd[p];
-            const int path_length_in = S.path_length[p];
+            const float4 o4 = *slot_plane<float4>(S, PT_PLANE_RAY_O, p), d4 = *slot_plane<float4>(S, PT_PLANE_RAY_D, p);
+            const float4 spectrum4 = *slot_plane<float4>(S, PT_PLANE_SPECTRUM, p);
+            const double2 pd_in = *slot_plane<double2>(S, PT_PLANE_PD, p);
             uint32_t warm = 0;
             if(flags & PT_F_HAS_EXT) {
                 const u2v h = hit_l[ls];
@@ -666,7 +677,7 @@ PT_D void shade_row(const PtDevScene &sc, const PtDevCamera &cam, const PtDevOpt
                 // not the pixel's last sample and the estimator cannot accept at it (see estimator_safe_to_overlap)
                 PtEstimator e = S.est[p];
                 out.a = 1.0f;
-                (void)estimator_add(e, S.cand + p * PT_MAX_CANDIDATES, opt, out);
+                (void)estimator_add(e, S.cand + (size_t)p * PT_MAX_CANDIDATES, opt, out);
                 e.pixel_sample++;
                 lane_samples++;
                 S.est[p] = e;
@@ -684,7 +695,7 @@ PT_D void shade_row(const PtDevScene &sc, const PtDevCamera &cam, const PtDevOpt
             if(finished) {
                 // getSample returns (worker.cpp:141-145); run the estimator
                 PtEstimator e = S.est[p];
-                PtCandidate *cand = S.cand + p * PT_MAX_CANDIDATES;
+                PtCandidate *cand = S.cand + (size_t)p * PT_MAX_CANDIDATES;
                 bool accepted = false;
                 if(flags & PT_F_COLLECTED) {
                     out.a = 1.0f;
@@ -712,9 +723,9 @@ PT_D void shade_row(const PtDevScene &sc, const PtDevCamera &cam, const PtDevOpt
                 rd = v3(d4.x, d4.y, d4.z);
                 contribution_unweighted = o4.w;
                 spectrum = c4(spectrum4);
-                divisor = divisor_in;
-                bounce_pd = bounce_pd_in;
-                path_length = path_length_in;
+                divisor = pd_in.x;
+                bounce_pd = pd_in.y;
+                path_length = __float_as_int(d4.w);
             }
         }
         else {
@@ -780,7 +791,7 @@ PT_D void shade_row(const PtDevScene &sc, const PtDevCamera &cam, const PtDevOpt
         const unsigned long long fin_mask = __ballot(stream_finished);
         if(fin_mask != 0ULL) {
             if(stream_finished) {
-                const uint32_t si = S.stream[p];
+                const uint32_t si = stream;
                 if(T.rng != nullptr) {
                     T.rng[si] = rng;
                 }
@@ -970,16 +981,14 @@ PT_D void shade_row(const PtDevScene &sc, const PtDevCamera &cam, const PtDevOpt
     if(alive) {
         word_l[ls] = SW::make(flags, n_rays, vis_init, nee_out_mask);
         SW::keep_waiting(S, p, nee_out_mask);
-        S.rng[p] = rng;
-        S.cursor[p] = cursor;
+        // (rng and cursor: the stream index in .w stays as it is)
+        *slot_plane<uint3>(S, PT_PLANE_ENGINE, p) = make_uint3((uint32_t)rng, (uint32_t)(rng >> 32), (uint32_t)cursor);
         if(flags & PT_F_IN_FLIGHT) {
-            S.ray_o[p] = make_float4(ext.o.x, ext.o.y, ext.o.z, contribution_unweighted);
-            S.ray_d[p] = make_float4(ext.d.x, ext.d.y, ext.d.z, 0.0f);
-            S.spectrum[p] = f4(spectrum);
-            S.out[p] = f4(out);
-            S.divisor[p] = divisor;
-            S.bounce_pd[p] = bounce_pd;
-            S.path_length[p] = path_length;
+            *slot_plane<float4>(S, PT_PLANE_RAY_O, p) = make_float4(ext.o.x, ext.o.y, ext.o.z, contribution_unweighted);
+            *slot_plane<float4>(S, PT_PLANE_RAY_D, p) = make_float4(ext.d.x, ext.d.y, ext.d.z, __int_as_float(path_length));
+            *slot_plane<float4>(S, PT_PLANE_SPECTRUM, p) = f4(spectrum);
+            *slot_plane<float4>(S, PT_PLANE_OUT, p) = f4(out);
+            *slot_plane<double2>(S, PT_PLANE_PD, p) = make_double2(divisor, bounce_pd);
         }
     }
     // (wavefront totals: per-lane counters would be two more registers live across every pass)
@@ -1000,6 +1009,14 @@ PT_D void shade_row(const PtDevScene &sc, const PtDevCamera &cam, const PtDevOpt
 #ifndef PT_PATH_WAVES
 #define PT_PATH_WAVES 4 /* 128 VGPRs: the traversal loop has no spills there; three waves per SIMD hide less of the node-fetch latency (profiles/) */
 #endif
+
+// The lane's number, computed afresh where it is asked for: the asm is opaque, so the compiler cannot reuse a lane number (or anything
+// computed from it) from before a shading pass and carry it through the pass in a register.
+PT_D uint32_t lane_afresh() {
+    uint32_t l;
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+    return l;
+}
 
 template<bool WIDE, bool IN_LDS, int STACK_LDS>
 __global__ __launch_bounds__(256, PT_PATH_WAVES) void pt_path_kernel(const PtPathArgs *__restrict__ args) {
@@ -1024,14 +1041,14 @@ __global__ __launch_bounds__(256, PT_PATH_WAVES) void pt_path_kernel(const PtPat
     // LDS of the workgroup: traversal stacks [STACK_LDS][256] | hit records [4 waves][rows * 64] | slot words [4 waves][rows * 64] |
     // emitter and material tables (PT_LDS_TABLE_BYTES) | start step of every lane's walk | (small scenes) the whole tree and all triangle records
     const int tid = threadIdx.x;
-    const uint32_t lane = (uint32_t)tid & 63u;
+    uint32_t lane = (uint32_t)tid & 63u;
     // (read from the first lane: the compiler does not know that tid >> 6 is the same in every lane, and would keep the wavefront's
     // number and everything computed from it -- the slot, ring and LDS bases -- in vector registers that the shading pass spills)
     const uint32_t wave_in_block = __builtin_amdgcn_readfirstlane((uint32_t)tid >> 6);
     const uint32_t wave = blockIdx.x * 4u + wave_in_block;
     const uint32_t n_slots = (uint32_t)rows * 64u;
     unsigned char *at = lds_raw;
-    lds_u2_ptr stack_l = (lds_u2_ptr)reinterpret_cast<uint2 *>(at) + tid;
+    const lds_u2_ptr stack_base = (lds_u2_ptr)reinterpret_cast<uint2 *>(at) + wave_in_block * 64u;
     at += (size_t)STACK_LDS * 256 * sizeof(uint2);
     lds_u2_ptr hit_l = (lds_u2_ptr)reinterpret_cast<uint2 *>(at) + wave_in_block * n_slots;
     at += (size_t)4 * n_slots * sizeof(uint2);
@@ -1045,7 +1062,9 @@ __global__ __launch_bounds__(256, PT_PATH_WAVES) void pt_path_kernel(const PtPat
     at += (size_t)PT_LDS_TABLE_MAX * 6 * sizeof(float4);
     float4 *materials_l = reinterpret_cast<float4 *>(at);
     at += (size_t)PT_LDS_TABLE_MAX * 4 * sizeof(float4);
-    uint32_t __attribute__((address_space(3))) *born_l = (uint32_t __attribute__((address_space(3))) *)reinterpret_cast<uint32_t *>(at) + tid; // wave step at which the lane's walk began
+    typedef uint32_t __attribute__((address_space(3))) *lds_u32_ptr;
+    const lds_u32_ptr born_base = (lds_u32_ptr)reinterpret_cast<uint32_t *>(at) + wave_in_block * 64u;
+    lds_u32_ptr born_l = born_base + lane; // wave step at which the lane's walk began
     // (the same kilobyte holds the list of ready slots of a compacted shading pass, one byte per slot of up to four rows, when the cost diagnostics are off)
     typedef unsigned char __attribute__((address_space(3))) *lds_u8_ptr;
     lds_u8_ptr list_l = (lds_u8_ptr)reinterpret_cast<unsigned char *>(at) + wave_in_block * 256u;
@@ -1106,8 +1125,15 @@ __global__ __launch_bounds__(256, PT_PATH_WAVES) void pt_path_kernel(const PtPat
     else {
         tr.recs = (typename RecPtr<IN_LDS>::type)(glb_f4_cptr)A->sc.recs;
     }
-    tr.stack_l = stack_l;
-    tr.my_spill = (glb_u2_ptr)(A->spill + ((size_t)wave * 64 + lane) * A->spill_depth);
+    // What depends on the lane number is derived again on every entry into the traversal loop (from a fresh lane number and the argument
+    // block) instead of living through a shading pass in vector registers.  (Bound only after a pass, the values would merge with the
+    // ones bound before it, and the compiler kept that merged value in scratch -- reloaded by every refill of the traversal loop.)
+    auto bind_lane = [&](const PtPathArgs *B, uint32_t l) {
+        lane = l;
+        tr.stack_l = stack_base + l;
+        tr.my_spill = (glb_u2_ptr)(B->spill + ((size_t)wave * 64 + l) * B->spill_depth);
+        born_l = born_base + l;
+    };
 
     const size_t slot_base = (size_t)wave * n_slots;
     const size_t queue_base = (size_t)wave * Q.cap;
@@ -1162,10 +1188,11 @@ __global__ __launch_bounds__(256, PT_PATH_WAVES) void pt_path_kernel(const PtPat
             const PtPathArgs *P = (const PtPathArgs *)(args_c4)((const char __attribute__((address_space(4))) *)A4 + pass_offset);
             uint32_t *const walk_save = P->walk_save;
             const size_t save_stride = P->save_stride;
+            const uint32_t lane_s = lane_afresh(); // (the lane number of the pass)
             // Nothing of the traversal lives in registers across a shading pass (which needs them all): the walks in progress and the
             // lane's counters are parked in this lane's column of the save area and read back afterwards.
             {
-                uint32_t *sv = walk_save + (size_t)wave * 64 + lane;
+                uint32_t *sv = walk_save + (size_t)wave * 64 + lane_s;
                 const size_t st = save_stride;
                 sv[0 * st] = __float_as_uint(w.o.x);
                 sv[1 * st] = __float_as_uint(w.o.y);
@@ -1195,11 +1222,11 @@ __global__ __launch_bounds__(256, PT_PATH_WAVES) void pt_path_kernel(const PtPat
             if(PT_COST_LDS_BYTES >= 1024 && !cost_on && P->compact_passes != 0 && rows > 1 && rows <= 4 && ctx.first_rows == 0u) {
                 uint32_t rows_used = 0;
                 for(uint32_t r = 0; r < (uint32_t)rows; r++) {
-                    const typename SW::T word = word_l[r * 64 + lane];
+                    const typename SW::T word = word_l[r * 64 + lane_s];
                     const bool is_ready = !(SW::flags(word) & PT_F_DONE) && SW::pending(word) == 0;
                     const unsigned long long m = __ballot(is_ready);
                     if(is_ready) {
-                        list_l[n_listed + (uint32_t)__popcll(m & ((1ULL << lane) - 1ULL))] = (unsigned char)(r * 64 + lane);
+                        list_l[n_listed + (uint32_t)__popcll(m & ((1ULL << lane_s) - 1ULL))] = (unsigned char)(r * 64 + lane_s);
                     }
                     n_listed += (uint32_t)__popcll(m);
                     rows_used += m != 0ULL ? 1u : 0u;
@@ -1211,11 +1238,11 @@ __global__ __launch_bounds__(256, PT_PATH_WAVES) void pt_path_kernel(const PtPat
 #pragma unroll 1
             for(uint32_t k = 0; k < n_chunks; k++) {
                 // (in a compacted pass `row` is not used: the first round is over)
-                uint32_t ls = k * 64u + lane;
+                uint32_t ls = k * 64u + lane_s;
                 if(compact) {
                     ls = ls < n_listed ? (uint32_t)list_l[ls] : PT_NO_SLOT;
                 }
-                shade_row<WIDE>(P->sc, P->cam, P->opt, P->S, P->T, P->Q, ctx, k, ls, lane, slot_base, queue_base, word_l, hit_l, P->image, P->counters, tb, n_samples, n_vertices);
+                shade_row<WIDE>(P->sc, P->cam, P->opt, P->S, P->T, P->Q, ctx, k, ls, lane_s, (uint32_t)slot_base, queue_base, word_l, hit_l, P->image, P->counters, tb, n_samples, n_vertices);
             }
             // the rays just written are read back by other lanes of this wavefront
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
@@ -1225,7 +1252,7 @@ __global__ __launch_bounds__(256, PT_PATH_WAVES) void pt_path_kernel(const PtPat
                 // registers that the pass has no room for)
                 asm volatile("" : "+s"(pass_offset));
                 const PtPathArgs *R = (const PtPathArgs *)(args_c4)((const char __attribute__((address_space(4))) *)A4 + pass_offset);
-                const uint32_t *sv = R->walk_save + (size_t)wave * 64 + lane;
+                const uint32_t *sv = R->walk_save + (size_t)wave * 64 + lane_afresh();
                 const size_t st = R->save_stride;
                 w.o = v3(__uint_as_float(sv[0 * st]), __uint_as_float(sv[1 * st]), __uint_as_float(sv[2 * st]));
                 w.d = v3(__uint_as_float(sv[3 * st]), __uint_as_float(sv[4 * st]), __uint_as_float(sv[5 * st]));
@@ -1251,8 +1278,9 @@ __global__ __launch_bounds__(256, PT_PATH_WAVES) void pt_path_kernel(const PtPat
             // the ring has new rays: its first 64 go to the lanes' window registers (which did not live across the pass)
             win_o = make_float4(0, 0, 0, 0);
             win_d = make_float4(0, 0, 0, __uint_as_float(PT_DEST_NULL));
-            if(lane < ctx.q_count) {
-                uint32_t i = ctx.q_head + lane;
+            const uint32_t lane_w = lane_afresh();
+            if(lane_w < ctx.q_count) {
+                uint32_t i = ctx.q_head + lane_w;
                 i = i >= Q.cap ? i - Q.cap : i;
                 win_o = Q.ray_o[queue_base + i];
                 win_d = Q.ray_d[queue_base + i];
@@ -1264,6 +1292,11 @@ __global__ __launch_bounds__(256, PT_PATH_WAVES) void pt_path_kernel(const PtPat
             }
         }
 
+        {
+            size_t bind_offset = 0;
+            asm volatile("" : "+s"(bind_offset));
+            bind_lane((const PtPathArgs *)(args_c4)((const char __attribute__((address_space(4))) *)A4 + bind_offset), lane_afresh());
+        }
         bool finished = false;
         for(;;) {
             // ---- 1. retire finished walks: the result goes to the slot's words in LDS -----------------------------------------------------
@@ -1317,8 +1350,11 @@ __global__ __launch_bounds__(256, PT_PATH_WAVES) void pt_path_kernel(const PtPat
                     const uint32_t take = ctx.q_count < n_idle ? ctx.q_count : n_idle;
                     const uint32_t rank = (uint32_t)__popcll(idle_mask & ((1ULL << lane) - 1ULL));
                     const int src = (int)(rank & 63u);
-                    const float4 ro = make_float4(__shfl(win_o.x, src), __shfl(win_o.y, src), __shfl(win_o.z, src), __shfl(win_o.w, src));
-                    const float4 rd = make_float4(__shfl(win_d.x, src), __shfl(win_d.y, src), __shfl(win_d.z, src), __shfl(win_d.w, src));
+                    // (ds_bpermute, which is what __shfl does for 0 <= src < 64, without the lane number __shfl computes: the compiler
+                    // hoisted that out of every loop and kept it in scratch)
+                    auto from = [src](float v) { return __int_as_float(__builtin_amdgcn_ds_bpermute(src << 2, __float_as_int(v))); };
+                    const float4 ro = make_float4(from(win_o.x), from(win_o.y), from(win_o.z), from(win_o.w));
+                    const float4 rd = make_float4(from(win_d.x), from(win_d.y), from(win_d.z), from(win_d.w));
                     if(!active && rank < take && __float_as_uint(rd.w) != PT_DEST_NULL) {
                         tr.start(w, rec, root, ro, rd);
                         if(cost_on) {
