@@ -3,6 +3,7 @@
 ``Scene``            Scene::Scene / Scene::getIntersection        (reference include/PathTrace/scene/scene.h:32,41)
 ``process_item``     processItem(WorkItem, RandomEngine&)          (include/PathTrace/worker.h:69)
 ``process_job``      processJob(FrameRenderJob)                    (include/PathTrace/worker.h:83-84)
+``process_job_controlled``  processJob that can be cancelled or given a time budget (include/PathTrace/render_control.h)
 
 The library is the only implementation behind these calls: if it is missing or no HIP device is usable they raise.
 """
@@ -18,10 +19,11 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PT_LIB_OVERRIDE") or os.path.join(HERE, "libpathtrace_hip.so")  # override: A/B builds of the same ABI
 
 PT_OK = 0
-ERRORS = {1: "PT_ERR_INVALID", 2: "PT_ERR_NO_DEVICE", 3: "PT_ERR_HIP", 4: "PT_ERR_UNSUPPORTED", 5: "PT_ERR_NOMEM"}
+PT_ERR_CANCELLED = 6
+ERRORS = {1: "PT_ERR_INVALID", 2: "PT_ERR_NO_DEVICE", 3: "PT_ERR_HIP", 4: "PT_ERR_UNSUPPORTED", 5: "PT_ERR_NOMEM", 6: "PT_ERR_CANCELLED"}
 
 EXPORTS = ["pt_device_count", "pt_last_error", "pt_scene_create", "pt_scene_destroy", "pt_scene_info", "pt_scene_emissive", "pt_scene_bvh_dump", "pt_intersect_batch",
-           "pt_render_streams", "pt_render_item", "pt_render_tiles", "pt_render_tiles_progress", "pt_render_tiles_multi", "pt_render_tiles_device", "pt_job_tiles", "pt_pixel_seed", "pt_rng_seed_to_state", "pt_post_process", "pt_post_process_device"]
+           "pt_render_streams", "pt_render_item", "pt_render_tiles", "pt_render_tiles_progress", "pt_render_tiles_multi", "pt_render_tiles_device", "pt_render_tiles_ctl", "pt_render_cancel", "pt_job_tiles", "pt_pixel_seed", "pt_rng_seed_to_state", "pt_post_process", "pt_post_process_device"]
 
 
 class PtError(RuntimeError):
@@ -68,6 +70,16 @@ class Stats(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class RenderControl(C.Structure):
+    """pt_render_control: the stop and the outcome of one controlled render.  cancel() may be called from a progress callback or from any
+    other thread while the render runs; a control that was cancelled stays cancelled (use a new one for the next render)."""
+    _fields_ = [("budget_ms", C.c_double), ("tile_done", C.c_void_p), ("streams_finished", C.c_uint64), ("streams_abandoned", C.c_uint64),
+                ("streams_unclaimed", C.c_uint64), ("drain_ms", C.c_double), ("cancel_requested", C.c_int32)]
+
+    def cancel(self):
+        _check(load().pt_render_cancel(C.byref(self)))
 
 
 TILE_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("w", "<i4"), ("h", "<i4")])
@@ -255,6 +267,13 @@ class Scene:
                                                cb, None))
         return image
 
+    def process_job_controlled(self, camera, options, base_seed=1234, tiles=None, budget_ms=0, progress=None, control=None, image=None):
+        """processJob that stops early when `control.cancel()` is called (from `progress` or any other thread) or after `budget_ms` of wall
+        time (0 = no budget).  Returns (image, tile_done, info).  A stop is a result, not an exception: info["status"] is PT_OK or
+        PT_ERR_CANCELLED, and info holds the stream counts, drain_ms and the launch statistics.  Finished pixels equal process_job's bit for
+        bit; every other pixel keeps its value in `image` (default: zeros), and tile_done[i] says whether tiles[i] finished."""
+        return _render_controlled([self], camera, options, base_seed, tiles, budget_ms, progress, control, image)
+
     def process_job_device(self, camera, options, d_image_ptr, stream_ptr, base_seed=1234, tiles=None, want_stats=False):
         """processJob writing into device memory (d_image_ptr: device address of width*height*4 floats)."""
         if tiles is None:
@@ -267,6 +286,38 @@ class Scene:
 
 
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_int, C.c_int, C.c_void_p)
+
+
+def _render_controlled(scenes, camera, options, base_seed, tiles, budget_ms, progress, control, image):
+    if tiles is None:
+        tiles = job_tiles(options["image_width"], options["image_height"])
+    tiles = np.ascontiguousarray(tiles, dtype=TILE_DTYPE)
+    if image is None:
+        image = np.zeros((options["image_height"], options["image_width"], 4), np.float32)
+    assert image.dtype == np.float32 and image.flags.c_contiguous and image.shape == (options["image_height"], options["image_width"], 4)
+    ctl = control if control is not None else RenderControl()
+    ctl.budget_ms = float(budget_ms or 0.0)
+    tile_done = np.zeros(len(tiles), np.uint8)
+    ctl.tile_done = tile_done.ctypes.data
+    handles = (C.c_void_p * len(scenes))(*[s._h for s in scenes])
+    stats = (Stats * len(scenes))()
+    cb = PROGRESS_FN(lambda done, total, user: progress(done, total)) if progress is not None else None
+    cp, op = _camera(camera), _options(options)
+    try:
+        rc = load().pt_render_tiles_ctl(handles, C.c_int(len(scenes)), C.byref(cp), C.byref(op), _ptr(tiles), C.c_size_t(len(tiles)), C.c_uint64(base_seed),
+                                        _ptr(image), stats, cb, None, C.byref(ctl))
+    finally:
+        ctl.tile_done = None
+    if rc not in (PT_OK, PT_ERR_CANCELLED):
+        _check(rc)
+    info = {"status": rc, "cancelled": rc == PT_ERR_CANCELLED, "streams_finished": ctl.streams_finished, "streams_abandoned": ctl.streams_abandoned,
+            "streams_unclaimed": ctl.streams_unclaimed, "drain_ms": ctl.drain_ms, "stats": [s.as_dict() for s in stats]}
+    return image, tile_done.astype(bool), info
+
+
+def process_job_controlled_multi(scenes, camera, options, base_seed=1234, tiles=None, budget_ms=0, progress=None, control=None, image=None):
+    """process_job_multi that can be stopped: see Scene.process_job_controlled."""
+    return _render_controlled(list(scenes), camera, options, base_seed, tiles, budget_ms, progress, control, image)
 
 
 def process_job_multi(scenes, camera, options, base_seed=1234, tiles=None, progress=None, want_stats=False):

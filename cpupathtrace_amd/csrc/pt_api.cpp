@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -182,6 +183,12 @@ struct pt_scene {
     uint32_t *host_tiles_done = nullptr; // pinned: tiles finished so far, written by the kernel (progress callback)
     unsigned long long *host_streams_done = nullptr; // pinned: the launch's count of finished streams, copied behind every launch
     uint64_t streams_expected = 0;                   // ... and what it must read once the stream has drained (finish_path)
+    // a controlled launch (pt_render_tiles_ctl) also leaves its count of abandoned streams in host_streams_done[1] and its final pull
+    // counter in host_streams_done[2]; finish_path accounts for every stream with them
+    bool streams_controlled = false;
+    uint32_t streams_first_total = 0;
+    uint32_t *host_cancel = nullptr; // pinned, fine-grained: the stop request of a controlled launch (PtStreams::cancel), written by the host
+    uint32_t *dev_cancel = nullptr;  // ... and its address on the device
     // cost-aware placement (render_tiles_impl): what every stream of the pilot launch cost, and the stream every slot of the main launch starts with
     DevBuf<uint32_t> sl_cost, stream_cost, place;
     bool debug_collect_costs = false;                // pt_debug_collect_costs: every launch records them
@@ -194,6 +201,9 @@ struct pt_scene {
         }
         if(host_streams_done != nullptr) {
             (void)hipHostFree(host_streams_done);
+        }
+        if(host_cancel != nullptr) {
+            (void)hipHostFree(host_cancel);
         }
         if(stream != nullptr) {
             (void)hipStreamDestroy(stream);
@@ -450,15 +460,90 @@ int ensure_path_workspace(pt_scene *s, uint32_t n, PtPathConfig *out_cfg, const 
     return PT_OK;
 }
 
+// The stop of one controlled call (pt_render_tiles_ctl), shared by the host threads of its replicas.  The stop travels to the device as
+// one word per replica in pinned, fine-grained host memory; the host loop of every launch polls the caller's cancel flag and the deadline,
+// and the first one to see either writes 1 into the word of every replica whose launch is prepared or running.
+struct RenderStop {
+    typedef std::chrono::steady_clock Clock;
+    pt_render_control *ctl = nullptr;
+    bool has_deadline = false;
+    Clock::time_point deadline;
+    std::atomic<bool> requested{false};
+    std::mutex mutex; // guards what follows
+    Clock::time_point requested_at;
+    std::vector<uint32_t *> words; // the cancel words of the launches prepared or running
+    double drain_ms = 0.0;         // the latest end of a launch after the request
+
+    // a launch takes part: its word starts as the stop's state (a request that came before the launch stops it at its first pass)
+    void enlist(uint32_t *word) {
+        std::lock_guard<std::mutex> lock(mutex);
+        __atomic_store_n(word, requested.load() ? 1U : 0U, __ATOMIC_SEQ_CST);
+        words.push_back(word);
+    }
+    // ... and has ended (seen by its host loop at `end`): its word may serve another call now
+    void retire(uint32_t *word, Clock::time_point end) {
+        std::lock_guard<std::mutex> lock(mutex);
+        words.erase(std::remove(words.begin(), words.end(), word), words.end());
+        if(requested.load()) {
+            drain_ms = std::max(drain_ms, std::chrono::duration<double, std::milli>(end - requested_at).count());
+        }
+    }
+    void poll() {
+        if(requested.load(std::memory_order_relaxed)) {
+            return;
+        }
+        const Clock::time_point now = Clock::now();
+        if(__atomic_load_n(&ctl->cancel, __ATOMIC_ACQUIRE) == 0 && !(has_deadline && now >= deadline)) {
+            return;
+        }
+        std::lock_guard<std::mutex> lock(mutex);
+        if(!requested.load()) {
+            requested_at = now;
+            requested.store(true);
+            for(uint32_t *w : words) {
+                __atomic_store_n(w, 1U, __ATOMIC_SEQ_CST);
+            }
+        }
+    }
+};
+
+// Streams of a launch that no wavefront took: the first round (streams 0 .. first_total-1) is always dealt out, beyond it the final value
+// of the pull counter says how many were handed out (it may overshoot the job: a wavefront's last pull asks for a whole row)
+uint64_t unclaimed_streams(uint64_t n, uint64_t first_total, uint64_t pulled) {
+    const uint64_t first = std::min(n, first_total);
+    return n - first - std::min(pulled, n - first);
+}
+
+// What a controlled launch did with its streams (finish_path)
+struct StreamTally {
+    uint64_t finished = 0, abandoned = 0, unclaimed = 0;
+};
+
 // Wait for the scene's stream and make sure the last launch rendered every stream it was given: a wavefront that left early or a stream
-// lost in the hand-out would otherwise return stale pixels with PT_OK.  Every entry point that synchronises anyway ends with this.
-int finish_path(pt_scene *s) {
+// lost in the hand-out would otherwise return stale pixels with PT_OK.  Every entry point that synchronises anyway ends with this.  A
+// controlled launch must account for every stream as finished, abandoned or never taken; `tally` (may be null) receives the three.
+int finish_path(pt_scene *s, StreamTally *tally = nullptr) {
     PT_HIP(hipStreamSynchronize(s->stream));
     if(s->host_streams_done != nullptr && s->streams_expected != 0) {
-        const unsigned long long done = *static_cast<volatile unsigned long long *>(s->host_streams_done);
+        const volatile unsigned long long *h = static_cast<volatile unsigned long long *>(s->host_streams_done);
+        const unsigned long long done = h[0];
         const uint64_t expected = s->streams_expected;
         s->streams_expected = 0;
-        if(done != expected) {
+        if(s->streams_controlled) {
+            s->streams_controlled = false;
+            StreamTally t;
+            t.finished = done;
+            t.abandoned = h[1];
+            t.unclaimed = unclaimed_streams(expected, s->streams_first_total, static_cast<uint32_t>(h[2]));
+            if(t.finished + t.abandoned + t.unclaimed != expected) {
+                return fail(PT_ERR_HIP, "path kernel ended with " + std::to_string(t.finished) + " finished, " + std::to_string(t.abandoned) + " abandoned and " +
+                                            std::to_string(t.unclaimed) + " unclaimed of " + std::to_string(expected) + " streams");
+            }
+            if(tally != nullptr) {
+                *tally = t;
+            }
+        }
+        else if(done != expected) {
             return fail(PT_ERR_HIP, "path kernel ended with " + std::to_string(done) + " of " + std::to_string(expected) + " streams finished");
         }
     }
@@ -467,8 +552,10 @@ int finish_path(pt_scene *s) {
 
 // Render the streams described by T (device pointers) with one launch on the scene's stream.  With a progress function the host polls
 // the count of finished tiles (pinned memory, written by the kernel) while the launch runs and reports every step from the calling thread.
+// With a RenderStop (controlled launches) the host loop runs whether or not there is a progress function: it forwards a stop request to the
+// launch through the scene's cancel word.
 int run_path(pt_scene *s, const PtDevCamera &cam, const PtDevOptions &opt, PtStreams T, float4 *d_image, pt_stats *stats, pt_progress_fn progress, void *progress_user,
-             const PathPlan *plan = nullptr, bool want_costs = false) {
+             const PathPlan *plan = nullptr, bool want_costs = false, RenderStop *stop = nullptr) {
     PtPathConfig cfg;
     hipStream_t st = s->stream;
     PathPlan debug_plan;
@@ -525,7 +612,8 @@ int run_path(pt_scene *s, const PtDevCamera &cam, const PtDevOptions &opt, PtStr
     }
     T.tile_left = nullptr;
     T.tiles_done = nullptr;
-    if(progress != nullptr && T.rect == nullptr && T.n_tiles > 0) {
+    T.cancel = nullptr;
+    if((progress != nullptr || stop != nullptr) && T.rect == nullptr && T.n_tiles > 0) {
         if(s->host_tiles_done == nullptr) {
             PT_HIP(hipHostMalloc(reinterpret_cast<void **>(&s->host_tiles_done), 64, hipHostMallocDefault));
         }
@@ -541,6 +629,27 @@ int run_path(pt_scene *s, const PtDevCamera &cam, const PtDevOptions &opt, PtStr
     PT_HIP(ev_end.create());
     PT_HIP(hipEventRecord(ev_begin.e, st));
     PT_HIP(s->path_args.ensure(1));
+    if(stop != nullptr) {
+        if(s->host_cancel == nullptr) {
+            // coherent (fine-grained): the device must not keep a cached copy of the word for the length of the launch
+            PT_HIP(hipHostMalloc(reinterpret_cast<void **>(&s->host_cancel), 64, hipHostMallocCoherent | hipHostMallocMapped));
+            PT_HIP(hipHostGetDevicePointer(reinterpret_cast<void **>(&s->dev_cancel), s->host_cancel, 0));
+        }
+        T.cancel = s->dev_cancel;
+    }
+    // (from here until the host loop has seen the launch end, a stop request reaches this launch)
+    struct Enlisted {
+        RenderStop *stop;
+        uint32_t *word;
+        ~Enlisted() {
+            if(stop != nullptr) {
+                stop->retire(word, RenderStop::Clock::now());
+            }
+        }
+    } enlisted{stop, s->host_cancel};
+    if(stop != nullptr) {
+        stop->enlist(s->host_cancel);
+    }
     pt_launch_path(st, s->dev, cam, opt, S, T, Q, cfg, d_image, s->counters.ptr, &s->host_path_args, s->path_args.ptr);
     PT_HIP(hipGetLastError());
     PT_HIP(hipEventRecord(ev_end.e, st));
@@ -551,13 +660,21 @@ int run_path(pt_scene *s, const PtDevCamera &cam, const PtDevOptions &opt, PtStr
     *s->host_streams_done = ~0ULL;
     s->streams_expected = T.n;
     PT_HIP(hipMemcpyAsync(s->host_streams_done, &s->counters.ptr->streams_done, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    s->streams_controlled = stop != nullptr;
+    if(stop != nullptr) {
+        s->host_streams_done[1] = ~0ULL;
+        s->host_streams_done[2] = ~0ULL;
+        s->streams_first_total = T.first_total;
+        PT_HIP(hipMemcpyAsync(s->host_streams_done + 1, &s->counters.ptr->streams_abandoned, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        PT_HIP(hipMemcpyAsync(s->host_streams_done + 2, s->pull_counter.ptr, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    }
     if(T.tiles_done != nullptr) {
         const int total = static_cast<int>(T.n_tiles);
         int reported = 0;
         for(;;) {
             const hipError_t q = hipEventQuery(ev_end.e);
             const int done = std::min(static_cast<int>(*static_cast<volatile uint32_t *>(s->host_tiles_done)), total);
-            while(reported < done) {
+            while(progress != nullptr && reported < done) {
                 progress(++reported, total, progress_user);
             }
             if(q == hipSuccess) {
@@ -566,10 +683,17 @@ int run_path(pt_scene *s, const PtDevCamera &cam, const PtDevOptions &opt, PtStr
             if(q != hipErrorNotReady) {
                 return fail(PT_ERR_HIP, std::string("path kernel: ") + hipGetErrorString(q));
             }
+            if(stop != nullptr) {
+                stop->poll(); // (after the callback: a cancel from it reaches the device at once)
+            }
             std::this_thread::sleep_for(std::chrono::microseconds(500));
         }
+        if(stop != nullptr) {
+            stop->retire(s->host_cancel, RenderStop::Clock::now());
+            enlisted.stop = nullptr;
+        }
         const int done = std::min(static_cast<int>(*static_cast<volatile uint32_t *>(s->host_tiles_done)), total);
-        while(reported < done) {
+        while(progress != nullptr && reported < done) {
             progress(++reported, total, progress_user);
         }
     }
@@ -594,7 +718,16 @@ int run_path(pt_scene *s, const PtDevCamera &cam, const PtDevOptions &opt, PtStr
         }
         PtDevCounters done{};
         PT_HIP(hipMemcpy(&done, s->counters.ptr, sizeof(done), hipMemcpyDeviceToHost));
-        if(done.streams_done != T.n) {
+        if(stop != nullptr) {
+            uint32_t pulled = 0;
+            PT_HIP(hipMemcpy(&pulled, s->pull_counter.ptr, sizeof(pulled), hipMemcpyDeviceToHost));
+            const uint64_t unclaimed = unclaimed_streams(T.n, T.first_total, pulled);
+            if(done.streams_done + done.streams_abandoned + unclaimed != T.n) {
+                return fail(PT_ERR_HIP, "path kernel ended with " + std::to_string(done.streams_done) + " finished, " + std::to_string(done.streams_abandoned) + " abandoned and " +
+                                            std::to_string(unclaimed) + " unclaimed of " + std::to_string(T.n) + " streams");
+            }
+        }
+        else if(done.streams_done != T.n) {
             return fail(PT_ERR_HIP, "path kernel ended with " + std::to_string(done.streams_done) + " of " + std::to_string(T.n) + " streams finished");
         }
         stats->node_visits = sum[0];
@@ -1427,7 +1560,7 @@ int pt_render_streams(pt_scene *s, const pt_camera_params *camera, const pt_opti
 }
 
 static int render_tiles_impl(pt_scene *s, const pt_camera_params *camera, const pt_options *options, const pt_tile *tiles, size_t n_tiles, uint64_t base_seed,
-                             float4 *d_image, pt_stats *stats, pt_progress_fn progress = nullptr, void *progress_user = nullptr) {
+                             float4 *d_image, pt_stats *stats, pt_progress_fn progress = nullptr, void *progress_user = nullptr, RenderStop *stop = nullptr) {
     PtDevOptions opt;
     int rc = derive_options(options, &opt);
     if(rc != PT_OK) {
@@ -1463,7 +1596,7 @@ static int render_tiles_impl(pt_scene *s, const pt_camera_params *camera, const 
         hipStream_t st = s->stream;
         PT_HIP(hipMemcpyAsync(s->tiles.ptr, rects.data(), n_tiles * sizeof(int4), hipMemcpyHostToDevice, st));
         PT_HIP(hipMemcpyAsync(s->tile_offset.ptr, offsets.data(), n_tiles * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-        if(progress != nullptr) {
+        if(progress != nullptr || stop != nullptr) {
             PT_HIP(s->tile_left.ensure(n_tiles));
             PT_HIP(hipMemcpyAsync(s->tile_left.ptr, left.data(), n_tiles * sizeof(uint32_t), hipMemcpyHostToDevice, st));
         }
@@ -1498,7 +1631,7 @@ static int render_tiles_impl(pt_scene *s, const pt_camera_params *camera, const 
                 T.chunks_per_tile = static_cast<uint32_t>(tiles[0].w) * static_cast<uint32_t>(tiles[0].h) / 64U;
             }
         }
-        return run_path(s, cam, opt, T, d_image, stats, progress, progress_user);
+        return run_path(s, cam, opt, T, d_image, stats, progress, progress_user, nullptr, false, stop);
     }
 }
 
@@ -1594,8 +1727,14 @@ int pt_render_item(pt_scene *s, const pt_camera_params *camera, const pt_options
     return finish_path(s);
 }
 
-int pt_render_tiles_multi(pt_scene *const *scenes, int n_scenes, const pt_camera_params *camera, const pt_options *options, const pt_tile *tiles, size_t n_tiles,
-                          uint64_t base_seed, float *out_image, pt_stats *stats, pt_progress_fn progress, void *progress_user) {
+} // extern "C"
+
+// pt_render_tiles_multi, and with a RenderStop pt_render_tiles_ctl: then every replica also loads the rectangles of its tiles from out_image
+// first (so that the pixels a stopped launch leaves unwritten keep their values), and reports which of its tiles finished and what became of
+// its streams (tile_done: [n_tiles] or null, tallies: [n_scenes]).
+static int render_tiles_multi_impl(pt_scene *const *scenes, int n_scenes, const pt_camera_params *camera, const pt_options *options, const pt_tile *tiles, size_t n_tiles,
+                                   uint64_t base_seed, float *out_image, pt_stats *stats, pt_progress_fn progress, void *progress_user, RenderStop *stop = nullptr,
+                                   uint8_t *tile_done = nullptr, StreamTally *tallies = nullptr) {
     if(scenes == nullptr || n_scenes < 1) {
         return fail(PT_ERR_INVALID, "no scenes");
     }
@@ -1650,9 +1789,11 @@ int pt_render_tiles_multi(pt_scene *const *scenes, int n_scenes, const pt_camera
     const size_t width = static_cast<size_t>(options->image_width), pixels = width * static_cast<size_t>(options->image_height);
     auto work = [&](int i) {
         std::vector<pt_tile> mine;
+        std::vector<size_t> mine_index;
         for(size_t k = 0; k < n_tiles; k++) {
             if(owner(k) == i) {
                 mine.push_back(tiles[k]);
+                mine_index.push_back(k);
             }
         }
         if(mine.empty()) {
@@ -1663,8 +1804,15 @@ int pt_render_tiles_multi(pt_scene *const *scenes, int n_scenes, const pt_camera
             std::lock_guard<std::mutex> lock(s->render_mutex);
             PT_HIP(hipSetDevice(s->device));
             PT_HIP(s->image.ensure(pixels));
+            if(stop != nullptr) {
+                for(const pt_tile &t : mine) {
+                    const size_t at = static_cast<size_t>(t.y) * width + static_cast<size_t>(t.x);
+                    PT_HIP(hipMemcpy2DAsync(s->image.ptr + at, width * sizeof(F4), out_image + at * 4, width * sizeof(F4), static_cast<size_t>(t.w) * sizeof(F4),
+                                            static_cast<size_t>(t.h), hipMemcpyHostToDevice, s->stream));
+                }
+            }
             int rc = render_tiles_impl(s, camera, options, mine.data(), mine.size(), base_seed, reinterpret_cast<float4 *>(s->image.ptr),
-                                       stats != nullptr ? stats + i : nullptr, progress != nullptr ? static_cast<pt_progress_fn>(trampoline) : nullptr, &shared);
+                                       stats != nullptr ? stats + i : nullptr, progress != nullptr ? static_cast<pt_progress_fn>(trampoline) : nullptr, &shared, stop);
             if(rc != PT_OK) {
                 return rc;
             }
@@ -1673,7 +1821,22 @@ int pt_render_tiles_multi(pt_scene *const *scenes, int n_scenes, const pt_camera
                 PT_HIP(hipMemcpy2DAsync(out_image + at * 4, width * sizeof(F4), s->image.ptr + at, width * sizeof(F4), static_cast<size_t>(t.w) * sizeof(F4),
                                         static_cast<size_t>(t.h), hipMemcpyDeviceToHost, s->stream));
             }
-            return finish_path(s);
+            if(stop == nullptr) {
+                return finish_path(s);
+            }
+            rc = finish_path(s, &tallies[i]);
+            if(rc != PT_OK) {
+                return rc;
+            }
+            if(tile_done != nullptr) {
+                // pixels of each tile not finished (render_tiles_impl set them to the tile's size, the kernel counted them down)
+                std::vector<uint32_t> left(mine.size());
+                PT_HIP(hipMemcpy(left.data(), s->tile_left.ptr, left.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+                for(size_t k = 0; k < mine.size(); k++) {
+                    tile_done[mine_index[k]] = left[k] == 0 ? 1 : 0;
+                }
+            }
+            return PT_OK;
         };
         rcs[static_cast<size_t>(i)] = run();
         if(rcs[static_cast<size_t>(i)] != PT_OK) {
@@ -1696,6 +1859,58 @@ int pt_render_tiles_multi(pt_scene *const *scenes, int n_scenes, const pt_camera
             return fail(rcs[static_cast<size_t>(i)], "scene " + std::to_string(i) + ": " + errors[static_cast<size_t>(i)]);
         }
     }
+    return PT_OK;
+}
+
+extern "C" {
+
+int pt_render_tiles_multi(pt_scene *const *scenes, int n_scenes, const pt_camera_params *camera, const pt_options *options, const pt_tile *tiles, size_t n_tiles,
+                          uint64_t base_seed, float *out_image, pt_stats *stats, pt_progress_fn progress, void *progress_user) {
+    return render_tiles_multi_impl(scenes, n_scenes, camera, options, tiles, n_tiles, base_seed, out_image, stats, progress, progress_user);
+}
+
+int pt_render_tiles_ctl(pt_scene *const *scenes, int n_scenes, const pt_camera_params *camera, const pt_options *options, const pt_tile *tiles, size_t n_tiles,
+                        uint64_t base_seed, float *out_image, pt_stats *stats, pt_progress_fn progress, void *progress_user, pt_render_control *ctl) {
+    const RenderStop::Clock::time_point start = RenderStop::Clock::now();
+    if(ctl == nullptr) {
+        return fail(PT_ERR_INVALID, "null control");
+    }
+    ctl->streams_finished = ctl->streams_abandoned = ctl->streams_unclaimed = 0;
+    ctl->drain_ms = 0.0;
+    if(ctl->tile_done != nullptr && n_tiles > 0) {
+        std::memset(ctl->tile_done, 0, n_tiles);
+    }
+    RenderStop stop;
+    stop.ctl = ctl;
+    if(ctl->budget_ms > 0.0) {
+        stop.has_deadline = true;
+        stop.deadline = start + std::chrono::duration_cast<RenderStop::Clock::duration>(std::chrono::duration<double, std::milli>(ctl->budget_ms));
+    }
+    stop.poll(); // (a control cancelled before the call, or a budget spent already: the launches start stopped)
+    std::vector<StreamTally> tallies(n_scenes > 0 ? static_cast<size_t>(n_scenes) : 0U);
+    const int rc = render_tiles_multi_impl(scenes, n_scenes, camera, options, tiles, n_tiles, base_seed, out_image, stats, progress, progress_user, &stop, ctl->tile_done,
+                                           tallies.data());
+    if(rc != PT_OK) {
+        return rc;
+    }
+    for(const StreamTally &t : tallies) {
+        ctl->streams_finished += t.finished;
+        ctl->streams_abandoned += t.abandoned;
+        ctl->streams_unclaimed += t.unclaimed;
+    }
+    ctl->drain_ms = stop.drain_ms;
+    if(ctl->streams_abandoned + ctl->streams_unclaimed != 0) {
+        return fail(PT_ERR_CANCELLED, "render stopped (" + std::string(__atomic_load_n(&ctl->cancel, __ATOMIC_ACQUIRE) != 0 ? "cancelled" : "budget spent") + "): " +
+                                          std::to_string(ctl->streams_abandoned) + " streams abandoned, " + std::to_string(ctl->streams_unclaimed) + " never taken");
+    }
+    return PT_OK;
+}
+
+int pt_render_cancel(pt_render_control *ctl) {
+    if(ctl == nullptr) {
+        return fail(PT_ERR_INVALID, "null control");
+    }
+    __atomic_store_n(&ctl->cancel, 1, __ATOMIC_RELEASE);
     return PT_OK;
 }
 

@@ -74,6 +74,8 @@ struct PtStreams {
     uint32_t *tiles_done;        // HOST-visible count of finished tiles (pinned memory), or null
     uint32_t *cost;              // [n] out, or null: traversal steps of the wavefront that passed while a ray of the stream was walking (summed over its rays)
     const uint32_t *place;       // [n_waves * slots per wave] or null: the stream that starts in every slot (0xffffffff: none) instead of the arithmetic first round
+    const uint32_t *cancel;      // HOST-written stop request (pinned, fine-grained), or null: never stop.  Read once per shading pass; once it
+                                 // is non-zero the wavefront takes no more streams and drops every stream that would start another sample
 };
 
 // Ray queues, one private ring per wavefront: entries [wave * cap, (wave + 1) * cap)

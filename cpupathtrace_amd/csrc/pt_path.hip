@@ -510,8 +510,9 @@ PT_D V *slot_plane(const PtSlots &S, uint32_t k, uint32_t p) {
 template<bool WIDE>
 PT_D void shade_row(const PtDevScene &sc, const PtDevCamera &cam, const PtDevOptions &opt, const PtSlots &S, const PtStreams &T, const PtLocalQueue &Q,
                     WaveCtx &ctx, uint32_t row, uint32_t ls_in, uint32_t lane, uint32_t slot_base, size_t queue_base, typename SlotWord<WIDE>::lds_ptr word_l, lds_u2_ptr hit_l,
-                    float4 *__restrict__ image, PtDevCounters *counters, const ShadeTables &tb, uint32_t &n_samples, uint32_t &n_vertices) {
-    // (n_samples, n_vertices: the wavefront's counts, the same in every lane)
+                    float4 *__restrict__ image, PtDevCounters *counters, const ShadeTables &tb, bool stop, uint32_t &n_samples, uint32_t &n_vertices) {
+    // (n_samples, n_vertices: the wavefront's counts, the same in every lane; stop: the host has asked the launch to stop (PtStreams::cancel),
+    // a scalar read once per pass -- no stream is taken any more, and a stream that would start another sample is dropped instead)
     // the lane's slot of the wave: lane `lane` of row `row`, or -- in a compacted pass (see the kernel) -- the slot the list names; PT_NO_SLOT = none
     const bool have_slot = ls_in != PT_NO_SLOT;
     const uint32_t ls = have_slot ? ls_in : 0u;
@@ -567,6 +568,7 @@ PT_D void shade_row(const PtDevScene &sc, const PtDevCamera &cam, const PtDevOpt
                 }
             }
             else {
+                ctx.pool_empty = ctx.pool_empty || stop; // (a stop request leaves the rest of the pool unclaimed)
                 if(!ctx.pool_empty) {
                     if(lane == 0) {
                         base = T.first_total + atomicAdd(T.next, (uint32_t)__popcll(want_mask));
@@ -623,6 +625,7 @@ PT_D void shade_row(const PtDevScene &sc, const PtDevCamera &cam, const PtDevOpt
     int32_t cursor = 0;
     uint32_t stream = 0;
     bool stream_finished = false;
+    bool stream_abandoned = false; // dropped at a sample boundary after a stop request: no pixel, no engine state, no cost, no tile count
 
     if(alive) {
         const uint4 engine = *slot_plane<uint4>(S, PT_PLANE_ENGINE, p);
@@ -770,9 +773,13 @@ PT_D void shade_row(const PtDevScene &sc, const PtDevCamera &cam, const PtDevOpt
             have_pixel = true;
             break;
         }
-        if(!have_pixel) {
-            // the stream has rendered its whole rectangle: hand the engine back and free the slot (it takes a new stream in the next pass)
-            stream_finished = true;
+        if(!have_pixel || stop) {
+            // the stream has rendered its whole rectangle: hand the engine back and free the slot (it takes a new stream in the next pass).
+            // After a stop request a stream that has a pixel left is dropped here instead, between two samples, with no ray in flight (a
+            // slot is only shaded once all its rays are back): every pixel it finished is exact, its current pixel is never written, and
+            // its slot is freed in the same way -- since the pool is closed, it dies in its next pass.
+            stream_finished = !have_pixel;
+            stream_abandoned = have_pixel;
             flags = 0;
         }
         else {
@@ -813,6 +820,12 @@ PT_D void shade_row(const PtDevScene &sc, const PtDevCamera &cam, const PtDevOpt
                 atomicAdd(&counters->streams_done, (unsigned long long)__popcll(fin_mask));
             }
         }
+        if(stop) {
+            const unsigned long long drop_mask = __ballot(stream_abandoned);
+            if(lane == 0 && drop_mask != 0ULL) {
+                atomicAdd(&counters->streams_abandoned, (unsigned long long)__popcll(drop_mask));
+            }
+        }
     }
 
     // ---- vertex, part 1: everything up to the Russian-roulette draw (worker.cpp:50-70) ---------------------------------------
@@ -838,7 +851,9 @@ PT_D void shade_row(const PtDevScene &sc, const PtDevCamera &cam, const PtDevOpt
         // BSDF::getSpectrum(..., synthetic = true) returns p = 0 for glass and mirror: their light samples never
         // contribute (worker.cpp:92), so no shadow ray is needed -- the light-sampling draws are still consumed below.
         want_nee = mat.bsdf == 0 && n_light_samples > 0;
-        safe_overlap = (flags & PT_F_SAFE) != 0; // decided when the sample started (estimator_safe_to_overlap)
+        // (decided when the sample started, estimator_safe_to_overlap; after a stop request no sample is overlapped, so that the next
+        // boundary -- where the stream is dropped -- comes as soon as this path ends)
+        safe_overlap = (flags & PT_F_SAFE) != 0 && !stop;
         // an extension ray: the bounce (may still be cancelled by the 1E-20 guards, worker.cpp:112,134) or the next sample's camera ray
         emit_ext = do_bounce || safe_overlap;
     }
@@ -1189,6 +1204,7 @@ __global__ __launch_bounds__(256, PT_PATH_WAVES) void pt_path_kernel(const PtPat
             uint32_t *const walk_save = P->walk_save;
             const size_t save_stride = P->save_stride;
             const uint32_t lane_s = lane_afresh(); // (the lane number of the pass)
+
             // Nothing of the traversal lives in registers across a shading pass (which needs them all): the walks in progress and the
             // lane's counters are parked in this lane's column of the save area and read back afterwards.
             {
@@ -1235,6 +1251,13 @@ __global__ __launch_bounds__(256, PT_PATH_WAVES) void pt_path_kernel(const PtPat
                 __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup"); // (the list is read by other lanes of this wavefront)
             }
             const uint32_t n_chunks = compact ? (n_listed + 63u) / 64u : (uint32_t)rows;
+            // The host's stop request, once per pass: a system-scope load from fine-grained host memory (every lane reads the same word,
+            // one request), made a scalar for the whole pass.  The streams see it at their next sample boundary (shade_row).
+            uint32_t stop_word = 0;
+            if(P->T.cancel != nullptr) {
+                stop_word = __hip_atomic_load(P->T.cancel, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            }
+            const bool stop = __builtin_amdgcn_readfirstlane(stop_word) != 0u;
 #pragma unroll 1
             for(uint32_t k = 0; k < n_chunks; k++) {
                 // (in a compacted pass `row` is not used: the first round is over)
@@ -1242,7 +1265,7 @@ __global__ __launch_bounds__(256, PT_PATH_WAVES) void pt_path_kernel(const PtPat
                 if(compact) {
                     ls = ls < n_listed ? (uint32_t)list_l[ls] : PT_NO_SLOT;
                 }
-                shade_row<WIDE>(P->sc, P->cam, P->opt, P->S, P->T, P->Q, ctx, k, ls, lane_s, (uint32_t)slot_base, queue_base, word_l, hit_l, P->image, P->counters, tb, n_samples, n_vertices);
+                shade_row<WIDE>(P->sc, P->cam, P->opt, P->S, P->T, P->Q, ctx, k, ls, lane_s, (uint32_t)slot_base, queue_base, word_l, hit_l, P->image, P->counters, tb, stop, n_samples, n_vertices);
             }
             // the rays just written are read back by other lanes of this wavefront
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");

@@ -126,7 +126,8 @@ struct PtCandidate {
 // (the host checks it against the number of streams when statistics are read back).
 struct PtDevCounters {
     unsigned long long streams_done;
-    unsigned long long pad[7];
+    unsigned long long streams_abandoned; // taken, then dropped at a sample boundary because the host asked the launch to stop (PtStreams::cancel)
+    unsigned long long pad[6];
 };
 
 #endif

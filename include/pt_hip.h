@@ -24,6 +24,7 @@ extern "C" {
 #define PT_ERR_HIP 3         /* a HIP runtime call failed */
 #define PT_ERR_UNSUPPORTED 4 /* scene outside what the kernels cover (see pt_scene_create) */
 #define PT_ERR_NOMEM 5
+#define PT_ERR_CANCELLED 6   /* a controlled render stopped early (budget or pt_render_cancel): see pt_render_tiles_ctl */
 
 enum { PT_OBJ_TRIANGLE = 0, PT_OBJ_SPHERE = 1 };
 enum { PT_BSDF_LAMBERTIAN = 0, PT_BSDF_GLASS = 1, PT_BSDF_MIRROR = 2 };
@@ -193,6 +194,36 @@ int pt_render_tiles_multi(pt_scene *const *scenes, int n_scenes, const pt_camera
  * `stats` is given; every waiting entry point checks that the launch rendered all its streams, this one with stats or PT_VERIFY=1. */
 int pt_render_tiles_device(pt_scene *scene, const pt_camera_params *camera, const pt_options *options, const pt_tile *tiles, size_t n_tiles,
                            uint64_t base_seed, float *d_out_image, void *stream, pt_stats *stats);
+
+/* Cancellable, time-budgeted processJob.  A controlled render is the same single launch per replica as pt_render_tiles_multi; it can be
+ * told to stop while it runs, either by pt_render_cancel (from the progress callback or any other thread) or by its budget.
+ *   - The stop is COOPERATIVE.  The host writes a word in pinned host memory; every wavefront of the launch reads it once per shading pass.
+ *     From then on no stream (pixel) is taken any more, and a stream that would start another sample is dropped at that sample boundary.
+ *     The launch then ends on its own.  It takes roughly one path's bounces plus the longest walk in flight (DESIGN.md reports drain_ms).
+ *     It is no watchdog: a walk that never ends never reaches a sample boundary.
+ *   - Pixels: a pixel is written only when its estimator finishes, so every written pixel is bit-identical to the full render's.  Every
+ *     other pixel keeps the value out_image held on entry (a pre-filled sentinel shows which is which).  tile_done says which tiles finished.
+ *   - Status: PT_OK = every tile finished, even if a stop came too late to drop anything; PT_ERR_CANCELLED = stopped, some tiles unfinished;
+ *     any other code = failure, as for pt_render_tiles_multi.  The launch must account for every stream
+ *     (finished + abandoned + unclaimed = pixels of the tiles); if it does not, the call fails with PT_ERR_HIP.
+ *   - The scenes are fully reusable afterwards: their next render of any kind equals a fresh scene's, bit for bit.
+ * scenes, n_scenes, tiles, progress: as pt_render_tiles_multi (stats, if not NULL, has n_scenes entries for what did run).  `cancel` is
+ * only ever set by pt_render_cancel; it is not cleared by a call, so a control that was cancelled before a call stops that call at once. */
+typedef struct pt_render_control {
+    double budget_ms;           /* in: wall-clock budget counted from the call's start; <= 0 = none */
+    uint8_t *tile_done;         /* in: [n_tiles] or NULL; out: tile_done[i] = 1 if every pixel of tiles[i] finished, else 0 */
+    uint64_t streams_finished;  /* out: streams (pixels) that finished */
+    uint64_t streams_abandoned; /* out: taken, then dropped at a sample boundary */
+    uint64_t streams_unclaimed; /* out: never taken */
+    double drain_ms;            /* out: from the stop request to the end of the launch(es), as the host saw it; 0 if no stop was requested */
+    int32_t cancel;             /* set by pt_render_cancel only */
+} pt_render_control;
+int pt_render_tiles_ctl(pt_scene *const *scenes, int n_scenes, const pt_camera_params *camera, const pt_options *options, const pt_tile *tiles,
+                        size_t n_tiles, uint64_t base_seed, float *out_image, pt_stats *stats, pt_progress_fn progress, void *user,
+                        pt_render_control *ctl);
+/* Requests the stop of the controlled render that runs (or will run) with `ctl`.  Thread-safe and non-blocking; it may be called from the
+ * progress callback or any other thread.  PT_ERR_INVALID for NULL. */
+int pt_render_cancel(pt_render_control *ctl);
 
 /* The tile list processJob builds (worker.cpp:398-414): tile_size = clamp(min(w, h) / 4, 1, 32), row-major, edge tiles clipped.
  * Returns the tile count; fills at most `capacity` entries. */

@@ -1,4 +1,5 @@
 // src/host/worker.cpp -- processItem / processJob of PathTrace/worker.h on top of the C ABI (include/pt_hip.h).
+#include <PathTrace/render_control.h>
 #include <PathTrace/worker.h>
 
 #include "../../include/pt_hip.h"
@@ -45,6 +46,47 @@ namespace {
         }
     }
 
+    std::vector<pt_tile> jobTiles(int width, int height) {
+        std::vector<pt_tile> tiles(pt_job_tiles(width, height, nullptr, 0));
+        pt_job_tiles(width, height, tiles.data(), tiles.size());
+        return tiles;
+    }
+
+    // one random base seed per call, like the reference's std::random_device-seeded workers; $PATHTRACE_SEED pins it
+    uint64_t jobSeed() {
+        if(const char *fixed = std::getenv("PATHTRACE_SEED")) {
+            return std::strtoull(fixed, nullptr, 0);
+        }
+        std::random_device device;
+        return (static_cast<uint64_t>(device()) << 32) | device();
+    }
+
+    // An exception thrown by the progress callback must not cross the C ABI (with several devices it would be thrown on a library thread
+    // and end the program): it is kept, the remaining calls are skipped, and it is thrown again once the devices have finished.
+    struct ForwardProgress {
+        const std::function<void(int, int)> *fn;
+        std::exception_ptr failure;
+
+        static void call(int completed, int total, void *user) {
+            ForwardProgress *f = static_cast<ForwardProgress *>(user);
+            if(f->failure) {
+                return;
+            }
+            try {
+                (*f->fn)(completed, total);
+            }
+            catch(...) {
+                f->failure = std::current_exception();
+            }
+        }
+    };
+
+    // worker_count (worker.h:83-84; threads in the reference, 0 = as many as the machine has): at most that many of the scene's device
+    // replicas take part.  Every device runs one persistent launch, so there is nothing else for the count to choose.
+    int replicaCount(const std::vector<pt_scene *> &replicas, int worker_count) {
+        return worker_count > 0 ? std::min(worker_count, static_cast<int>(replicas.size())) : static_cast<int>(replicas.size());
+    }
+
 } // namespace
 
 WorkItem::WorkItem() noexcept : job(nullptr), offset_x(0), offset_y(0), width(0), height(0) {}
@@ -80,50 +122,57 @@ Image<> processJob(const FrameRenderJob &job, const std::function<void(int, int)
     const pt_camera_params camera = cameraParams(job.camera);
     const pt_options options = renderOptions(job.options);
 
-    std::vector<pt_tile> tiles(pt_job_tiles(width, height, nullptr, 0));
-    pt_job_tiles(width, height, tiles.data(), tiles.size());
-
-    // one random base seed per call, like the reference's std::random_device-seeded workers; $PATHTRACE_SEED pins it
-    uint64_t base_seed;
-    if(const char *fixed = std::getenv("PATHTRACE_SEED")) {
-        base_seed = std::strtoull(fixed, nullptr, 0);
-    }
-    else {
-        std::random_device device;
-        base_seed = (static_cast<uint64_t>(device()) << 32) | device();
-    }
+    const std::vector<pt_tile> tiles = jobTiles(width, height);
+    const uint64_t base_seed = jobSeed();
 
     // The tiles are dealt to the scene's device replicas ($PATHTRACE_DEVICES; one by default) and rendered by one persistent launch
     // per device.  progress_callback is called as the reference calls it (worker.h:75-78, src/worker.cpp:354-360): once per finished
     // tile, (completed, total), never concurrently -- while the devices are still rendering.
-    // An exception thrown by the callback must not cross the C ABI (with several devices it would be thrown on a library thread and end
-    // the program): it is kept, the remaining calls are skipped, and it is thrown again here once the devices have finished.
-    struct Forward {
-        const std::function<void(int, int)> *fn;
-        std::exception_ptr failure;
-    } forward{&progress_callback, nullptr};
-    auto trampoline = [](int completed, int total, void *user) {
-        Forward *f = static_cast<Forward *>(user);
-        if(f->failure) {
-            return;
-        }
-        try {
-            (*f->fn)(completed, total);
-        }
-        catch(...) {
-            f->failure = std::current_exception();
-        }
-    };
+    ForwardProgress forward{&progress_callback, nullptr};
     static_assert(sizeof(Color<float>) == 4 * sizeof(float), "Image<Color<float>> is a packed RGBA float array");
-    // worker_count (worker.h:83-84; threads in the reference, 0 = as many as the machine has): at most that many of the scene's device
-    // replicas take part.  Every device runs one persistent launch, so there is nothing else for the count to choose.
     const std::vector<pt_scene *> &replicas = job.scene.deviceScenes();
-    const int n_replicas = worker_count > 0 ? std::min(worker_count, static_cast<int>(replicas.size())) : static_cast<int>(replicas.size());
-    const int status = pt_render_tiles_multi(replicas.data(), n_replicas, &camera, &options, tiles.data(), tiles.size(), base_seed,
-                                             reinterpret_cast<float *>(frame.data()), nullptr, trampoline, &forward);
+    const int status = pt_render_tiles_multi(replicas.data(), replicaCount(replicas, worker_count), &camera, &options, tiles.data(), tiles.size(), base_seed,
+                                             reinterpret_cast<float *>(frame.data()), nullptr, &ForwardProgress::call, &forward);
     if(forward.failure) {
         std::rethrow_exception(forward.failure);
     }
     check(status, "processJob");
+    return frame;
+}
+
+Image<> processJob(const FrameRenderJob &job, RenderControl &control, const std::function<void(int, int)> &progress_callback, int worker_count) {
+    control.cancelled_ = false;
+    control.finished_.clear();
+    control.tile_count_ = 0;
+    const int width = std::max(job.options.image_width, 0);
+    const int height = std::max(job.options.image_height, 0);
+    Image<> frame(width, height); // (pixels a stop leaves unwritten stay transparent black)
+    if(width == 0 || height == 0) {
+        return frame;
+    }
+    const pt_camera_params camera = cameraParams(job.camera);
+    const pt_options options = renderOptions(job.options);
+    const std::vector<pt_tile> tiles = jobTiles(width, height);
+    const uint64_t base_seed = jobSeed();
+    ForwardProgress forward{&progress_callback, nullptr};
+    std::vector<uint8_t> done(tiles.size(), 0);
+    control.ctl_.tile_done = done.data();
+    const std::vector<pt_scene *> &replicas = job.scene.deviceScenes();
+    const int status = pt_render_tiles_ctl(replicas.data(), replicaCount(replicas, worker_count), &camera, &options, tiles.data(), tiles.size(), base_seed,
+                                           reinterpret_cast<float *>(frame.data()), nullptr, &ForwardProgress::call, &forward, &control.ctl_);
+    control.ctl_.tile_done = nullptr;
+    if(forward.failure) {
+        std::rethrow_exception(forward.failure);
+    }
+    if(status != PT_ERR_CANCELLED) {
+        check(status, "processJob");
+    }
+    control.cancelled_ = status == PT_ERR_CANCELLED;
+    control.tile_count_ = tiles.size();
+    for(size_t i = 0; i < tiles.size(); i++) {
+        if(done[i] != 0) {
+            control.finished_.push_back(RenderControl::Tile{tiles[i].x, tiles[i].y, tiles[i].w, tiles[i].h});
+        }
+    }
     return frame;
 }
