@@ -6,7 +6,7 @@ import pytest
 import oracle
 from cpupathtrace_amd import binding, scenes
 from tests.cases import golden, golden_mesh, opt_from, post_cases, scene_set
-from tests.util import assert_bits_equal, miss_equal
+from tests.util import assert_bits_equal, env, miss_equal
 
 pytestmark = pytest.mark.gpu
 
@@ -736,19 +736,25 @@ def test_every_device_of_the_host_renders_its_tiles(sset):
             r.close()
 
 
-def _scene_with_env(desc, **env):
-    """binding.Scene(desc) under the given environment (the library reads its knobs when a scene is created)."""
-    import os
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update({k: str(v) for k, v in env.items()})
-    try:
-        return binding.Scene(desc)
-    finally:
-        for k, v in old.items():
-            if v is None:
-                del os.environ[k]
-            else:
-                os.environ[k] = v
+# statistics of a render call that describe how the work was scheduled (they may move under a knob; samples, vertices and rays may not)
+SCHEDULE_STATS = ("wave_steps", "shading_passes", "wavefronts", "slot_rows")
+
+
+def _render_with_env(desc, cam, opt, base_seed, **values):
+    """process_job of a new scene of `desc` with the given knobs set across scene creation AND the render: the library reads some of its
+    knobs when a scene is created (PT_ROWS, PT_REFILL_IDLE, PT_COMPACT, ...) and others at every render call (PT_BURST, PT_LEAF_MIN,
+    PT_FIRST_LANES, PT_SPREAD_WAVES, PT_FIRST_SPREAD, PT_FIRST_SHIFT; pt_api.cpp, ensure_path_workspace / run_path)."""
+    with env(**values):
+        scene = binding.Scene(desc)
+        try:
+            img, stats = scene.process_job(cam, opt, base_seed=base_seed, want_stats=True)
+        finally:
+            scene.close()
+    return img.copy(), stats
+
+
+def _moved(st0, st1):
+    return {k: (st0[k], st1[k]) for k in SCHEDULE_STATS if st0[k] != st1[k]}
 
 
 @pytest.mark.gpu
@@ -762,29 +768,25 @@ def test_compacted_passes_render_the_same_frame(oracle_lib):
              # 14 light samples per vertex: the kernel with the 64-bit slot word (its waiting mask lives with the slot's state in HBM)
              ("lit room", (_lit_room(12, _three_emitters), scenes.camera((0, 0, -3), (0, 0, 0), (0, 1, 0), 1.0, 1.0, -1.0)), scenes.options(1024, 1024, 3, 12))]
     for name, (desc, cam), opt in cases:
-        by_rows = _scene_with_env(desc, PT_COMPACT=0)
-        by_list = _scene_with_env(desc, PT_COMPACT=1)
         handle = oracle_lib.scene_create(desc)
         try:
-            want, st_rows = by_rows.process_job(cam, opt, base_seed=91, want_stats=True)
-            want = want.copy()
+            want, st_rows = _render_with_env(desc, cam, opt, 91, PT_COMPACT=0)
             assert st_rows["samples"] < 1024 * 1024 * opt["max_sample_count"], "%s: no pixel stopped early, the case tests nothing" % name
-            got, st_list = by_list.process_job(cam, opt, base_seed=91, want_stats=True)
+            got, st_list = _render_with_env(desc, cam, opt, 91, PT_COMPACT=1)
             assert_bits_equal(got, want, "%s: frame of compacted passes against row-by-row passes" % name)
             assert st_list["samples"] == st_rows["samples"] and st_list["vertices"] == st_rows["vertices"]
+            assert _moved(st_rows, st_list), "%s: PT_COMPACT changed no scheduling statistic (%s)" % (name, st_list)
             rng = np.random.default_rng(17)
             xs, ys = rng.integers(0, 1024, 1000).astype(np.int32), rng.integers(0, 1024, 1000).astype(np.int32)
             states = np.array([binding.seed_to_state(binding.pixel_seed(91, int(x), int(y))) for x, y in zip(xs, ys)], np.uint64)
             ref, _ = handle.render_streams(cam, opt, oracle.pixel_streams(xs, ys, states), n_threads=16)
             assert_bits_equal(got[ys, xs], ref[ys, xs], "%s: sampled pixels against the oracle" % name)
         finally:
-            by_rows.close()
-            by_list.close()
             handle.close()
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("env", [
+@pytest.mark.parametrize("knobs", [
     {"PT_BURST": 1, "PT_LEAF_MIN": 64},
     {"PT_REFILL_IDLE": 64, "PT_MIN_READY": 512},
     {"PT_REFILL_IDLE": 1, "PT_MIN_READY": 1, "PT_READY_SHIFT": 3},
@@ -794,7 +796,7 @@ def test_compacted_passes_render_the_same_frame(oracle_lib):
     {"PT_ROWS": 2, "PT_BLOCKS_PER_CU": 1},
     {"PT_ROWS": 3, "PT_FIRST_LANES": 4, "PT_COMPACT": 0},
 ], ids=lambda e: ",".join("%s=%s" % (k[3:].lower(), v) for k, v in e.items()))
-def test_scheduler_knobs_do_not_change_the_frame(env):
+def test_scheduler_knobs_do_not_change_the_frame(knobs):
     """How a wavefront schedules its work -- burst length, refill and pass thresholds, early passes, rows of slots, lanes that take rays,
     compacted passes -- decides WHEN a stream's next draw is made, never which: a 1024 x 1024 adaptive frame (several rows of slots per
     wavefront, slots that die at different samples) is the same bit for bit under extreme settings, with the tree in HBM and in LDS."""
@@ -802,14 +804,10 @@ def test_scheduler_knobs_do_not_change_the_frame(env):
              ("box", scenes.box_scene(), scenes.options(1024, 1024, 4, 12))]
     for name, (desc, cam), opt in cases:
         for lds_small in (1, 0):
-            plain = _scene_with_env(desc, PT_LDS_SMALL=lds_small)
-            tuned = _scene_with_env(desc, PT_LDS_SMALL=lds_small, **env)
-            try:
-                want, st0 = plain.process_job(cam, opt, base_seed=55, want_stats=True)
-                want = want.copy()
-                got, st1 = tuned.process_job(cam, opt, base_seed=55, want_stats=True)
-                assert_bits_equal(got, want, "%s (small trees %s): frame under %s" % (name, "in LDS" if lds_small else "in HBM", env))
-                assert st1["samples"] == st0["samples"] and st1["vertices"] == st0["vertices"] and st1["rays_traced"] == st0["rays_traced"]
-            finally:
-                plain.close()
-                tuned.close()
+            want, st0 = _render_with_env(desc, cam, opt, 55, PT_LDS_SMALL=lds_small)
+            got, st1 = _render_with_env(desc, cam, opt, 55, PT_LDS_SMALL=lds_small, **knobs)
+            where = "%s (small trees %s)" % (name, "in LDS" if lds_small else "in HBM")
+            assert_bits_equal(got, want, "%s: frame under %s" % (where, knobs))
+            assert st1["samples"] == st0["samples"] and st1["vertices"] == st0["vertices"] and st1["rays_traced"] == st0["rays_traced"]
+            # the knobs were applied: the work was scheduled differently
+            assert _moved(st0, st1), "%s: %s changed no scheduling statistic (%s)" % (where, knobs, st1)

@@ -1,4 +1,7 @@
-"""Bit-exact comparison helpers for the parity tests."""
+"""Bit-exact comparison helpers for the parity tests, and a scoped environment for the library's knobs."""
+import contextlib
+import os
+
 import numpy as np
 
 
@@ -30,3 +33,19 @@ def miss_equal(got_t, want_t, what=""):
     gm, wm = got_t < 0, want_t < 0
     assert (gm == wm).all(), "%s: hit/miss differs for %d rays" % (what, int((gm != wm).sum()))
     assert_bits_equal(got_t[~wm], want_t[~wm], what)
+
+
+@contextlib.contextmanager
+def env(**values):
+    """The given environment variables for the duration of the block (the library reads some knobs when a scene is created and others
+    at every render call, so scene creation AND the renders belong inside it); the previous values are restored afterwards."""
+    old = {k: os.environ.get(k) for k in values}
+    os.environ.update({k: str(v) for k, v in values.items()})
+    try:
+        yield
+    finally:
+        for k, v in old.items():
+            if v is None:
+                del os.environ[k]
+            else:
+                os.environ[k] = v
