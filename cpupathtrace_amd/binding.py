@@ -4,6 +4,7 @@
 ``process_item``     processItem(WorkItem, RandomEngine&)          (include/PathTrace/worker.h:69)
 ``process_job``      processJob(FrameRenderJob)                    (include/PathTrace/worker.h:83-84)
 ``process_job_controlled``  processJob that can be cancelled or given a time budget (include/PathTrace/render_control.h)
+``Frame``            a controlled processJob that can be continued: each call resumes where the last one stopped (include/PathTrace/frame_render.h)
 
 The library is the only implementation behind these calls: if it is missing or no HIP device is usable they raise.
 """
@@ -24,6 +25,10 @@ ERRORS = {1: "PT_ERR_INVALID", 2: "PT_ERR_NO_DEVICE", 3: "PT_ERR_HIP", 4: "PT_ER
 
 EXPORTS = ["pt_device_count", "pt_last_error", "pt_scene_create", "pt_scene_destroy", "pt_scene_info", "pt_scene_emissive", "pt_scene_bvh_dump", "pt_intersect_batch",
            "pt_render_streams", "pt_render_item", "pt_render_tiles", "pt_render_tiles_progress", "pt_render_tiles_multi", "pt_render_tiles_device", "pt_render_tiles_ctl", "pt_render_cancel", "pt_job_tiles", "pt_pixel_seed", "pt_rng_seed_to_state", "pt_post_process", "pt_post_process_device"]
+FRAME_EXPORTS = ["pt_frame_create", "pt_frame_render", "pt_frame_get_info", "pt_frame_destroy"]
+EXPORTS += FRAME_EXPORTS
+
+
 
 
 class PtError(RuntimeError):
@@ -80,6 +85,16 @@ class RenderControl(C.Structure):
 
     def cancel(self):
         _check(load().pt_render_cancel(C.byref(self)))
+
+
+class FrameInfo(C.Structure):
+    """pt_frame_info: where a resumable frame stands."""
+    _fields_ = [("streams_total", C.c_uint64), ("streams_finished", C.c_uint64), ("streams_parked", C.c_uint64), ("streams_untouched", C.c_uint64),
+                ("tiles_total", C.c_uint64), ("tiles_done", C.c_uint64), ("samples_carried", C.c_uint64), ("parked_with_candidates", C.c_uint64),
+                ("park_bytes", C.c_uint64), ("launches", C.c_int32), ("status", C.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 TILE_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("w", "<i4"), ("h", "<i4")])
@@ -318,6 +333,68 @@ def _render_controlled(scenes, camera, options, base_seed, tiles, budget_ms, pro
 def process_job_controlled_multi(scenes, camera, options, base_seed=1234, tiles=None, budget_ms=0, progress=None, control=None, image=None):
     """process_job_multi that can be stopped: see Scene.process_job_controlled."""
     return _render_controlled(list(scenes), camera, options, base_seed, tiles, budget_ms, progress, control, image)
+
+
+class Frame:
+    """A processJob that can be stopped and continued (pt_frame_*): each render() goes on where the last one stopped, and the finished
+    frame equals process_job / process_job_multi with the same seed bit for bit.  scenes: one Scene, or several replicas (tiles are dealt
+    as process_job_multi deals them).  The scenes must stay open while the frame lives."""
+
+    def __init__(self, scenes, camera, options, base_seed=1234, tiles=None):
+        self._scenes = list(scenes) if isinstance(scenes, (list, tuple)) else [scenes]
+        if tiles is None:
+            tiles = job_tiles(options["image_width"], options["image_height"])
+        self.tiles = np.ascontiguousarray(tiles, dtype=TILE_DTYPE)
+        self.image = np.zeros((options["image_height"], options["image_width"], 4), np.float32)
+        handles = (C.c_void_p * len(self._scenes))(*[sc._h for sc in self._scenes])
+        cp, op = _camera(camera), _options(options)
+        h = C.c_void_p()
+        _check(load().pt_frame_create(handles, C.c_int(len(self._scenes)), C.byref(cp), C.byref(op), _ptr(self.tiles), C.c_size_t(len(self.tiles)),
+                                      C.c_uint64(base_seed), C.byref(h)))
+        self._h = h
+
+    def render(self, budget_ms=0, progress=None, control=None):
+        """Continue the frame for at most `budget_ms` of wall time (0 = until it is complete), or until `control.cancel()`.  Returns
+        (image, tile_done, info) as Scene.process_job_controlled does: image is the frame so far (the same array every call), tile_done the
+        frame's finished tiles, info["status"] PT_OK once the frame is complete and PT_ERR_CANCELLED before; info["frame"] is info()."""
+        if self._h is None:
+            raise ValueError("frame is closed")
+        ctl = control if control is not None else RenderControl()
+        ctl.budget_ms = float(budget_ms or 0.0)
+        tile_done = np.zeros(len(self.tiles), np.uint8)
+        ctl.tile_done = tile_done.ctypes.data
+        stats = (Stats * len(self._scenes))()
+        cb = PROGRESS_FN(lambda done, total, user: progress(done, total)) if progress is not None else None
+        try:
+            rc = load().pt_frame_render(self._h, _ptr(self.image), stats, cb, None, C.byref(ctl))
+        finally:
+            ctl.tile_done = None
+        if rc not in (PT_OK, PT_ERR_CANCELLED):
+            _check(rc)
+        info = {"status": rc, "cancelled": rc == PT_ERR_CANCELLED, "streams_finished": ctl.streams_finished, "streams_abandoned": ctl.streams_abandoned,
+                "streams_unclaimed": ctl.streams_unclaimed, "drain_ms": ctl.drain_ms, "stats": [st.as_dict() for st in stats], "frame": self.info()}
+        return self.image, tile_done.astype(bool), info
+
+    def info(self):
+        fi = FrameInfo()
+        _check(load().pt_frame_get_info(self._h, C.byref(fi)))
+        return fi.as_dict()
+
+    @property
+    def done(self):
+        i = self.info()
+        return i["streams_finished"] == i["streams_total"]
+
+    def close(self):
+        if self._h is not None:
+            load().pt_frame_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def process_job_multi(scenes, camera, options, base_seed=1234, tiles=None, progress=None, want_stats=False):

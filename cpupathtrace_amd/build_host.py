@@ -20,7 +20,7 @@ def up_to_date():
     if not os.path.exists(LIB):
         return False
     t = os.path.getmtime(LIB)
-    deps = sources() + glob.glob(os.path.join(ROOT, "include", "**", "*.h"), recursive=True) + [os.path.join(HERE, "libpathtrace_hip.so")]
+    deps = sources() + glob.glob(os.path.join(SRC, "*.h")) + glob.glob(os.path.join(ROOT, "include", "**", "*.h"), recursive=True) + [os.path.join(HERE, "libpathtrace_hip.so")]
     return all(os.path.getmtime(d) <= t for d in deps)
 
 

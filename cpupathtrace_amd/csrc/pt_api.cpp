@@ -610,6 +610,7 @@ int run_path(pt_scene *s, const PtDevCamera &cam, const PtDevOptions &opt, PtStr
             T.tiles_per_row = 0;
         }
     }
+    uint32_t *const own_left = T.tile_left; // (a resumable frame keeps its own count of pixels per tile from launch to launch)
     T.tile_left = nullptr;
     T.tiles_done = nullptr;
     T.cancel = nullptr;
@@ -619,7 +620,7 @@ int run_path(pt_scene *s, const PtDevCamera &cam, const PtDevOptions &opt, PtStr
         }
         *s->host_tiles_done = 0;
         T.tiles_done = s->host_tiles_done;
-        T.tile_left = s->tile_left.ptr; // filled by the caller (pixels per tile)
+        T.tile_left = own_left != nullptr ? own_left : s->tile_left.ptr; // filled by the caller (pixels per tile)
     }
     PT_HIP(hipMemsetAsync(s->counters.ptr, 0, sizeof(PtDevCounters), st));
     PT_HIP(hipMemsetAsync(s->pull_counter.ptr, 0, 64 * sizeof(uint32_t), st));
@@ -1559,6 +1560,33 @@ int pt_render_streams(pt_scene *s, const pt_camera_params *camera, const pt_opti
     }
 }
 
+// A regular grid of equal tiles (what pt_job_tiles makes of a frame whose sides are multiples of the tile size) lets the kernel spread a
+// wavefront's first rows over the frame's columns as well as over its bands: tiles per grid row, 64-stream chunks per tile (0, 0: no grid).
+static void tile_grid(const pt_tile *tiles, size_t n_tiles, uint32_t *tiles_per_row, uint32_t *chunks_per_tile) {
+    *tiles_per_row = 0;
+    *chunks_per_tile = 0;
+    if(n_tiles > 0 && (static_cast<uint32_t>(tiles[0].w) * static_cast<uint32_t>(tiles[0].h)) % 64U == 0) {
+        bool regular = true;
+        uint32_t per_row = 0;
+        for(size_t k = 0; k < n_tiles && regular; k++) {
+            regular = tiles[k].w == tiles[0].w && tiles[k].h == tiles[0].h;
+            if(per_row == 0 && k > 0 && tiles[k].y != tiles[0].y) {
+                per_row = static_cast<uint32_t>(k);
+            }
+        }
+        if(per_row == 0) {
+            per_row = static_cast<uint32_t>(n_tiles);
+        }
+        for(size_t k = 0; k < n_tiles && regular; k++) {
+            regular = tiles[k].x == tiles[0].x + static_cast<int32_t>(k % per_row) * tiles[0].w && tiles[k].y == tiles[0].y + static_cast<int32_t>(k / per_row) * tiles[0].h;
+        }
+        if(regular && n_tiles % per_row == 0 && per_row % 4 == 0) {
+            *tiles_per_row = per_row;
+            *chunks_per_tile = static_cast<uint32_t>(tiles[0].w) * static_cast<uint32_t>(tiles[0].h) / 64U;
+        }
+    }
+}
+
 static int render_tiles_impl(pt_scene *s, const pt_camera_params *camera, const pt_options *options, const pt_tile *tiles, size_t n_tiles, uint64_t base_seed,
                              float4 *d_image, pt_stats *stats, pt_progress_fn progress = nullptr, void *progress_user = nullptr, RenderStop *stop = nullptr) {
     PtDevOptions opt;
@@ -1609,28 +1637,7 @@ static int render_tiles_impl(pt_scene *s, const pt_camera_params *camera, const 
         T.base_seed = base_seed;
         // A regular grid of equal tiles (what pt_job_tiles makes of a frame whose sides are multiples of the tile size) lets the kernel
         // spread a wavefront's first rows over the frame's columns as well as over its bands: tiles per grid row, 64-stream chunks per tile.
-        T.tiles_per_row = 0;
-        T.chunks_per_tile = 0;
-        if(n_tiles > 0 && (static_cast<uint32_t>(tiles[0].w) * static_cast<uint32_t>(tiles[0].h)) % 64U == 0) {
-            bool regular = true;
-            uint32_t per_row = 0;
-            for(size_t k = 0; k < n_tiles && regular; k++) {
-                regular = tiles[k].w == tiles[0].w && tiles[k].h == tiles[0].h;
-                if(per_row == 0 && k > 0 && tiles[k].y != tiles[0].y) {
-                    per_row = static_cast<uint32_t>(k);
-                }
-            }
-            if(per_row == 0) {
-                per_row = static_cast<uint32_t>(n_tiles);
-            }
-            for(size_t k = 0; k < n_tiles && regular; k++) {
-                regular = tiles[k].x == tiles[0].x + static_cast<int32_t>(k % per_row) * tiles[0].w && tiles[k].y == tiles[0].y + static_cast<int32_t>(k / per_row) * tiles[0].h;
-            }
-            if(regular && n_tiles % per_row == 0 && per_row % 4 == 0) {
-                T.tiles_per_row = per_row;
-                T.chunks_per_tile = static_cast<uint32_t>(tiles[0].w) * static_cast<uint32_t>(tiles[0].h) / 64U;
-            }
-        }
+        tile_grid(tiles, n_tiles, &T.tiles_per_row, &T.chunks_per_tile);
         return run_path(s, cam, opt, T, d_image, stats, progress, progress_user, nullptr, false, stop);
     }
 }
@@ -1729,6 +1736,20 @@ int pt_render_item(pt_scene *s, const pt_camera_params *camera, const pt_options
 
 } // extern "C"
 
+// The replica that renders each tile of a multi-device call (render_tiles_multi_impl, and a frame's tiles for good: pt_frame_create).
+static std::vector<int> tile_owners(const pt_tile *tiles, size_t n_tiles, int n_scenes) {
+    size_t per_row = 0;
+    while(per_row < n_tiles && tiles[per_row].y == tiles[0].y) {
+        per_row++;
+    }
+    const bool diagonal = n_scenes > 1 && per_row > 0 && n_tiles % per_row == 0 && per_row % static_cast<size_t>(n_scenes) == 0;
+    std::vector<int> owners(n_tiles);
+    for(size_t k = 0; k < n_tiles; k++) {
+        owners[k] = static_cast<int>((diagonal ? k % per_row + k / per_row : k) % static_cast<size_t>(n_scenes));
+    }
+    return owners;
+}
+
 // pt_render_tiles_multi, and with a RenderStop pt_render_tiles_ctl: then every replica also loads the rectangles of its tiles from out_image
 // first (so that the pixels a stopped launch leaves unwritten keep their values), and reports which of its tiles finished and what became of
 // its streams (tile_done: [n_tiles] or null, tallies: [n_scenes]).
@@ -1761,13 +1782,9 @@ static int render_tiles_multi_impl(pt_scene *const *scenes, int n_scenes, const 
     // frame -- cpupathtrace_amd/sharding.py uses the same rule), one host thread per scene drives its device, every device renders into its
     // own frame in HBM and only the rectangles of ITS tiles travel to the caller's image.  Engines are per pixel, so the image does not
     // depend on n_scenes.  progress calls are serialised and counted over all devices.
-    size_t per_row = 0;
-    while(per_row < n_tiles && tiles[per_row].y == tiles[0].y) {
-        per_row++;
-    }
-    const bool diagonal = n_scenes > 1 && per_row > 0 && n_tiles % per_row == 0 && per_row % static_cast<size_t>(n_scenes) == 0;
+    const std::vector<int> owners = tile_owners(tiles, n_tiles, n_scenes);
     auto owner = [&](size_t k) -> int {
-        return static_cast<int>((diagonal ? k % per_row + k / per_row : k) % static_cast<size_t>(n_scenes));
+        return owners[k];
     };
     struct Shared {
         std::mutex progress_mutex;
@@ -1948,6 +1965,426 @@ int pt_render_tiles_device(pt_scene *s, const pt_camera_params *camera, const pt
         }
     }
     return rc;
+}
+
+} // extern "C"
+
+// ---- resumable frames (pt_frame_*) -----------------------------------------------------------------------------------------------
+// A frame is a pt_render_tiles_ctl job that keeps what a stop leaves: per replica, the status of every stream after a launch, the park
+// records of the streams a stop dropped with samples taken, the work list of the next launch (pt_frame.hip builds it from the status:
+// parked streams first, then the untouched ones) and the count of unfinished pixels per tile.  The work list and the park records come in
+// pairs that swap on every launch: a launch reads one and writes the other.
+
+struct pt_frame {
+    struct Replica {
+        pt_scene *s = nullptr;
+        std::vector<pt_tile> tiles; // its tiles, in the frame's order ...
+        std::vector<size_t> index;  // ... and where they are in the frame's list
+        uint32_t n_streams = 0;
+        uint32_t n_todo = 0, n_parked = 0; // the next launch's work list: its length, and the parked streams at its head
+        uint64_t samples_carried = 0, with_candidates = 0;
+        bool ready = false; // the device tables exist
+        bool in_order = true; // the work list is every stream of the replica in order (stream i at index i)
+        int cur = 0;        // todo[cur] and park[cur] are what the next launch reads
+        DevBuf<int4> d_tiles;
+        DevBuf<uint32_t> d_offset, d_left, d_status, d_blocks, d_park_count;
+        DevBuf<uint2> d_todo[2];
+        DevBuf<PtParkRecord> d_park[2];
+        DevBuf<unsigned long long> d_result;
+    };
+    pt_camera_params camera{};
+    pt_options options{};
+    std::vector<pt_tile> tiles;
+    uint64_t base_seed = 0;
+    std::vector<std::unique_ptr<Replica>> reps;
+    std::vector<uint8_t> tile_done;
+    uint64_t tiles_done = 0, streams_total = 0;
+    int32_t launches = 0;
+    int status = PT_OK; // a failed frame returns this (and `error`) from every later call
+    std::string error;
+    mutable std::mutex mutex; // one call at a time
+};
+
+namespace {
+
+// The device tables of a replica, made by its first launch: the tile table, the first stream of every tile and its pixel count, the
+// status of every stream (all untouched) and the first work list (every stream, none parked).
+int frame_prepare(pt_frame::Replica &r) {
+    const size_t n_tiles = r.tiles.size();
+    std::vector<int4> rects(n_tiles);
+    std::vector<uint32_t> offsets(n_tiles), left(n_tiles);
+    uint32_t at = 0;
+    for(size_t k = 0; k < n_tiles; k++) {
+        const pt_tile &t = r.tiles[k];
+        rects[k] = make_int4(t.x, t.y, t.w, t.h);
+        offsets[k] = at;
+        left[k] = static_cast<uint32_t>(t.w) * static_cast<uint32_t>(t.h);
+        at += left[k];
+    }
+    std::vector<uint2> todo(r.n_streams);
+    for(uint32_t i = 0; i < r.n_streams; i++) {
+        todo[i] = make_uint2(i, PT_NO_PARK);
+    }
+    PT_HIP(r.d_tiles.upload(rects));
+    PT_HIP(r.d_offset.upload(offsets));
+    PT_HIP(r.d_left.upload(left));
+    PT_HIP(r.d_todo[0].upload(todo));
+    PT_HIP(r.d_todo[1].ensure(r.n_streams));
+    PT_HIP(r.d_status.ensure(r.n_streams));
+    PT_HIP(hipMemset(r.d_status.ptr, 0, static_cast<size_t>(r.n_streams) * sizeof(uint32_t)));
+    PT_HIP(r.d_blocks.ensure(2 * ((static_cast<size_t>(r.n_streams) + 1023) / 1024)));
+    PT_HIP(r.d_park_count.ensure(1));
+    PT_HIP(r.d_park[0].ensure(1));
+    PT_HIP(r.d_result.ensure(8));
+    r.ready = true;
+    return PT_OK;
+}
+
+// The rectangles of the replica's unfinished tiles between the caller's image and the scene's frame in HBM
+int frame_copy_open_tiles(const pt_frame &f, const pt_frame::Replica &r, float *out_image, bool to_device) {
+    const size_t width = static_cast<size_t>(f.options.image_width);
+    pt_scene *s = r.s;
+    for(size_t k = 0; k < r.tiles.size(); k++) {
+        if(f.tile_done[r.index[k]] != 0) {
+            continue;
+        }
+        const pt_tile &t = r.tiles[k];
+        const size_t at = static_cast<size_t>(t.y) * width + static_cast<size_t>(t.x);
+        if(to_device) {
+            PT_HIP(hipMemcpy2DAsync(s->image.ptr + at, width * sizeof(F4), out_image + at * 4, width * sizeof(F4), static_cast<size_t>(t.w) * sizeof(F4),
+                                    static_cast<size_t>(t.h), hipMemcpyHostToDevice, s->stream));
+        }
+        else {
+            PT_HIP(hipMemcpy2DAsync(out_image + at * 4, width * sizeof(F4), s->image.ptr + at, width * sizeof(F4), static_cast<size_t>(t.w) * sizeof(F4),
+                                    static_cast<size_t>(t.h), hipMemcpyDeviceToHost, s->stream));
+        }
+    }
+    return PT_OK;
+}
+
+// What one replica's launch of pt_frame_render did
+struct FrameLaunch {
+    StreamTally tally;
+    uint64_t parked = 0; // streams it parked
+};
+
+// One launch of a replica: its work list, under the scene's lock, then the next work list
+int frame_launch(pt_frame &f, pt_frame::Replica &r, float *out_image, pt_stats *stats, pt_progress_fn progress, void *progress_user, RenderStop *stop,
+                 FrameLaunch *out) {
+    pt_scene *s = r.s;
+    std::lock_guard<std::mutex> lock(s->render_mutex);
+    PT_HIP(hipSetDevice(s->device));
+    PtDevOptions opt;
+    int rc = derive_options(&f.options, &opt);
+    if(rc != PT_OK) {
+        return rc;
+    }
+    const PtDevCamera cam = derive_camera(&f.camera);
+    if(!r.ready) {
+        rc = frame_prepare(r);
+        if(rc != PT_OK) {
+            return rc;
+        }
+    }
+    const size_t pixels = static_cast<size_t>(f.options.image_width) * static_cast<size_t>(f.options.image_height);
+    PT_HIP(s->image.ensure(pixels));
+    rc = frame_copy_open_tiles(f, r, out_image, true);
+    if(rc != PT_OK) {
+        return rc;
+    }
+    // park storage: one record per slot at most (a stop closes the pool, so a slot drops one stream at most), and never more than the streams left
+    PtPathConfig cfg;
+    rc = ensure_path_workspace(s, r.n_todo, &cfg);
+    if(rc != PT_OK) {
+        return rc;
+    }
+    const int cur = r.cur, next = cur ^ 1;
+    const uint32_t cap = std::min<uint32_t>(r.n_todo, s->path_slots);
+    PT_HIP(r.d_park[next].ensure(cap));
+    PT_HIP(hipMemsetAsync(r.d_park_count.ptr, 0, sizeof(uint32_t), s->stream));
+    PtStreams T{};
+    T.n = r.n_todo;
+    T.tiles = r.d_tiles.ptr;
+    T.tile_offset = r.d_offset.ptr;
+    T.n_tiles = static_cast<uint32_t>(r.tiles.size());
+    T.base_seed = f.base_seed;
+    // The first round is spread over the work list.  The first launch's list is every stream in order, so it is spread over the tile grid
+    // as pt_render_tiles spreads it (an uninterrupted frame is scheduled exactly like one); a later list is no tile grid.
+    T.tiles_per_row = 0;
+    T.chunks_per_tile = 0;
+    if(r.in_order) {
+        tile_grid(r.tiles.data(), r.tiles.size(), &T.tiles_per_row, &T.chunks_per_tile);
+    }
+    T.tile_left = r.d_left.ptr;
+    T.todo = r.d_todo[cur].ptr;
+    T.park_in = r.d_park[cur].ptr;
+    T.park_out = r.d_park[next].ptr;
+    T.park_count = r.d_park_count.ptr;
+    T.park_cap = cap;
+    T.status = r.d_status.ptr;
+    rc = run_path(s, cam, opt, T, reinterpret_cast<float4 *>(s->image.ptr), stats, progress, progress_user, nullptr, false, stop);
+    if(rc != PT_OK) {
+        return rc;
+    }
+    rc = frame_copy_open_tiles(f, r, out_image, false);
+    if(rc != PT_OK) {
+        return rc;
+    }
+    rc = finish_path(s, &out->tally);
+    if(rc != PT_OK) {
+        return rc;
+    }
+    if(pt_launch_frame_compact(s->stream, r.d_todo[cur].ptr, r.n_todo, r.d_status.ptr, r.d_park[next].ptr, r.d_todo[next].ptr, r.d_blocks.ptr, r.d_result.ptr) != 0) {
+        PT_HIP(hipGetLastError());
+        return fail(PT_ERR_HIP, "frame: work list kernel failed to launch");
+    }
+    unsigned long long res[8];
+    PT_HIP(hipMemcpyAsync(res, r.d_result.ptr, sizeof(res), hipMemcpyDeviceToHost, s->stream));
+    std::vector<uint32_t> left(r.tiles.size());
+    PT_HIP(hipMemcpyAsync(left.data(), r.d_left.ptr, left.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
+    PT_HIP(hipStreamSynchronize(s->stream));
+    // every stream of the work list is finished, parked or still to do, and the stop dropped no more than the parked and returned ones
+    const StreamTally &t = out->tally;
+    if(t.finished + res[0] + res[1] != r.n_todo || res[0] > t.abandoned || res[0] > cap) {
+        return fail(PT_ERR_HIP, "frame: " + std::to_string(t.finished) + " finished, " + std::to_string(res[0]) + " parked and " + std::to_string(res[1]) +
+                                    " left of " + std::to_string(r.n_todo) + " streams (" + std::to_string(t.abandoned) + " dropped)");
+    }
+    r.n_todo = static_cast<uint32_t>(res[0] + res[1]);
+    r.n_parked = static_cast<uint32_t>(res[0]);
+    r.in_order = r.n_todo == r.n_streams && (r.n_parked == 0 || r.n_parked == r.n_todo); // (parked first, each part in order)
+    r.samples_carried = res[3];
+    r.with_candidates = res[4];
+    r.cur = next;
+    out->parked = res[0];
+    for(size_t k = 0; k < left.size(); k++) {
+        f.tile_done[r.index[k]] = left[k] == 0 ? 1 : 0;
+    }
+    return PT_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int pt_frame_create(pt_scene *const *scenes, int n_scenes, const pt_camera_params *camera, const pt_options *options, const pt_tile *tiles, size_t n_tiles,
+                    uint64_t base_seed, pt_frame **out) {
+    if(out == nullptr) {
+        return fail(PT_ERR_INVALID, "null frame pointer");
+    }
+    *out = nullptr;
+    if(scenes == nullptr || n_scenes < 1) {
+        return fail(PT_ERR_INVALID, "no scenes");
+    }
+    for(int i = 0; i < n_scenes; i++) {
+        if(scenes[i] == nullptr) {
+            return fail(PT_ERR_INVALID, "null scene");
+        }
+    }
+    if(camera == nullptr || options == nullptr || (tiles == nullptr && n_tiles > 0)) {
+        return fail(PT_ERR_INVALID, "null argument");
+    }
+    if(options->image_width <= 0 || options->image_height <= 0) {
+        return fail(PT_ERR_INVALID, "image size must be positive");
+    }
+    uint64_t total = 0;
+    for(size_t k = 0; k < n_tiles; k++) {
+        const pt_tile &t = tiles[k];
+        if(t.w <= 0 || t.h <= 0 || t.x < 0 || t.y < 0 || t.x + t.w > options->image_width || t.y + t.h > options->image_height) {
+            return fail(PT_ERR_INVALID, "tile outside the image or empty");
+        }
+        total += static_cast<uint64_t>(t.w) * static_cast<uint64_t>(t.h);
+    }
+    if(total > 0x0fffffffULL) {
+        return fail(PT_ERR_INVALID, "too many pixels in one frame");
+    }
+    PtDevOptions opt;
+    const int rc = derive_options(options, &opt);
+    if(rc != PT_OK) {
+        return rc;
+    }
+    if(device_count_quiet() < 1) {
+        return fail(PT_ERR_NO_DEVICE, "pt_frame_create: no HIP device (a frame renders on the GPU only)");
+    }
+    std::unique_ptr<pt_frame> f(new pt_frame());
+    f->camera = *camera;
+    f->options = *options;
+    f->tiles.assign(tiles, tiles + n_tiles);
+    f->base_seed = base_seed;
+    f->tile_done.assign(n_tiles, 0);
+    f->streams_total = total;
+    for(int i = 0; i < n_scenes; i++) {
+        f->reps.emplace_back(new pt_frame::Replica());
+        f->reps.back()->s = scenes[i];
+    }
+    const std::vector<int> owners = n_tiles > 0 ? tile_owners(tiles, n_tiles, n_scenes) : std::vector<int>();
+    for(size_t k = 0; k < n_tiles; k++) {
+        pt_frame::Replica &r = *f->reps[static_cast<size_t>(owners[k])];
+        r.tiles.push_back(tiles[k]);
+        r.index.push_back(k);
+        r.n_streams += static_cast<uint32_t>(tiles[k].w) * static_cast<uint32_t>(tiles[k].h);
+    }
+    for(auto &r : f->reps) {
+        r->n_todo = r->n_streams;
+    }
+    *out = f.release();
+    return PT_OK;
+}
+
+int pt_frame_render(pt_frame *f, float *out_image, pt_stats *stats, pt_progress_fn progress, void *progress_user, pt_render_control *ctl) {
+    const RenderStop::Clock::time_point start = RenderStop::Clock::now();
+    if(f == nullptr) {
+        return fail(PT_ERR_INVALID, "null frame");
+    }
+    std::lock_guard<std::mutex> frame_lock(f->mutex);
+    if(f->status != PT_OK) {
+        return fail(f->status, f->error);
+    }
+    const int n_scenes = static_cast<int>(f->reps.size());
+    if(stats != nullptr) {
+        std::memset(stats, 0, sizeof(*stats) * static_cast<size_t>(n_scenes));
+    }
+    if(ctl != nullptr) {
+        ctl->streams_finished = ctl->streams_abandoned = ctl->streams_unclaimed = 0;
+        ctl->drain_ms = 0.0;
+    }
+    auto report_tiles = [&]() {
+        if(ctl != nullptr && ctl->tile_done != nullptr && !f->tile_done.empty()) {
+            std::memcpy(ctl->tile_done, f->tile_done.data(), f->tile_done.size());
+        }
+    };
+    bool complete = true;
+    for(const auto &r : f->reps) {
+        complete = complete && r->n_todo == 0;
+    }
+    if(complete) {
+        report_tiles();
+        return PT_OK;
+    }
+    if(out_image == nullptr) {
+        return fail(PT_ERR_INVALID, "null image");
+    }
+    pt_render_control none{};
+    RenderStop stop;
+    stop.ctl = ctl != nullptr ? ctl : &none;
+    if(ctl != nullptr && ctl->budget_ms > 0.0) {
+        stop.has_deadline = true;
+        stop.deadline = start + std::chrono::duration_cast<RenderStop::Clock::duration>(std::chrono::duration<double, std::milli>(ctl->budget_ms));
+    }
+    stop.poll();
+    // progress over the whole frame, serialised over the replicas (as pt_render_tiles_multi)
+    struct Shared {
+        std::mutex mutex;
+        int completed = 0, total = 0;
+        pt_progress_fn fn = nullptr;
+        void *user = nullptr;
+    } shared;
+    shared.completed = static_cast<int>(f->tiles_done);
+    shared.total = static_cast<int>(f->tiles.size());
+    shared.fn = progress;
+    shared.user = progress_user;
+    auto trampoline = [](int, int, void *p) {
+        Shared *sh = static_cast<Shared *>(p);
+        std::lock_guard<std::mutex> lock(sh->mutex);
+        sh->completed++;
+        sh->fn(sh->completed, sh->total, sh->user);
+    };
+    std::vector<int> rcs(static_cast<size_t>(n_scenes), PT_OK);
+    std::vector<std::string> errors(static_cast<size_t>(n_scenes));
+    std::vector<FrameLaunch> launched(static_cast<size_t>(n_scenes));
+    std::vector<char> ran(static_cast<size_t>(n_scenes), 0);
+    auto work = [&](int i) {
+        pt_frame::Replica &r = *f->reps[static_cast<size_t>(i)];
+        if(r.n_todo == 0) {
+            return;
+        }
+        ran[static_cast<size_t>(i)] = 1;
+        rcs[static_cast<size_t>(i)] = frame_launch(*f, r, out_image, stats != nullptr ? stats + i : nullptr, progress != nullptr ? static_cast<pt_progress_fn>(trampoline) : nullptr,
+                                                   &shared, &stop, &launched[static_cast<size_t>(i)]);
+        if(rcs[static_cast<size_t>(i)] != PT_OK) {
+            errors[static_cast<size_t>(i)] = g_last_error;
+        }
+    };
+    std::vector<std::thread> threads;
+    for(int i = 1; i < n_scenes; i++) {
+        threads.emplace_back(work, i);
+    }
+    work(0);
+    for(std::thread &t : threads) {
+        t.join();
+    }
+    for(int i = 0; i < n_scenes; i++) {
+        f->launches += ran[static_cast<size_t>(i)];
+    }
+    for(int i = 0; i < n_scenes; i++) {
+        if(rcs[static_cast<size_t>(i)] != PT_OK) {
+            f->status = rcs[static_cast<size_t>(i)];
+            f->error = "frame failed: scene " + std::to_string(i) + ": " + errors[static_cast<size_t>(i)];
+            return fail(f->status, f->error);
+        }
+    }
+    f->tiles_done = static_cast<uint64_t>(std::count(f->tile_done.begin(), f->tile_done.end(), 1));
+    report_tiles();
+    uint64_t left = 0, parked = 0;
+    for(int i = 0; i < n_scenes; i++) {
+        const FrameLaunch &l = launched[static_cast<size_t>(i)];
+        left += f->reps[static_cast<size_t>(i)]->n_todo;
+        parked += l.parked;
+        if(ctl != nullptr) {
+            ctl->streams_finished += l.tally.finished;
+            ctl->streams_abandoned += l.parked;
+            ctl->streams_unclaimed += l.tally.unclaimed + (l.tally.abandoned - l.parked); // (dropped before their first sample: they start afresh)
+        }
+    }
+    if(ctl != nullptr) {
+        ctl->drain_ms = stop.drain_ms;
+    }
+    if(left != 0) {
+        return fail(PT_ERR_CANCELLED, "frame stopped (" + std::string(__atomic_load_n(&stop.ctl->cancel, __ATOMIC_ACQUIRE) != 0 ? "cancelled" : "budget spent") + "): " +
+                                          std::to_string(parked) + " streams parked, " + std::to_string(left) + " streams left");
+    }
+    return PT_OK;
+}
+
+int pt_frame_get_info(const pt_frame *f, pt_frame_info *info) {
+    if(f == nullptr || info == nullptr) {
+        return fail(PT_ERR_INVALID, "null argument");
+    }
+    std::lock_guard<std::mutex> lock(f->mutex);
+    std::memset(info, 0, sizeof(*info));
+    info->streams_total = f->streams_total;
+    info->tiles_total = f->tiles.size();
+    info->tiles_done = f->tiles_done;
+    for(const auto &r : f->reps) {
+        info->streams_parked += r->n_parked;
+        info->streams_untouched += r->n_todo - r->n_parked;
+        info->samples_carried += r->samples_carried;
+        info->parked_with_candidates += r->with_candidates;
+        info->park_bytes += (r->d_park[0].count + r->d_park[1].count) * sizeof(PtParkRecord);
+    }
+    info->streams_finished = f->streams_total - info->streams_parked - info->streams_untouched;
+    info->launches = f->launches;
+    info->status = f->status;
+    return PT_OK;
+}
+
+int pt_frame_destroy(pt_frame *f) {
+    if(f == nullptr) {
+        return fail(PT_ERR_INVALID, "null frame");
+    }
+    {
+        std::lock_guard<std::mutex> frame_lock(f->mutex);
+        for(auto &r : f->reps) {
+            // (the buffers go on the scene's device, and not while the scene's stream may still use them)
+            std::lock_guard<std::mutex> lock(r->s->render_mutex);
+            if(r->ready || r->d_park[0].ptr != nullptr || r->d_park[1].ptr != nullptr) {
+                (void)hipSetDevice(r->s->device);
+                (void)hipStreamSynchronize(r->s->stream);
+            }
+            r.reset();
+        }
+    }
+    delete f;
+    return PT_OK;
 }
 
 } // extern "C"

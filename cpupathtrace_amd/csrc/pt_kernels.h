@@ -76,6 +76,14 @@ struct PtStreams {
     const uint32_t *place;       // [n_waves * slots per wave] or null: the stream that starts in every slot (0xffffffff: none) instead of the arithmetic first round
     const uint32_t *cancel;      // HOST-written stop request (pinned, fine-grained), or null: never stop.  Read once per shading pass; once it
                                  // is non-zero the wavefront takes no more streams and drops every stream that would start another sample
+    // A resumable frame (pt_frame_render; all null otherwise).  With `todo`, stream i of the launch is stream todo[i].x of the frame (the
+    // index into the tile table), and todo[i].y names its park record in park_in, or PT_NO_PARK: it starts afresh from its seed.
+    const uint2 *todo;           // [n] or null
+    const PtParkRecord *park_in; // the records todo names
+    PtParkRecord *park_out;      // [park_cap]: a stream dropped by a stop request with samples taken parks here (one record per slot at most)
+    uint32_t *park_count;        // records written to park_out
+    uint32_t park_cap;
+    uint32_t *status;            // [streams of the frame] or null: PT_STREAM_* of every stream this launch finished or parked
 };
 
 // Ray queues, one private ring per wavefront: entries [wave * cap, (wave + 1) * cap)
@@ -132,6 +140,12 @@ struct PtPathArgs {
 // fills *host_args (which must stay valid until the launch has been issued), copies it to d_args on `stream` and launches
 void pt_launch_path(hipStream_t stream, const PtDevScene &scene, const PtDevCamera &camera, const PtDevOptions &options, PtSlots slots, PtStreams streams,
                     PtLocalQueue queue, const PtPathConfig &cfg, float4 *image, PtDevCounters *counters, PtPathArgs *host_args, PtPathArgs *d_args);
+// the work list of a resumable frame's next launch (pt_frame.hip): the streams of `todo` that `status` does not call finished, parked ones
+// first, each part in the order of `todo` (block_counts: [2 * ceil(n / 1024)]).  result[0..4] = parked streams, untouched ones, untouched ones
+// whose earlier record went unused (0 by construction: such a stream would start afresh), samples the parked streams carry, parked streams
+// with closed candidates.  Returns 0, or 1 when a launch failed.
+int pt_launch_frame_compact(hipStream_t stream, const uint2 *todo, uint32_t n, uint32_t *status, const PtParkRecord *parked, uint2 *todo_out, uint32_t *block_counts,
+                            unsigned long long *result);
 int pt_path_blocks_per_cu(const PtPathConfig &cfg); // resident workgroups per CU of the instantiation cfg selects (wide, in_lds, stack_lds) with cfg.lds_bytes
 size_t pt_path_lds_bytes(int wide, int rows, int stack_lds, uint32_t n_lds_pairs, uint32_t n_lds_leaf_records); // leaf records: triangles + 1 spare + spheres, 0 = scene not in LDS
 int pt_path_stack_lds(int in_lds, size_t lds_bytes_with_default_window); // entries of the stack window: 8, or 4 for a scene in LDS that would not leave room for four workgroups per CU

@@ -488,6 +488,46 @@ struct ShadeTables {
     bool emis_in_lds, materials_in_lds;
 };
 
+// dst[0 .. n) = src[0 .. n), one word at a time (a record is never held in registers whole)
+PT_D void copy_words(void *dst, const void *src, uint32_t n) {
+    uint32_t *d = static_cast<uint32_t *>(dst);
+    const uint32_t *s = static_cast<const uint32_t *>(src);
+#pragma unroll 1
+    for(uint32_t i = 0; i < n; i++) {
+        d[i] = s[i];
+    }
+}
+
+// words of the candidates an estimator has closed (n_candidates counts on beyond the PT_MAX_CANDIDATES it keeps)
+PT_D uint32_t closed_candidate_words(int32_t n_candidates) {
+    return (uint32_t)(n_candidates < PT_MAX_CANDIDATES ? n_candidates : PT_MAX_CANDIDATES) * (uint32_t)(sizeof(PtCandidate) / 4);
+}
+
+// A resumable frame's stream leaves its slot (PtStreams::status): finished; or dropped by a stop request at a sample boundary, where a
+// stream that has taken samples parks its engine, pixel, estimator and closed candidates in a record of park_out for a later launch.  A
+// stream dropped before its first sample is untouched: it starts afresh from its seed next time, which gives the same bits.
+PT_D void park_stream(const PtStreams &T, const PtSlots &S, uint32_t p, uint32_t stream, uint64_t rng, int32_t cursor, bool have_pixel) {
+    uint32_t status = PT_STREAM_FINISHED;
+    if(have_pixel) {
+        status = PT_STREAM_UNTOUCHED;
+        const PtEstimator *e = S.est + p;
+        if(e->pixel_sample > 0 || cursor > 0) {
+            const uint32_t k = atomicAdd(T.park_count, 1u);
+            if(k < T.park_cap) { // (always: a launch parks at most one stream per slot, and the host sizes park_out for that)
+                PtParkRecord *rec = T.park_out + k;
+                rec->stream = stream;
+                rec->cursor = cursor;
+                rec->rng[0] = (uint32_t)rng;
+                rec->rng[1] = (uint32_t)(rng >> 32);
+                copy_words(&rec->est, e, (uint32_t)(sizeof(PtEstimator) / 4));
+                copy_words(rec->cand, S.cand + (size_t)p * PT_MAX_CANDIDATES, closed_candidate_words(e->n_candidates));
+                status = PT_STREAM_PARKED + k;
+            }
+        }
+    }
+    T.status[stream] = status;
+}
+
 // Plane k of slot p (PtSlots): the scalar base plus a 32-bit byte offset, which becomes the saddr + voffset form of the load or store --
 // no 64-bit address per plane lives in vector registers.
 template<typename V>
@@ -585,19 +625,37 @@ PT_D void shade_row(const PtDevScene &sc, const PtDevCamera &cam, const PtDevOpt
                 int4 rc;
                 uint64_t r;
                 uint32_t tile = 0;
+                uint32_t park = PT_NO_PARK;
+                int32_t cursor0 = 0;
                 if(T.rect != nullptr) {
                     rc = T.rect[mine];
                     r = T.rng[mine];
                 }
                 else {
+                    if(T.todo != nullptr) {
+                        // a resumable frame: the launch's stream `mine` is the frame's stream todo[mine], parked or fresh
+                        const uint2 entry = T.todo[mine];
+                        mine = entry.x;
+                        park = entry.y;
+                    }
                     tile_stream(T, mine, rc, r, tile);
                 }
+                flags = PT_F_STREAM;
+                if(park != PT_NO_PARK) {
+                    // a parked stream goes on at the sample boundary where it was dropped: engine, pixel, estimator and closed
+                    // candidates come from its record, and the start of the next sample does not reset the estimator (PT_F_PIXEL)
+                    const PtParkRecord *rec = T.park_in + park;
+                    r = (uint64_t)rec->rng[0] | ((uint64_t)rec->rng[1] << 32);
+                    cursor0 = rec->cursor;
+                    copy_words(S.est + p, &rec->est, (uint32_t)(sizeof(PtEstimator) / 4));
+                    copy_words(S.cand + (size_t)p * PT_MAX_CANDIDATES, rec->cand, closed_candidate_words(rec->est.n_candidates));
+                    flags = PT_F_STREAM | PT_F_PIXEL | (estimator_safe_to_overlap(S.est[p], opt) ? PT_F_SAFE : 0u);
+                }
                 *slot_plane<int4>(S, PT_PLANE_RECT, p) = rc;
-                *slot_plane<uint4>(S, PT_PLANE_ENGINE, p) = make_uint4((uint32_t)r, (uint32_t)(r >> 32), 0u, mine);
+                *slot_plane<uint4>(S, PT_PLANE_ENGINE, p) = make_uint4((uint32_t)r, (uint32_t)(r >> 32), (uint32_t)cursor0, mine);
                 if(T.cost != nullptr) {
                     __hip_atomic_store(&S.cost[p], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 }
-                flags = PT_F_STREAM;
             }
             else if(want) {
                 flags = PT_F_DONE;
@@ -780,6 +838,9 @@ PT_D void shade_row(const PtDevScene &sc, const PtDevCamera &cam, const PtDevOpt
             // its slot is freed in the same way -- since the pool is closed, it dies in its next pass.
             stream_finished = !have_pixel;
             stream_abandoned = have_pixel;
+            if(T.status != nullptr) {
+                park_stream(T, S, p, stream, rng, cursor, have_pixel);
+            }
             flags = 0;
         }
         else {

@@ -122,6 +122,23 @@ struct PtCandidate {
     int32_t pad[3];
 };
 
+// What a stream of a resumable frame (pt_frame_render) leaves behind when a stop drops it between two samples: enough to go on with the
+// same pixel in a later launch as if nothing had happened (528 bytes).
+struct PtParkRecord {
+    uint32_t stream;     /* stream of the frame */
+    int32_t cursor;      /* index of the current pixel inside the stream's rectangle */
+    uint32_t rng[2];     /* the engine's xorshift state at the sample boundary (x, y) */
+    PtEstimator est;
+    PtCandidate cand[PT_MAX_CANDIDATES]; /* the first est.n_candidates are written */
+};
+
+// Status of a stream of a resumable frame after a launch (PtStreams::status): untouched (never taken, or taken and dropped before its
+// first sample), finished, or parked in park record (value - PT_STREAM_PARKED) of the launch's PtStreams::park_out.
+#define PT_STREAM_UNTOUCHED 0u
+#define PT_STREAM_FINISHED 1u
+#define PT_STREAM_PARKED 2u
+#define PT_NO_PARK 0xffffffffu
+
 // What a launch of the path kernel reports besides the per-wave work counters: streams that rendered their whole rectangle
 // (the host checks it against the number of streams when statistics are read back).
 struct PtDevCounters {

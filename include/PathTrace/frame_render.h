@@ -1,0 +1,45 @@
+// PathTrace/frame_render.h -- a processJob that can be stopped and continued (an extension of PathTrace/render_control.h).
+#ifndef PATHTRACE_FRAME_RENDER_H
+#define PATHTRACE_FRAME_RENDER_H
+
+#include <PathTrace/image/image.h>
+#include <PathTrace/render_control.h>
+#include <PathTrace/worker.h>
+
+#include "../pt_hip.h"
+
+#include <cstdint>
+#include <functional>
+#include <vector>
+
+// One frame of a FrameRenderJob, rendered in as many calls as the caller likes: every render() continues where the last one stopped
+// (its RenderControl's budget ran out or it was cancelled).  The pixels a stop catches half-way park their state on the device and resume
+// from it, so no sample is drawn twice, and the finished frame is bit for bit what processJob gives with the same seed
+// ($PATHTRACE_SEED, or a random one) on the replicas $PATHTRACE_DEVICES selects.  The job's scene must outlive the FrameRender.
+class FrameRender {
+public:
+    explicit FrameRender(const FrameRenderJob &job, int worker_count = 0);
+    ~FrameRender();
+    FrameRender(const FrameRender &) = delete;
+    FrameRender &operator=(const FrameRender &) = delete;
+
+    // Continues the frame under `control` (use a fresh control per call: a cancelled control stays cancelled) and returns whether the
+    // frame is complete.  control reports the tiles of the whole frame that have finished, and what this call did with its streams
+    // (streamsAbandoned: parked for the next call).  Throws std::runtime_error if the device fails; the frame is unusable then.
+    bool render(RenderControl &control, const std::function<void(int, int)> &progress_callback = [](int, int) {});
+    // the frame so far: finished pixels are final, the others transparent black (0, 0, 0, 0)
+    const Image<> &image() const noexcept { return image_; }
+    bool complete() const noexcept { return complete_; }
+    // where the frame stands (pt_frame_info: streams finished / parked / untouched, tiles, samples the parked streams carry)
+    pt_frame_info info() const;
+    std::uint64_t seed() const noexcept { return seed_; }
+
+private:
+    Image<> image_;
+    std::vector<pt_tile> tiles_;
+    pt_frame *frame_ = nullptr;
+    std::uint64_t seed_ = 0;
+    bool complete_ = false;
+};
+
+#endif

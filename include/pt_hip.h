@@ -225,6 +225,45 @@ int pt_render_tiles_ctl(pt_scene *const *scenes, int n_scenes, const pt_camera_p
  * progress callback or any other thread.  PT_ERR_INVALID for NULL. */
 int pt_render_cancel(pt_render_control *ctl);
 
+/* A resumable frame: a controlled render that can be continued.  pt_frame_create fixes a job (scenes, camera, options, tiles, seed) and
+ * launches nothing; every pt_frame_render continues it -- one launch per replica that still has work -- until the frame is complete.  A
+ * stop (budget or pt_render_cancel) drops every stream at its next sample boundary as in pt_render_tiles_ctl, but a stream that has taken
+ * samples PARKS there: its engine state, pixel, estimator and closed candidates go to the frame's park storage in HBM, and the next call
+ * resumes it from them.  Pixels are seeded per pixel from (base_seed, x, y), so the finished frame is bit-identical to one uninterrupted
+ * pt_render_tiles_multi / pt_render_tiles_ctl call with the same arguments, however it was sliced.
+ *   - pt_frame_create copies camera, options and tiles, and deals the tiles to the replicas as pt_render_tiles_multi does, for good.
+ *   - pt_frame_render: PT_OK = the frame is complete (a complete frame returns PT_OK at once, without a launch); PT_ERR_CANCELLED =
+ *     stopped again.  Pass the same out_image every time: a pixel is written by the call that finishes it and never again; the others keep
+ *     the caller's values.  ctl (may be NULL: run the rest of the frame to completion) is used as by pt_render_tiles_ctl, except that
+ *     tile_done ([n_tiles] of the frame) reports the whole frame's tiles, streams_abandoned counts the streams this call parked, and
+ *     streams_unclaimed the streams it left to start afresh (never taken, or dropped before their first sample).  progress reports
+ *     (completed, total) over the whole frame, strictly increasing from call to call.  stats: n_scenes entries, zero for replicas that did not launch.
+ *   - Scenes must outlive their frames.  Several frames may share a scene and their calls may be interleaved with each other and with
+ *     any other render on the scene, in any order: each frame owns its park storage, and the scene's calls are serialised as always.
+ *   - A failure (any code but PT_OK and PT_ERR_CANCELLED) leaves the frame failed: every later call returns the same code.
+ *   - Park storage: two buffers per replica of min(streams left, slots of the launch) records of 528 bytes.
+ * pt_render_tiles_ctl and every other entry point are unchanged: they never park. */
+typedef struct pt_frame pt_frame;
+typedef struct pt_frame_info {
+    uint64_t streams_total;          /* pixels of the frame's tiles */
+    uint64_t streams_finished;
+    uint64_t streams_parked;         /* dropped with samples taken: resumed from their park record by the next call */
+    uint64_t streams_untouched;      /* to start afresh from their seed */
+    uint64_t tiles_total;
+    uint64_t tiles_done;
+    uint64_t samples_carried;        /* samples the parked streams have taken of their current pixel */
+    uint64_t parked_with_candidates; /* parked streams whose estimator holds closed candidates */
+    uint64_t park_bytes;             /* device memory of the park storage, all replicas */
+    int32_t launches;                /* launches made so far, all replicas */
+    int32_t status;                  /* PT_OK, or the code that failed the frame */
+} pt_frame_info;
+int pt_frame_create(pt_scene *const *scenes, int n_scenes, const pt_camera_params *camera, const pt_options *options, const pt_tile *tiles,
+                    size_t n_tiles, uint64_t base_seed, pt_frame **out);
+int pt_frame_render(pt_frame *frame, float *out_image, pt_stats *stats, pt_progress_fn progress, void *user, pt_render_control *ctl);
+/* (the info of a frame: `pt_frame_info` names the struct, so the function is pt_frame_get_info) */
+int pt_frame_get_info(const pt_frame *frame, pt_frame_info *info);
+int pt_frame_destroy(pt_frame *frame);
+
 /* The tile list processJob builds (worker.cpp:398-414): tile_size = clamp(min(w, h) / 4, 1, 32), row-major, edge tiles clipped.
  * Returns the tile count; fills at most `capacity` entries. */
 size_t pt_job_tiles(int32_t image_width, int32_t image_height, pt_tile *out, size_t capacity);

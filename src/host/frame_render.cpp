@@ -1,0 +1,69 @@
+// src/host/frame_render.cpp -- FrameRender of PathTrace/frame_render.h on top of the resumable frames of the C ABI (pt_frame_*).
+#include <PathTrace/frame_render.h>
+
+#include "../../include/pt_hip.h"
+#include "job_params.h"
+
+#include <algorithm>
+#include <exception>
+#include <stdexcept>
+#include <vector>
+
+using namespace pathtrace_host;
+
+FrameRender::FrameRender(const FrameRenderJob &job, int worker_count) :
+  image_(std::max(job.options.image_width, 0), std::max(job.options.image_height, 0)) {
+    seed_ = jobSeed();
+    if(image_.getWidth() == 0 || image_.getHeight() == 0) {
+        complete_ = true;
+        return;
+    }
+    const pt_camera_params camera = cameraParams(job.camera);
+    const pt_options options = renderOptions(job.options);
+    tiles_ = jobTiles(static_cast<int>(image_.getWidth()), static_cast<int>(image_.getHeight()));
+    const std::vector<pt_scene *> &replicas = job.scene.deviceScenes();
+    check(pt_frame_create(replicas.data(), replicaCount(replicas, worker_count), &camera, &options, tiles_.data(), tiles_.size(), seed_, &frame_), "FrameRender");
+}
+
+FrameRender::~FrameRender() {
+    if(frame_ != nullptr) {
+        pt_frame_destroy(frame_);
+    }
+}
+
+bool FrameRender::render(RenderControl &control, const std::function<void(int, int)> &progress_callback) {
+    control.cancelled_ = false;
+    control.finished_.clear();
+    control.tile_count_ = tiles_.size();
+    if(frame_ == nullptr) {
+        return complete_;
+    }
+    static_assert(sizeof(Color<float>) == 4 * sizeof(float), "Image<Color<float>> is a packed RGBA float array");
+    ForwardProgress forward{&progress_callback, nullptr};
+    std::vector<uint8_t> done(tiles_.size(), 0);
+    control.ctl_.tile_done = done.data();
+    const int status = pt_frame_render(frame_, reinterpret_cast<float *>(image_.data()), nullptr, &ForwardProgress::call, &forward, &control.ctl_);
+    control.ctl_.tile_done = nullptr;
+    if(forward.failure) {
+        std::rethrow_exception(forward.failure);
+    }
+    if(status != PT_ERR_CANCELLED) {
+        check(status, "FrameRender::render");
+    }
+    control.cancelled_ = status == PT_ERR_CANCELLED;
+    for(size_t i = 0; i < tiles_.size(); i++) {
+        if(done[i] != 0) {
+            control.finished_.push_back(RenderControl::Tile{tiles_[i].x, tiles_[i].y, tiles_[i].w, tiles_[i].h});
+        }
+    }
+    complete_ = status == PT_OK;
+    return complete_;
+}
+
+pt_frame_info FrameRender::info() const {
+    pt_frame_info i{};
+    if(frame_ != nullptr) {
+        check(pt_frame_get_info(frame_, &i), "FrameRender::info");
+    }
+    return i;
+}
