@@ -5,6 +5,7 @@
 ``process_job``      processJob(FrameRenderJob)                    (include/PathTrace/worker.h:83-84)
 ``process_job_controlled``  processJob that can be cancelled or given a time budget (include/PathTrace/render_control.h)
 ``Frame``            a controlled processJob that can be continued: each call resumes where the last one stopped (include/PathTrace/frame_render.h)
+``process_views``    processJob for many cameras of one scene in one launch (include/PathTrace/view_batch.h)
 
 The library is the only implementation behind these calls: if it is missing or no HIP device is usable they raise.
 """
@@ -27,6 +28,8 @@ EXPORTS = ["pt_device_count", "pt_last_error", "pt_scene_create", "pt_scene_dest
            "pt_render_streams", "pt_render_item", "pt_render_tiles", "pt_render_tiles_progress", "pt_render_tiles_multi", "pt_render_tiles_device", "pt_render_tiles_ctl", "pt_render_cancel", "pt_job_tiles", "pt_pixel_seed", "pt_rng_seed_to_state", "pt_post_process", "pt_post_process_device"]
 FRAME_EXPORTS = ["pt_frame_create", "pt_frame_render", "pt_frame_get_info", "pt_frame_destroy"]
 EXPORTS += FRAME_EXPORTS
+VIEW_EXPORTS = ["pt_render_views", "pt_render_views_device"]
+EXPORTS += VIEW_EXPORTS
 
 
 
@@ -289,6 +292,21 @@ class Scene:
         bit; every other pixel keeps its value in `image` (default: zeros), and tile_done[i] says whether tiles[i] finished."""
         return _render_controlled([self], camera, options, base_seed, tiles, budget_ms, progress, control, image)
 
+    def process_views(self, cameras, options, base_seeds=1234, want_stats=False, progress=None):
+        """processJob for V cameras of this scene in one launch: a (V, H, W, 4) float32 array whose view v equals
+        process_job(cameras[v], options, base_seed=base_seeds[v]) bit for bit.  base_seeds: one int for every view, or V ints.
+        progress(completed, total) counts the tiles of all views."""
+        out = process_views_multi([self], cameras, options, base_seeds=base_seeds, progress=progress, want_stats=want_stats)
+        return (out[0], out[1][0]) if want_stats else out
+
+    def process_views_device(self, cameras, options, d_images_ptr, stream_ptr, base_seeds=1234, want_stats=False):
+        """process_views writing into device memory (d_images_ptr: device address of V*H*W*4 floats, e.g. a [V, H, W, 4] tensor)."""
+        cams, seeds = _view_tables(cameras, base_seeds)
+        op, st = _options(options), Stats()
+        _check(load().pt_render_views_device(self._h, cams, seeds.ctypes.data_as(C.POINTER(C.c_uint64)), C.c_int32(len(seeds)), C.byref(op),
+                                             C.c_void_p(d_images_ptr), C.c_void_p(stream_ptr), C.byref(st) if want_stats else None))
+        return st.as_dict() if want_stats else None
+
     def process_job_device(self, camera, options, d_image_ptr, stream_ptr, base_seed=1234, tiles=None, want_stats=False):
         """processJob writing into device memory (d_image_ptr: device address of width*height*4 floats)."""
         if tiles is None:
@@ -409,6 +427,49 @@ def process_job_multi(scenes, camera, options, base_seed=1234, tiles=None, progr
     cp, op = _camera(camera), _options(options)
     _check(load().pt_render_tiles_multi(handles, C.c_int(len(scenes)), C.byref(cp), C.byref(op), _ptr(tiles), C.c_size_t(len(tiles)), C.c_uint64(base_seed),
                                         _ptr(image), stats if want_stats else None, cb, None))
+    return (image, [s.as_dict() for s in stats]) if want_stats else image
+
+
+_CAMERA_KEYS = ("origin", "look_at", "up", "focal_length", "height", "aspect_ratio")
+
+
+def _view_tables(cameras, base_seeds):
+    """The camera and seed tables of a view batch, checked before the library is touched: cameras must be a non-empty list of camera
+    dicts (scenes.camera), base_seeds one int or one int per camera, each in [0, 2**64)."""
+    if isinstance(cameras, dict) or not isinstance(cameras, (list, tuple)) or len(cameras) == 0:
+        raise ValueError("cameras must be a non-empty list of camera dicts")
+    for i, cam in enumerate(cameras):
+        if not isinstance(cam, dict) or any(k not in cam for k in _CAMERA_KEYS):
+            raise ValueError("camera %d is not a camera dict (it needs %s)" % (i, ", ".join(_CAMERA_KEYS)))
+        for k in ("origin", "look_at", "up"):
+            if len(cam[k]) != 3:
+                raise ValueError("camera %d: %s must have 3 components" % (i, k))
+    if isinstance(base_seeds, (int, np.integer)) and not isinstance(base_seeds, bool):
+        base_seeds = [int(base_seeds)] * len(cameras)
+    if isinstance(base_seeds, (str, bytes, dict)) or not hasattr(base_seeds, "__len__") or len(base_seeds) != len(cameras):
+        raise ValueError("base_seeds must be an int or one int per camera (%d)" % len(cameras))
+    seeds = []
+    for s in base_seeds:
+        if isinstance(s, bool) or not isinstance(s, (int, np.integer)) or not 0 <= int(s) < 2 ** 64:
+            raise ValueError("base seed %r is not an int in [0, 2**64)" % (s,))
+        seeds.append(int(s))
+    cams = (CameraParams * len(cameras))(*[_camera(c) for c in cameras])
+    return cams, np.array(seeds, dtype=np.uint64)
+
+
+def process_views_multi(scenes, cameras, options, base_seeds=1234, progress=None, want_stats=False):
+    """Scene.process_views over several Scene replicas (one per device): the views' tiles are dealt as process_job_multi deals a frame's."""
+    cams, seeds = _view_tables(cameras, base_seeds)
+    scenes = list(scenes)
+    if len(scenes) == 0:
+        raise ValueError("no scenes")
+    image = np.zeros((len(seeds), options["image_height"], options["image_width"], 4), np.float32)
+    handles = (C.c_void_p * len(scenes))(*[s._h for s in scenes])
+    stats = (Stats * len(scenes))()
+    cb = PROGRESS_FN(lambda done, total, user: progress(done, total)) if progress is not None else None
+    op = _options(options)
+    _check(load().pt_render_views(handles, C.c_int(len(scenes)), cams, seeds.ctypes.data_as(C.POINTER(C.c_uint64)), C.c_int32(len(seeds)), C.byref(op),
+                                  _ptr(image), stats if want_stats else None, cb, None))
     return (image, [s.as_dict() for s in stats]) if want_stats else image
 
 

@@ -191,6 +191,9 @@ struct pt_scene {
     uint32_t *dev_cancel = nullptr;  // ... and its address on the device
     // cost-aware placement (render_tiles_impl): what every stream of the pilot launch cost, and the stream every slot of the main launch starts with
     DevBuf<uint32_t> sl_cost, stream_cost, place;
+    // a view batch (pt_render_views): the cameras and seeds of its views
+    DevBuf<PtViewCamera> view_cams;
+    DevBuf<uint64_t> view_seeds;
     bool debug_collect_costs = false;                // pt_debug_collect_costs: every launch records them
     std::vector<uint32_t> debug_place;               // pt_debug_set_place: the next launch starts from this table ...
     uint32_t debug_place_waves = 0, debug_place_slots = 0; // ... with this many wavefronts and slots in each
@@ -1587,18 +1590,28 @@ static void tile_grid(const pt_tile *tiles, size_t n_tiles, uint32_t *tiles_per_
     }
 }
 
+// A view batch (pt_render_views): n > 1 views of one scene whose frames are stacked into one image of n * image_height rows; view v has the
+// camera cams[v] and the seed seeds[v].  The tiles of such a call lie in the stacked image.
+struct ViewSet {
+    std::vector<PtViewCamera> cams;
+    std::vector<uint64_t> seeds;
+    int32_t rows(const pt_options *options) const { return static_cast<int32_t>(cams.size()) * options->image_height; }
+};
+
 static int render_tiles_impl(pt_scene *s, const pt_camera_params *camera, const pt_options *options, const pt_tile *tiles, size_t n_tiles, uint64_t base_seed,
-                             float4 *d_image, pt_stats *stats, pt_progress_fn progress = nullptr, void *progress_user = nullptr, RenderStop *stop = nullptr) {
+                             float4 *d_image, pt_stats *stats, pt_progress_fn progress = nullptr, void *progress_user = nullptr, RenderStop *stop = nullptr,
+                             const ViewSet *views = nullptr) {
     PtDevOptions opt;
     int rc = derive_options(options, &opt);
     if(rc != PT_OK) {
         return rc;
     }
     const PtDevCamera cam = derive_camera(camera);
+    const int32_t rows = views != nullptr ? views->rows(options) : options->image_height;
     uint64_t total = 0;
     for(size_t i = 0; i < n_tiles; i++) {
         const pt_tile &t = tiles[i];
-        if(t.w <= 0 || t.h <= 0 || t.x < 0 || t.y < 0 || t.x + t.w > options->image_width || t.y + t.h > options->image_height) {
+        if(t.w <= 0 || t.h <= 0 || t.x < 0 || t.y < 0 || t.x + t.w > options->image_width || t.y + t.h > rows) {
             return fail(PT_ERR_INVALID, "tile outside the image or empty");
         }
         total += static_cast<uint64_t>(t.w) * static_cast<uint64_t>(t.h);
@@ -1628,6 +1641,12 @@ static int render_tiles_impl(pt_scene *s, const pt_camera_params *camera, const 
             PT_HIP(s->tile_left.ensure(n_tiles));
             PT_HIP(hipMemcpyAsync(s->tile_left.ptr, left.data(), n_tiles * sizeof(uint32_t), hipMemcpyHostToDevice, st));
         }
+        if(views != nullptr) {
+            PT_HIP(s->view_cams.ensure(views->cams.size()));
+            PT_HIP(s->view_seeds.ensure(views->seeds.size()));
+            PT_HIP(hipMemcpyAsync(s->view_cams.ptr, views->cams.data(), views->cams.size() * sizeof(PtViewCamera), hipMemcpyHostToDevice, st));
+            PT_HIP(hipMemcpyAsync(s->view_seeds.ptr, views->seeds.data(), views->seeds.size() * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        }
         PT_HIP(hipStreamSynchronize(st)); // the tables are this function's vectors
         PtStreams T{};
         T.n = n32;
@@ -1635,6 +1654,12 @@ static int render_tiles_impl(pt_scene *s, const pt_camera_params *camera, const 
         T.tile_offset = s->tile_offset.ptr;
         T.n_tiles = static_cast<uint32_t>(n_tiles);
         T.base_seed = base_seed;
+        if(views != nullptr) {
+            T.n_views = static_cast<uint32_t>(views->cams.size());
+            T.view_height = static_cast<uint32_t>(options->image_height);
+            T.views = s->view_cams.ptr;
+            T.view_seed = s->view_seeds.ptr;
+        }
         // A regular grid of equal tiles (what pt_job_tiles makes of a frame whose sides are multiples of the tile size) lets the kernel
         // spread a wavefront's first rows over the frame's columns as well as over its bands: tiles per grid row, 64-stream chunks per tile.
         tile_grid(tiles, n_tiles, &T.tiles_per_row, &T.chunks_per_tile);
@@ -1755,7 +1780,7 @@ static std::vector<int> tile_owners(const pt_tile *tiles, size_t n_tiles, int n_
 // its streams (tile_done: [n_tiles] or null, tallies: [n_scenes]).
 static int render_tiles_multi_impl(pt_scene *const *scenes, int n_scenes, const pt_camera_params *camera, const pt_options *options, const pt_tile *tiles, size_t n_tiles,
                                    uint64_t base_seed, float *out_image, pt_stats *stats, pt_progress_fn progress, void *progress_user, RenderStop *stop = nullptr,
-                                   uint8_t *tile_done = nullptr, StreamTally *tallies = nullptr) {
+                                   uint8_t *tile_done = nullptr, StreamTally *tallies = nullptr, const ViewSet *views = nullptr) {
     if(scenes == nullptr || n_scenes < 1) {
         return fail(PT_ERR_INVALID, "no scenes");
     }
@@ -1771,9 +1796,10 @@ static int render_tiles_multi_impl(pt_scene *const *scenes, int n_scenes, const 
     if(tiles == nullptr || out_image == nullptr) {
         return fail(PT_ERR_INVALID, "null argument");
     }
+    const int32_t rows = views != nullptr ? views->rows(options) : options->image_height; // (a view batch: the stacked image)
     for(size_t k = 0; k < n_tiles; k++) {
         const pt_tile &t = tiles[k];
-        if(t.w <= 0 || t.h <= 0 || t.x < 0 || t.y < 0 || t.x + t.w > options->image_width || t.y + t.h > options->image_height) {
+        if(t.w <= 0 || t.h <= 0 || t.x < 0 || t.y < 0 || t.x + t.w > options->image_width || t.y + t.h > rows) {
             return fail(PT_ERR_INVALID, "tile outside the image or empty");
         }
     }
@@ -1803,7 +1829,7 @@ static int render_tiles_multi_impl(pt_scene *const *scenes, int n_scenes, const 
     };
     std::vector<int> rcs(static_cast<size_t>(n_scenes), PT_OK);
     std::vector<std::string> errors(static_cast<size_t>(n_scenes));
-    const size_t width = static_cast<size_t>(options->image_width), pixels = width * static_cast<size_t>(options->image_height);
+    const size_t width = static_cast<size_t>(options->image_width), pixels = width * static_cast<size_t>(rows);
     auto work = [&](int i) {
         std::vector<pt_tile> mine;
         std::vector<size_t> mine_index;
@@ -1829,7 +1855,7 @@ static int render_tiles_multi_impl(pt_scene *const *scenes, int n_scenes, const 
                 }
             }
             int rc = render_tiles_impl(s, camera, options, mine.data(), mine.size(), base_seed, reinterpret_cast<float4 *>(s->image.ptr),
-                                       stats != nullptr ? stats + i : nullptr, progress != nullptr ? static_cast<pt_progress_fn>(trampoline) : nullptr, &shared, stop);
+                                       stats != nullptr ? stats + i : nullptr, progress != nullptr ? static_cast<pt_progress_fn>(trampoline) : nullptr, &shared, stop, views);
             if(rc != PT_OK) {
                 return rc;
             }
@@ -1960,6 +1986,107 @@ int pt_render_tiles_device(pt_scene *s, const pt_camera_params *camera, const pt
         PT_HIP(hipStreamWaitEvent(caller, ev.e, 0));
         // This entry point does not wait for the device (the frame stays in HBM for the caller's stream).  With statistics it has waited
         // and checked already (run_path); PT_VERIFY=1 makes every call wait and check.
+        if(stats == nullptr && env_int("PT_VERIFY", 0) != 0) {
+            rc = finish_path(s);
+        }
+    }
+    return rc;
+}
+
+} // extern "C"
+
+// ---- view batches (pt_render_views*): V cameras of one scene in one launch per replica ------------------------------------------------
+// The views' frames are stacked into one image of V * H rows, view v = rows [v H, (v + 1) H), and the job is the tile list pt_job_tiles(W, H)
+// of every view, moved down by v H, view after view.  The kernel finds a pixel's view from its row (pt_path.hip): its seed and camera ray
+// are what pt_render_tiles(cameras[v], base_seeds[v]) gives the pixel at the local row, and the image store needs no change -- row-major
+// W x (V H) is [V][H][W].  One view is that call itself.
+
+// The arguments every view-batch entry point checks before anything is launched; fills the stacked tile list and, for V > 1, the view set.
+static int prepare_views(const pt_camera_params *cameras, const uint64_t *base_seeds, int32_t n_views, const pt_options *options, std::vector<pt_tile> *tiles,
+                         ViewSet *views) {
+    if(cameras == nullptr || base_seeds == nullptr || options == nullptr) {
+        return fail(PT_ERR_INVALID, "null argument");
+    }
+    if(n_views <= 0) {
+        return fail(PT_ERR_INVALID, "a view batch needs at least one view");
+    }
+    if(options->image_width <= 0 || options->image_height <= 0) {
+        return fail(PT_ERR_INVALID, "image size must be positive");
+    }
+    const uint64_t rows = static_cast<uint64_t>(n_views) * static_cast<uint64_t>(options->image_height);
+    if(rows > 0x7fffffffULL || rows * static_cast<uint64_t>(options->image_width) > 0x0fffffffULL) {
+        return fail(PT_ERR_INVALID, "too many pixels in one call");
+    }
+    const size_t per_view = pt_job_tiles(options->image_width, options->image_height, nullptr, 0);
+    tiles->resize(per_view * static_cast<size_t>(n_views));
+    pt_job_tiles(options->image_width, options->image_height, tiles->data(), per_view);
+    for(int32_t v = 1; v < n_views; v++) {
+        for(size_t k = 0; k < per_view; k++) {
+            pt_tile t = (*tiles)[k];
+            t.y += v * options->image_height;
+            (*tiles)[static_cast<size_t>(v) * per_view + k] = t;
+        }
+    }
+    views->cams.clear();
+    views->seeds.clear();
+    if(n_views > 1) {
+        views->cams.resize(static_cast<size_t>(n_views));
+        for(int32_t v = 0; v < n_views; v++) {
+            views->cams[static_cast<size_t>(v)] = PtViewCamera{derive_camera(cameras + v), {0, 0, 0}};
+        }
+        views->seeds.assign(base_seeds, base_seeds + n_views);
+    }
+    return PT_OK;
+}
+
+extern "C" {
+
+int pt_render_views(pt_scene *const *scenes, int n_scenes, const pt_camera_params *cameras, const uint64_t *base_seeds, int32_t n_views, const pt_options *options,
+                    float *out_images, pt_stats *stats, pt_progress_fn progress, void *progress_user) {
+    std::vector<pt_tile> tiles;
+    ViewSet views;
+    int rc = prepare_views(cameras, base_seeds, n_views, options, &tiles, &views);
+    if(rc != PT_OK) {
+        return rc;
+    }
+    if(out_images == nullptr) {
+        return fail(PT_ERR_INVALID, "null argument");
+    }
+    return render_tiles_multi_impl(scenes, n_scenes, cameras, options, tiles.data(), tiles.size(), base_seeds[0], out_images, stats, progress, progress_user, nullptr,
+                                   nullptr, nullptr, n_views > 1 ? &views : nullptr);
+}
+
+int pt_render_views_device(pt_scene *s, const pt_camera_params *cameras, const uint64_t *base_seeds, int32_t n_views, const pt_options *options, float *d_out_images,
+                           void *stream, pt_stats *stats) {
+    std::vector<pt_tile> tiles;
+    ViewSet views;
+    int rc = prepare_views(cameras, base_seeds, n_views, options, &tiles, &views);
+    if(rc != PT_OK) {
+        return rc;
+    }
+    rc = check_render_args(s, cameras, options);
+    if(rc != PT_OK) {
+        return rc;
+    }
+    if(stats != nullptr) {
+        std::memset(stats, 0, sizeof(*stats));
+    }
+    if(d_out_images == nullptr) {
+        return fail(PT_ERR_INVALID, "null argument");
+    }
+    std::lock_guard<std::mutex> lock(s->render_mutex);
+    PT_HIP(hipSetDevice(s->device));
+    // ordered after the caller's stream and before its later work, as pt_render_tiles_device
+    hipStream_t caller = static_cast<hipStream_t>(stream);
+    Event ev;
+    PT_HIP(ev.create(hipEventDisableTiming));
+    PT_HIP(hipEventRecord(ev.e, caller));
+    PT_HIP(hipStreamWaitEvent(s->stream, ev.e, 0));
+    rc = render_tiles_impl(s, cameras, options, tiles.data(), tiles.size(), base_seeds[0], reinterpret_cast<float4 *>(d_out_images), stats, nullptr, nullptr, nullptr,
+                           n_views > 1 ? &views : nullptr);
+    if(rc == PT_OK) {
+        PT_HIP(hipEventRecord(ev.e, s->stream));
+        PT_HIP(hipStreamWaitEvent(caller, ev.e, 0));
         if(stats == nullptr && env_int("PT_VERIFY", 0) != 0) {
             rc = finish_path(s);
         }

@@ -423,16 +423,10 @@ PT_D V3 ld3(const float *p) {
     return v3(p[0], p[1], p[2]);
 }
 
-PT_D Ray camera_shoot(const PtDevCamera &cam, float x, float y, float pixel_width, float pixel_height, uint64_t &rng) {
-    float offset_x = rng_uniform(rng, -pixel_width / 2.0f, pixel_width / 2.0f);
-    float offset_y = rng_uniform(rng, -pixel_height / 2.0f, pixel_height / 2.0f);
-    float sensor_x = x + offset_x;
-    float sensor_y = y + offset_y;
-    V3 origin = ld3(cam.origin), forward = ld3(cam.forward), up = ld3(cam.up), right = ld3(cam.right);
-    V3 sensor_pos = ((origin - forward) - up * sensor_y) - right * sensor_x;
-
-    float aperture_offset_x = 0.0f;
-    float aperture_offset_y = 0.0f;
+// The aperture sampler of a thin-lens camera (camera.cpp:7-50): the lens offset of a camera ray, in the reference's order of draws
+PT_D void aperture_offsets(const PtDevCamera &cam, uint64_t &rng, float &aperture_offset_x, float &aperture_offset_y) {
+    aperture_offset_x = 0.0f;
+    aperture_offset_y = 0.0f;
     if(cam.aperture_kind == 1) {
         // CircularApertureSampler, camera.cpp:7-19
         float r = __builtin_sqrtf(rng_uniform01(rng));
@@ -463,11 +457,48 @@ PT_D Ray camera_shoot(const PtDevCamera &cam, float x, float y, float pixel_widt
         aperture_offset_x = sx * cam.aperture_width_half;
         aperture_offset_y = sy * cam.aperture_height_half;
     }
+}
+
+PT_D Ray camera_shoot(const PtDevCamera &cam, float x, float y, float pixel_width, float pixel_height, uint64_t &rng) {
+    float offset_x = rng_uniform(rng, -pixel_width / 2.0f, pixel_width / 2.0f);
+    float offset_y = rng_uniform(rng, -pixel_height / 2.0f, pixel_height / 2.0f);
+    float sensor_x = x + offset_x;
+    float sensor_y = y + offset_y;
+    V3 origin = ld3(cam.origin), forward = ld3(cam.forward), up = ld3(cam.up), right = ld3(cam.right);
+    V3 sensor_pos = ((origin - forward) - up * sensor_y) - right * sensor_x;
+
+    float aperture_offset_x, aperture_offset_y;
+    aperture_offsets(cam, rng, aperture_offset_x, aperture_offset_y);
     Ray ray;
     ray.o = (origin + up * aperture_offset_x) + right * aperture_offset_y;
     if(cam.focal_plane_dist > 0.0f) {
         V3 base_dir = normalize(origin - sensor_pos);
         V3 ray_target = origin + base_dir * (cam.focal_plane_dist / dot(forward, base_dir));
+        ray.d = normalize(ray_target - ray.o);
+    }
+    else {
+        ray.d = normalize(ray.o - sensor_pos);
+    }
+    return ray;
+}
+
+// camera_shoot with a camera that differs from lane to lane (a view batch's table in global memory, pt_path.hip): the same operations on
+// the same values, ordered so that no field is loaded before it is needed -- the draws and the aperture sampler first (they read the
+// aperture's fields only), the camera's four vectors after it -- so that none of them lives in vector registers across the sampler.
+PT_D Ray camera_shoot_lane(const PtDevCamera &cam, float x, float y, float pixel_width, float pixel_height, uint64_t &rng) {
+    float offset_x = rng_uniform(rng, -pixel_width / 2.0f, pixel_width / 2.0f);
+    float offset_y = rng_uniform(rng, -pixel_height / 2.0f, pixel_height / 2.0f);
+    float sensor_x = x + offset_x;
+    float sensor_y = y + offset_y;
+    float aperture_offset_x, aperture_offset_y;
+    aperture_offsets(cam, rng, aperture_offset_x, aperture_offset_y);
+    V3 origin = ld3(cam.origin), up = ld3(cam.up), right = ld3(cam.right);
+    Ray ray;
+    ray.o = (origin + up * aperture_offset_x) + right * aperture_offset_y;
+    V3 sensor_pos = ((origin - ld3(cam.forward)) - up * sensor_y) - right * sensor_x;
+    if(cam.focal_plane_dist > 0.0f) {
+        V3 base_dir = normalize(origin - sensor_pos);
+        V3 ray_target = origin + base_dir * (cam.focal_plane_dist / dot(ld3(cam.forward), base_dir));
         ray.d = normalize(ray_target - ray.o);
     }
     else {

@@ -84,6 +84,12 @@ struct PtStreams {
     uint32_t *park_count;        // records written to park_out
     uint32_t park_cap;
     uint32_t *status;            // [streams of the frame] or null: PT_STREAM_* of every stream this launch finished or parked
+    // A batch of views (pt_render_views): n_views > 1 frames of opt.image_height rows stacked into one tall image, view v = rows
+    // [v * H, (v + 1) * H).  A pixel's view is its row / H; it is seeded from (view_seed[view], x, row - view * H) and its camera ray is
+    // made by views[view] at that local row.  n_views <= 1: base_seed and the launch's camera, as every other entry point.
+    uint32_t n_views, view_height; // view_height = opt.image_height (H)
+    const PtViewCamera *views;   // [n_views] or null
+    const uint64_t *view_seed;   // [n_views] or null
 };
 
 // Ray queues, one private ring per wavefront: entries [wave * cap, (wave + 1) * cap)

@@ -434,6 +434,7 @@ struct SlotWord<true> {
     static PT_D void keep_waiting(const PtSlots &S, size_t p, uint32_t mask) { S.nee_mask[p] = mask; }
 };
 
+#define PT_F_VIEW_RAY 256u /* a view batch's camera ray is made at the end of the pass (shade_row); in the register only, never in the slot word */
 #define PT_DEST_SLOT_MASK 0xffffu
 #define PT_NO_SLOT 0xffffffffu
 #define PT_DEST_J_SHIFT 16
@@ -465,7 +466,15 @@ PT_D void tile_stream(const PtStreams &T, uint32_t i, int4 &rect, uint64_t &rng,
     const uint32_t k = i - T.tile_offset[lo];
     const int32_t x = t.x + (int32_t)(k % (uint32_t)t.z), y = t.y + (int32_t)(k / (uint32_t)t.z);
     rect = make_int4(x, y, 1, 1);
-    const uint64_t seed = pixel_seed(T.base_seed, x, y);
+    uint64_t base_seed = T.base_seed;
+    int32_t seed_y = y;
+    if(T.n_views > 1) {
+        // a view batch: the pixel's own view and its row inside it (wave-uniform branch: n_views is a scalar of the launch)
+        const uint32_t view = (uint32_t)y / T.view_height;
+        base_seed = T.view_seed[view];
+        seed_y = y - (int32_t)(view * T.view_height);
+    }
+    const uint64_t seed = pixel_seed(base_seed, x, seed_y);
     rng = seed ^ (~seed << 32); // RandomEngine(seed), base.h:26
     tile = lo;
 }
@@ -808,6 +817,12 @@ PT_D void shade_row(const PtDevScene &sc, const PtDevCamera &cam, const PtDevOpt
         y_camera = -y_camera;
         return camera_shoot(cam, x_camera, y_camera, opt.pixel_width, opt.pixel_height, rng);
     };
+    // In a view batch (T.n_views > 1: a scalar, so every test of it is wave-uniform) a camera ray is not made where it is called for but once,
+    // at the end of the pass: the camera differs from lane to lane there (lanes of one row of slots may hold pixels of different
+    // views), and its fields are vector registers that the start of a sample has no room for.  The order of draws is unchanged: a lane that
+    // starts a sample makes no other draw in the pass, and the overlapped camera ray is the last draw of a vertex.
+    // (Which lanes want one is a flag bit of the register `flags`, never stored: a lane mask of its own, live across the light samples, costs spills.)
+    const bool batch = T.n_views > 1;
     if(start_sample) {
         bool have_pixel = false;
         while(cursor < rect.z * rect.w) {
@@ -844,7 +859,14 @@ PT_D void shade_row(const PtDevScene &sc, const PtDevCamera &cam, const PtDevOpt
             flags = 0;
         }
         else {
-            ext = shoot_camera(rect, cursor);
+            if(batch) {
+                flags |= PT_F_VIEW_RAY;
+                ext.o = v3(0, 0, 0); // (a constant: what ext held must not stay live until the ray is made)
+                ext.d = v3(0, 0, 1);
+            }
+            else {
+                ext = shoot_camera(rect, cursor);
+            }
             emit_ext = true;
             out = c4(0, 0, 0, 0);
             spectrum = c4(1, 1, 1, 1);
@@ -1026,7 +1048,14 @@ PT_D void shade_row(const PtDevScene &sc, const PtDevCamera &cam, const PtDevOpt
         const bool path_ends = !do_bounce || cancel_ext;
         if(path_ends && safe_overlap) {
             // start the next sample of this pixel now; this sample is finished by the next pass over the slot (PT_F_OVERLAP)
-            ext = shoot_camera(rect, cursor);
+            if(batch) {
+                flags |= PT_F_VIEW_RAY;
+                ext.o = v3(0, 0, 0); // (a constant: what ext held must not stay live until the ray is made)
+                ext.d = v3(0, 0, 1);
+            }
+            else {
+                ext = shoot_camera(rect, cursor);
+            }
             spectrum = c4(1, 1, 1, 1);
             contribution_unweighted = 1.0f;
             divisor = 1.0;
@@ -1045,6 +1074,19 @@ PT_D void shade_row(const PtDevScene &sc, const PtDevCamera &cam, const PtDevOpt
         else {
             flags &= ~PT_F_HAS_EXT;
         }
+    }
+
+    // ---- a view batch's camera rays: the pixel's view is its row / H, its camera that view's record of the table ------------------------------
+    if(flags & PT_F_VIEW_RAY) {
+        flags &= ~PT_F_VIEW_RAY;
+        const int32_t px = rect.x + cursor % rect.z, row = rect.y + cursor / rect.z;
+        const uint32_t view = (uint32_t)row / (uint32_t)opt.image_height;
+        const int32_t py = row - (int32_t)(view * (uint32_t)opt.image_height);
+        const float one_half = 1.0f / 2.0f;
+        const float x_camera = 2 * (((float)px + one_half) / (float)opt.image_width - one_half);
+        float y_camera = 2 * (((float)py + one_half) / (float)opt.image_height - one_half);
+        y_camera = -y_camera;
+        ext = camera_shoot_lane(T.views[view].cam, x_camera, y_camera, opt.pixel_width, opt.pixel_height, rng);
     }
 
     // ---- write the extension ray and the path state ------------------------------------------------------------------------------

@@ -84,6 +84,12 @@ struct PtDevCamera {
     float focal_plane_dist;
 };
 
+// A camera of a view batch's table (PtStreams::views), read per lane: padded to 80 bytes so that a record is five 16-byte loads
+struct alignas(16) PtViewCamera {
+    PtDevCamera cam;
+    uint32_t pad[3];
+};
+
 struct PtDevOptions {
     int32_t image_width;
     int32_t image_height;

@@ -195,6 +195,18 @@ int pt_render_tiles_multi(pt_scene *const *scenes, int n_scenes, const pt_camera
 int pt_render_tiles_device(pt_scene *scene, const pt_camera_params *camera, const pt_options *options, const pt_tile *tiles, size_t n_tiles,
                            uint64_t base_seed, float *d_out_image, void *stream, pt_stats *stats);
 
+/* processJob for n_views cameras of one scene in one launch per replica (a turntable, a camera path, a stereo pair: small frames that one
+ * at a time leave most of the device idle).  Every view is options->image_width x image_height, tiled as pt_job_tiles; view v's pixels are
+ * seeded from (base_seeds[v], x, y) and equal pt_render_tiles(camera = cameras[v], base_seed = base_seeds[v]) bit for bit; one view is
+ * that call.  out_images: [n_views][height][width][4] floats.  The views' tiles are dealt to the replicas as in pt_render_tiles_multi;
+ * progress counts the tiles of all views (n_views * pt_job_tiles(width, height)).  PT_ERR_INVALID without a launch for n_views <= 0, null
+ * tables, or more than 0x0fffffff pixels in all.  The views share the options; there is no controlled or resumable form. */
+int pt_render_views(pt_scene *const *scenes, int n_scenes, const pt_camera_params *cameras, const uint64_t *base_seeds, int32_t n_views,
+                    const pt_options *options, float *out_images, pt_stats *stats, pt_progress_fn progress, void *user);
+/* Same, one scene, into DEVICE memory (e.g. a [V, H, W, 4] torch tensor's data_ptr), ordered on `stream` as pt_render_tiles_device. */
+int pt_render_views_device(pt_scene *scene, const pt_camera_params *cameras, const uint64_t *base_seeds, int32_t n_views,
+                           const pt_options *options, float *d_out_images, void *stream, pt_stats *stats);
+
 /* Cancellable, time-budgeted processJob.  A controlled render is the same single launch per replica as pt_render_tiles_multi; it can be
  * told to stop while it runs, either by pt_render_cancel (from the progress callback or any other thread) or by its budget.
  *   - The stop is COOPERATIVE.  The host writes a word in pinned host memory; every wavefront of the launch reads it once per shading pass.

@@ -1,4 +1,4 @@
-// job_params.h -- what processJob and FrameRender (worker.cpp, frame_render.cpp) share: the translation of a FrameRenderJob into the C ABI
+// job_params.h -- what processJob, FrameRender and processViews (worker.cpp, frame_render.cpp, view_batch.cpp) share: the translation of a FrameRenderJob into the C ABI
 // of pt_hip.h, the job's tiles and seed, and the forwarding of progress reports.  Internal to libPathTrace.so.
 #ifndef PATHTRACE_HOST_JOB_PARAMS_H
 #define PATHTRACE_HOST_JOB_PARAMS_H
@@ -63,6 +63,16 @@ namespace pathtrace_host {
         }
         std::random_device device;
         return (static_cast<uint64_t>(device()) << 32) | device();
+    }
+
+    // the seeds of a batch of n views (processViews): view v takes jobSeed() + v, so that processJob with $PATHTRACE_SEED = seeds[v] renders it again
+    inline std::vector<uint64_t> viewSeeds(size_t n) {
+        const uint64_t base = jobSeed();
+        std::vector<uint64_t> seeds(n);
+        for(size_t v = 0; v < n; v++) {
+            seeds[v] = base + static_cast<uint64_t>(v);
+        }
+        return seeds;
     }
 
     // An exception thrown by the progress callback must not cross the C ABI (with several devices it would be thrown on a library thread
