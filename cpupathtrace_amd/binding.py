@@ -6,6 +6,8 @@
 ``process_job_controlled``  processJob that can be cancelled or given a time budget (include/PathTrace/render_control.h)
 ``Frame``            a controlled processJob that can be continued: each call resumes where the last one stopped (include/PathTrace/frame_render.h)
 ``process_views``    processJob for many cameras of one scene in one launch (include/PathTrace/view_batch.h)
+``denoise``          feature-guided denoising of a finished frame, what RenderOptions::allow_bias asks for (include/PathTrace/denoise.h);
+                     ``Scene.render_features`` gives the features, ``Scene.process_job(..., allow_bias=True)`` does both
 
 The library is the only implementation behind these calls: if it is missing or no HIP device is usable they raise.
 """
@@ -30,6 +32,8 @@ FRAME_EXPORTS = ["pt_frame_create", "pt_frame_render", "pt_frame_get_info", "pt_
 EXPORTS += FRAME_EXPORTS
 VIEW_EXPORTS = ["pt_render_views", "pt_render_views_device"]
 EXPORTS += VIEW_EXPORTS
+DENOISE_EXPORTS = ["pt_denoise_params_default", "pt_render_features", "pt_render_features_device", "pt_denoise", "pt_denoise_device"]
+EXPORTS += DENOISE_EXPORTS
 
 
 
@@ -49,6 +53,55 @@ def post_process(image, steps=POST_TONE_MAP | POST_GAMMA, gamma=1.8, device=0):
     h, w = img.shape[:2]
     _check(load().pt_post_process(C.c_int(device), _ptr(img), C.c_int32(w), C.c_int32(h), C.c_uint32(steps), C.c_float(gamma)))
     return img
+
+
+class DenoiseParams(C.Structure):
+    """pt_denoise_params: a-trous passes (0..10) and the three edge-stopping sigmas (>= 0; 0 turns a term off)."""
+    _fields_ = [("iterations", C.c_int32), ("sigma_luminance", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+def denoise_params_default():
+    """The library's default parameters (pt_denoise_params_default) as a dict."""
+    p = DenoiseParams()
+    _check(load().pt_denoise_params_default(C.byref(p)))
+    return p.as_dict()
+
+
+def _denoise_params(params):
+    """None = the library's defaults (a NULL pointer); otherwise a dict whose missing keys take the defaults."""
+    if params is None:
+        return None
+    unknown = set(params) - {k for k, _ in DenoiseParams._fields_}
+    if unknown:
+        raise ValueError("unknown denoise parameters: %s" % ", ".join(sorted(unknown)))
+    p = DenoiseParams()
+    _check(load().pt_denoise_params_default(C.byref(p)))
+    for k, v in params.items():
+        setattr(p, k, v)
+    return C.byref(p)
+
+
+def denoise(image, features, params=None, device=0):
+    """Feature-guided denoising (pt_denoise) of an (h, w, 4) float32 frame with the (h, w, 3, 4) features of Scene.render_features for the
+    same camera; returns a new array (alpha copied).  params: None = defaults, or a dict of DenoiseParams fields."""
+    img = np.ascontiguousarray(image, dtype=np.float32)
+    feat = np.ascontiguousarray(features, dtype=np.float32)
+    if img.ndim != 3 or img.shape[2] != 4 or feat.shape != img.shape[:2] + (3, 4):
+        raise ValueError("image must be (h, w, 4) and features (h, w, 3, 4)")
+    out = np.empty_like(img)
+    h, w = img.shape[:2]
+    _check(load().pt_denoise(C.c_int(device), _ptr(img), _ptr(feat), C.c_int32(w), C.c_int32(h), _denoise_params(params), _ptr(out)))
+    return out
+
+
+def denoise_device(d_rgba_ptr, d_features_ptr, width, height, d_out_ptr, stream_ptr=0, params=None, device=0):
+    """pt_denoise_device on device memory (e.g. torch tensors' data_ptr()): rgba and out width*height*4 floats (out may equal rgba), features
+    width*height*12 floats; ordered on stream_ptr (0 = the default stream), which is synchronised before the call returns."""
+    _check(load().pt_denoise_device(C.c_int(device), C.c_void_p(d_rgba_ptr), C.c_void_p(d_features_ptr), C.c_int32(width), C.c_int32(height),
+                                    _denoise_params(params), C.c_void_p(d_out_ptr), C.c_void_p(stream_ptr)))
 
 
 class SceneDesc(C.Structure):
@@ -250,8 +303,10 @@ class Scene:
                                         C.byref(st) if want_stats else None))
         return (image, states, st.as_dict()) if want_stats else (image, states)
 
-    def process_job(self, camera, options, base_seed=1234, tiles=None, image=None, want_stats=False):
-        """processJob: every pixel of the given tiles (default: all tiles of the image) with per-pixel engines."""
+    def process_job(self, camera, options, base_seed=1234, tiles=None, image=None, want_stats=False, allow_bias=False):
+        """processJob: every pixel of the given tiles (default: all tiles of the image) with per-pixel engines.  allow_bias (RenderOptions::
+        allow_bias) returns the finished frame denoised: denoise(image, render_features(camera, options)) -- a new array, `image` keeps the
+        noisy frame."""
         if tiles is None:
             tiles = job_tiles(options["image_width"], options["image_height"])
         tiles = np.ascontiguousarray(tiles, dtype=TILE_DTYPE)
@@ -260,7 +315,22 @@ class Scene:
         cp, op, st = _camera(camera), _options(options), Stats()
         _check(load().pt_render_tiles(self._h, C.byref(cp), C.byref(op), _ptr(tiles), C.c_size_t(len(tiles)), C.c_uint64(base_seed), _ptr(image),
                                       C.byref(st) if want_stats else None))
+        if allow_bias:
+            image = denoise(image, self.render_features(camera, options), device=self.device)
         return (image, st.as_dict()) if want_stats else image
+
+    def render_features(self, camera, options):
+        """First-hit features of the frame (pt_render_features): an (H, W, 3, 4) float32 array, the mean over 4 deterministic primary rays
+        per pixel of [albedo rgb, coverage], [normal xyz, t], [position xyz, emission luminance]."""
+        out = np.empty((options["image_height"], options["image_width"], 3, 4), np.float32)
+        cp, op = _camera(camera), _options(options)
+        _check(load().pt_render_features(self._h, C.byref(cp), C.byref(op), _ptr(out)))
+        return out
+
+    def render_features_device(self, camera, options, d_features_ptr, stream_ptr=0):
+        """render_features into device memory (d_features_ptr: device address of H*W*12 floats, e.g. an (H, W, 3, 4) tensor), ordered on stream_ptr."""
+        cp, op = _camera(camera), _options(options)
+        _check(load().pt_render_features_device(self._h, C.byref(cp), C.byref(op), C.c_void_p(d_features_ptr), C.c_void_p(stream_ptr)))
 
     def process_work_item(self, camera, options, x, y, w, h, rng_state, want_stats=False):
         """processItem(WorkItem(job, x, y, w, h), engine) returning the item's own (h, w, 4) tile and the engine state afterwards."""

@@ -23,6 +23,7 @@
 #include "pt_build.h"
 #include "pt_bvh.h"
 #include "pt_kernels.h"
+#include "pt_denoise.h"
 #include "pt_post.h"
 
 namespace {
@@ -194,6 +195,9 @@ struct pt_scene {
     // a view batch (pt_render_views): the cameras and seeds of its views
     DevBuf<PtViewCamera> view_cams;
     DevBuf<uint64_t> view_seeds;
+    // the first-hit features of a frame (pt_render_features*): the frame's features and the walks' spill area
+    DevBuf<F4> features;
+    DevBuf<uint2> feature_spill;
     bool debug_collect_costs = false;                // pt_debug_collect_costs: every launch records them
     std::vector<uint32_t> debug_place;               // pt_debug_set_place: the next launch starts from this table ...
     uint32_t debug_place_waves = 0, debug_place_slots = 0; // ... with this many wavefronts and slots in each
@@ -2566,3 +2570,234 @@ int pt_post_process(int device, float *rgba, int32_t width, int32_t height, uint
     PT_HIP(hipMemcpy(rgba, frame.ptr, count * sizeof(F4), hipMemcpyDeviceToHost));
     return PT_OK;
 }
+
+// ---- feature-guided denoising (pt_path.hip: pt_feature_kernel; pt_denoise.hip) -------------------------------------------------------
+
+static int features_check(pt_scene *s, const pt_camera_params *camera, const pt_options *options, const float *out) {
+    int rc = check_render_args(s, camera, options);
+    if(rc != PT_OK) {
+        return rc;
+    }
+    if(out == nullptr) {
+        return fail(PT_ERR_INVALID, "null argument");
+    }
+    if(static_cast<long long>(options->image_width) * options->image_height > 0x0fffffffLL) {
+        return fail(PT_ERR_INVALID, "more than 0x0fffffff pixels");
+    }
+    return PT_OK;
+}
+
+// Enqueues the feature pass on the scene's stream (render_mutex held): into `d_out`, width * height * 3 float4.
+static int features_launch(pt_scene *s, const pt_camera_params *camera, const pt_options *options, float4 *d_out) {
+    int rc = setup_path(s);
+    if(rc != PT_OK) {
+        return rc;
+    }
+    PtDevCamera cam = derive_camera(camera);
+    cam.aperture_kind = PT_APERTURE_NONE; // the rays are a pure function of camera and pixel
+    PtPathConfig cfg = s->path_cfg;
+    const size_t n = static_cast<size_t>(options->image_width) * static_cast<size_t>(options->image_height);
+    PT_HIP(s->feature_spill.ensure(((n + 255) / 256) * 256 * cfg.spill_depth));
+    cfg.spill = s->feature_spill.ptr;
+    pt_launch_features(s->stream, s->dev, cam, options->image_width, options->image_height, d_out, cfg);
+    PT_HIP(hipGetLastError());
+    return PT_OK;
+}
+
+namespace {
+
+// The denoiser's scratch buffers: one set per device, grown on demand, one call at a time per device.  They live as long as the process
+// (never freed: a static destructor would run after the HIP runtime has gone).
+struct DenoiseWorkspace {
+    std::mutex mutex;
+    size_t pixels = 0;  // capacity of the per-pixel buffers
+    size_t staged = 0;  // ... and of the host form's upload/download buffers
+    PtDenoiseScratch scratch{};
+    float4 *in_rgba = nullptr, *in_features = nullptr;
+};
+
+DenoiseWorkspace &denoise_workspace(int device) {
+    static std::mutex table_mutex;
+    static std::vector<DenoiseWorkspace *> table;
+    std::lock_guard<std::mutex> lock(table_mutex);
+    if(static_cast<size_t>(device) >= table.size()) {
+        table.resize(static_cast<size_t>(device) + 1, nullptr);
+    }
+    if(table[static_cast<size_t>(device)] == nullptr) {
+        table[static_cast<size_t>(device)] = new DenoiseWorkspace();
+    }
+    return *table[static_cast<size_t>(device)];
+}
+
+template<typename T>
+hipError_t regrow(T **p, size_t count) {
+    if(*p != nullptr) {
+        hipError_t e = hipFree(*p);
+        *p = nullptr;
+        if(e != hipSuccess) {
+            return e;
+        }
+    }
+    return hipMalloc(reinterpret_cast<void **>(p), std::max<size_t>(count, 1) * sizeof(T));
+}
+
+int denoise_ensure(DenoiseWorkspace &ws, size_t n, bool staged) {
+    PtDenoiseScratch &d = ws.scratch;
+    if(n > ws.pixels) {
+        ws.pixels = 0;
+        PT_HIP(regrow(&d.col[0], n));
+        PT_HIP(regrow(&d.col[1], n));
+        PT_HIP(regrow(&d.var[0], n));
+        PT_HIP(regrow(&d.var[1], n));
+        PT_HIP(regrow(&d.guide, n));
+        PT_HIP(regrow(&d.grad, n));
+        PT_HIP(regrow(&d.cls, n));
+        ws.pixels = n;
+    }
+    if(staged && n > ws.staged) {
+        ws.staged = 0;
+        PT_HIP(regrow(&ws.in_rgba, n));
+        PT_HIP(regrow(&ws.in_features, 3 * n));
+        ws.staged = n;
+    }
+    return PT_OK;
+}
+
+int denoise_check(int device, const void *rgba, const void *features, int32_t width, int32_t height, const pt_denoise_params *params, const void *out,
+                  PtDenoiseParams *resolved) {
+    if(rgba == nullptr || features == nullptr || out == nullptr) {
+        return fail(PT_ERR_INVALID, "null argument");
+    }
+    if(width <= 0 || height <= 0) {
+        return fail(PT_ERR_INVALID, "image size must be positive");
+    }
+    if(static_cast<long long>(width) * height > 0x0fffffffLL) {
+        return fail(PT_ERR_INVALID, "more than 0x0fffffff pixels");
+    }
+    pt_denoise_params p{};
+    pt_denoise_params_default(&p);
+    if(params != nullptr) {
+        p = *params;
+    }
+    if(p.iterations < 0 || p.iterations > 10) {
+        return fail(PT_ERR_INVALID, "iterations must be 0..10");
+    }
+    for(float sigma : {p.sigma_luminance, p.sigma_normal, p.sigma_depth}) {
+        if(!std::isfinite(sigma) || sigma < 0.0F) {
+            return fail(PT_ERR_INVALID, "sigmas must be finite and not negative");
+        }
+    }
+    const int n_dev = device_count_quiet();
+    if(n_dev <= 0) {
+        return fail(PT_ERR_NO_DEVICE, "no HIP device available; libpathtrace_hip has no CPU path");
+    }
+    if(device < 0 || device >= n_dev) {
+        return fail(PT_ERR_NO_DEVICE, "device index out of range");
+    }
+    *resolved = PtDenoiseParams{p.iterations, p.sigma_luminance, p.sigma_normal, p.sigma_depth};
+    return PT_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int pt_denoise_params_default(pt_denoise_params *out) {
+    if(out == nullptr) {
+        return fail(PT_ERR_INVALID, "null argument");
+    }
+    out->iterations = 5;
+    out->sigma_luminance = 32.0F;
+    out->sigma_normal = 128.0F;
+    out->sigma_depth = 1.0F;
+    return PT_OK;
+}
+
+int pt_render_features(pt_scene *s, const pt_camera_params *camera, const pt_options *options, float *out_features) {
+    int rc = features_check(s, camera, options, out_features);
+    if(rc != PT_OK) {
+        return rc;
+    }
+    const size_t n = static_cast<size_t>(options->image_width) * static_cast<size_t>(options->image_height);
+    std::lock_guard<std::mutex> lock(s->render_mutex);
+    PT_HIP(hipSetDevice(s->device));
+    PT_HIP(s->features.ensure(3 * n));
+    rc = features_launch(s, camera, options, reinterpret_cast<float4 *>(s->features.ptr));
+    if(rc != PT_OK) {
+        return rc;
+    }
+    PT_HIP(hipMemcpyAsync(out_features, s->features.ptr, 3 * n * sizeof(F4), hipMemcpyDeviceToHost, s->stream));
+    PT_HIP(hipStreamSynchronize(s->stream));
+    return PT_OK;
+}
+
+int pt_render_features_device(pt_scene *s, const pt_camera_params *camera, const pt_options *options, float *d_out_features, void *stream) {
+    int rc = features_check(s, camera, options, d_out_features);
+    if(rc != PT_OK) {
+        return rc;
+    }
+    std::lock_guard<std::mutex> lock(s->render_mutex);
+    PT_HIP(hipSetDevice(s->device));
+    // order after the caller's stream, trace on the library's stream, then make the caller's stream wait for it
+    hipStream_t caller = static_cast<hipStream_t>(stream);
+    Event ev;
+    PT_HIP(ev.create(hipEventDisableTiming));
+    PT_HIP(hipEventRecord(ev.e, caller));
+    PT_HIP(hipStreamWaitEvent(s->stream, ev.e, 0));
+    rc = features_launch(s, camera, options, reinterpret_cast<float4 *>(d_out_features));
+    if(rc != PT_OK) {
+        return rc;
+    }
+    PT_HIP(hipEventRecord(ev.e, s->stream));
+    PT_HIP(hipStreamWaitEvent(caller, ev.e, 0));
+    if(caller == nullptr) {
+        PT_HIP(hipStreamSynchronize(s->stream));
+    }
+    return PT_OK;
+}
+
+int pt_denoise_device(int device, const float *d_rgba, const float *d_features, int32_t width, int32_t height, const pt_denoise_params *params, float *d_out_rgba,
+                      void *stream) {
+    PtDenoiseParams p{};
+    int rc = denoise_check(device, d_rgba, d_features, width, height, params, d_out_rgba, &p);
+    if(rc != PT_OK) {
+        return rc;
+    }
+    const size_t n = static_cast<size_t>(width) * static_cast<size_t>(height);
+    DenoiseWorkspace &ws = denoise_workspace(device);
+    std::lock_guard<std::mutex> lock(ws.mutex);
+    PT_HIP(hipSetDevice(device));
+    rc = denoise_ensure(ws, n, false);
+    if(rc != PT_OK) {
+        return rc;
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    PT_HIP(pt_denoise_run(st, reinterpret_cast<const float4 *>(d_rgba), reinterpret_cast<const float4 *>(d_features), width, height, p, ws.scratch,
+                          reinterpret_cast<float4 *>(d_out_rgba)));
+    PT_HIP(hipStreamSynchronize(st)); // the scratch buffers are the device's: the next call may reuse them
+    return PT_OK;
+}
+
+int pt_denoise(int device, const float *rgba, const float *features, int32_t width, int32_t height, const pt_denoise_params *params, float *out_rgba) {
+    PtDenoiseParams p{};
+    int rc = denoise_check(device, rgba, features, width, height, params, out_rgba, &p);
+    if(rc != PT_OK) {
+        return rc;
+    }
+    const size_t n = static_cast<size_t>(width) * static_cast<size_t>(height);
+    DenoiseWorkspace &ws = denoise_workspace(device);
+    std::lock_guard<std::mutex> lock(ws.mutex);
+    PT_HIP(hipSetDevice(device));
+    rc = denoise_ensure(ws, n, true);
+    if(rc != PT_OK) {
+        return rc;
+    }
+    PT_HIP(hipMemcpy(ws.in_rgba, rgba, n * sizeof(F4), hipMemcpyHostToDevice));
+    PT_HIP(hipMemcpy(ws.in_features, features, 3 * n * sizeof(F4), hipMemcpyHostToDevice));
+    // in place: the last kernel reads a pixel's alpha before it writes that pixel, and no kernel reads another pixel of the input
+    PT_HIP(pt_denoise_run(nullptr, ws.in_rgba, ws.in_features, width, height, p, ws.scratch, ws.in_rgba));
+    PT_HIP(hipMemcpy(out_rgba, ws.in_rgba, n * sizeof(F4), hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
+} // extern "C"

@@ -160,6 +160,9 @@ int pt_path_stack_lds(int in_lds, size_t lds_bytes_with_default_window); // entr
 int pt_launch_replay(hipStream_t stream, const PtDevScene &scene, const PtLocalQueue &Q, uint32_t n_logs, uint32_t parts, int waves_per_simd, const PtPathConfig &cfg,
                      uint2 *spill, unsigned long long *out);
 void pt_launch_closest(hipStream_t stream, const PtDevScene &scene, const float *rays6, uint32_t n, uint2 *out, const PtPathConfig &cfg);
+// first-hit features of a width x height frame for the denoiser (pt_feature_kernel): out[3 * pixel + k], k = albedo + coverage, normal + t,
+// position + emission luminance; `camera` must have no aperture sampler.  The walk, its instantiation and cfg.spill are pt_launch_closest's.
+void pt_launch_features(hipStream_t stream, const PtDevScene &scene, const PtDevCamera &camera, int32_t width, int32_t height, float4 *out, const PtPathConfig &cfg);
 // diagnostic (tools/step_timing.py): stamped walks, `lanes_per_wave` rays per wavefront; out[ray] = (steps, cycles waiting for records, cycles in all, price of a stamp pair)
 void pt_launch_steptime(hipStream_t stream, const PtDevScene &scene, const float *rays6, uint32_t n, uint32_t lanes_per_wave, uint4 *out, uint2 *spill, uint32_t spill_depth, int flags);
 

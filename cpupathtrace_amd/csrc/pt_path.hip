@@ -1601,6 +1601,89 @@ __global__ __launch_bounds__(256) void pt_closest_kernel(PtDevScene sc, const fl
     out[gid] = make_uint2(__float_as_uint(w.best_ref == PT_REF_NONE ? -1.0f : w.best_t), w.best_ref);
 }
 
+// First-hit features of a frame for the denoiser (pt_denoise.hip): each pixel traces K = 4 primary rays at the sub-pixel offsets
+// (-1/4, -1/4), (+1/4, -1/4), (-1/4, +1/4), (+1/4, +1/4) through a camera without aperture sampling and without pixel jitter (the caller
+// passes aperture_kind = none; pixel_width = pixel_height = 0 make camera_shoot's two offsets +0), so the rays are a pure function of
+// camera and pixel.  The walk is pt_closest_kernel's.  out[3 p + k], the mean over the rays (summed in ray order, then * 0.25f; a miss adds 0):
+//   k = 0: albedo rgb (diffuse for Lambertian, specular for glass and mirror, white for no material), fraction of rays that hit
+//   k = 1: shading normal xyz (object_normal), hit distance t
+//   k = 2: hit position xyz (o + d * t), luminance of the material's emission
+template<int STACK_LDS, bool IN_LDS>
+__global__ __launch_bounds__(256) void pt_feature_kernel(PtDevScene sc, PtDevCamera cam, int32_t width, int32_t height, float4 *__restrict__ out, uint2 *__restrict__ spill,
+                                                         uint32_t spill_depth) {
+    extern __shared__ __align__(16) unsigned char lds_raw[];
+    const int tid = threadIdx.x;
+    lds_u2_ptr stack_l = (lds_u2_ptr)reinterpret_cast<uint2 *>(lds_raw) + tid;
+    float4 *lds_recs = reinterpret_cast<float4 *>(lds_raw + (size_t)STACK_LDS * 256 * sizeof(uint2));
+    if(IN_LDS) {
+        for(uint32_t i = tid; i < 4u * (sc.pair_base + sc.n_pairs); i += 256) {
+            lds_recs[i] = sc.recs[i];
+        }
+        __syncthreads();
+    }
+    Tracer<STACK_LDS, IN_LDS> tr;
+    if(IN_LDS) {
+        tr.recs = (typename RecPtr<IN_LDS>::type)(lds_f4_cptr)lds_recs;
+    }
+    else {
+        tr.recs = (typename RecPtr<IN_LDS>::type)(glb_f4_cptr)sc.recs;
+    }
+    tr.stack_l = stack_l;
+    const size_t gid = (size_t)blockIdx.x * 256 + tid;
+    tr.my_spill = (glb_u2_ptr)(spill + gid * spill_depth);
+    if(gid >= (size_t)width * (size_t)height) {
+        return;
+    }
+    const int32_t px = (int32_t)(gid % (size_t)width), py = (int32_t)(gid / (size_t)width);
+    RootBox root;
+    root.ref = sc.root_ref;
+    for(int k = 0; k < 3; k++) {
+        root.lo[k] = sc.root_lo[k];
+        root.hi[k] = sc.root_hi[k];
+    }
+    float4 acc0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), acc1 = acc0, acc2 = acc0, emis = acc0;
+    for(int k = 0; k < 4; k++) {
+        const float dx = (k & 1) ? 0.25f : -0.25f, dy = (k & 2) ? 0.25f : -0.25f;
+        // the camera ray of the path kernel (worker.cpp:166-168) with x + 1/2 + dx in place of x + 1/2
+        const float one_half = 1.0f / 2.0f;
+        const float x_camera = 2 * (((float)px + one_half + dx) / (float)width - one_half);
+        float y_camera = 2 * (((float)py + one_half + dy) / (float)height - one_half);
+        y_camera = -y_camera;
+        uint64_t rng = 0; // (drawn from, never used: both offsets are +0 and there is no aperture)
+        const Ray ray = camera_shoot(cam, x_camera, y_camera, 0.0f, 0.0f, rng);
+        Walk w;
+        typename Tracer<STACK_LDS, IN_LDS>::Rec rec;
+        rec.r0 = rec.r1 = rec.r2 = rec.r3 = (f4v){0.0f, 0.0f, 0.0f, 0.0f};
+        tr.start(w, rec, root, make_float4(ray.o.x, ray.o.y, ray.o.z, 0.0f), make_float4(ray.d.x, ray.d.y, ray.d.z, __uint_as_float(0u)));
+        uint32_t n_nodes = 0, n_leaves = 0;
+        while(tr.step(w, rec, 1, n_nodes, n_leaves)) {
+        }
+        float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), n4 = a, p4 = a, e4 = a;
+        if(w.best_ref != PT_REF_NONE) {
+            const float t = w.best_t;
+            const V3 pos = ray.o + ray.d * t;
+            uint32_t material_index;
+            const V3 n = object_normal(sc, w.best_ref, pos, material_index);
+            const Material mat = material_load(sc.materials, material_index);
+            const bool lambertian = mat.bsdf == 0; // PT_BSDF_LAMBERTIAN
+            a = make_float4(lambertian ? mat.diffuse.r : mat.specular.r, lambertian ? mat.diffuse.g : mat.specular.g, lambertian ? mat.diffuse.b : mat.specular.b, 1.0f);
+            n4 = make_float4(n.x, n.y, n.z, t);
+            p4 = make_float4(pos.x, pos.y, pos.z, 0.0f);
+            e4 = make_float4(mat.emission.r, mat.emission.g, mat.emission.b, 0.0f);
+        }
+        acc0 = make_float4(acc0.x + a.x, acc0.y + a.y, acc0.z + a.z, acc0.w + a.w);
+        acc1 = make_float4(acc1.x + n4.x, acc1.y + n4.y, acc1.z + n4.z, acc1.w + n4.w);
+        acc2 = make_float4(acc2.x + p4.x, acc2.y + p4.y, acc2.z + p4.z, 0.0f);
+        emis = make_float4(emis.x + e4.x, emis.y + e4.y, emis.z + e4.z, 0.0f);
+    }
+    const float q = 0.25f;
+    const float er = emis.x * q, eg = emis.y * q, eb = emis.z * q;
+    float4 *o = out + 3 * gid;
+    o[0] = make_float4(acc0.x * q, acc0.y * q, acc0.z * q, acc0.w * q);
+    o[1] = make_float4(acc1.x * q, acc1.y * q, acc1.z * q, acc1.w * q);
+    o[2] = make_float4(acc2.x * q, acc2.y * q, acc2.z * q, (0.2126f * er + 0.7152f * eg) + 0.0722f * eb);
+}
+
 // ---- diagnostic: where the cycles of a traversal step go -------------------------------------------------------------------------------
 // One walk per lane as in pt_closest_kernel, but only the first `lanes_per_wave` lanes of every wavefront get a ray, and every step is
 // stamped (s_memtime): cycles spent waiting for the record that was requested at the end of the previous step, and everything else.
@@ -1807,6 +1890,14 @@ void launch_closest(hipStream_t stream, const PtDevScene &scene, const float *ra
     hipLaunchKernelGGL((pt_closest_kernel<STACK_LDS, IN_LDS>), dim3((n + 255) / 256), dim3(256), lds, stream, scene, rays6, n, out, cfg.spill, cfg.spill_depth);
 }
 
+template<int STACK_LDS, bool IN_LDS>
+void launch_features(hipStream_t stream, const PtDevScene &scene, const PtDevCamera &cam, int32_t width, int32_t height, float4 *out, const PtPathConfig &cfg) {
+    const size_t lds = (size_t)STACK_LDS * 256 * sizeof(uint2) + (IN_LDS ? ((size_t)scene.n_lds_pairs + scene.pair_base) * 64 : 0);
+    const size_t n = (size_t)width * (size_t)height;
+    hipLaunchKernelGGL((pt_feature_kernel<STACK_LDS, IN_LDS>), dim3((unsigned)((n + 255) / 256)), dim3(256), lds, stream, scene, cam, width, height, out, cfg.spill,
+                       cfg.spill_depth);
+}
+
 } // namespace
 
 // the instantiations of the path kernel: slot word (compact | wide) x records (HBM | LDS) x stack window (8 entries; 4 for scenes in LDS that need the room)
@@ -1891,6 +1982,21 @@ void pt_launch_closest(hipStream_t stream, const PtDevScene &scene, const float 
     }
     else {
         launch_closest<PT_PATH_STACK_LDS, false>(stream, scene, rays6, n, out, cfg);
+    }
+}
+
+void pt_launch_features(hipStream_t stream, const PtDevScene &scene, const PtDevCamera &camera, int32_t width, int32_t height, float4 *out, const PtPathConfig &cfg) {
+    if(width <= 0 || height <= 0) {
+        return;
+    }
+    if(cfg.in_lds && cfg.stack_lds == PT_PATH_STACK_LDS_SMALL) {
+        launch_features<PT_PATH_STACK_LDS_SMALL, true>(stream, scene, camera, width, height, out, cfg);
+    }
+    else if(cfg.in_lds) {
+        launch_features<PT_PATH_STACK_LDS, true>(stream, scene, camera, width, height, out, cfg);
+    }
+    else {
+        launch_features<PT_PATH_STACK_LDS, false>(stream, scene, camera, width, height, out, cfg);
     }
 }
 

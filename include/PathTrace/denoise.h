@@ -1,0 +1,26 @@
+// PathTrace/denoise.h -- feature-guided denoising of a finished frame (an extension of PathTrace/worker.h).
+#ifndef PATHTRACE_DENOISE_H
+#define PATHTRACE_DENOISE_H
+
+#include <PathTrace/camera.h>
+#include <PathTrace/image/image.h>
+#include <PathTrace/scene/scene.h>
+#include <PathTrace/worker.h>
+
+// The filter's parameters (pt_denoise_params of pt_hip.h); the defaults are SVGF's, but for sigma_luminance.  A sigma of 0 turns its term off.
+struct DenoiseParams {
+    int iterations = 5;            // a-trous passes, 0..10
+    float sigma_luminance = 32.0F; // luminance edge-stopping, in standard deviations of the local luminance
+    float sigma_normal = 128.0F;   // exponent of max(0, n_p . n_q)
+    float sigma_depth = 1.0F;      // depth edge-stopping, in units of the depth change the local gradient predicts
+};
+
+// What processJob returns when options.allow_bias is set, for callers who keep the noisy frame as well: the first-hit features of
+// camera's view of scene (4 deterministic primary rays per pixel, the aperture ignored) guide an edge-avoiding a-trous filter -- the
+// spatial part of SVGF -- over `frame`.  Computed on the scene's first device replica.  frame must be options.image_width x image_height;
+// alpha is copied.  denoise(processJob(job without bias), scene, camera, options) equals processJob(job with bias) bit for bit when
+// both renders have the same seed ($PATHTRACE_SEED).  Throws std::invalid_argument for a frame of another size or parameters outside
+// their range, std::runtime_error if the device fails.
+Image<> denoise(const Image<> &frame, const Scene &scene, const Camera &camera, const RenderOptions &options, const DenoiseParams &params = {});
+
+#endif

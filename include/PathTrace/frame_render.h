@@ -15,7 +15,8 @@
 // One frame of a FrameRenderJob, rendered in as many calls as the caller likes: every render() continues where the last one stopped
 // (its RenderControl's budget ran out or it was cancelled).  The pixels a stop catches half-way park their state on the device and resume
 // from it, so no sample is drawn twice, and the finished frame is bit for bit what processJob gives with the same seed
-// ($PATHTRACE_SEED, or a random one) on the replicas $PATHTRACE_DEVICES selects.  The job's scene must outlive the FrameRender.
+// ($PATHTRACE_SEED, or a random one) on the replicas $PATHTRACE_DEVICES selects -- without denoising: options.allow_bias is ignored (a
+// stopped frame has holes; denoise the finished frame with PathTrace/denoise.h).  The job's scene must outlive the FrameRender.
 class FrameRender {
 public:
     explicit FrameRender(const FrameRenderJob &job, int worker_count = 0);

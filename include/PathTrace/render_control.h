@@ -51,7 +51,8 @@ private:
 
 // processJob (PathTrace/worker.h) under a RenderControl: the same tiles, seeding, device replicas and progress reports.  It returns
 // normally when stopped; then control.cancelled() is true, the pixels of control.finishedTiles() are final and the others are transparent
-// black (0, 0, 0, 0) -- or partly final, if a tile was stopped halfway.  Throws std::runtime_error if the device fails.
+// black (0, 0, 0, 0) -- or partly final, if a tile was stopped halfway.  options.allow_bias is ignored: a stopped frame has holes, and is
+// never denoised.  Throws std::runtime_error if the device fails.
 Image<> processJob(
   const FrameRenderJob &job, RenderControl &control, const std::function<void(int, int)> &progress_callback = [](int, int) {}, int worker_count = 0);
 

@@ -80,7 +80,8 @@ typedef struct pt_camera_params {
     float focal_plane_dist;
 } pt_camera_params;
 
-/* RenderOptions (worker.h:14-31); allow_bias is never read by the reference and has no field here. */
+/* RenderOptions (worker.h:14-31).  allow_bias is never read by the reference and has no field here: a caller who allows bias denoises the
+ * finished frame with pt_render_features + pt_denoise (below), as the C++ processJob does. */
 typedef struct pt_options {
     int32_t image_width;
     int32_t image_height;
@@ -293,6 +294,41 @@ uint64_t pt_rng_seed_to_state(uint64_t seed);
 #define PT_POST_GAMMA 2u
 int pt_post_process(int device, float *rgba, int32_t width, int32_t height, uint32_t steps, float gamma);
 int pt_post_process_device(int device, float *d_rgba, int32_t width, int32_t height, uint32_t steps, float gamma, void *stream);
+
+/* Feature-guided denoising of a finished frame (what RenderOptions::allow_bias asks for).
+ *
+ * pt_render_features: first-hit features of every pixel of the frame `options` describes (only image_width and image_height are read).
+ * Each pixel traces 4 deterministic primary rays, at sub-pixel offsets (-1/4, -1/4), (+1/4, -1/4), (-1/4, +1/4), (+1/4, +1/4), through
+ * `camera` with its aperture sampler ignored; the rays are a pure function of camera and pixel.  out_features: [height][width][3][4] floats,
+ * each the mean over the 4 rays (a miss adds zeros):
+ *   [0] = albedo rgb (diffuse for Lambertian, specular for glass and mirror, white for PT_NO_MATERIAL), fraction of the rays that hit
+ *   [1] = shading normal xyz, hit distance t
+ *   [2] = hit position xyz, luminance (0.2126 r + 0.7152 g + 0.0722 b) of the material's emission
+ * Serialised on the scene like every render call.  The _device form writes into DEVICE memory, ordered on `stream` (a hipStream_t, NULL = the
+ * library's own stream followed by a synchronisation) as pt_render_tiles_device.
+ *
+ * pt_denoise: an edge-avoiding a-trous filter guided by those features -- the spatial part of SVGF (Schied et al. 2017): demodulate by the
+ * albedo, a per-pixel luminance variance from an edge-aware 3x3 neighbourhood, `iterations` passes of the 5x5 B3-spline kernel at step 2^i
+ * with normal, depth and luminance weights, remodulate.  rgba and out_rgba: [height][width][4] floats; out_rgba may equal rgba; alpha is
+ * copied unchanged.  fp32, deterministic, no atomics.  params NULL = pt_denoise_params_default; a sigma of 0 turns its term off.  The
+ * _device form works on DEVICE memory, ordered on `stream` (NULL = the default stream), which it synchronises before returning.  The
+ * scratch buffers belong to the library (one set per device, grown on demand, one call at a time per device).
+ * PT_ERR_INVALID before anything is uploaded or launched: a null pointer, a size <= 0, more than 0x0fffffff pixels, iterations outside
+ * 0..10, a negative or non-finite sigma. */
+typedef struct pt_denoise_params {
+    int32_t iterations;    /* a-trous passes, 0..10 */
+    float sigma_luminance; /* luminance edge-stopping, in standard deviations of the local luminance */
+    float sigma_normal;    /* exponent of max(0, n_p . n_q) */
+    float sigma_depth;     /* depth edge-stopping, in units of the depth change the local gradient predicts */
+} pt_denoise_params;
+/* 5 passes, sigma_luminance 32, sigma_normal 128, sigma_depth 1: SVGF's defaults but for sigma_luminance (4 there), which is wider here
+ * because the variance comes from one low-sample frame, not from temporal moments */
+int pt_denoise_params_default(pt_denoise_params *out);
+int pt_render_features(pt_scene *scene, const pt_camera_params *camera, const pt_options *options, float *out_features);
+int pt_render_features_device(pt_scene *scene, const pt_camera_params *camera, const pt_options *options, float *d_out_features, void *stream);
+int pt_denoise(int device, const float *rgba, const float *features, int32_t width, int32_t height, const pt_denoise_params *params, float *out_rgba);
+int pt_denoise_device(int device, const float *d_rgba, const float *d_features, int32_t width, int32_t height, const pt_denoise_params *params,
+                      float *d_out_rgba, void *stream);
 
 #ifdef __cplusplus
 }

@@ -95,6 +95,12 @@ namespace pathtrace_host {
         }
     };
 
+    // the device of a Scene's first replica: Scene::Scene creates it on $PATHTRACE_DEVICE (0 by default), src/host/scene.cpp
+    inline int sceneDevice() {
+        const char *device_env = std::getenv("PATHTRACE_DEVICE");
+        return device_env != nullptr ? std::atoi(device_env) : 0;
+    }
+
     // worker_count (worker.h:83-84; threads in the reference, 0 = as many as the machine has): at most that many of the scene's device
     // replicas take part.  Every device runs one persistent launch, so there is nothing else for the count to choose.
     inline int replicaCount(const std::vector<pt_scene *> &replicas, int worker_count) {

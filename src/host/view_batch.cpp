@@ -1,4 +1,5 @@
 // src/host/view_batch.cpp -- processViews of PathTrace/view_batch.h on top of pt_render_views (include/pt_hip.h).
+#include <PathTrace/denoise.h>
 #include <PathTrace/view_batch.h>
 
 #include "../../include/pt_hip.h"
@@ -54,6 +55,9 @@ std::vector<Image<>> processViews(const Scene &scene, const std::vector<const Ca
     check(status, "processViews");
     for(size_t v = 0; v < cameras.size(); v++) {
         std::memcpy(views[v].data(), stacked.data() + v * per_view * 4, per_view * 4 * sizeof(float));
+        if(options.allow_bias) {
+            views[v] = denoise(views[v], scene, *cameras[v], options); // as processJob denoises its frame
+        }
     }
     return views;
 }

@@ -1,4 +1,5 @@
 // src/host/worker.cpp -- processItem / processJob of PathTrace/worker.h on top of the C ABI (include/pt_hip.h).
+#include <PathTrace/denoise.h>
 #include <PathTrace/render_control.h>
 #include <PathTrace/worker.h>
 
@@ -63,6 +64,10 @@ Image<> processJob(const FrameRenderJob &job, const std::function<void(int, int)
         std::rethrow_exception(forward.failure);
     }
     check(status, "processJob");
+    if(job.options.allow_bias) {
+        // the finished frame, denoised on replica 0 (PathTrace/denoise.h)
+        return denoise(frame, job.scene, job.camera, job.options);
+    }
     return frame;
 }
 

@@ -1,0 +1,244 @@
+"""numpy float32 restatement of the feature-guided denoiser of cpupathtrace_amd/csrc/pt_denoise.hip: the definition the GPU
+filter is checked against.  Every array operation is the fp32 operation the kernels perform, in the same order; only expf, powf and the
+per-tap accumulation order of numpy's vectorised passes (the same order as the kernel's loops) are shared, so the two agree to a few ulp.
+
+Inputs: rgba (H, W, 4) and features (H, W, 3, 4) as pt_render_features writes them:
+  F0 = (albedo rgb, coverage), F1 = (normal xyz, mean t), F2 = (position xyz, luminance of the mean emission).
+"""
+import numpy as np
+
+F = np.float32
+LUM = (F(0.2126), F(0.7152), F(0.0722))
+ALBEDO_MIN = F(0.01)
+B3 = (F(1.0 / 16.0), F(1.0 / 4.0), F(3.0 / 8.0), F(1.0 / 4.0), F(1.0 / 16.0))  # 5x5 a-trous taps (B3 spline)
+G3 = (F(0.25), F(0.5), F(0.25))                                                  # 3x3 prefilter of the variance
+DEPTH_REL = F(1e-3)   # floor of the depth scale, relative to the pixel's own distance
+LUM_EPS = F(1e-10)
+
+DEFAULTS = {"iterations": 5, "sigma_luminance": 32.0, "sigma_normal": 128.0, "sigma_depth": 1.0}
+
+CLS_COVERED, CLS_EMISSIVE = 1, 2
+
+
+def lum(c):
+    return (LUM[0] * c[..., 0] + LUM[1] * c[..., 1]) + LUM[2] * c[..., 2]
+
+
+def _shift(a, dx, dy, fill=0):
+    """b[y, x] = a[y + dy, x + dx] where that lies in the image, else `fill`; and the mask of where it does."""
+    h, w = a.shape[:2]
+    b = np.full_like(a, fill)
+    m = np.zeros((h, w), bool)
+    ys, ye = max(0, -dy), min(h, h - dy)
+    xs, xe = max(0, -dx), min(w, w - dx)
+    if ys < ye and xs < xe:
+        b[ys:ye, xs:xe] = a[ys + dy:ye + dy, xs + dx:xe + dx]
+        m[ys:ye, xs:xe] = True
+    return b, m
+
+
+def prepare(rgba, features):
+    """Step 1: the demodulated colour c (rgb / max(albedo, 0.01) on covered, non-emissive pixels), its luminance, the guide (n, t), the
+    class of every pixel (bit 0 covered, bit 1 emissive) and the factor the last step multiplies by again."""
+    rgba = np.asarray(rgba, F)
+    feat = np.asarray(features, F)
+    f0, f1, f2 = feat[..., 0, :], feat[..., 1, :], feat[..., 2, :]
+    covered = f0[..., 3] > 0
+    emissive = f2[..., 3] > 0
+    cls = np.where(covered, CLS_COVERED, 0) | np.where(emissive, CLS_EMISSIVE, 0)
+    demod = covered & ~emissive
+    factor = np.where(demod[..., None], np.maximum(f0[..., :3], ALBEDO_MIN), F(1.0)).astype(F)
+    c = np.where(demod[..., None], rgba[..., :3] / factor, rgba[..., :3]).astype(F)
+    return c, lum(c).astype(F), f1.copy(), cls.astype(np.int32), factor
+
+
+def _depth_arg(t_p, t_q, gx, gy, ox, oy, sigma_depth):
+    if sigma_depth == 0:
+        return np.zeros_like(t_p)
+    scale = F(sigma_depth) * (np.abs(gx * F(ox) + gy * F(oy)) + DEPTH_REL * t_p)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.abs(t_p - t_q) / scale
+
+
+def _normal_w(g_p, g_q, sigma_normal):
+    d = (g_p[..., 0] * g_q[..., 0] + g_p[..., 1] * g_q[..., 1]) + g_p[..., 2] * g_q[..., 2]
+    return np.power(np.maximum(F(0.0), d), F(sigma_normal)).astype(F)
+
+
+def gradient(guide, cls):
+    """Screen-space gradient of t per pixel: central differences over neighbours of the same class, one-sided where only one is."""
+    t = guide[..., 3]
+    out = []
+    for dx, dy in ((1, 0), (0, 1)):
+        tn, mn = _shift(t, dx, dy)
+        cn, _ = _shift(cls, dx, dy, -1)
+        tp, mp = _shift(t, -dx, -dy)
+        cp, _ = _shift(cls, -dx, -dy, -1)
+        nxt = mn & (cn == cls)
+        prv = mp & (cp == cls)
+        g = np.where(nxt & prv, (tn - tp) * F(0.5), np.where(nxt, tn - t, np.where(prv, t - tp, F(0.0))))
+        out.append(np.where((cls & CLS_COVERED) != 0, g, F(0.0)).astype(F))
+    return out[0], out[1]
+
+
+def variance(l, guide, cls, gx, gy, sigma_normal, sigma_depth):
+    """Step 2: variance of the luminance over the edge-aware 3x3 neighbourhood (normal and depth weights, same class only)."""
+    t = guide[..., 3]
+    sw = np.zeros_like(l)
+    m1 = np.zeros_like(l)
+    m2 = np.zeros_like(l)
+    covered = (cls & CLS_COVERED) != 0
+    for dy in (-1, 0, 1):
+        for dx in (-1, 0, 1):
+            lq, m = _shift(l, dx, dy)
+            if dx == 0 and dy == 0:
+                w = np.ones_like(l)
+            else:
+                gq, _ = _shift(guide, dx, dy)
+                cq, _ = _shift(cls, dx, dy, -1)
+                ok = m & covered & (cq == cls)
+                with np.errstate(invalid="ignore", over="ignore"):
+                    w = _normal_w(guide, gq, sigma_normal) * np.exp(-_depth_arg(t, gq[..., 3], gx, gy, dx, dy, sigma_depth)).astype(F)
+                w = np.where(ok, w, F(0.0)).astype(F)
+            sw = sw + w
+            m1 = m1 + w * lq
+            m2 = m2 + w * (lq * lq)
+    mean = m1 / sw
+    return np.maximum(F(0.0), m2 / sw - mean * mean).astype(F)
+
+
+def atrous(c, l, var, guide, cls, gx, gy, step, sigma_luminance, sigma_normal, sigma_depth):
+    """Step 3, one pass at `step` pixels: the 5x5 B3 kernel times the normal, depth and luminance weights; the variance is filtered with
+    the squared weights.  Pixels that no ray hit keep their values."""
+    t = guide[..., 3]
+    covered = (cls & CLS_COVERED) != 0
+    g = np.zeros_like(var)
+    gs = np.zeros_like(var)
+    for dy in (-1, 0, 1):
+        for dx in (-1, 0, 1):
+            vq, m = _shift(var, dx, dy)
+            k = np.where(m, G3[dy + 1] * G3[dx + 1], F(0.0)).astype(F)
+            g = g + k * vq
+            gs = gs + k
+    g = g / gs
+    lum_scale = F(sigma_luminance) * np.sqrt(g) + LUM_EPS
+    sw = np.zeros_like(var)
+    sc = np.zeros_like(c)
+    sv = np.zeros_like(var)
+    for dy in (-2, -1, 0, 1, 2):
+        for dx in (-2, -1, 0, 1, 2):
+            ox, oy = dx * step, dy * step
+            h = B3[dy + 2] * B3[dx + 2]
+            cq, m = _shift(c, ox, oy)
+            lq, _ = _shift(l, ox, oy)
+            vq, _ = _shift(var, ox, oy)
+            if dx == 0 and dy == 0:
+                w = np.full_like(var, h)
+            else:
+                gq, _ = _shift(guide, ox, oy)
+                clq, _ = _shift(cls, ox, oy, -1)
+                ok = m & covered & (clq == cls)
+                with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+                    a = _depth_arg(t, gq[..., 3], gx, gy, ox, oy, sigma_depth)
+                    if sigma_luminance != 0:
+                        a = a + np.abs(l - lq) / lum_scale
+                    w = (h * _normal_w(guide, gq, sigma_normal)) * np.exp(-a).astype(F)
+                w = np.where(ok, w, F(0.0)).astype(F)
+            sw = sw + w
+            sc = sc + w[..., None] * cq
+            sv = sv + (w * w) * vq
+    c_out = (sc / sw[..., None]).astype(F)
+    v_out = (sv / (sw * sw)).astype(F)
+    c_out = np.where(covered[..., None], c_out, c)
+    v_out = np.where(covered, v_out, var)
+    return c_out, lum(c_out).astype(F), v_out
+
+
+def denoise(rgba, features, iterations=5, sigma_luminance=32.0, sigma_normal=128.0, sigma_depth=1.0):
+    """The whole filter: (H, W, 4) float32 in, (H, W, 4) float32 out; alpha is copied from the input."""
+    rgba = np.asarray(rgba, F)
+    c, l, guide, cls, factor = prepare(rgba, features)
+    gx, gy = gradient(guide, cls)
+    var = variance(l, guide, cls, gx, gy, sigma_normal, sigma_depth)
+    for i in range(iterations):
+        c, l, var = atrous(c, l, var, guide, cls, gx, gy, 1 << i, sigma_luminance, sigma_normal, sigma_depth)
+    out = np.empty_like(rgba)
+    out[..., :3] = c * factor
+    out[..., 3] = rgba[..., 3]
+    return out
+
+
+# ---- the features, restated on the host from the CPU oracle (oracle/): what pt_render_features must give bit for bit ----------------------
+
+SUBPIXEL = ((-0.25, -0.25), (0.25, -0.25), (-0.25, 0.25), (0.25, 0.25))
+
+
+def feature_rays(checker, cam, width, height):
+    """The K = 4 primary rays of every pixel, ray-major: (4, H * W, 6), made by oracle camera_shoot with the aperture ignored and no jitter."""
+    ys, xs = np.mgrid[0:height, 0:width]
+    xs, ys = xs.ravel().astype(F), ys.ravel().astype(F)
+    pinhole = dict(cam, aperture_kind=0)
+    half = F(1.0) / F(2.0)
+    out = []
+    for dx, dy in SUBPIXEL:
+        x_camera = F(2) * (((xs + half) + F(dx)) / F(width) - half)
+        y_camera = -(F(2) * (((ys + half) + F(dy)) / F(height) - half))
+        rays, _ = checker.camera_shoot(pinhole, np.stack([x_camera, y_camera], axis=1), 0.0, 0.0, np.zeros(len(xs), np.uint64))
+        out.append(rays)
+    return np.stack(out)
+
+
+def host_features(checker, scene, cam, width, height):
+    """(H, W, 3, 4) float32: per pixel the mean over the 4 rays, summed in ray order then * 0.25 (a miss adds zeros), of
+    [albedo rgb, 1], [normal xyz, t], [position xyz, -]; [2][3] = luminance of the mean emission."""
+    handle = checker.scene_create(scene)
+    kind = np.asarray(scene["obj_kind"])
+    local = np.zeros(len(kind), np.int64)  # object index -> index among the triangles / the spheres
+    for k in (0, 1):
+        sel = kind == k
+        local[sel] = np.arange(int(sel.sum()))
+    mats = np.asarray(scene["materials"])
+    n_pix = width * height
+    acc = np.zeros((3, n_pix, 4), F)
+    emis = np.zeros((n_pix, 3), F)
+    try:
+        for rays in feature_rays(checker, cam, width, height):
+            t, obj = handle.intersect(rays)
+            hit = (obj >= 0) & (t >= 0)  # (a scene of one object reports object 0 with t = -1 for a miss)
+            idx = np.nonzero(hit)[0]
+            th = t[idx]
+            pos = (rays[idx, :3] + rays[idx, 3:] * th[:, None]).astype(F)
+            nrm = np.zeros((len(idx), 3), F)
+            mat = np.zeros(len(idx), np.uint32)
+            o = obj[idx]
+            tri = kind[o] == 0
+            if tri.any():
+                ti = local[o[tri]]
+                nrm[tri] = checker.tri_normal(np.asarray(scene["tri_pos"])[ti], np.asarray(scene["tri_nrm"])[ti], pos[tri])
+                mat[tri] = np.asarray(scene["tri_material"])[ti]
+            if (~tri).any():
+                si = local[o[~tri]]
+                nrm[~tri] = checker.sphere_normal(np.asarray(scene["sph"])[si], pos[~tri])
+                mat[~tri] = np.asarray(scene["sph_material"])[si]
+            alb = np.ones((len(idx), 3), F)
+            em = np.zeros((len(idx), 3), F)
+            has = mat != 0xFFFFFFFF
+            if has.any():
+                m = mats[mat[has]]
+                alb[has] = np.where((m["bsdf"] == 0)[:, None], m["diffuse"][:, :3], m["specular"][:, :3])
+                em[has] = m["emission"][:, :3]
+            v = np.zeros((3, n_pix, 4), F)
+            v[0, idx, :3], v[0, idx, 3] = alb, F(1.0)
+            v[1, idx, :3], v[1, idx, 3] = nrm, th
+            v[2, idx, :3] = pos
+            e = np.zeros((n_pix, 3), F)
+            e[idx] = em
+            acc = (acc + v).astype(F)
+            emis = (emis + e).astype(F)
+    finally:
+        handle.close()
+    q = F(0.25)
+    out = (acc * q).astype(F)
+    me = (emis * q).astype(F)
+    out[2, :, 3] = lum(me)
+    return np.ascontiguousarray(out.transpose(1, 0, 2).reshape(height, width, 3, 4))
