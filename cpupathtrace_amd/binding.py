@@ -8,6 +8,8 @@
 ``process_views``    processJob for many cameras of one scene in one launch (include/PathTrace/view_batch.h)
 ``denoise``          feature-guided denoising of a finished frame, what RenderOptions::allow_bias asks for (include/PathTrace/denoise.h);
                      ``Scene.render_features`` gives the features, ``Scene.process_job(..., allow_bias=True)`` does both
+``TemporalDenoiser`` the same over a sequence of frames, with the history of the earlier ones reprojected (include/PathTrace/temporal_denoise.h);
+                     ``Scene.denoise_sequence`` renders the features and pushes every frame
 
 The library is the only implementation behind these calls: if it is missing or no HIP device is usable they raise.
 """
@@ -34,6 +36,9 @@ VIEW_EXPORTS = ["pt_render_views", "pt_render_views_device"]
 EXPORTS += VIEW_EXPORTS
 DENOISE_EXPORTS = ["pt_denoise_params_default", "pt_render_features", "pt_render_features_device", "pt_denoise", "pt_denoise_device"]
 EXPORTS += DENOISE_EXPORTS
+TEMPORAL_EXPORTS = ["pt_temporal_params_default", "pt_temporal_create", "pt_temporal_denoise", "pt_temporal_denoise_device", "pt_temporal_reset",
+                    "pt_temporal_destroy"]
+EXPORTS += TEMPORAL_EXPORTS
 
 
 
@@ -102,6 +107,100 @@ def denoise_device(d_rgba_ptr, d_features_ptr, width, height, d_out_ptr, stream_
     width*height*12 floats; ordered on stream_ptr (0 = the default stream), which is synchronised before the call returns."""
     _check(load().pt_denoise_device(C.c_int(device), C.c_void_p(d_rgba_ptr), C.c_void_p(d_features_ptr), C.c_int32(width), C.c_int32(height),
                                     _denoise_params(params), C.c_void_p(d_out_ptr), C.c_void_p(stream_ptr)))
+
+
+class TemporalParams(C.Structure):
+    """pt_temporal_params: the spatial filter's DenoiseParams and the temporal step's fields."""
+    _fields_ = [("spatial", DenoiseParams), ("alpha_color", C.c_float), ("alpha_moments", C.c_float), ("max_history", C.c_int32),
+                ("moments_min_history", C.c_int32), ("sigma_luminance_temporal", C.c_float), ("normal_min", C.c_float),
+                ("position_tolerance", C.c_float)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_[1:]}
+        d["spatial"] = self.spatial.as_dict()
+        return d
+
+
+def temporal_params_default():
+    """The library's default temporal parameters (pt_temporal_params_default) as a dict; "spatial" is a dict of DenoiseParams fields."""
+    p = TemporalParams()
+    _check(load().pt_temporal_params_default(C.byref(p)))
+    return p.as_dict()
+
+
+def _temporal_params(params):
+    """None = the library's defaults (a NULL pointer); otherwise a dict whose missing keys (and missing "spatial" keys) take the defaults."""
+    if params is None:
+        return None
+    unknown = set(params) - {k for k, _ in TemporalParams._fields_}
+    if unknown:
+        raise ValueError("unknown temporal parameters: %s" % ", ".join(sorted(unknown)))
+    p = TemporalParams()
+    _check(load().pt_temporal_params_default(C.byref(p)))
+    for k, v in params.items():
+        if k == "spatial":
+            unknown = set(v) - {f for f, _ in DenoiseParams._fields_}
+            if unknown:
+                raise ValueError("unknown denoise parameters: %s" % ", ".join(sorted(unknown)))
+            for f, x in v.items():
+                setattr(p.spatial, f, x)
+        else:
+            setattr(p, k, v)
+    return p
+
+
+class TemporalDenoiser:
+    """A pt_temporal handle: denoises the frames of one sequence (one static scene, one image size) one push at a time, each with the
+    reprojected history of the ones before.  params: None = defaults, or a dict of TemporalParams fields."""
+
+    def __init__(self, width, height, params=None, device=0):
+        self.width, self.height, self.device = int(width), int(height), device
+        p = _temporal_params(params)
+        h = C.c_void_p()
+        _check(load().pt_temporal_create(C.c_int(device), C.c_int32(self.width), C.c_int32(self.height), C.byref(p) if p is not None else None,
+                                         C.byref(h)))
+        self._h = h
+
+    def denoise(self, image, features, camera):
+        """One push: the (h, w, 4) frame, its (h, w, 3, 4) features and its camera (dict).  Returns (out, history): the denoised frame and
+        the (h, w) int32 history length of every pixel (0 where no ray hit, 1 where the pixel has no history)."""
+        img = np.ascontiguousarray(image, dtype=np.float32)
+        feat = np.ascontiguousarray(features, dtype=np.float32)
+        if img.shape != (self.height, self.width, 4) or feat.shape != (self.height, self.width, 3, 4):
+            raise ValueError("image must be (%d, %d, 4) and features (%d, %d, 3, 4)" % (self.height, self.width, self.height, self.width))
+        out = np.empty_like(img)
+        hist = np.empty((self.height, self.width), np.int32)
+        cp = _camera(camera)
+        _check(load().pt_temporal_denoise(self._h, _ptr(img), _ptr(feat), C.byref(cp), _ptr(out), _ptr(hist)))
+        return out, hist
+
+    def denoise_device(self, d_rgba_ptr, d_features_ptr, camera, d_out_ptr, d_history_ptr=0, stream_ptr=0):
+        """One push on device memory (e.g. torch tensors' data_ptr()): rgba and out h*w*4 floats (out may equal rgba), features h*w*12 floats,
+        history h*w int32 (0 = not written); ordered on stream_ptr (0 = the default stream), which is synchronised before the call returns."""
+        cp = _camera(camera)
+        _check(load().pt_temporal_denoise_device(self._h, C.c_void_p(d_rgba_ptr), C.c_void_p(d_features_ptr), C.byref(cp), C.c_void_p(d_out_ptr),
+                                                 C.c_void_p(d_history_ptr or None), C.c_void_p(stream_ptr)))
+
+    def reset(self):
+        """Forget the history: the next push has none."""
+        _check(load().pt_temporal_reset(self._h))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            load().pt_temporal_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
 
 class SceneDesc(C.Structure):
@@ -325,6 +424,18 @@ class Scene:
         out = np.empty((options["image_height"], options["image_width"], 3, 4), np.float32)
         cp, op = _camera(camera), _options(options)
         _check(load().pt_render_features(self._h, C.byref(cp), C.byref(op), _ptr(out)))
+        return out
+
+    def denoise_sequence(self, frames, cameras, options, params=None):
+        """Temporal denoising of a sequence of frames of this scene, frames[v] seen through cameras[v] (e.g. process_views' output): a fresh
+        TemporalDenoiser pushes every frame with its render_features; returns a (V, H, W, 4) float32 array."""
+        frames = np.asarray(frames, dtype=np.float32)
+        if len(frames) != len(cameras):
+            raise ValueError("one camera per frame")
+        out = np.empty_like(frames)
+        with TemporalDenoiser(options["image_width"], options["image_height"], params=params, device=self.device) as t:
+            for v, cam in enumerate(cameras):
+                out[v], _ = t.denoise(frames[v], self.render_features(cam, options), cam)
         return out
 
     def render_features_device(self, camera, options, d_features_ptr, stream_ptr=0):

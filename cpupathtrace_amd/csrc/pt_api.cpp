@@ -2801,3 +2801,286 @@ int pt_denoise(int device, const float *rgba, const float *features, int32_t wid
 }
 
 } // extern "C"
+
+// ---- temporal denoising of a sequence (pt_denoise.hip: pt_temporal_run) ----------------------------------------------------------------
+
+// One sequence's history and scratch, all on `device` and owned by the handle (no shared workspace: two sequences may interleave).
+struct pt_temporal {
+    int device = 0;
+    int32_t width = 0, height = 0;
+    PtTemporalParams params{};
+    std::mutex mutex;
+    DevBuf<float4> col[2], guide, col_hist, pos[2], nrm[2], in_rgba, in_features;
+    DevBuf<float> var[2];
+    DevBuf<float2> grad, moments[2];
+    DevBuf<int32_t> len[2];
+    DevBuf<uint32_t> cls[2];
+    int cur = 0;
+    bool has_prev = false;
+    PtDevCamera prev{};       // the last push's camera (its basis: all the feature rays depend on) ...
+    float prev_rows[3][3] = {}; // ... and its reprojection rows (PtReprojection)
+    PtDevCamera pending{};        // the same of the push in flight, until temporal_commit
+    float pending_rows[3][3] = {};
+};
+
+namespace {
+
+// The basis of `c` (derive_camera), its reprojection rows (PtReprojection) and its pixel footprint for images `height` pixels high;
+// PT_ERR_INVALID for a degenerate basis.
+int temporal_camera(const pt_camera_params *c, int32_t height, PtDevCamera *cam, float rows[3][3], float *footprint) {
+    const float scalars[] = {c->origin[0], c->origin[1], c->origin[2], c->look_at[0], c->look_at[1], c->look_at[2], c->up[0], c->up[1], c->up[2],
+                             c->focal_length, c->height, c->aspect_ratio};
+    for(float v : scalars) {
+        if(!std::isfinite(v)) {
+            return fail(PT_ERR_INVALID, "camera: non-finite parameter");
+        }
+    }
+    *cam = derive_camera(c);
+    const Vec3 f = ld(cam->forward), u = ld(cam->up), r = ld(cam->right);
+    Vec3 row[3] = {cross(u, r), cross(r, f), cross(f, u)}; // the inverse of [f u r], times det
+    const float det = dot(f, row[0]);
+    if(!std::isfinite(det) || det == 0.0F) {
+        return fail(PT_ERR_INVALID, "camera: degenerate basis (look_at = origin, a zero up, height, focal length or aspect ratio, or up along the view)");
+    }
+    for(int i = 0; i < 3; i++) {
+        if(det < 0.0F) { // (a negative aspect ratio): the same ratios, and "in front" stays row[0] . d > 0
+            row[i] = scale(row[i], -1.0F);
+        }
+        const float v[3] = {row[i].x, row[i].y, row[i].z};
+        for(int k = 0; k < 3; k++) {
+            if(!std::isfinite(v[k])) {
+                return fail(PT_ERR_INVALID, "camera: degenerate basis");
+            }
+            rows[i][k] = v[k];
+        }
+    }
+    *footprint = c->height / (c->focal_length * static_cast<float>(height));
+    return PT_OK;
+}
+
+int temporal_check_params(const pt_temporal_params &p) {
+    if(p.spatial.iterations < 0 || p.spatial.iterations > 10) {
+        return fail(PT_ERR_INVALID, "iterations must be 0..10");
+    }
+    for(float sigma : {p.spatial.sigma_luminance, p.spatial.sigma_normal, p.spatial.sigma_depth, p.sigma_luminance_temporal, p.position_tolerance}) {
+        if(!std::isfinite(sigma) || sigma < 0.0F) {
+            return fail(PT_ERR_INVALID, "sigmas and position_tolerance must be finite and not negative");
+        }
+    }
+    for(float a : {p.alpha_color, p.alpha_moments}) {
+        if(!(a > 0.0F && a <= 1.0F)) {
+            return fail(PT_ERR_INVALID, "alphas must be in (0, 1]");
+        }
+    }
+    if(p.max_history < 1 || p.moments_min_history < 1) {
+        return fail(PT_ERR_INVALID, "max_history and moments_min_history must be at least 1");
+    }
+    if(!std::isfinite(p.normal_min)) {
+        return fail(PT_ERR_INVALID, "normal_min must be finite");
+    }
+    return PT_OK;
+}
+
+// Checks a push's arguments without touching the handle or a device.
+int temporal_check_push(const pt_temporal *t, const void *rgba, const void *features, const pt_camera_params *camera, const void *out) {
+    if(t == nullptr || rgba == nullptr || features == nullptr || camera == nullptr || out == nullptr) {
+        return fail(PT_ERR_INVALID, "null argument");
+    }
+    PtDevCamera cam{};
+    float rows[3][3];
+    float footprint = 0.0F;
+    return temporal_camera(camera, 1, &cam, rows, &footprint);
+}
+
+// Enqueues one push on `st` (handle mutex held by the caller).  The launch rewrites the colour history, so the handle has no usable history
+// until the caller, once every copy of the push's outputs has succeeded, commits the push with temporal_commit; a failure in between leaves
+// it with none (its next push starts afresh) rather than pairing this push's camera with the last push's buffers.
+int temporal_push(pt_temporal *t, hipStream_t st, const float4 *rgba, const float4 *features, const pt_camera_params *camera, float4 *out) {
+    PtReprojection rp{};
+    PtDevCamera cam{};
+    float rows[3][3];
+    int rc = temporal_camera(camera, t->height, &cam, rows, &rp.footprint);
+    if(rc != PT_OK) {
+        return rc;
+    }
+    if(!t->has_prev) {
+        rp.mode = PT_REPROJECT_NONE;
+    }
+    else if(std::memcmp(cam.origin, t->prev.origin, sizeof cam.origin) == 0 && std::memcmp(cam.forward, t->prev.forward, sizeof cam.forward) == 0 &&
+            std::memcmp(cam.up, t->prev.up, sizeof cam.up) == 0 && std::memcmp(cam.right, t->prev.right, sizeof cam.right) == 0) {
+        rp.mode = PT_REPROJECT_IDENTICAL;
+    }
+    else { // into the previous camera
+        rp.mode = PT_REPROJECT_CAMERA;
+        std::memcpy(rp.origin, t->prev.origin, sizeof rp.origin);
+        std::memcpy(rp.row, t->prev_rows, sizeof rp.row);
+    }
+    PtDenoiseScratch s{};
+    s.col[0] = t->col[0].ptr;
+    s.col[1] = t->col[1].ptr;
+    s.var[0] = t->var[0].ptr;
+    s.var[1] = t->var[1].ptr;
+    s.guide = t->guide.ptr;
+    s.grad = t->grad.ptr;
+    PtTemporalState state{};
+    state.col_hist = t->col_hist.ptr;
+    for(int i = 0; i < 2; i++) {
+        state.moments[i] = t->moments[i].ptr;
+        state.len[i] = t->len[i].ptr;
+        state.pos[i] = t->pos[i].ptr;
+        state.nrm[i] = t->nrm[i].ptr;
+        state.cls[i] = t->cls[i].ptr;
+    }
+    state.cur = t->cur;
+    t->has_prev = false;
+    t->pending = cam;
+    std::memcpy(t->pending_rows, rows, sizeof rows);
+    PT_HIP(pt_temporal_run(st, rgba, features, t->width, t->height, t->params, rp, s, state, out));
+    return PT_OK;
+}
+
+// The push enqueued by temporal_push has completed and its outputs were read: it becomes the history of the next push.
+void temporal_commit(pt_temporal *t) {
+    t->prev = t->pending;
+    std::memcpy(t->prev_rows, t->pending_rows, sizeof t->prev_rows);
+    t->has_prev = true;
+    t->cur ^= 1;
+}
+
+} // namespace
+
+extern "C" {
+
+int pt_temporal_params_default(pt_temporal_params *out) {
+    if(out == nullptr) {
+        return fail(PT_ERR_INVALID, "null argument");
+    }
+    pt_denoise_params_default(&out->spatial);
+    out->alpha_color = 0.2F;
+    out->alpha_moments = 0.2F;
+    out->max_history = 32;
+    out->moments_min_history = 4;
+    out->sigma_luminance_temporal = 4.0F;
+    out->normal_min = 0.9F;
+    out->position_tolerance = 2.0F;
+    return PT_OK;
+}
+
+int pt_temporal_create(int device, int32_t width, int32_t height, const pt_temporal_params *params, pt_temporal **out) {
+    if(out == nullptr) {
+        return fail(PT_ERR_INVALID, "null argument");
+    }
+    *out = nullptr;
+    if(width <= 0 || height <= 0) {
+        return fail(PT_ERR_INVALID, "image size must be positive");
+    }
+    if(static_cast<long long>(width) * height > 0x0fffffffLL) {
+        return fail(PT_ERR_INVALID, "more than 0x0fffffff pixels");
+    }
+    pt_temporal_params p{};
+    pt_temporal_params_default(&p);
+    if(params != nullptr) {
+        p = *params;
+    }
+    int rc = temporal_check_params(p);
+    if(rc != PT_OK) {
+        return rc;
+    }
+    const int n_dev = device_count_quiet();
+    if(n_dev <= 0) {
+        return fail(PT_ERR_NO_DEVICE, "no HIP device available; libpathtrace_hip has no CPU path");
+    }
+    if(device < 0 || device >= n_dev) {
+        return fail(PT_ERR_NO_DEVICE, "device index out of range");
+    }
+    std::unique_ptr<pt_temporal> t(new pt_temporal());
+    t->device = device;
+    t->width = width;
+    t->height = height;
+    t->params = PtTemporalParams{PtDenoiseParams{p.spatial.iterations, p.spatial.sigma_luminance, p.spatial.sigma_normal, p.spatial.sigma_depth},
+                                 p.alpha_color, p.alpha_moments, p.max_history, p.moments_min_history, p.sigma_luminance_temporal, p.normal_min,
+                                 p.position_tolerance};
+    const size_t n = static_cast<size_t>(width) * static_cast<size_t>(height);
+    PT_HIP(hipSetDevice(device));
+    PT_HIP(t->guide.ensure(n));
+    PT_HIP(t->col_hist.ensure(n));
+    PT_HIP(t->grad.ensure(n));
+    for(int i = 0; i < 2; i++) {
+        PT_HIP(t->col[i].ensure(n));
+        PT_HIP(t->var[i].ensure(n));
+        PT_HIP(t->moments[i].ensure(n));
+        PT_HIP(t->len[i].ensure(n));
+        PT_HIP(t->pos[i].ensure(n));
+        PT_HIP(t->nrm[i].ensure(n));
+        PT_HIP(t->cls[i].ensure(n));
+    }
+    *out = t.release();
+    return PT_OK;
+}
+
+int pt_temporal_denoise(pt_temporal *t, const float *rgba, const float *features, const pt_camera_params *camera, float *out_rgba, int32_t *out_history) {
+    int rc = temporal_check_push(t, rgba, features, camera, out_rgba);
+    if(rc != PT_OK) {
+        return rc;
+    }
+    std::lock_guard<std::mutex> lock(t->mutex);
+    const size_t n = static_cast<size_t>(t->width) * static_cast<size_t>(t->height);
+    PT_HIP(hipSetDevice(t->device));
+    PT_HIP(t->in_rgba.ensure(n));
+    PT_HIP(t->in_features.ensure(3 * n));
+    PT_HIP(hipMemcpy(t->in_rgba.ptr, rgba, n * sizeof(float4), hipMemcpyHostToDevice));
+    PT_HIP(hipMemcpy(t->in_features.ptr, features, 3 * n * sizeof(float4), hipMemcpyHostToDevice));
+    // in place, as pt_denoise
+    rc = temporal_push(t, nullptr, t->in_rgba.ptr, t->in_features.ptr, camera, t->in_rgba.ptr);
+    if(rc != PT_OK) {
+        return rc;
+    }
+    PT_HIP(hipMemcpy(out_rgba, t->in_rgba.ptr, n * sizeof(float4), hipMemcpyDeviceToHost));
+    if(out_history != nullptr) {
+        PT_HIP(hipMemcpy(out_history, t->len[t->cur].ptr, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    }
+    temporal_commit(t);
+    return PT_OK;
+}
+
+int pt_temporal_denoise_device(pt_temporal *t, const float *d_rgba, const float *d_features, const pt_camera_params *camera, float *d_out_rgba,
+                               int32_t *d_out_history, void *stream) {
+    int rc = temporal_check_push(t, d_rgba, d_features, camera, d_out_rgba);
+    if(rc != PT_OK) {
+        return rc;
+    }
+    std::lock_guard<std::mutex> lock(t->mutex);
+    const size_t n = static_cast<size_t>(t->width) * static_cast<size_t>(t->height);
+    PT_HIP(hipSetDevice(t->device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    rc = temporal_push(t, st, reinterpret_cast<const float4 *>(d_rgba), reinterpret_cast<const float4 *>(d_features), camera, reinterpret_cast<float4 *>(d_out_rgba));
+    if(rc != PT_OK) {
+        return rc;
+    }
+    if(d_out_history != nullptr) {
+        PT_HIP(hipMemcpyAsync(d_out_history, t->len[t->cur].ptr, n * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+    }
+    PT_HIP(hipStreamSynchronize(st));
+    temporal_commit(t);
+    return PT_OK;
+}
+
+int pt_temporal_reset(pt_temporal *t) {
+    if(t == nullptr) {
+        return fail(PT_ERR_INVALID, "null argument");
+    }
+    std::lock_guard<std::mutex> lock(t->mutex);
+    t->has_prev = false;
+    return PT_OK;
+}
+
+int pt_temporal_destroy(pt_temporal *t) {
+    if(t == nullptr) {
+        return fail(PT_ERR_INVALID, "null argument");
+    }
+    (void)hipSetDevice(t->device);
+    delete t;
+    return PT_OK;
+}
+
+} // extern "C"

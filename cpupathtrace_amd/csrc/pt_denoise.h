@@ -25,4 +25,40 @@ struct PtDenoiseScratch {
 hipError_t pt_denoise_run(hipStream_t stream, const float4 *rgba, const float4 *features, int32_t width, int32_t height, const PtDenoiseParams &params,
                           const PtDenoiseScratch &scratch, float4 *out);
 
+// ---- the temporal form (pt_temporal_*): one push of a frame of a sequence ----------------------------------------------------------
+
+struct PtTemporalParams {
+    PtDenoiseParams spatial;
+    float alpha_color, alpha_moments;
+    int32_t max_history, moments_min_history;
+    float sigma_luminance_temporal, normal_min, position_tolerance;
+};
+
+enum { PT_REPROJECT_NONE = 0, PT_REPROJECT_IDENTICAL = 1, PT_REPROJECT_CAMERA = 2 };
+
+// Where the previous push's camera saw a point: X - origin = a forward + b up + c right, (a, b, c) = row . (X - origin) up to a positive
+// factor (rows of the inverse of [forward up right], times |det|).  Derived on the host (pt_api.cpp).
+struct PtReprojection {
+    float origin[3];
+    float row[3][3];
+    float footprint; // the current camera's pixel footprint per unit hit distance: height / (focal_length * image height)
+    int32_t mode;    // PT_REPROJECT_*: no previous push, the same camera bit for bit (each pixel is its own tap), another camera
+};
+
+// The device buffers of one temporal denoiser, width * height entries each; [cur] is written by this push, [cur ^ 1] holds the last one's.
+struct PtTemporalState {
+    float4 *col_hist;     // colour history: demodulated rgb + luminance after the first a-trous pass (read, then rewritten)
+    float2 *moments[2];   // integrated luminance moments mu1, mu2
+    int32_t *len[2];      // history length n (0 = no ray hit)
+    float4 *pos[2];       // mean hit position
+    float4 *nrm[2];       // mean normal
+    uint32_t *cls[2];     // class (as PtDenoiseScratch::cls)
+    int cur;
+};
+
+// One push: prepare, accumulate, variance, `iterations` a-trous launches (the first writes the colour history), finish.  scratch.cls is
+// not used (state.cls[cur] is).  Enqueues on `stream` and returns the launch status; it does not wait.
+hipError_t pt_temporal_run(hipStream_t stream, const float4 *rgba, const float4 *features, int32_t width, int32_t height, const PtTemporalParams &params,
+                           const PtReprojection &reprojection, const PtDenoiseScratch &scratch, const PtTemporalState &state, float4 *out);
+
 #endif

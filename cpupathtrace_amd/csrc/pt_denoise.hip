@@ -7,6 +7,11 @@
 //   atrous    one pass of the 5x5 B3-spline kernel at step 2^i with normal, depth and luminance weights (variance: squared weights)
 //   finish    rgb = c * the factor of `prepare`, alpha copied from the input
 //
+// pt_temporal_run, the temporal half of SVGF (tests/temporal_ref.py), adds one step between prepare and variance:
+//   accumulate  reproject each covered pixel into the previous push's camera, blend the history of the bilinear taps that see the same
+//               surface into c and into the luminance moments
+// and runs variance and atrous in their kTemporal form: the moments' variance and sigma_luminance_temporal where the history is long enough.
+//
 // One thread per pixel in 16 x 16 workgroups, float4 loads, fp32, no atomics: the result does not depend on the launch.  Every tap is
 // read from global memory (L1/L2 serve the overlap of neighbouring workgroups); no tile is staged in LDS.
 #include "pt_denoise.h"
@@ -19,6 +24,22 @@ namespace {
 constexpr float kAlbedoMin = 0.01f;
 constexpr float kDepthRel = 1e-3f; // floor of the depth scale, relative to the pixel's own hit distance
 constexpr float kLumEps = 1e-10f;
+constexpr float kMinHistoryWeight = 1e-3f; // below this bilinear weight of valid taps a pixel has no history
+
+// What the temporal form (pt_temporal_run) adds to the variance and a-trous kernels; unused (null) in pt_denoise's instantiation.
+struct PtTemporalPixel {
+    const int32_t *len;     // history length n of every pixel
+    const float2 *moments;  // integrated luminance moments mu1, mu2
+    int32_t min_history;    // moments_min_history
+    float sigma_luminance_temporal;
+};
+
+// the pixel's variance comes from its temporal moments: a history of moments_min_history pushes and more (and never a pixel without history,
+// so that a push without history is pt_denoise exactly)
+__device__ __forceinline__ bool temporal_variance_px(const PtTemporalPixel &tp, int p) {
+    const int32_t n = tp.len[p];
+    return n >= tp.min_history && n >= 2;
+}
 
 __device__ __forceinline__ float lum_of(float r, float g, float b) {
     return (0.2126f * r + 0.7152f * g) + 0.0722f * b;
@@ -64,9 +85,12 @@ __global__ __launch_bounds__(256) void pt_denoise_prepare_kernel(const float4 *_
     cls[p] = (covered ? PTDN_COVERED : 0u) | (emissive ? PTDN_EMISSIVE : 0u);
 }
 
+// kTemporal (pt_temporal_run): where the pixel's history is long enough (temporal_variance_px), its variance is that of the integrated
+// luminance moments instead; the spatial estimate is computed as in pt_denoise either way.
+template<bool kTemporal>
 __global__ __launch_bounds__(256) void pt_denoise_variance_kernel(const float4 *__restrict__ col, const float4 *__restrict__ guide, const uint32_t *__restrict__ cls,
                                                                   int32_t width, int32_t height, float sigma_normal, float sigma_depth, float2 *__restrict__ grad,
-                                                                  float *__restrict__ var) {
+                                                                  float *__restrict__ var, PtTemporalPixel tp) {
     const int x = blockIdx.x * 16 + threadIdx.x, y = blockIdx.y * 16 + threadIdx.y;
     if(x >= width || y >= height) {
         return;
@@ -115,13 +139,22 @@ __global__ __launch_bounds__(256) void pt_denoise_variance_kernel(const float4 *
         }
     }
     const float mean = m1 / sw;
-    var[p] = fmaxf(0.0f, m2 / sw - mean * mean);
+    float v = fmaxf(0.0f, m2 / sw - mean * mean);
+    if constexpr(kTemporal) {
+        if(temporal_variance_px(tp, p)) {
+            const float2 m = tp.moments[p];
+            v = fmaxf(0.0f, m.y - m.x * m.x);
+        }
+    }
+    var[p] = v;
 }
 
+// kTemporal: the luminance sigma is tp.sigma_luminance_temporal at pixels whose variance came from the temporal moments.
+template<bool kTemporal>
 __global__ __launch_bounds__(256) void pt_denoise_atrous_kernel(const float4 *__restrict__ col_in, const float *__restrict__ var_in, const float4 *__restrict__ guide,
                                                                 const uint32_t *__restrict__ cls, const float2 *__restrict__ grad, int32_t width, int32_t height,
                                                                 int32_t step, float sigma_luminance, float sigma_normal, float sigma_depth,
-                                                                float4 *__restrict__ col_out, float *__restrict__ var_out) {
+                                                                float4 *__restrict__ col_out, float *__restrict__ var_out, PtTemporalPixel tp) {
     const int x = blockIdx.x * 16 + threadIdx.x, y = blockIdx.y * 16 + threadIdx.y;
     if(x >= width || y >= height) {
         return;
@@ -147,7 +180,13 @@ __global__ __launch_bounds__(256) void pt_denoise_atrous_kernel(const float4 *__
         }
     }
     g = g / gs;
-    const float lum_scale = sigma_luminance * sqrtf(g) + kLumEps;
+    float sl = sigma_luminance;
+    if constexpr(kTemporal) {
+        if(temporal_variance_px(tp, p)) {
+            sl = tp.sigma_luminance_temporal;
+        }
+    }
+    const float lum_scale = sl * sqrtf(g) + kLumEps;
     const float4 gp = guide[p];
     const float2 gr = grad[p];
     const float lp = col_in[p].w;
@@ -168,7 +207,7 @@ __global__ __launch_bounds__(256) void pt_denoise_atrous_kernel(const float4 *__
             else if(cls[q] == cp) {
                 const float4 gq = guide[q];
                 float a = depth_arg(gp.w, gq.w, gr, (float)ox, (float)oy, sigma_depth);
-                if(sigma_luminance != 0.0f) {
+                if(sl != 0.0f) {
                     a = a + fabsf(lp - col_in[q].w) / lum_scale;
                 }
                 w = (h * normal_weight(gp, gq, sigma_normal)) * expf(-a);
@@ -187,6 +226,137 @@ __global__ __launch_bounds__(256) void pt_denoise_atrous_kernel(const float4 *__
     const float r = sr / sw, gg = sg / sw, b = sb / sw;
     col_out[p] = make_float4(r, gg, b, lum_of(r, gg, b));
     var_out[p] = sv / (sw * sw);
+}
+
+// the previous push's history, as the temporal step reads it
+struct PtTemporalPrev {
+    const float4 *col;
+    const float2 *moments;
+    const int32_t *len;
+    const float4 *pos, *nrm;
+    const uint32_t *cls;
+};
+
+struct PtTemporalBlend {
+    float alpha_color, alpha_moments;
+    int32_t max_history;
+    float normal_min, position_tolerance;
+};
+
+__device__ __forceinline__ float dot3(float ax, float ay, float az, float bx, float by, float bz) {
+    return (ax * bx + ay * by) + az * bz;
+}
+
+// Temporal step of pt_temporal_run: reprojects every covered pixel's first-hit position into the previous push's camera, gathers the
+// previous push's history at the 2x2 bilinear taps that see the same surface, and blends.  Only + - * /, one square root and comparisons,
+// all correctly rounded (the build has -ffp-contract=off), so the history lengths equal tests/temporal_ref.py's exactly.
+__global__ __launch_bounds__(256) void pt_temporal_accumulate_kernel(const float4 *__restrict__ feat, const float4 *__restrict__ col_in,
+                                                                     const uint32_t *__restrict__ cls, int32_t width, int32_t height, PtReprojection rp,
+                                                                     PtTemporalPrev prev, PtTemporalBlend bl, float4 *__restrict__ col_out,
+                                                                     float2 *__restrict__ mom_out, int32_t *__restrict__ len_out, float4 *__restrict__ pos_out,
+                                                                     float4 *__restrict__ nrm_out) {
+    const int x = blockIdx.x * 16 + threadIdx.x, y = blockIdx.y * 16 + threadIdx.y;
+    if(x >= width || y >= height) {
+        return;
+    }
+    const int p = y * width + x;
+    const float4 c = col_in[p];
+    const float l = c.w;
+    const uint32_t cp = cls[p];
+    if(!(cp & PTDN_COVERED)) { // no ray hit: the input stays, no history
+        col_out[p] = c;
+        mom_out[p] = make_float2(l, l * l);
+        len_out[p] = 0;
+        pos_out[p] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        nrm_out[p] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        return;
+    }
+    const float4 f0 = feat[3 * p], f1 = feat[3 * p + 1], f2 = feat[3 * p + 2];
+    const float cov = f0.w;
+    const float X = f2.x / cov, Y = f2.y / cov, Z = f2.z / cov;          // mean hit position of the rays that hit
+    const float t = f1.w / cov;                                          // ... and hit distance
+    const float len2 = dot3(f1.x, f1.y, f1.z, f1.x, f1.y, f1.z);         // their mean normal at unit length (a pixel on an edge matches itself)
+    const float inv = 1.0f / sqrtf(len2);
+    const float nx = len2 > 0.0f ? f1.x * inv : 0.0f, ny = len2 > 0.0f ? f1.y * inv : 0.0f, nz = len2 > 0.0f ? f1.z * inv : 0.0f;
+    pos_out[p] = make_float4(X, Y, Z, 0.0f);
+    nrm_out[p] = make_float4(nx, ny, nz, 0.0f);
+
+    float px = 0.0f, py = 0.0f;
+    bool found = false;
+    if(rp.mode == PT_REPROJECT_IDENTICAL) {
+        px = (float)x;
+        py = (float)y;
+        found = true;
+    }
+    else if(rp.mode == PT_REPROJECT_CAMERA) {
+        // X - origin = a forward + b up + c right; the rows are the inverse of [forward up right] times |det|
+        const float dx = X - rp.origin[0], dy = Y - rp.origin[1], dz = Z - rp.origin[2];
+        const float a = dot3(dx, dy, dz, rp.row[0][0], rp.row[0][1], rp.row[0][2]);
+        const float b = dot3(dx, dy, dz, rp.row[1][0], rp.row[1][1], rp.row[1][2]);
+        const float cc = dot3(dx, dy, dz, rp.row[2][0], rp.row[2][1], rp.row[2][2]);
+        if(a > 0.0f) { // in front of the previous camera
+            const float xc = cc / a, yc = b / a;
+            // worker.cpp: x_camera = 2 ((x + 1/2) / W - 1/2), y_camera = -2 ((y + 1/2) / H - 1/2)
+            px = (xc * 0.5f + 0.5f) * (float)width - 0.5f;
+            py = (0.5f - yc * 0.5f) * (float)height - 0.5f;
+            found = px > -2.0f && px < (float)width + 1.0f && py > -2.0f && py < (float)height + 1.0f; // (false for NaN)
+        }
+    }
+    int32_t n = 1;
+    float sw = 0.0f, sr = 0.0f, sg = 0.0f, sb = 0.0f, s1 = 0.0f, s2 = 0.0f;
+    if(found) {
+        const int x0 = (int)floorf(px), y0 = (int)floorf(py);
+        const float fx = px - (float)x0, fy = py - (float)y0;
+        const float r = bl.position_tolerance * (t * rp.footprint);
+        const float r2 = r * r;
+        int32_t nmax = 0;
+        for(int k = 0; k < 4; k++) {
+            const int ox = k & 1, oy = k >> 1;
+            const float w = (ox ? fx : 1.0f - fx) * (oy ? fy : 1.0f - fy);
+            const int qx = x0 + ox, qy = y0 + oy;
+            if(!(w > 0.0f) || qx < 0 || qy < 0 || qx >= width || qy >= height) {
+                continue;
+            }
+            const int q = qy * width + qx;
+            if(prev.cls[q] != cp) {
+                continue;
+            }
+            const float4 nq = prev.nrm[q];
+            if(!(dot3(nx, ny, nz, nq.x, nq.y, nq.z) >= bl.normal_min)) {
+                continue;
+            }
+            const float4 xq = prev.pos[q];
+            const float ex = X - xq.x, ey = Y - xq.y, ez = Z - xq.z;
+            if(!(dot3(ex, ey, ez, ex, ey, ez) <= r2)) {
+                continue;
+            }
+            const float4 hc = prev.col[q];
+            const float2 hm = prev.moments[q];
+            sw = sw + w;
+            sr = sr + w * hc.x;
+            sg = sg + w * hc.y;
+            sb = sb + w * hc.z;
+            s1 = s1 + w * hm.x;
+            s2 = s2 + w * hm.y;
+            nmax = max(nmax, prev.len[q]);
+        }
+        if(!(sw < kMinHistoryWeight)) {
+            n = min(1 + nmax, bl.max_history);
+        }
+    }
+    len_out[p] = n;
+    if(n == 1) { // no history: the current frame as it is
+        col_out[p] = c;
+        mom_out[p] = make_float2(l, l * l);
+        return;
+    }
+    const float inv_n = 1.0f / (float)n;
+    const float ac = fmaxf(inv_n, bl.alpha_color), am = fmaxf(inv_n, bl.alpha_moments);
+    const float r = (1.0f - ac) * (sr / sw) + ac * c.x;
+    const float g = (1.0f - ac) * (sg / sw) + ac * c.y;
+    const float b = (1.0f - ac) * (sb / sw) + ac * c.z;
+    col_out[p] = make_float4(r, g, b, lum_of(r, g, b));
+    mom_out[p] = make_float2((1.0f - am) * (s1 / sw) + am * l, (1.0f - am) * (s2 / sw) + am * (l * l));
 }
 
 // (rgba and out may be the same array: no __restrict__ on them)
@@ -215,14 +385,49 @@ hipError_t pt_denoise_run(hipStream_t stream, const float4 *rgba, const float4 *
                           const PtDenoiseScratch &s, float4 *out) {
     const dim3 block(16, 16), grid((width + 15) / 16, (height + 15) / 16);
     hipLaunchKernelGGL(pt_denoise_prepare_kernel, grid, block, 0, stream, rgba, features, width, height, s.col[0], s.guide, s.cls);
-    hipLaunchKernelGGL(pt_denoise_variance_kernel, grid, block, 0, stream, s.col[0], s.guide, s.cls, width, height, params.sigma_normal, params.sigma_depth,
-                       s.grad, s.var[0]);
+    hipLaunchKernelGGL(pt_denoise_variance_kernel<false>, grid, block, 0, stream, s.col[0], s.guide, s.cls, width, height, params.sigma_normal,
+                       params.sigma_depth, s.grad, s.var[0], PtTemporalPixel{});
     int cur = 0;
     for(int i = 0; i < params.iterations; i++) {
-        hipLaunchKernelGGL(pt_denoise_atrous_kernel, grid, block, 0, stream, s.col[cur], s.var[cur], s.guide, s.cls, s.grad, width, height, 1 << i,
-                           params.sigma_luminance, params.sigma_normal, params.sigma_depth, s.col[cur ^ 1], s.var[cur ^ 1]);
+        hipLaunchKernelGGL(pt_denoise_atrous_kernel<false>, grid, block, 0, stream, s.col[cur], s.var[cur], s.guide, s.cls, s.grad, width, height, 1 << i,
+                           params.sigma_luminance, params.sigma_normal, params.sigma_depth, s.col[cur ^ 1], s.var[cur ^ 1], PtTemporalPixel{});
         cur ^= 1;
     }
     hipLaunchKernelGGL(pt_denoise_finish_kernel, grid, block, 0, stream, s.col[cur], rgba, features, width, height, out);
+    return hipGetLastError();
+}
+
+hipError_t pt_temporal_run(hipStream_t stream, const float4 *rgba, const float4 *features, int32_t width, int32_t height, const PtTemporalParams &params,
+                           const PtReprojection &reprojection, const PtDenoiseScratch &scratch, const PtTemporalState &state, float4 *out) {
+    const dim3 block(16, 16), grid((width + 15) / 16, (height + 15) / 16);
+    const int cur = state.cur, prv = state.cur ^ 1;
+    PtDenoiseScratch s = scratch;
+    s.cls = state.cls[cur];
+    // prepare -> col[1]; integrate -> col[0]; a-trous pass 0 -> the colour history; passes 1.. alternate col[1], col[0], ...
+    hipLaunchKernelGGL(pt_denoise_prepare_kernel, grid, block, 0, stream, rgba, features, width, height, s.col[1], s.guide, s.cls);
+    const PtTemporalPrev prev{state.col_hist, state.moments[prv], state.len[prv], state.pos[prv], state.nrm[prv], state.cls[prv]};
+    const PtTemporalBlend bl{params.alpha_color, params.alpha_moments, params.max_history, params.normal_min, params.position_tolerance};
+    hipLaunchKernelGGL(pt_temporal_accumulate_kernel, grid, block, 0, stream, features, s.col[1], s.cls, width, height, reprojection, prev, bl, s.col[0],
+                       state.moments[cur], state.len[cur], state.pos[cur], state.nrm[cur]);
+    const PtTemporalPixel tp{state.len[cur], state.moments[cur], params.moments_min_history, params.sigma_luminance_temporal};
+    const PtDenoiseParams &sp = params.spatial;
+    hipLaunchKernelGGL(pt_denoise_variance_kernel<true>, grid, block, 0, stream, s.col[0], s.guide, s.cls, width, height, sp.sigma_normal, sp.sigma_depth,
+                       s.grad, s.var[0], tp);
+    const float4 *col = s.col[0];
+    int v = 0;
+    for(int i = 0; i < sp.iterations; i++) {
+        float4 *dst = i == 0 ? state.col_hist : s.col[i & 1];
+        hipLaunchKernelGGL(pt_denoise_atrous_kernel<true>, grid, block, 0, stream, col, s.var[v], s.guide, s.cls, s.grad, width, height, 1 << i,
+                           sp.sigma_luminance, sp.sigma_normal, sp.sigma_depth, dst, s.var[v ^ 1], tp);
+        col = dst;
+        v ^= 1;
+    }
+    if(sp.iterations == 0) { // the integrated colour is the history
+        const hipError_t e = hipMemcpyAsync(state.col_hist, s.col[0], static_cast<size_t>(width) * height * sizeof(float4), hipMemcpyDeviceToDevice, stream);
+        if(e != hipSuccess) {
+            return e;
+        }
+    }
+    hipLaunchKernelGGL(pt_denoise_finish_kernel, grid, block, 0, stream, col, rgba, features, width, height, out);
     return hipGetLastError();
 }

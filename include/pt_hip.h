@@ -330,6 +330,47 @@ int pt_denoise(int device, const float *rgba, const float *features, int32_t wid
 int pt_denoise_device(int device, const float *d_rgba, const float *d_features, int32_t width, int32_t height, const pt_denoise_params *params,
                       float *d_out_rgba, void *stream);
 
+/* Temporal denoising of a sequence of frames of one static scene (a camera path, a turntable): the temporal half of SVGF (Schied et al. 2017)
+ * in front of pt_denoise's spatial filter.  A pt_temporal handle keeps the history of the frames pushed so far, on its own
+ * device buffers (two handles may be interleaved).  Each push of a frame, its pt_render_features and its camera:
+ *   - reprojects every covered pixel's mean hit position into the previous push's camera (a pinhole: the feature rays ignore the aperture)
+ *     and takes the 2x2 bilinear taps there.  A tap is kept if it lies in the image, has the pixel's class (covered, emissive), a normal with
+ *     dot >= normal_min and a position within position_tolerance pixel footprints (hit distance * height / (focal_length * image height)).
+ *     A camera equal to the previous one bit for bit makes each pixel its own tap.
+ *   - blends the demodulated colour and the luminance moments with the kept taps' history, weights renormalised:
+ *     (1 - a) h + a x, a = max(1/n, alpha), n = min(1 + the taps' longest history, max_history); n = 1 (no valid tap) keeps x.
+ *   - filters as pt_denoise with params.spatial, but where n >= max(2, moments_min_history) the luminance variance is mu2 - mu1^2 of the
+ *     moments and the luminance sigma is sigma_luminance_temporal.  The output of the first a-trous pass is the next push's colour history.
+ * A push without history (the first, the first after pt_temporal_reset, or one whose every tap was rejected) equals pt_denoise(params.spatial)
+ * bit for bit.  rgba, features, out_rgba as for pt_denoise (out_rgba may equal rgba); out_history (may be NULL): [height][width] int32 n,
+ * 0 where no ray hit.  fp32, deterministic, no atomics.  The _device form takes DEVICE memory and is ordered on `stream` (NULL = the default
+ * stream), which it synchronises before returning.  Calls on one handle are serialised.
+ * PT_ERR_INVALID before anything touches a device: a null pointer, a size <= 0 or above 0x0fffffff pixels, an alpha outside (0, 1],
+ * max_history or moments_min_history < 1, spatial parameters pt_denoise refuses, a negative or non-finite sigma_luminance_temporal or
+ * position_tolerance, a non-finite normal_min, or a camera whose basis is degenerate (non-finite, or forward, up and right not independent). */
+typedef struct pt_temporal_params {
+    pt_denoise_params spatial;      /* the spatial filter of every push */
+    float alpha_color;              /* lower bound of the colour's blend weight, (0, 1] */
+    float alpha_moments;            /* ... of the luminance moments', (0, 1] */
+    int32_t max_history;            /* history length cap, >= 1 */
+    int32_t moments_min_history;    /* history length from which the variance is temporal, >= 1 */
+    float sigma_luminance_temporal; /* luminance sigma at those pixels */
+    float normal_min;               /* least dot product of the normals of a kept tap */
+    float position_tolerance;       /* largest distance of a kept tap's position, in pixel footprints */
+} pt_temporal_params;
+/* spatial = pt_denoise_params_default, alpha_color = alpha_moments = 0.2, max_history 32, moments_min_history 4 (SVGF's), and
+ * sigma_luminance_temporal 4, normal_min 0.9, position_tolerance 2 */
+int pt_temporal_params_default(pt_temporal_params *out);
+typedef struct pt_temporal pt_temporal;
+/* params NULL = pt_temporal_params_default */
+int pt_temporal_create(int device, int32_t width, int32_t height, const pt_temporal_params *params, pt_temporal **out);
+int pt_temporal_denoise(pt_temporal *t, const float *rgba, const float *features, const pt_camera_params *camera, float *out_rgba, int32_t *out_history);
+int pt_temporal_denoise_device(pt_temporal *t, const float *d_rgba, const float *d_features, const pt_camera_params *camera, float *d_out_rgba,
+                               int32_t *d_out_history, void *stream);
+/* forgets the history: the next push has none */
+int pt_temporal_reset(pt_temporal *t);
+int pt_temporal_destroy(pt_temporal *t);
+
 #ifdef __cplusplus
 }
 #endif
