@@ -2,7 +2,7 @@
 """bench.py -- Msamples/s of the hot path (processJob) on N MI355X, one process per GPU.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload dragon|dragons16|cornell|box] [--spp S] [--mesh-n M]
-                    [--scaling weak|strong] [--size PIXELS] [--dump-outputs DIR]
+                    [--scaling weak|strong] [--size PIXELS] [--dump-outputs DIR] [--full]
 
 Metric (BASELINE.json / reference benchmark/main.cpp:20,30): Msamples/s = image_width * image_height * spp / wall seconds
 of processJob with min_sample_count == max_sample_count == spp; one sample = one camera path with all its bounces and
@@ -10,7 +10,7 @@ shadow rays.  A "step" is one whole processJob of the workload's frame.  Default
 DragonBox scene (benchmark/main.cpp:59-105) with the procedural 7.2 M-triangle stand-in for assets/xyzrgb_dragon.obj
 (absent from the reference mount), 1024 x 1024, 1024 spp.
 
-N > 1 renders the SAME frame (strong scaling: the metric is quoted on one frame, BASELINE.json) unless --scaling weak is given, and then
+N > 1 renders the SAME frame (strong scaling: the metric is quoted on one frame, BASELINE.json) unless --scaling weak is given, and with --full
 adds one step of the weak-scaling frame (sqrt(N) times the resolution per side) under "weak" in the JSON line.  One process per GPU over RCCL.  Started either by the launcher (`python -m torch.distributed.run --nproc-per-node N
 bench.py --gpus N ...`: RANK / LOCAL_RANK / WORLD_SIZE come from the environment) or directly (`python bench.py --gpus N`):
 then this process starts the N ranks itself as child processes BEFORE anything touches a GPU, hands them RANK / LOCAL_RANK /
@@ -24,6 +24,11 @@ gathered to rank 0 over RCCL at the end of every step (the multi-GPU form of doW
   --scaling weak   the same view at sqrt(N) times the resolution per side (1448, 2048, 2896 pixels for 2, 4, 8 GPUs):
                    every GPU renders `size`^2 pixels of interleaved 32x32 tiles with the same per-pixel work.
 Inputs are synthetic (procedural mesh), resident in HBM before the timed region; scene build/upload is reported separately.
+
+A plain run does only what the headline figure needs: it builds the scene, warms up, times the steps, writes --dump-outputs and prints
+the line (with `roofline`, which is derived from the last timed step's own counters and runs nothing).  --full adds what takes runs of
+its own: the CPU baseline on the host (`cpu_baseline`, --cpu-seconds) and, at N > 1 on the fixed frame, the step of the weak-scaling
+frame (`weak`).
 
 Prints ONE JSON line on rank 0.
 """
@@ -189,13 +194,15 @@ def parse_args(argv=None):
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default="dragon")
     ap.add_argument("--scaling", choices=["weak", "strong"], default="strong")
-    ap.add_argument("--no-weak-extra", action="store_true", help="N > 1, strong: skip the extra step of the weak-scaling frame")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline figure does not need: the CPU baseline (N = 1) and the "
+                    "extra step of the weak-scaling frame (N > 1, strong)")
+    ap.add_argument("--no-weak-extra", action="store_true", help="N > 1, strong, --full: skip the extra step of the weak-scaling frame")
     ap.add_argument("--size", type=int, default=1024, help="pixels per side: at one GPU (weak: sqrt(N) times as many at N GPUs) or of the fixed frame (strong)")
     ap.add_argument("--spp", type=int, default=1024)
     ap.add_argument("--min-spp", type=int, default=0, help="min_sample_count (0 = --spp: the metric's fixed sample count); below --spp the per-pixel estimator may stop early "
                     "(src/worker.cpp:239-259) and the value is on the max-spp basis, as the reference's benchmark counts items (benchmark/main.cpp:30)")
     ap.add_argument("--mesh-n", type=int, default=1900, help="stand-in mesh resolution (nu = nv); 1900 -> 7.2 M triangles")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="CPU baseline budget (0 = skip)")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="CPU baseline budget with --full (0 = skip)")
     ap.add_argument("--seed", type=int, default=1234)
     ap.add_argument("--frame-out", default=None, help="rank 0 writes the last gathered frame here as .npy (tests)")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
@@ -379,10 +386,10 @@ def run_rank(args):
         return time.perf_counter() - t_begin, st
 
     elapsed, stats = timed(job, args.warmup, args.steps)
-    # N > 1 on the metric's fixed frame: one more step on the weak-scaling frame (the same view at sqrt(N) times the resolution per side,
-    # the same pixels per GPU as the one-GPU run), reported under "weak" -- never as `value`
+    # --full, N > 1 on the metric's fixed frame: one more step on the weak-scaling frame (the same view at sqrt(N) times the resolution per
+    # side, the same pixels per GPU as the one-GPU run), reported under "weak" -- never as `value`
     weak = None
-    if world > 1 and args.scaling == "strong" and not args.no_weak_extra:
+    if args.full and world > 1 and args.scaling == "strong" and not args.no_weak_extra:
         w2, h2 = frame_for(world, args.size, "weak")
         from cpupathtrace_amd import scenes as _scenes
         opt2 = _scenes.options(w2, h2, args.min_spp or args.spp, args.spp)
@@ -440,7 +447,7 @@ def run_rank(args):
             out["weak"] = weak
         if stats is not None:
             out["roofline"] = roofline(stats, args, value, world)
-        if world == 1 and args.cpu_seconds > 0 and not standin:
+        if args.full and world == 1 and args.cpu_seconds > 0 and not standin:
             out["cpu_baseline"] = cpu_baseline(sc, cam, opt, args.cpu_seconds)
         os.write(result_fd, (json.dumps(out) + "\n").encode())
 

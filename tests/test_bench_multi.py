@@ -45,10 +45,10 @@ def _check(line, frame_path, world, side, scaling):
 
 @pytest.mark.parametrize("scaling,side", [("weak", 88), ("strong", 64), (None, 64)])
 def test_bench_spawns_its_own_ranks(tmp_path, scaling, side):
-    """Without --scaling an N > 1 run is on the metric's fixed frame (strong) and carries the weak-scaling frame as an extra field."""
+    """Without --scaling an N > 1 run is on the metric's fixed frame (strong); with --full it carries the weak-scaling frame as an extra field."""
     frame = str(tmp_path / "frame.npy")
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--size", "64", "--spp", "1", "--steps", "1", "--warmup", "1"] + (["--scaling", scaling] if scaling else []) +
-                       ["--frame-out", frame], env=_env(), capture_output=True, text=True, timeout=300)
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--size", "64", "--spp", "1", "--steps", "1", "--warmup", "1", "--full"] +
+                       (["--scaling", scaling] if scaling else []) + ["--frame-out", frame], env=_env(), capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, "exactly one JSON line"
@@ -76,6 +76,7 @@ def test_bench_under_the_launcher(tmp_path):
     _check(lines[0], frame, 2, 64, "strong")
     out = json.loads(lines[0])
     assert out["steps"] == 2 and out["ms_per_step"] > 0
+    assert "weak" not in out, "a run without --full times the headline frame only"
     assert os.listdir(str(tmp_path / "dump")) == ["image.npy"]
     assert np.array_equal(np.load(str(tmp_path / "dump" / "image.npy")), _expected(64, 64, 1234)), "--dump-outputs holds the gathered frame"
 

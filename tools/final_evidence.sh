@@ -5,7 +5,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 out=gpurun_out/final
 rm -rf $out; mkdir -p $out
 export PYTHONUNBUFFERED=1
-PT_DEBUG=1 timeout -k 10 500 python3 bench.py > $out/bench.json 2> $out/bench.log || { echo "bench failed"; tail -5 $out/bench.log; exit 1; }
+PT_DEBUG=1 timeout -k 10 500 python3 bench.py --full > $out/bench.json 2> $out/bench.log || { echo "bench failed"; tail -5 $out/bench.log; exit 1; }
 echo "bench done"; cat $out/bench.json
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof -- python3 bench.py --cpu-seconds 0 > $out/under_rocprof.json 2> $out/under_rocprof.log || { echo "rocprof failed"; tail -5 $out/under_rocprof.log; exit 1; }
 cp $(find $out/prof -name "*kernel_stats.csv" | head -1) $out/kernel_stats.csv
