@@ -5,6 +5,7 @@
 ``process_job``      processJob(FrameRenderJob)                    (include/PathTrace/worker.h:83-84)
 ``process_job_controlled``  processJob that can be cancelled or given a time budget (include/PathTrace/render_control.h)
 ``Frame``            a controlled processJob that can be continued: each call resumes where the last one stopped (include/PathTrace/frame_render.h)
+                     ``Frame.preview`` shows it between two calls, optionally denoised
 ``process_views``    processJob for many cameras of one scene in one launch (include/PathTrace/view_batch.h)
 ``denoise``          feature-guided denoising of a finished frame, what RenderOptions::allow_bias asks for (include/PathTrace/denoise.h);
                      ``Scene.render_features`` gives the features, ``Scene.process_job(..., allow_bias=True)`` does both
@@ -31,6 +32,8 @@ ERRORS = {1: "PT_ERR_INVALID", 2: "PT_ERR_NO_DEVICE", 3: "PT_ERR_HIP", 4: "PT_ER
 EXPORTS = ["pt_device_count", "pt_last_error", "pt_scene_create", "pt_scene_destroy", "pt_scene_info", "pt_scene_emissive", "pt_scene_bvh_dump", "pt_intersect_batch",
            "pt_render_streams", "pt_render_item", "pt_render_tiles", "pt_render_tiles_progress", "pt_render_tiles_multi", "pt_render_tiles_device", "pt_render_tiles_ctl", "pt_render_cancel", "pt_job_tiles", "pt_pixel_seed", "pt_rng_seed_to_state", "pt_post_process", "pt_post_process_device"]
 FRAME_EXPORTS = ["pt_frame_create", "pt_frame_render", "pt_frame_get_info", "pt_frame_destroy"]
+PREVIEW_EXPORTS = ["pt_frame_preview"]
+EXPORTS += PREVIEW_EXPORTS
 EXPORTS += FRAME_EXPORTS
 VIEW_EXPORTS = ["pt_render_views", "pt_render_views_device"]
 EXPORTS += VIEW_EXPORTS
@@ -578,6 +581,19 @@ class Frame:
         fi = FrameInfo()
         _check(load().pt_frame_get_info(self._h, C.byref(fi)))
         return fi.as_dict()
+
+    def preview(self, denoise=None):
+        """The frame as it stands (pt_frame_preview): (rgba, samples).  rgba (h, w, 4) float32: finished pixels as self.image, parked ones
+        the running mean of their samples so far, holes (untouched pixels) 0.  samples (h, w) int32: -1 finished, the samples a parked
+        pixel has taken, 0 a hole.  denoise: None or False = the raw preview; True = filtered with the default DenoiseParams; a dict as
+        binding.denoise takes.  Changes nothing the frame will do."""
+        if self._h is None:
+            raise ValueError("frame is closed")
+        rgba = np.empty_like(self.image)
+        samples = np.empty(self.image.shape[:2], np.int32)
+        params = None if denoise is None or denoise is False else _denoise_params({} if denoise is True else denoise)
+        _check(load().pt_frame_preview(self._h, _ptr(self.image), params, _ptr(rgba), _ptr(samples)))
+        return rgba, samples
 
     @property
     def done(self):

@@ -2122,6 +2122,14 @@ struct pt_frame {
         DevBuf<uint2> d_todo[2];
         DevBuf<PtParkRecord> d_park[2];
         DevBuf<unsigned long long> d_result;
+        // pt_frame_preview: the replica's gathered work list; on replica 0 also the frame's view and sample counts, which pixels a tile
+        // covers, the frame's first-hit features and the other replicas' entries on their way in
+        DevBuf<F4> pv_rgba, pv_view, pv_features, pv_stage_rgba;
+        DevBuf<int2> pv_at, pv_stage_at;
+        DevBuf<int32_t> pv_samples;
+        DevBuf<uint8_t> pv_cover;
+        bool pv_cover_ready = false, pv_features_ready = false;
+        bool previewed = false; // device buffers of the preview exist
     };
     pt_camera_params camera{};
     pt_options options{};
@@ -2507,7 +2515,7 @@ int pt_frame_destroy(pt_frame *f) {
         for(auto &r : f->reps) {
             // (the buffers go on the scene's device, and not while the scene's stream may still use them)
             std::lock_guard<std::mutex> lock(r->s->render_mutex);
-            if(r->ready || r->d_park[0].ptr != nullptr || r->d_park[1].ptr != nullptr) {
+            if(r->ready || r->previewed || r->d_park[0].ptr != nullptr || r->d_park[1].ptr != nullptr) {
                 (void)hipSetDevice(r->s->device);
                 (void)hipStreamSynchronize(r->s->stream);
             }
@@ -2663,17 +2671,8 @@ int denoise_ensure(DenoiseWorkspace &ws, size_t n, bool staged) {
     return PT_OK;
 }
 
-int denoise_check(int device, const void *rgba, const void *features, int32_t width, int32_t height, const pt_denoise_params *params, const void *out,
-                  PtDenoiseParams *resolved) {
-    if(rgba == nullptr || features == nullptr || out == nullptr) {
-        return fail(PT_ERR_INVALID, "null argument");
-    }
-    if(width <= 0 || height <= 0) {
-        return fail(PT_ERR_INVALID, "image size must be positive");
-    }
-    if(static_cast<long long>(width) * height > 0x0fffffffLL) {
-        return fail(PT_ERR_INVALID, "more than 0x0fffffff pixels");
-    }
+// The parameters pt_denoise takes (NULL = the defaults), checked without a device
+int denoise_params_resolve(const pt_denoise_params *params, PtDenoiseParams *resolved) {
     pt_denoise_params p{};
     pt_denoise_params_default(&p);
     if(params != nullptr) {
@@ -2687,6 +2686,26 @@ int denoise_check(int device, const void *rgba, const void *features, int32_t wi
             return fail(PT_ERR_INVALID, "sigmas must be finite and not negative");
         }
     }
+    *resolved = PtDenoiseParams{p.iterations, p.sigma_luminance, p.sigma_normal, p.sigma_depth};
+    return PT_OK;
+}
+
+int denoise_check(int device, const void *rgba, const void *features, int32_t width, int32_t height, const pt_denoise_params *params, const void *out,
+                  PtDenoiseParams *resolved) {
+    if(rgba == nullptr || features == nullptr || out == nullptr) {
+        return fail(PT_ERR_INVALID, "null argument");
+    }
+    if(width <= 0 || height <= 0) {
+        return fail(PT_ERR_INVALID, "image size must be positive");
+    }
+    if(static_cast<long long>(width) * height > 0x0fffffffLL) {
+        return fail(PT_ERR_INVALID, "more than 0x0fffffff pixels");
+    }
+    PtDenoiseParams p{};
+    const int rc = denoise_params_resolve(params, &p);
+    if(rc != PT_OK) {
+        return rc;
+    }
     const int n_dev = device_count_quiet();
     if(n_dev <= 0) {
         return fail(PT_ERR_NO_DEVICE, "no HIP device available; libpathtrace_hip has no CPU path");
@@ -2694,7 +2713,7 @@ int denoise_check(int device, const void *rgba, const void *features, int32_t wi
     if(device < 0 || device >= n_dev) {
         return fail(PT_ERR_NO_DEVICE, "device index out of range");
     }
-    *resolved = PtDenoiseParams{p.iterations, p.sigma_luminance, p.sigma_normal, p.sigma_depth};
+    *resolved = p;
     return PT_OK;
 }
 
@@ -2797,6 +2816,146 @@ int pt_denoise(int device, const float *rgba, const float *features, int32_t wid
     // in place: the last kernel reads a pixel's alpha before it writes that pixel, and no kernel reads another pixel of the input
     PT_HIP(pt_denoise_run(nullptr, ws.in_rgba, ws.in_features, width, height, p, ws.scratch, ws.in_rgba));
     PT_HIP(hipMemcpy(out_rgba, ws.in_rgba, n * sizeof(F4), hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
+int pt_frame_preview(pt_frame *f, const float *image, const pt_denoise_params *denoise, float *out_rgba, int32_t *out_samples) {
+    if(f == nullptr || image == nullptr || out_rgba == nullptr) {
+        return fail(PT_ERR_INVALID, "null argument");
+    }
+    PtDenoiseParams dp{};
+    if(denoise != nullptr) {
+        const int rc = denoise_params_resolve(denoise, &dp);
+        if(rc != PT_OK) {
+            return rc;
+        }
+    }
+    const int32_t width = f->options.image_width, height = f->options.image_height;
+    const size_t n = static_cast<size_t>(width) * static_cast<size_t>(height);
+    if(n > 0x0fffffffULL) {
+        return fail(PT_ERR_INVALID, "more than 0x0fffffff pixels");
+    }
+    std::lock_guard<std::mutex> frame_lock(f->mutex);
+    if(f->status != PT_OK) {
+        return fail(f->status, f->error);
+    }
+    bool any_ready = false;
+    for(const auto &r : f->reps) {
+        any_ready = any_ready || r->ready;
+    }
+    if(!any_ready) {
+        // before the first pt_frame_render every pixel is a hole, and a frame of holes stays one when it is filtered
+        std::memset(out_rgba, 0, n * sizeof(F4));
+        if(out_samples != nullptr) {
+            std::memset(out_samples, 0, n * sizeof(int32_t));
+        }
+        return PT_OK;
+    }
+    // 1. every replica gathers its work list on its own device; the other replicas' entries come to the host
+    const size_t n_reps = f->reps.size();
+    std::vector<std::vector<F4>> far_rgba(n_reps);
+    std::vector<std::vector<int2>> far_at(n_reps);
+    for(size_t i = 0; i < n_reps; i++) {
+        pt_frame::Replica &r = *f->reps[i];
+        if(!r.ready || r.n_todo == 0) {
+            continue;
+        }
+        pt_scene *s = r.s;
+        std::lock_guard<std::mutex> lock(s->render_mutex);
+        PT_HIP(hipSetDevice(s->device));
+        r.previewed = true;
+        PT_HIP(r.pv_rgba.ensure(r.n_todo));
+        PT_HIP(r.pv_at.ensure(r.n_todo));
+        if(pt_launch_frame_gather(s->stream, r.d_todo[r.cur].ptr, r.n_todo, r.n_parked, r.d_park[r.cur].ptr, r.d_tiles.ptr, r.d_offset.ptr,
+                                  static_cast<uint32_t>(r.tiles.size()), width, reinterpret_cast<float4 *>(r.pv_rgba.ptr), r.pv_at.ptr) != 0) {
+            PT_HIP(hipGetLastError());
+            return fail(PT_ERR_HIP, "preview: gather kernel failed to launch");
+        }
+        if(i != 0) {
+            far_rgba[i].resize(r.n_todo);
+            far_at[i].resize(r.n_todo);
+            PT_HIP(hipMemcpyAsync(far_rgba[i].data(), r.pv_rgba.ptr, r.n_todo * sizeof(F4), hipMemcpyDeviceToHost, s->stream));
+            PT_HIP(hipMemcpyAsync(far_at[i].data(), r.pv_at.ptr, r.n_todo * sizeof(int2), hipMemcpyDeviceToHost, s->stream));
+            PT_HIP(hipStreamSynchronize(s->stream));
+        }
+    }
+    // 2. replica 0's device: the caller's image, the holes no tile covers, every replica's entries over them; then the filter
+    pt_frame::Replica &r0 = *f->reps[0];
+    pt_scene *s0 = r0.s;
+    std::lock_guard<std::mutex> lock(s0->render_mutex);
+    PT_HIP(hipSetDevice(s0->device));
+    hipStream_t st = s0->stream;
+    r0.previewed = true;
+    PT_HIP(r0.pv_view.ensure(n));
+    PT_HIP(r0.pv_samples.ensure(n));
+    if(!r0.pv_cover_ready) {
+        std::vector<uint8_t> cover(n, 0);
+        for(const pt_tile &t : f->tiles) {
+            for(int32_t y = t.y; y < t.y + t.h; y++) {
+                std::memset(cover.data() + static_cast<size_t>(y) * width + t.x, 1, static_cast<size_t>(t.w));
+            }
+        }
+        PT_HIP(r0.pv_cover.upload(cover));
+        r0.pv_cover_ready = true;
+    }
+    float4 *view = reinterpret_cast<float4 *>(r0.pv_view.ptr);
+    PT_HIP(hipMemcpyAsync(view, image, n * sizeof(F4), hipMemcpyHostToDevice, st));
+    if(pt_launch_frame_preview_base(st, view, r0.pv_samples.ptr, r0.pv_cover.ptr, static_cast<uint32_t>(n)) != 0) {
+        PT_HIP(hipGetLastError());
+        return fail(PT_ERR_HIP, "preview: base kernel failed to launch");
+    }
+    for(size_t i = 0; i < n_reps; i++) {
+        const pt_frame::Replica &r = *f->reps[i];
+        if(!r.ready) {
+            // (no launch yet: every pixel of its tiles is a hole)
+            for(const pt_tile &t : r.tiles) {
+                const size_t at = static_cast<size_t>(t.y) * width + static_cast<size_t>(t.x);
+                PT_HIP(hipMemset2DAsync(view + at, width * sizeof(F4), 0, static_cast<size_t>(t.w) * sizeof(F4), static_cast<size_t>(t.h), st));
+                PT_HIP(hipMemset2DAsync(r0.pv_samples.ptr + at, width * sizeof(int32_t), 0, static_cast<size_t>(t.w) * sizeof(int32_t), static_cast<size_t>(t.h), st));
+            }
+            continue;
+        }
+        if(r.n_todo == 0) {
+            continue;
+        }
+        const float4 *rgba = reinterpret_cast<const float4 *>(r0.pv_rgba.ptr);
+        const int2 *at = r0.pv_at.ptr;
+        if(i != 0) {
+            PT_HIP(r0.pv_stage_rgba.ensure(r.n_todo));
+            PT_HIP(r0.pv_stage_at.ensure(r.n_todo));
+            PT_HIP(hipMemcpyAsync(r0.pv_stage_rgba.ptr, far_rgba[i].data(), r.n_todo * sizeof(F4), hipMemcpyHostToDevice, st));
+            PT_HIP(hipMemcpyAsync(r0.pv_stage_at.ptr, far_at[i].data(), r.n_todo * sizeof(int2), hipMemcpyHostToDevice, st));
+            rgba = reinterpret_cast<const float4 *>(r0.pv_stage_rgba.ptr);
+            at = r0.pv_stage_at.ptr;
+        }
+        if(pt_launch_frame_scatter(st, rgba, at, r.n_todo, view, r0.pv_samples.ptr) != 0) {
+            PT_HIP(hipGetLastError());
+            return fail(PT_ERR_HIP, "preview: scatter kernel failed to launch");
+        }
+    }
+    std::unique_lock<std::mutex> ws_lock;
+    if(denoise != nullptr) {
+        if(!r0.pv_features_ready) {
+            PT_HIP(r0.pv_features.ensure(3 * n));
+            const int rc = features_launch(s0, &f->camera, &f->options, reinterpret_cast<float4 *>(r0.pv_features.ptr));
+            if(rc != PT_OK) {
+                return rc;
+            }
+            r0.pv_features_ready = true;
+        }
+        DenoiseWorkspace &ws = denoise_workspace(s0->device);
+        ws_lock = std::unique_lock<std::mutex>(ws.mutex); // (held until the stream has been synchronised below)
+        const int rc = denoise_ensure(ws, n, false);
+        if(rc != PT_OK) {
+            return rc;
+        }
+        PT_HIP(pt_denoise_masked_run(st, view, reinterpret_cast<const float4 *>(r0.pv_features.ptr), r0.pv_samples.ptr, width, height, dp, ws.scratch, view));
+    }
+    PT_HIP(hipMemcpyAsync(out_rgba, view, n * sizeof(F4), hipMemcpyDeviceToHost, st));
+    if(out_samples != nullptr) {
+        PT_HIP(hipMemcpyAsync(out_samples, r0.pv_samples.ptr, n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    }
+    PT_HIP(hipStreamSynchronize(st));
     return PT_OK;
 }
 

@@ -25,6 +25,11 @@ struct PtDenoiseScratch {
 hipError_t pt_denoise_run(hipStream_t stream, const float4 *rgba, const float4 *features, int32_t width, int32_t height, const PtDenoiseParams &params,
                           const PtDenoiseScratch &scratch, float4 *out);
 
+// pt_denoise_run with holes (pt_frame_preview): a pixel whose `samples` entry is 0 is a hole, never a tap of another pixel and filled from
+// its own taps (pt_denoise.hip).  Without holes the result equals pt_denoise_run's bit for bit.  `out` may equal rgba.
+hipError_t pt_denoise_masked_run(hipStream_t stream, const float4 *rgba, const float4 *features, const int32_t *samples, int32_t width, int32_t height,
+                                 const PtDenoiseParams &params, const PtDenoiseScratch &scratch, float4 *out);
+
 // ---- the temporal form (pt_temporal_*): one push of a frame of a sequence ----------------------------------------------------------
 
 struct PtTemporalParams {

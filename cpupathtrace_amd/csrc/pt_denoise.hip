@@ -12,6 +12,14 @@
 //               surface into c and into the luminance moments
 // and runs variance and atrous in their kTemporal form: the moments' variance and sigma_luminance_temporal where the history is long enough.
 //
+// pt_denoise_masked_run, the preview of an unfinished frame (pt_frame_preview; tests/preview_ref.py), runs prepare,
+// variance, atrous and finish in their kMasked form: a pixel without samples is a HOLE (class bit PTDN_HOLE, colour 0).  A hole is of
+// another class than every pixel but holes, so it is never a tap; the 3x3 prefilter of the variance skips it too.  In every a-trous pass a
+// hole takes the normalised weighted mean of the taps of its own class that are not holes (its own weight 0, no luminance term: the normal
+// and depth terms of a covered hole, the B3 weights alone for an uncovered one), or keeps its value when no such tap has weight.  A hole's
+// variance is read by no other pixel: it records whether a pass has filled the hole (1) or not (0).  Without holes every kMasked kernel
+// computes what its plain form does, operation for operation.
+//
 // One thread per pixel in 16 x 16 workgroups, float4 loads, fp32, no atomics: the result does not depend on the launch.  Every tap is
 // read from global memory (L1/L2 serve the overlap of neighbouring workgroups); no tile is staged in LDS.
 #include "pt_denoise.h"
@@ -20,6 +28,7 @@ namespace {
 
 #define PTDN_COVERED 1u
 #define PTDN_EMISSIVE 2u
+#define PTDN_HOLE 4u // kMasked only
 
 constexpr float kAlbedoMin = 0.01f;
 constexpr float kDepthRel = 1e-3f; // floor of the depth scale, relative to the pixel's own hit distance
@@ -64,8 +73,11 @@ __device__ __forceinline__ float depth_arg(float tp, float tq, float2 g, float o
     return fabsf(tp - tq) / scale;
 }
 
+// kMasked: `samples` (the preview's sample counts) marks the holes, 0; a hole's colour is 0 whatever the input holds.
+template<bool kMasked>
 __global__ __launch_bounds__(256) void pt_denoise_prepare_kernel(const float4 *__restrict__ rgba, const float4 *__restrict__ feat, int32_t width, int32_t height,
-                                                                 float4 *__restrict__ col, float4 *__restrict__ guide, uint32_t *__restrict__ cls) {
+                                                                 const int32_t *__restrict__ samples, float4 *__restrict__ col, float4 *__restrict__ guide,
+                                                                 uint32_t *__restrict__ cls) {
     const int x = blockIdx.x * 16 + threadIdx.x, y = blockIdx.y * 16 + threadIdx.y;
     if(x >= width || y >= height) {
         return;
@@ -80,14 +92,22 @@ __global__ __launch_bounds__(256) void pt_denoise_prepare_kernel(const float4 *_
         g = g / fmaxf(f0.y, kAlbedoMin);
         b = b / fmaxf(f0.z, kAlbedoMin);
     }
-    col[p] = make_float4(r, g, b, lum_of(r, g, b));
     guide[p] = f1;
+    if constexpr(kMasked) {
+        if(samples[p] == 0) {
+            col[p] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            cls[p] = (covered ? PTDN_COVERED : 0u) | (emissive ? PTDN_EMISSIVE : 0u) | PTDN_HOLE;
+            return;
+        }
+    }
+    col[p] = make_float4(r, g, b, lum_of(r, g, b));
     cls[p] = (covered ? PTDN_COVERED : 0u) | (emissive ? PTDN_EMISSIVE : 0u);
 }
 
 // kTemporal (pt_temporal_run): where the pixel's history is long enough (temporal_variance_px), its variance is that of the integrated
 // luminance moments instead; the spatial estimate is computed as in pt_denoise either way.
-template<bool kTemporal>
+// kMasked: a hole's variance is 0 (not filled yet); its gradient is computed as any pixel's (over neighbours of its class: holes).
+template<bool kTemporal, bool kMasked>
 __global__ __launch_bounds__(256) void pt_denoise_variance_kernel(const float4 *__restrict__ col, const float4 *__restrict__ guide, const uint32_t *__restrict__ cls,
                                                                   int32_t width, int32_t height, float sigma_normal, float sigma_depth, float2 *__restrict__ grad,
                                                                   float *__restrict__ var, PtTemporalPixel tp) {
@@ -113,6 +133,12 @@ __global__ __launch_bounds__(256) void pt_denoise_variance_kernel(const float4 *
         gr = make_float2(d[0], d[1]);
     }
     grad[p] = gr;
+    if constexpr(kMasked) {
+        if(cp & PTDN_HOLE) {
+            var[p] = 0.0f;
+            return;
+        }
+    }
     float sw = 0.0f, m1 = 0.0f, m2 = 0.0f;
     for(int dy = -1; dy <= 1; dy++) {
         for(int dx = -1; dx <= 1; dx++) {
@@ -150,7 +176,8 @@ __global__ __launch_bounds__(256) void pt_denoise_variance_kernel(const float4 *
 }
 
 // kTemporal: the luminance sigma is tp.sigma_luminance_temporal at pixels whose variance came from the temporal moments.
-template<bool kTemporal>
+// kMasked: holes are no taps (the variance prefilter included), and a hole is filled (pt_denoise_masked_run).
+template<bool kTemporal, bool kMasked>
 __global__ __launch_bounds__(256) void pt_denoise_atrous_kernel(const float4 *__restrict__ col_in, const float *__restrict__ var_in, const float4 *__restrict__ guide,
                                                                 const uint32_t *__restrict__ cls, const float2 *__restrict__ grad, int32_t width, int32_t height,
                                                                 int32_t step, float sigma_luminance, float sigma_normal, float sigma_depth,
@@ -161,6 +188,48 @@ __global__ __launch_bounds__(256) void pt_denoise_atrous_kernel(const float4 *__
     }
     const int p = y * width + x;
     const uint32_t cp = cls[p];
+    if constexpr(kMasked) {
+        if(cp & PTDN_HOLE) {
+            const uint32_t want = cp & ~PTDN_HOLE; // taps of the hole's class that are not holes
+            const float4 gp = guide[p];
+            const float2 gr = grad[p];
+            float sw = 0.0f, sr = 0.0f, sg = 0.0f, sb = 0.0f;
+            for(int dy = -2; dy <= 2; dy++) {
+                for(int dx = -2; dx <= 2; dx++) {
+                    const int ox = dx * step, oy = dy * step;
+                    const int qx = x + ox, qy = y + oy;
+                    if((dx == 0 && dy == 0) || qx < 0 || qy < 0 || qx >= width || qy >= height) {
+                        continue;
+                    }
+                    const int q = qy * width + qx;
+                    if(cls[q] != want) {
+                        continue;
+                    }
+                    const float h = b3_tap(dy) * b3_tap(dx);
+                    float w = h;
+                    if(cp & PTDN_COVERED) {
+                        const float4 gq = guide[q];
+                        w = (h * normal_weight(gp, gq, sigma_normal)) * expf(-depth_arg(gp.w, gq.w, gr, (float)ox, (float)oy, sigma_depth));
+                    }
+                    const float4 cq = col_in[q];
+                    sw = sw + w;
+                    sr = sr + w * cq.x;
+                    sg = sg + w * cq.y;
+                    sb = sb + w * cq.z;
+                }
+            }
+            if(sw > 0.0f) {
+                const float r = sr / sw, gg = sg / sw, b = sb / sw;
+                col_out[p] = make_float4(r, gg, b, lum_of(r, gg, b));
+                var_out[p] = 1.0f;
+            }
+            else {
+                col_out[p] = col_in[p];
+                var_out[p] = var_in[p];
+            }
+            return;
+        }
+    }
     if(!(cp & PTDN_COVERED)) { // no ray hit: nothing to filter against
         col_out[p] = col_in[p];
         var_out[p] = var_in[p];
@@ -173,6 +242,11 @@ __global__ __launch_bounds__(256) void pt_denoise_atrous_kernel(const float4 *__
             const int qx = x + dx, qy = y + dy;
             if(qx < 0 || qy < 0 || qx >= width || qy >= height) {
                 continue;
+            }
+            if constexpr(kMasked) {
+                if(cls[qy * width + qx] & PTDN_HOLE) {
+                    continue;
+                }
             }
             const float k = (dy == 0 ? 0.5f : 0.25f) * (dx == 0 ? 0.5f : 0.25f);
             g = g + k * var_in[qy * width + qx];
@@ -360,8 +434,10 @@ __global__ __launch_bounds__(256) void pt_temporal_accumulate_kernel(const float
 }
 
 // (rgba and out may be the same array: no __restrict__ on them)
+// kMasked: a hole that a pass filled has alpha 1, one that none did is (0, 0, 0, 0).
+template<bool kMasked>
 __global__ __launch_bounds__(256) void pt_denoise_finish_kernel(const float4 *__restrict__ col, const float4 *rgba, const float4 *__restrict__ feat, int32_t width,
-                                                                int32_t height, float4 *out) {
+                                                                int32_t height, const uint32_t *__restrict__ cls, const float *__restrict__ var, float4 *out) {
     const int x = blockIdx.x * 16 + threadIdx.x, y = blockIdx.y * 16 + threadIdx.y;
     if(x >= width || y >= height) {
         return;
@@ -369,7 +445,16 @@ __global__ __launch_bounds__(256) void pt_denoise_finish_kernel(const float4 *__
     const int p = y * width + x;
     const float4 f0 = feat[3 * p], f2 = feat[3 * p + 2];
     const float4 c = col[p];
-    const float alpha = rgba[p].w;
+    float alpha = rgba[p].w;
+    if constexpr(kMasked) {
+        if(cls[p] & PTDN_HOLE) {
+            if(!(var[p] > 0.0f)) {
+                out[p] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                return;
+            }
+            alpha = 1.0f;
+        }
+    }
     float4 o = make_float4(c.x, c.y, c.z, alpha);
     if(f0.w > 0.0f && !(f2.w > 0.0f)) {
         o.x = c.x * fmaxf(f0.x, kAlbedoMin);
@@ -384,16 +469,32 @@ __global__ __launch_bounds__(256) void pt_denoise_finish_kernel(const float4 *__
 hipError_t pt_denoise_run(hipStream_t stream, const float4 *rgba, const float4 *features, int32_t width, int32_t height, const PtDenoiseParams &params,
                           const PtDenoiseScratch &s, float4 *out) {
     const dim3 block(16, 16), grid((width + 15) / 16, (height + 15) / 16);
-    hipLaunchKernelGGL(pt_denoise_prepare_kernel, grid, block, 0, stream, rgba, features, width, height, s.col[0], s.guide, s.cls);
-    hipLaunchKernelGGL(pt_denoise_variance_kernel<false>, grid, block, 0, stream, s.col[0], s.guide, s.cls, width, height, params.sigma_normal,
+    hipLaunchKernelGGL(pt_denoise_prepare_kernel<false>, grid, block, 0, stream, rgba, features, width, height, nullptr, s.col[0], s.guide, s.cls);
+    hipLaunchKernelGGL((pt_denoise_variance_kernel<false, false>), grid, block, 0, stream, s.col[0], s.guide, s.cls, width, height, params.sigma_normal,
                        params.sigma_depth, s.grad, s.var[0], PtTemporalPixel{});
     int cur = 0;
     for(int i = 0; i < params.iterations; i++) {
-        hipLaunchKernelGGL(pt_denoise_atrous_kernel<false>, grid, block, 0, stream, s.col[cur], s.var[cur], s.guide, s.cls, s.grad, width, height, 1 << i,
+        hipLaunchKernelGGL((pt_denoise_atrous_kernel<false, false>), grid, block, 0, stream, s.col[cur], s.var[cur], s.guide, s.cls, s.grad, width, height, 1 << i,
                            params.sigma_luminance, params.sigma_normal, params.sigma_depth, s.col[cur ^ 1], s.var[cur ^ 1], PtTemporalPixel{});
         cur ^= 1;
     }
-    hipLaunchKernelGGL(pt_denoise_finish_kernel, grid, block, 0, stream, s.col[cur], rgba, features, width, height, out);
+    hipLaunchKernelGGL(pt_denoise_finish_kernel<false>, grid, block, 0, stream, s.col[cur], rgba, features, width, height, nullptr, nullptr, out);
+    return hipGetLastError();
+}
+
+hipError_t pt_denoise_masked_run(hipStream_t stream, const float4 *rgba, const float4 *features, const int32_t *samples, int32_t width, int32_t height,
+                                 const PtDenoiseParams &params, const PtDenoiseScratch &s, float4 *out) {
+    const dim3 block(16, 16), grid((width + 15) / 16, (height + 15) / 16);
+    hipLaunchKernelGGL(pt_denoise_prepare_kernel<true>, grid, block, 0, stream, rgba, features, width, height, samples, s.col[0], s.guide, s.cls);
+    hipLaunchKernelGGL((pt_denoise_variance_kernel<false, true>), grid, block, 0, stream, s.col[0], s.guide, s.cls, width, height, params.sigma_normal,
+                       params.sigma_depth, s.grad, s.var[0], PtTemporalPixel{});
+    int cur = 0;
+    for(int i = 0; i < params.iterations; i++) {
+        hipLaunchKernelGGL((pt_denoise_atrous_kernel<false, true>), grid, block, 0, stream, s.col[cur], s.var[cur], s.guide, s.cls, s.grad, width, height, 1 << i,
+                           params.sigma_luminance, params.sigma_normal, params.sigma_depth, s.col[cur ^ 1], s.var[cur ^ 1], PtTemporalPixel{});
+        cur ^= 1;
+    }
+    hipLaunchKernelGGL(pt_denoise_finish_kernel<true>, grid, block, 0, stream, s.col[cur], rgba, features, width, height, s.cls, s.var[cur], out);
     return hipGetLastError();
 }
 
@@ -404,20 +505,20 @@ hipError_t pt_temporal_run(hipStream_t stream, const float4 *rgba, const float4 
     PtDenoiseScratch s = scratch;
     s.cls = state.cls[cur];
     // prepare -> col[1]; integrate -> col[0]; a-trous pass 0 -> the colour history; passes 1.. alternate col[1], col[0], ...
-    hipLaunchKernelGGL(pt_denoise_prepare_kernel, grid, block, 0, stream, rgba, features, width, height, s.col[1], s.guide, s.cls);
+    hipLaunchKernelGGL(pt_denoise_prepare_kernel<false>, grid, block, 0, stream, rgba, features, width, height, nullptr, s.col[1], s.guide, s.cls);
     const PtTemporalPrev prev{state.col_hist, state.moments[prv], state.len[prv], state.pos[prv], state.nrm[prv], state.cls[prv]};
     const PtTemporalBlend bl{params.alpha_color, params.alpha_moments, params.max_history, params.normal_min, params.position_tolerance};
     hipLaunchKernelGGL(pt_temporal_accumulate_kernel, grid, block, 0, stream, features, s.col[1], s.cls, width, height, reprojection, prev, bl, s.col[0],
                        state.moments[cur], state.len[cur], state.pos[cur], state.nrm[cur]);
     const PtTemporalPixel tp{state.len[cur], state.moments[cur], params.moments_min_history, params.sigma_luminance_temporal};
     const PtDenoiseParams &sp = params.spatial;
-    hipLaunchKernelGGL(pt_denoise_variance_kernel<true>, grid, block, 0, stream, s.col[0], s.guide, s.cls, width, height, sp.sigma_normal, sp.sigma_depth,
+    hipLaunchKernelGGL((pt_denoise_variance_kernel<true, false>), grid, block, 0, stream, s.col[0], s.guide, s.cls, width, height, sp.sigma_normal, sp.sigma_depth,
                        s.grad, s.var[0], tp);
     const float4 *col = s.col[0];
     int v = 0;
     for(int i = 0; i < sp.iterations; i++) {
         float4 *dst = i == 0 ? state.col_hist : s.col[i & 1];
-        hipLaunchKernelGGL(pt_denoise_atrous_kernel<true>, grid, block, 0, stream, col, s.var[v], s.guide, s.cls, s.grad, width, height, 1 << i,
+        hipLaunchKernelGGL((pt_denoise_atrous_kernel<true, false>), grid, block, 0, stream, col, s.var[v], s.guide, s.cls, s.grad, width, height, 1 << i,
                            sp.sigma_luminance, sp.sigma_normal, sp.sigma_depth, dst, s.var[v ^ 1], tp);
         col = dst;
         v ^= 1;
@@ -428,6 +529,6 @@ hipError_t pt_temporal_run(hipStream_t stream, const float4 *rgba, const float4 
             return e;
         }
     }
-    hipLaunchKernelGGL(pt_denoise_finish_kernel, grid, block, 0, stream, col, rgba, features, width, height, out);
+    hipLaunchKernelGGL(pt_denoise_finish_kernel<false>, grid, block, 0, stream, col, rgba, features, width, height, nullptr, nullptr, out);
     return hipGetLastError();
 }

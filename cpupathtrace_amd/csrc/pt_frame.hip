@@ -5,6 +5,8 @@
 // of the old list (a stable partition in two kernels: counts per block of 1024 entries, then every block places its entries behind the
 // counts of the blocks before it).  Parked streams first: the next launch's first round takes them all (it deals out at least as many
 // streams as the launch before could park, one per slot), so no record has to outlive the launch that reads it.
+//
+// The same work list is what pt_frame_preview shows between two launches: the gather kernels below read it without changing it.
 #include <hip/hip_runtime.h>
 
 #include "pt_kernels.h"
@@ -122,6 +124,81 @@ __global__ __launch_bounds__(kThreads) void pt_frame_place_kernel(const uint2 *_
     }
 }
 
+// ---- the preview of a frame (pt_frame_preview, pt_api.cpp) -----------------------------------------------------------------------------
+// Each replica gathers its work list into compact entries (gather); replica 0's device lays the frame out from the caller's image (base)
+// and writes every replica's entries over it (scatter).
+
+// One thread per entry of a replica's work list todo[0 .. n): entry i < n_parked is a parked stream with its record in `park`, the others
+// are untouched.  Writes the entry's preview colour and (pixel, samples): the running mean pixel_value * (1 / collected_sample_count) and
+// pixel_sample of a parked stream (estimator_finish's first step, pt_shading.h), (0, 0, 0, 0) and 0 samples for an untouched one.  A parked
+// entry reads three fields of its 528-byte record, not the record.
+__global__ __launch_bounds__(kThreads) void pt_frame_gather_kernel(const uint2 *__restrict__ todo, uint32_t n, uint32_t n_parked,
+                                                                   const PtParkRecord *__restrict__ park, const int4 *__restrict__ tiles,
+                                                                   const uint32_t *__restrict__ tile_offset, uint32_t n_tiles, int32_t width,
+                                                                   float4 *__restrict__ out_rgba, int2 *__restrict__ out_at) {
+    const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
+    if(i >= n) {
+        return;
+    }
+    const uint2 e = todo[i];
+    // the stream's pixel, as tile_stream (pt_path.hip) finds it: the last tile whose first stream is not behind it
+    uint32_t lo = 0, hi = n_tiles;
+    while(hi - lo > 1) {
+        const uint32_t mid = (lo + hi) / 2;
+        if(tile_offset[mid] <= e.x) {
+            lo = mid;
+        }
+        else {
+            hi = mid;
+        }
+    }
+    const int4 t = tiles[lo];
+    const uint32_t k = e.x - tile_offset[lo];
+    const int32_t x = t.x + (int32_t)(k % (uint32_t)t.z), y = t.y + (int32_t)(k / (uint32_t)t.z);
+    float4 c = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    int32_t samples = 0;
+    if(i < n_parked) {
+        const PtEstimator &est = park[e.y].est;
+        const float4 pv = *reinterpret_cast<const float4 *>(est.pixel_value);
+        const int32_t collected = est.collected_sample_count;
+        samples = est.pixel_sample;
+        if(collected > 0) {
+            const float inv = 1.0f / (float)collected;
+            c = make_float4(pv.x * inv, pv.y * inv, pv.z * inv, pv.w * inv);
+        }
+    }
+    out_rgba[i] = c;
+    out_at[i] = make_int2(y * width + x, samples);
+}
+
+// One thread per pixel: a pixel of some tile keeps the caller's colour and is finished (-1) until a scatter says otherwise; a pixel of
+// no tile is a hole.
+__global__ __launch_bounds__(kThreads) void pt_frame_preview_base_kernel(float4 *__restrict__ view, int32_t *__restrict__ samples,
+                                                                         const uint8_t *__restrict__ cover, uint32_t n_pixels) {
+    const uint32_t p = blockIdx.x * kThreads + threadIdx.x;
+    if(p >= n_pixels) {
+        return;
+    }
+    if(cover[p] != 0) {
+        samples[p] = -1;
+    }
+    else {
+        view[p] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        samples[p] = 0;
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void pt_frame_scatter_kernel(const float4 *__restrict__ rgba, const int2 *__restrict__ at, uint32_t n,
+                                                                    float4 *__restrict__ view, int32_t *__restrict__ samples) {
+    const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
+    if(i >= n) {
+        return;
+    }
+    const int2 a = at[i];
+    view[a.x] = rgba[i];
+    samples[a.x] = a.y;
+}
+
 } // namespace
 
 int pt_launch_frame_compact(hipStream_t stream, const uint2 *todo, uint32_t n, uint32_t *status, const PtParkRecord *parked, uint2 *todo_out, uint32_t *block_counts,
@@ -135,5 +212,30 @@ int pt_launch_frame_compact(hipStream_t stream, const uint2 *todo, uint32_t n, u
     const uint32_t n_blocks = (n + kPerBlock - 1) / kPerBlock;
     pt_frame_count_kernel<<<n_blocks, kThreads, 0, stream>>>(todo, n, status, block_counts);
     pt_frame_place_kernel<<<n_blocks, kThreads, 0, stream>>>(todo, n, status, block_counts, n_blocks, parked, todo_out, result);
+    return hipGetLastError() == hipSuccess ? 0 : 1;
+}
+
+int pt_launch_frame_gather(hipStream_t stream, const uint2 *todo, uint32_t n, uint32_t n_parked, const PtParkRecord *park, const int4 *tiles,
+                           const uint32_t *tile_offset, uint32_t n_tiles, int32_t width, float4 *out_rgba, int2 *out_at) {
+    if(n == 0) {
+        return 0;
+    }
+    pt_frame_gather_kernel<<<(n + kThreads - 1) / kThreads, kThreads, 0, stream>>>(todo, n, n_parked, park, tiles, tile_offset, n_tiles, width, out_rgba, out_at);
+    return hipGetLastError() == hipSuccess ? 0 : 1;
+}
+
+int pt_launch_frame_preview_base(hipStream_t stream, float4 *view, int32_t *samples, const uint8_t *cover, uint32_t n_pixels) {
+    if(n_pixels == 0) {
+        return 0;
+    }
+    pt_frame_preview_base_kernel<<<(n_pixels + kThreads - 1) / kThreads, kThreads, 0, stream>>>(view, samples, cover, n_pixels);
+    return hipGetLastError() == hipSuccess ? 0 : 1;
+}
+
+int pt_launch_frame_scatter(hipStream_t stream, const float4 *rgba, const int2 *at, uint32_t n, float4 *view, int32_t *samples) {
+    if(n == 0) {
+        return 0;
+    }
+    pt_frame_scatter_kernel<<<(n + kThreads - 1) / kThreads, kThreads, 0, stream>>>(rgba, at, n, view, samples);
     return hipGetLastError() == hipSuccess ? 0 : 1;
 }

@@ -152,6 +152,14 @@ void pt_launch_path(hipStream_t stream, const PtDevScene &scene, const PtDevCame
 // with closed candidates.  Returns 0, or 1 when a launch failed.
 int pt_launch_frame_compact(hipStream_t stream, const uint2 *todo, uint32_t n, uint32_t *status, const PtParkRecord *parked, uint2 *todo_out, uint32_t *block_counts,
                             unsigned long long *result);
+// The preview of a frame (pt_frame.hip; pt_frame_preview).  gather: one compact entry per entry of a replica's work list todo[0 .. n), the
+// first n_parked parked in `park` -- out_rgba the running mean (0 for an untouched stream), out_at (y * width + x, samples taken).  base: the
+// view of replica 0's device, which holds the caller's image: samples -1 where cover[p] != 0, else a hole (0, 0, 0, 0) with 0 samples.
+// scatter: the n entries into the view.  Each returns 0, or 1 when the launch failed.
+int pt_launch_frame_gather(hipStream_t stream, const uint2 *todo, uint32_t n, uint32_t n_parked, const PtParkRecord *park, const int4 *tiles,
+                           const uint32_t *tile_offset, uint32_t n_tiles, int32_t width, float4 *out_rgba, int2 *out_at);
+int pt_launch_frame_preview_base(hipStream_t stream, float4 *view, int32_t *samples, const uint8_t *cover, uint32_t n_pixels);
+int pt_launch_frame_scatter(hipStream_t stream, const float4 *rgba, const int2 *at, uint32_t n, float4 *view, int32_t *samples);
 int pt_path_blocks_per_cu(const PtPathConfig &cfg); // resident workgroups per CU of the instantiation cfg selects (wide, in_lds, stack_lds) with cfg.lds_bytes
 size_t pt_path_lds_bytes(int wide, int rows, int stack_lds, uint32_t n_lds_pairs, uint32_t n_lds_leaf_records); // leaf records: triangles + 1 spare + spheres, 0 = scene not in LDS
 int pt_path_stack_lds(int in_lds, size_t lds_bytes_with_default_window); // entries of the stack window: 8, or 4 for a scene in LDS that would not leave room for four workgroups per CU

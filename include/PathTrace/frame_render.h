@@ -16,7 +16,8 @@
 // (its RenderControl's budget ran out or it was cancelled).  The pixels a stop catches half-way park their state on the device and resume
 // from it, so no sample is drawn twice, and the finished frame is bit for bit what processJob gives with the same seed
 // ($PATHTRACE_SEED, or a random one) on the replicas $PATHTRACE_DEVICES selects -- without denoising: options.allow_bias is ignored (a
-// stopped frame has holes; denoise the finished frame with PathTrace/denoise.h).  The job's scene must outlive the FrameRender.
+// stopped frame has holes: preview() shows one, denoised if asked; denoise the finished frame with PathTrace/denoise.h).  The job's scene
+// must outlive the FrameRender.
 class FrameRender {
 public:
     explicit FrameRender(const FrameRenderJob &job, int worker_count = 0);
@@ -33,6 +34,11 @@ public:
     bool complete() const noexcept { return complete_; }
     // where the frame stands (pt_frame_info: streams finished / parked / untouched, tiles, samples the parked streams carry)
     pt_frame_info info() const;
+    // The frame as it stands, for a viewer between two render() calls (pt_frame_preview): finished pixels as image(), parked ones the
+    // running mean of their samples so far, untouched ones (0, 0, 0, 0).  `samples` (if not null) gets one count per pixel, row-major:
+    // -1 finished, the samples taken of a parked pixel, 0 untouched.  With `denoise` the preview is filtered as pt_denoise filters a frame,
+    // holes filled from their neighbours.  out is resized to the frame.  Changes nothing the frame will do.  Throws std::runtime_error on failure.
+    void preview(Image<> &out, std::vector<std::int32_t> *samples = nullptr, const pt_denoise_params *denoise = nullptr) const;
     std::uint64_t seed() const noexcept { return seed_; }
 
 private:

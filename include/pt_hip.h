@@ -330,6 +330,26 @@ int pt_denoise(int device, const float *rgba, const float *features, int32_t wid
 int pt_denoise_device(int device, const float *d_rgba, const float *d_features, int32_t width, int32_t height, const pt_denoise_params *params,
                       float *d_out_rgba, void *stream);
 
+/* The frame as it stands: what a viewer shows between two pt_frame_render calls.  `image` is the buffer the caller passes
+ * to pt_frame_render (it holds the finished pixels); out_rgba is [height][width][4] floats and may equal `image` only when the caller no
+ * longer needs the frame's own image (the next pt_frame_render would keep the preview's values in its unfinished pixels).  out_samples
+ * is [height][width] int32 or NULL.  Per pixel:
+ *   - finished: rgba copied from `image` bit for bit; samples = -1.
+ *   - parked: the plain running mean of its estimator, pixel_value * (1 / collected_sample_count) in fp32 (the first step of the finish:
+ *     alpha is 1), or (0, 0, 0, 0) if no sample was collected; samples = the samples the pixel has taken (>= 1).  A pixel whose
+ *     estimator holds closed candidates may finish at another value: the preview never applies the candidate rule.
+ *   - untouched, or in no tile of the frame: a hole, (0, 0, 0, 0); samples = 0.  Before the first pt_frame_render every pixel is a hole.
+ * A complete frame previews as `image` bit for bit, every sample count -1.  Every replica gathers its parked pixels on its own device.
+ * denoise != NULL: the preview is then filtered as pt_denoise filters a frame, with those parameters, on replica 0's device and with the
+ * frame's first-hit features (pt_render_features with the frame's camera and size: computed on the first denoised preview and kept on
+ * the device until pt_frame_destroy).  Holes are never taps of another pixel; a hole takes the normalised weighted mean of its other taps
+ * in every pass (its own weight 0, no luminance term) and then has alpha 1, or stays (0, 0, 0, 0) if no pass found one.  Without holes
+ * the result equals pt_denoise of the raw preview bit for bit.  out_samples is the raw preview's either way.
+ * The preview changes nothing the frame will do, and takes the frame's lock (scene work is serialised with the scene's other calls).
+ * PT_ERR_INVALID before any device is touched: null frame, image or out_rgba, or denoise parameters pt_denoise refuses; a failed
+ * frame returns its stored status. */
+int pt_frame_preview(pt_frame *frame, const float *image, const pt_denoise_params *denoise, float *out_rgba, int32_t *out_samples);
+
 /* Temporal denoising of a sequence of frames of one static scene (a camera path, a turntable): the temporal half of SVGF (Schied et al. 2017)
  * in front of pt_denoise's spatial filter.  A pt_temporal handle keeps the history of the frames pushed so far, on its own
  * device buffers (two handles may be interleaved).  Each push of a frame, its pt_render_features and its camera:

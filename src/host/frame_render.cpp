@@ -67,3 +67,18 @@ pt_frame_info FrameRender::info() const {
     }
     return i;
 }
+
+void FrameRender::preview(Image<> &out, std::vector<std::int32_t> *samples, const pt_denoise_params *denoise) const {
+    if(out.getWidth() != image_.getWidth() || out.getHeight() != image_.getHeight()) {
+        out = Image<>(image_.getWidth(), image_.getHeight());
+    }
+    if(samples != nullptr) {
+        samples->assign(static_cast<size_t>(image_.getWidth()) * static_cast<size_t>(image_.getHeight()), 0);
+    }
+    if(frame_ == nullptr) {
+        return;
+    }
+    check(pt_frame_preview(frame_, reinterpret_cast<const float *>(image_.data()), denoise, reinterpret_cast<float *>(out.data()),
+                           samples != nullptr ? samples->data() : nullptr),
+          "FrameRender::preview");
+}
