@@ -7,6 +7,8 @@
 ``Frame``            a controlled processJob that can be continued: each call resumes where the last one stopped (include/PathTrace/frame_render.h)
                      ``Frame.preview`` shows it between two calls, optionally denoised
 ``process_views``    processJob for many cameras of one scene in one launch (include/PathTrace/view_batch.h)
+``ViewsFrame``       process_views that can be stopped, continued and previewed: a Frame over a view batch (include/PathTrace/view_batch_render.h)
+``denoise_views``    denoise for a whole view batch, one launch per stage; ``Scene.render_features_views`` gives its features
 ``denoise``          feature-guided denoising of a finished frame, what RenderOptions::allow_bias asks for (include/PathTrace/denoise.h);
                      ``Scene.render_features`` gives the features, ``Scene.process_job(..., allow_bias=True)`` does both
 ``TemporalDenoiser`` the same over a sequence of frames, with the history of the earlier ones reprojected (include/PathTrace/temporal_denoise.h);
@@ -39,6 +41,8 @@ VIEW_EXPORTS = ["pt_render_views", "pt_render_views_device"]
 EXPORTS += VIEW_EXPORTS
 DENOISE_EXPORTS = ["pt_denoise_params_default", "pt_render_features", "pt_render_features_device", "pt_denoise", "pt_denoise_device"]
 EXPORTS += DENOISE_EXPORTS
+VIEWS_FRAME_EXPORTS = ["pt_frame_create_views", "pt_render_features_views", "pt_render_features_views_device", "pt_denoise_views", "pt_denoise_views_device"]
+EXPORTS += VIEWS_FRAME_EXPORTS
 TEMPORAL_EXPORTS = ["pt_temporal_params_default", "pt_temporal_create", "pt_temporal_denoise", "pt_temporal_denoise_device", "pt_temporal_reset",
                     "pt_temporal_destroy"]
 EXPORTS += TEMPORAL_EXPORTS
@@ -110,6 +114,26 @@ def denoise_device(d_rgba_ptr, d_features_ptr, width, height, d_out_ptr, stream_
     width*height*12 floats; ordered on stream_ptr (0 = the default stream), which is synchronised before the call returns."""
     _check(load().pt_denoise_device(C.c_int(device), C.c_void_p(d_rgba_ptr), C.c_void_p(d_features_ptr), C.c_int32(width), C.c_int32(height),
                                     _denoise_params(params), C.c_void_p(d_out_ptr), C.c_void_p(stream_ptr)))
+
+
+def denoise_views(images, features, params=None, device=0):
+    """denoise for a view batch (pt_denoise_views): (V, h, w, 4) float32 frames with the (V, h, w, 3, 4) features of
+    Scene.render_features_views, 3 + iterations launches whatever V is; view v of the result equals denoise(images[v], features[v]) bit for
+    bit.  Returns a new array."""
+    img = np.ascontiguousarray(images, dtype=np.float32)
+    feat = np.ascontiguousarray(features, dtype=np.float32)
+    if img.ndim != 4 or img.shape[3] != 4 or feat.shape != img.shape[:3] + (3, 4):
+        raise ValueError("images must be (V, h, w, 4) and features (V, h, w, 3, 4)")
+    out = np.empty_like(img)
+    v, h, w = img.shape[:3]
+    _check(load().pt_denoise_views(C.c_int(device), _ptr(img), _ptr(feat), C.c_int32(w), C.c_int32(h), C.c_int32(v), _denoise_params(params), _ptr(out)))
+    return out
+
+
+def denoise_views_device(d_rgba_ptr, d_features_ptr, width, height, n_views, d_out_ptr, stream_ptr=0, params=None, device=0):
+    """pt_denoise_views_device on device memory: as denoise_device, every array holding n_views frames."""
+    _check(load().pt_denoise_views_device(C.c_int(device), C.c_void_p(d_rgba_ptr), C.c_void_p(d_features_ptr), C.c_int32(width), C.c_int32(height),
+                                          C.c_int32(n_views), _denoise_params(params), C.c_void_p(d_out_ptr), C.c_void_p(stream_ptr)))
 
 
 class TemporalParams(C.Structure):
@@ -441,6 +465,21 @@ class Scene:
                 out[v], _ = t.denoise(frames[v], self.render_features(cam, options), cam)
         return out
 
+    def render_features_views(self, cameras, options):
+        """render_features for V cameras in one launch (pt_render_features_views): a (V, H, W, 3, 4) float32 array whose view v equals
+        render_features(cameras[v], options) bit for bit."""
+        cams, _ = _view_tables(cameras, 0)
+        out = np.empty((len(cams), options["image_height"], options["image_width"], 3, 4), np.float32)
+        op = _options(options)
+        _check(load().pt_render_features_views(self._h, cams, C.c_int32(len(cams)), C.byref(op), _ptr(out)))
+        return out
+
+    def render_features_views_device(self, cameras, options, d_features_ptr, stream_ptr=0):
+        """render_features_views into device memory (d_features_ptr: device address of V*H*W*12 floats), ordered on stream_ptr."""
+        cams, _ = _view_tables(cameras, 0)
+        op = _options(options)
+        _check(load().pt_render_features_views_device(self._h, cams, C.c_int32(len(cams)), C.byref(op), C.c_void_p(d_features_ptr), C.c_void_p(stream_ptr)))
+
     def render_features_device(self, camera, options, d_features_ptr, stream_ptr=0):
         """render_features into device memory (d_features_ptr: device address of H*W*12 floats, e.g. an (H, W, 3, 4) tensor), ordered on stream_ptr."""
         cp, op = _camera(camera), _options(options)
@@ -610,6 +649,38 @@ class Frame:
             self.close()
         except Exception:
             pass
+
+
+class ViewsFrame(Frame):
+    """process_views that can be stopped and continued (pt_frame_create_views): a Frame over a view batch.  render, info, preview, done and
+    close are Frame's; image and the preview are (V, H, W, 4), the preview's sample counts (V, H, W), tile_done covers the tiles of all
+    views (V x job_tiles(W, H), view after view).  The finished images equal process_views / process_views_multi with the same seeds bit
+    for bit, however the calls were sliced.  base_seeds: one int for every view, or V ints."""
+
+    def __init__(self, scenes, cameras, options, base_seeds=1234):
+        self._scenes = list(scenes) if isinstance(scenes, (list, tuple)) else [scenes]
+        cams, seeds = _view_tables(cameras, base_seeds)
+        per_view = job_tiles(options["image_width"], options["image_height"])
+        self.tiles = np.concatenate([per_view] * len(seeds))
+        self.tiles["y"] += np.repeat(np.arange(len(seeds), dtype=np.int32) * options["image_height"], len(per_view))
+        self.image = np.zeros((len(seeds), options["image_height"], options["image_width"], 4), np.float32)
+        handles = (C.c_void_p * len(self._scenes))(*[sc._h for sc in self._scenes])
+        op = _options(options)
+        h = C.c_void_p()
+        self._h = None
+        _check(load().pt_frame_create_views(handles, C.c_int(len(self._scenes)), cams, seeds.ctypes.data_as(C.POINTER(C.c_uint64)), C.c_int32(len(seeds)),
+                                            C.byref(op), C.byref(h)))
+        self._h = h
+
+    def preview(self, denoise=None):
+        """Frame.preview per view: (rgba (V, H, W, 4), samples (V, H, W)).  Denoised, a hole is filled from pixels of its own view only."""
+        if self._h is None:
+            raise ValueError("frame is closed")
+        rgba = np.empty_like(self.image)
+        samples = np.empty(self.image.shape[:3], np.int32)
+        params = None if denoise is None or denoise is False else _denoise_params({} if denoise is True else denoise)
+        _check(load().pt_frame_preview(self._h, _ptr(self.image), params, _ptr(rgba), _ptr(samples)))
+        return rgba, samples
 
 
 def process_job_multi(scenes, camera, options, base_seed=1234, tiles=None, progress=None, want_stats=False):

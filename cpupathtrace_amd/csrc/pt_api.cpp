@@ -198,6 +198,7 @@ struct pt_scene {
     // the first-hit features of a frame (pt_render_features*): the frame's features and the walks' spill area
     DevBuf<F4> features;
     DevBuf<uint2> feature_spill;
+    DevBuf<PtViewCamera> feature_cams; // pt_render_features_views: the views' cameras, aperture none
     bool debug_collect_costs = false;                // pt_debug_collect_costs: every launch records them
     std::vector<uint32_t> debug_place;               // pt_debug_set_place: the next launch starts from this table ...
     uint32_t debug_place_waves = 0, debug_place_slots = 0; // ... with this many wavefronts and slots in each
@@ -2122,6 +2123,8 @@ struct pt_frame {
         DevBuf<uint2> d_todo[2];
         DevBuf<PtParkRecord> d_park[2];
         DevBuf<unsigned long long> d_result;
+        DevBuf<PtViewCamera> d_view_cams; // a view frame's tables
+        DevBuf<uint64_t> d_view_seeds;
         // pt_frame_preview: the replica's gathered work list; on replica 0 also the frame's view and sample counts, which pixels a tile
         // covers, the frame's first-hit features and the other replicas' entries on their way in
         DevBuf<F4> pv_rgba, pv_view, pv_features, pv_stage_rgba;
@@ -2135,6 +2138,13 @@ struct pt_frame {
     pt_options options{};
     std::vector<pt_tile> tiles;
     uint64_t base_seed = 0;
+    // a frame over a view batch (pt_frame_create_views, V > 1): the image is the V frames stacked, `views` the frame's own copy of the
+    // cameras and seeds (every replica keeps them in device tables of its own: the scene's are any other batch's to overwrite between two
+    // slices) and `cameras` what the preview's feature pass takes.  A plain frame has n_views = 1 and no tables.
+    int32_t n_views = 1;
+    ViewSet views;
+    std::vector<pt_camera_params> cameras;
+    int32_t rows() const { return n_views * options.image_height; }
     std::vector<std::unique_ptr<Replica>> reps;
     std::vector<uint8_t> tile_done;
     uint64_t tiles_done = 0, streams_total = 0;
@@ -2220,12 +2230,16 @@ int frame_launch(pt_frame &f, pt_frame::Replica &r, float *out_image, pt_stats *
     }
     const PtDevCamera cam = derive_camera(&f.camera);
     if(!r.ready) {
+        if(f.n_views > 1) {
+            PT_HIP(r.d_view_cams.upload(f.views.cams));
+            PT_HIP(r.d_view_seeds.upload(f.views.seeds));
+        }
         rc = frame_prepare(r);
         if(rc != PT_OK) {
             return rc;
         }
     }
-    const size_t pixels = static_cast<size_t>(f.options.image_width) * static_cast<size_t>(f.options.image_height);
+    const size_t pixels = static_cast<size_t>(f.options.image_width) * static_cast<size_t>(f.rows());
     PT_HIP(s->image.ensure(pixels));
     rc = frame_copy_open_tiles(f, r, out_image, true);
     if(rc != PT_OK) {
@@ -2247,6 +2261,12 @@ int frame_launch(pt_frame &f, pt_frame::Replica &r, float *out_image, pt_stats *
     T.tile_offset = r.d_offset.ptr;
     T.n_tiles = static_cast<uint32_t>(r.tiles.size());
     T.base_seed = f.base_seed;
+    if(f.n_views > 1) {
+        T.n_views = static_cast<uint32_t>(f.n_views);
+        T.view_height = static_cast<uint32_t>(f.options.image_height);
+        T.views = r.d_view_cams.ptr;
+        T.view_seed = r.d_view_seeds.ptr;
+    }
     // The first round is spread over the work list.  The first launch's list is every stream in order, so it is spread over the tile grid
     // as pt_render_tiles spreads it (an uninterrupted frame is scheduled exactly like one); a later list is no tile grid.
     T.tiles_per_row = 0;
@@ -2303,10 +2323,9 @@ int frame_launch(pt_frame &f, pt_frame::Replica &r, float *out_image, pt_stats *
 
 } // namespace
 
-extern "C" {
-
-int pt_frame_create(pt_scene *const *scenes, int n_scenes, const pt_camera_params *camera, const pt_options *options, const pt_tile *tiles, size_t n_tiles,
-                    uint64_t base_seed, pt_frame **out) {
+// pt_frame_create; `views` (a batch of more than one view, else null) makes it a frame over the stacked image, whose tiles lie in views->rows
+static int frame_create_impl(pt_scene *const *scenes, int n_scenes, const pt_camera_params *camera, const pt_options *options, const pt_tile *tiles, size_t n_tiles,
+                             uint64_t base_seed, const ViewSet *views, pt_frame **out) {
     if(out == nullptr) {
         return fail(PT_ERR_INVALID, "null frame pointer");
     }
@@ -2325,10 +2344,11 @@ int pt_frame_create(pt_scene *const *scenes, int n_scenes, const pt_camera_param
     if(options->image_width <= 0 || options->image_height <= 0) {
         return fail(PT_ERR_INVALID, "image size must be positive");
     }
+    const int32_t rows = views != nullptr ? views->rows(options) : options->image_height;
     uint64_t total = 0;
     for(size_t k = 0; k < n_tiles; k++) {
         const pt_tile &t = tiles[k];
-        if(t.w <= 0 || t.h <= 0 || t.x < 0 || t.y < 0 || t.x + t.w > options->image_width || t.y + t.h > options->image_height) {
+        if(t.w <= 0 || t.h <= 0 || t.x < 0 || t.y < 0 || t.x + t.w > options->image_width || t.y + t.h > rows) {
             return fail(PT_ERR_INVALID, "tile outside the image or empty");
         }
         total += static_cast<uint64_t>(t.w) * static_cast<uint64_t>(t.h);
@@ -2349,6 +2369,11 @@ int pt_frame_create(pt_scene *const *scenes, int n_scenes, const pt_camera_param
     f->options = *options;
     f->tiles.assign(tiles, tiles + n_tiles);
     f->base_seed = base_seed;
+    if(views != nullptr) {
+        f->n_views = static_cast<int32_t>(views->cams.size());
+        f->views = *views;
+        f->cameras.assign(camera, camera + f->n_views);
+    }
     f->tile_done.assign(n_tiles, 0);
     f->streams_total = total;
     for(int i = 0; i < n_scenes; i++) {
@@ -2367,6 +2392,29 @@ int pt_frame_create(pt_scene *const *scenes, int n_scenes, const pt_camera_param
     }
     *out = f.release();
     return PT_OK;
+}
+
+extern "C" {
+
+int pt_frame_create(pt_scene *const *scenes, int n_scenes, const pt_camera_params *camera, const pt_options *options, const pt_tile *tiles, size_t n_tiles,
+                    uint64_t base_seed, pt_frame **out) {
+    return frame_create_impl(scenes, n_scenes, camera, options, tiles, n_tiles, base_seed, nullptr, out);
+}
+
+int pt_frame_create_views(pt_scene *const *scenes, int n_scenes, const pt_camera_params *cameras, const uint64_t *base_seeds, int32_t n_views,
+                          const pt_options *options, pt_frame **out) {
+    if(out == nullptr) {
+        return fail(PT_ERR_INVALID, "null frame pointer");
+    }
+    *out = nullptr;
+    std::vector<pt_tile> tiles;
+    ViewSet views;
+    const int rc = prepare_views(cameras, base_seeds, n_views, options, &tiles, &views);
+    if(rc != PT_OK) {
+        return rc;
+    }
+    // (one view: pt_frame_create over pt_job_tiles with its seed -- no view table, the same launches)
+    return frame_create_impl(scenes, n_scenes, cameras, options, tiles.data(), tiles.size(), base_seeds[0], n_views > 1 ? &views : nullptr, out);
 }
 
 int pt_frame_render(pt_frame *f, float *out_image, pt_stats *stats, pt_progress_fn progress, void *progress_user, pt_render_control *ctl) {
@@ -2612,6 +2660,44 @@ static int features_launch(pt_scene *s, const pt_camera_params *camera, const pt
     return PT_OK;
 }
 
+// The arguments of the view forms (pt_render_features_views*), checked without a device
+static int features_views_check(pt_scene *s, const pt_camera_params *cameras, int32_t n_views, const pt_options *options, const float *out) {
+    if(n_views <= 0) {
+        return fail(PT_ERR_INVALID, "a view batch needs at least one view");
+    }
+    if(options != nullptr && options->image_width > 0 && options->image_height > 0 &&
+       static_cast<uint64_t>(n_views) * static_cast<uint64_t>(options->image_height) * static_cast<uint64_t>(options->image_width) > 0x0fffffffULL) {
+        return fail(PT_ERR_INVALID, "more than 0x0fffffff pixels");
+    }
+    return features_check(s, cameras, options, out);
+}
+
+// features_launch for the stacked frames of n_views cameras, in one launch: into `d_out`, n_views * width * height * 3 float4.
+static int features_views_launch(pt_scene *s, const pt_camera_params *cameras, int32_t n_views, const pt_options *options, float4 *d_out) {
+    if(n_views == 1) {
+        return features_launch(s, cameras, options, d_out);
+    }
+    int rc = setup_path(s);
+    if(rc != PT_OK) {
+        return rc;
+    }
+    std::vector<PtViewCamera> table(static_cast<size_t>(n_views));
+    for(int32_t v = 0; v < n_views; v++) {
+        table[static_cast<size_t>(v)] = PtViewCamera{derive_camera(cameras + v), {0, 0, 0}};
+        table[static_cast<size_t>(v)].cam.aperture_kind = PT_APERTURE_NONE; // the rays are a pure function of camera and pixel
+    }
+    PT_HIP(s->feature_cams.ensure(table.size()));
+    PT_HIP(hipMemcpyAsync(s->feature_cams.ptr, table.data(), table.size() * sizeof(PtViewCamera), hipMemcpyHostToDevice, s->stream));
+    PT_HIP(hipStreamSynchronize(s->stream)); // the table is this function's vector
+    PtPathConfig cfg = s->path_cfg;
+    const size_t n = static_cast<size_t>(n_views) * static_cast<size_t>(options->image_width) * static_cast<size_t>(options->image_height);
+    PT_HIP(s->feature_spill.ensure(((n + 255) / 256) * 256 * cfg.spill_depth));
+    cfg.spill = s->feature_spill.ptr;
+    pt_launch_features_views(s->stream, s->dev, s->feature_cams.ptr, n_views, options->image_width, options->image_height, d_out, cfg);
+    PT_HIP(hipGetLastError());
+    return PT_OK;
+}
+
 namespace {
 
 // The denoiser's scratch buffers: one set per device, grown on demand, one call at a time per device.  They live as long as the process
@@ -2775,6 +2861,49 @@ int pt_render_features_device(pt_scene *s, const pt_camera_params *camera, const
     return PT_OK;
 }
 
+int pt_render_features_views(pt_scene *s, const pt_camera_params *cameras, int32_t n_views, const pt_options *options, float *out_features) {
+    int rc = features_views_check(s, cameras, n_views, options, out_features);
+    if(rc != PT_OK) {
+        return rc;
+    }
+    const size_t n = static_cast<size_t>(n_views) * static_cast<size_t>(options->image_width) * static_cast<size_t>(options->image_height);
+    std::lock_guard<std::mutex> lock(s->render_mutex);
+    PT_HIP(hipSetDevice(s->device));
+    PT_HIP(s->features.ensure(3 * n));
+    rc = features_views_launch(s, cameras, n_views, options, reinterpret_cast<float4 *>(s->features.ptr));
+    if(rc != PT_OK) {
+        return rc;
+    }
+    PT_HIP(hipMemcpyAsync(out_features, s->features.ptr, 3 * n * sizeof(F4), hipMemcpyDeviceToHost, s->stream));
+    PT_HIP(hipStreamSynchronize(s->stream));
+    return PT_OK;
+}
+
+int pt_render_features_views_device(pt_scene *s, const pt_camera_params *cameras, int32_t n_views, const pt_options *options, float *d_out_features, void *stream) {
+    int rc = features_views_check(s, cameras, n_views, options, d_out_features);
+    if(rc != PT_OK) {
+        return rc;
+    }
+    std::lock_guard<std::mutex> lock(s->render_mutex);
+    PT_HIP(hipSetDevice(s->device));
+    // ordered as pt_render_features_device
+    hipStream_t caller = static_cast<hipStream_t>(stream);
+    Event ev;
+    PT_HIP(ev.create(hipEventDisableTiming));
+    PT_HIP(hipEventRecord(ev.e, caller));
+    PT_HIP(hipStreamWaitEvent(s->stream, ev.e, 0));
+    rc = features_views_launch(s, cameras, n_views, options, reinterpret_cast<float4 *>(d_out_features));
+    if(rc != PT_OK) {
+        return rc;
+    }
+    PT_HIP(hipEventRecord(ev.e, s->stream));
+    PT_HIP(hipStreamWaitEvent(caller, ev.e, 0));
+    if(caller == nullptr) {
+        PT_HIP(hipStreamSynchronize(s->stream));
+    }
+    return PT_OK;
+}
+
 int pt_denoise_device(int device, const float *d_rgba, const float *d_features, int32_t width, int32_t height, const pt_denoise_params *params, float *d_out_rgba,
                       void *stream) {
     PtDenoiseParams p{};
@@ -2819,6 +2948,63 @@ int pt_denoise(int device, const float *rgba, const float *features, int32_t wid
     return PT_OK;
 }
 
+// The view forms: n_views frames stacked, every stage one launch for all of them (pt_denoise_views_run)
+static int denoise_views_check(int device, const void *rgba, const void *features, int32_t width, int32_t height, int32_t n_views, const pt_denoise_params *params,
+                               const void *out, PtDenoiseParams *resolved) {
+    if(n_views <= 0) {
+        return fail(PT_ERR_INVALID, "a view batch needs at least one view");
+    }
+    if(width > 0 && height > 0 && static_cast<uint64_t>(n_views) * static_cast<uint64_t>(width) * static_cast<uint64_t>(height) > 0x0fffffffULL) {
+        return fail(PT_ERR_INVALID, "more than 0x0fffffff pixels");
+    }
+    return denoise_check(device, rgba, features, width, height, params, out, resolved);
+}
+
+int pt_denoise_views_device(int device, const float *d_rgba, const float *d_features, int32_t width, int32_t height, int32_t n_views, const pt_denoise_params *params,
+                            float *d_out_rgba, void *stream) {
+    PtDenoiseParams p{};
+    int rc = denoise_views_check(device, d_rgba, d_features, width, height, n_views, params, d_out_rgba, &p);
+    if(rc != PT_OK) {
+        return rc;
+    }
+    const size_t n = static_cast<size_t>(n_views) * static_cast<size_t>(width) * static_cast<size_t>(height);
+    DenoiseWorkspace &ws = denoise_workspace(device);
+    std::lock_guard<std::mutex> lock(ws.mutex);
+    PT_HIP(hipSetDevice(device));
+    rc = denoise_ensure(ws, n, false);
+    if(rc != PT_OK) {
+        return rc;
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    PT_HIP(pt_denoise_views_run(st, reinterpret_cast<const float4 *>(d_rgba), reinterpret_cast<const float4 *>(d_features), nullptr, width, height, n_views, p,
+                                ws.scratch, reinterpret_cast<float4 *>(d_out_rgba)));
+    PT_HIP(hipStreamSynchronize(st)); // the scratch buffers are the device's: the next call may reuse them
+    return PT_OK;
+}
+
+int pt_denoise_views(int device, const float *rgba, const float *features, int32_t width, int32_t height, int32_t n_views, const pt_denoise_params *params,
+                     float *out_rgba) {
+    PtDenoiseParams p{};
+    int rc = denoise_views_check(device, rgba, features, width, height, n_views, params, out_rgba, &p);
+    if(rc != PT_OK) {
+        return rc;
+    }
+    const size_t n = static_cast<size_t>(n_views) * static_cast<size_t>(width) * static_cast<size_t>(height);
+    DenoiseWorkspace &ws = denoise_workspace(device);
+    std::lock_guard<std::mutex> lock(ws.mutex);
+    PT_HIP(hipSetDevice(device));
+    rc = denoise_ensure(ws, n, true);
+    if(rc != PT_OK) {
+        return rc;
+    }
+    PT_HIP(hipMemcpy(ws.in_rgba, rgba, n * sizeof(F4), hipMemcpyHostToDevice));
+    PT_HIP(hipMemcpy(ws.in_features, features, 3 * n * sizeof(F4), hipMemcpyHostToDevice));
+    // in place, as pt_denoise
+    PT_HIP(pt_denoise_views_run(nullptr, ws.in_rgba, ws.in_features, nullptr, width, height, n_views, p, ws.scratch, ws.in_rgba));
+    PT_HIP(hipMemcpy(out_rgba, ws.in_rgba, n * sizeof(F4), hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
 int pt_frame_preview(pt_frame *f, const float *image, const pt_denoise_params *denoise, float *out_rgba, int32_t *out_samples) {
     if(f == nullptr || image == nullptr || out_rgba == nullptr) {
         return fail(PT_ERR_INVALID, "null argument");
@@ -2830,8 +3016,9 @@ int pt_frame_preview(pt_frame *f, const float *image, const pt_denoise_params *d
             return rc;
         }
     }
+    // (a view frame's image is its views stacked: every step below but the features and the filter sees one frame of rows() rows)
     const int32_t width = f->options.image_width, height = f->options.image_height;
-    const size_t n = static_cast<size_t>(width) * static_cast<size_t>(height);
+    const size_t n = static_cast<size_t>(width) * static_cast<size_t>(f->rows());
     if(n > 0x0fffffffULL) {
         return fail(PT_ERR_INVALID, "more than 0x0fffffff pixels");
     }
@@ -2937,7 +3124,8 @@ int pt_frame_preview(pt_frame *f, const float *image, const pt_denoise_params *d
     if(denoise != nullptr) {
         if(!r0.pv_features_ready) {
             PT_HIP(r0.pv_features.ensure(3 * n));
-            const int rc = features_launch(s0, &f->camera, &f->options, reinterpret_cast<float4 *>(r0.pv_features.ptr));
+            const int rc = f->n_views > 1 ? features_views_launch(s0, f->cameras.data(), f->n_views, &f->options, reinterpret_cast<float4 *>(r0.pv_features.ptr))
+                                          : features_launch(s0, &f->camera, &f->options, reinterpret_cast<float4 *>(r0.pv_features.ptr));
             if(rc != PT_OK) {
                 return rc;
             }
@@ -2949,7 +3137,8 @@ int pt_frame_preview(pt_frame *f, const float *image, const pt_denoise_params *d
         if(rc != PT_OK) {
             return rc;
         }
-        PT_HIP(pt_denoise_masked_run(st, view, reinterpret_cast<const float4 *>(r0.pv_features.ptr), r0.pv_samples.ptr, width, height, dp, ws.scratch, view));
+        // (one view: pt_denoise_masked_run itself; more: its view form, a hole filled from its own view only)
+        PT_HIP(pt_denoise_views_run(st, view, reinterpret_cast<const float4 *>(r0.pv_features.ptr), r0.pv_samples.ptr, width, height, f->n_views, dp, ws.scratch, view));
     }
     PT_HIP(hipMemcpyAsync(out_rgba, view, n * sizeof(F4), hipMemcpyDeviceToHost, st));
     if(out_samples != nullptr) {

@@ -30,6 +30,13 @@ hipError_t pt_denoise_run(hipStream_t stream, const float4 *rgba, const float4 *
 hipError_t pt_denoise_masked_run(hipStream_t stream, const float4 *rgba, const float4 *features, const int32_t *samples, int32_t width, int32_t height,
                                  const PtDenoiseParams &params, const PtDenoiseScratch &scratch, float4 *out);
 
+// A batch of n_views frames stacked as [n_views][height][width] (every array, the scratch buffers included, holds n_views * width * height
+// pixels): view v comes out bit for bit as pt_denoise_run (samples == nullptr) or pt_denoise_masked_run gives on view v alone -- no tap
+// crosses a view border.  3 + iterations launches for all views (the view is the grid's z; per 65535 views), n_views == 1 is the single
+// frame's call itself.  `out` may equal rgba.
+hipError_t pt_denoise_views_run(hipStream_t stream, const float4 *rgba, const float4 *features, const int32_t *samples, int32_t width, int32_t height,
+                                int32_t n_views, const PtDenoiseParams &params, const PtDenoiseScratch &scratch, float4 *out);
+
 // ---- the temporal form (pt_temporal_*): one push of a frame of a sequence ----------------------------------------------------------
 
 struct PtTemporalParams {

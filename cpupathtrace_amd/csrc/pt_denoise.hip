@@ -20,9 +20,16 @@
 // variance is read by no other pixel: it records whether a pass has filled the hole (1) or not (0).  Without holes every kMasked kernel
 // computes what its plain form does, operation for operation.
 //
+// pt_denoise_views_run, a batch of V frames stacked as [V][H][W] (pt_denoise_views, the preview of a view frame), runs the
+// plain or the kMasked kernels in their kViews form: the view is blockIdx.z, and every array is moved to that view's first pixel before
+// anything is read.  From there on the kernel is the single frame's, bounds tests included, so no tap crosses a view border and view v is
+// bit for bit what the single-frame run gives on view v alone.  kViews is a template parameter: the single-frame instantiations are untouched.
+//
 // One thread per pixel in 16 x 16 workgroups, float4 loads, fp32, no atomics: the result does not depend on the launch.  Every tap is
 // read from global memory (L1/L2 serve the overlap of neighbouring workgroups); no tile is staged in LDS.
 #include "pt_denoise.h"
+
+#include <algorithm>
 
 namespace {
 
@@ -50,6 +57,11 @@ __device__ __forceinline__ bool temporal_variance_px(const PtTemporalPixel &tp, 
     return n >= tp.min_history && n >= 2;
 }
 
+// kViews: the first pixel of the workgroup's view in the stacked arrays
+__device__ __forceinline__ size_t view_first_pixel(int32_t width, int32_t height) {
+    return (size_t)blockIdx.z * ((size_t)width * (size_t)height);
+}
+
 __device__ __forceinline__ float lum_of(float r, float g, float b) {
     return (0.2126f * r + 0.7152f * g) + 0.0722f * b;
 }
@@ -74,13 +86,24 @@ __device__ __forceinline__ float depth_arg(float tp, float tq, float2 g, float o
 }
 
 // kMasked: `samples` (the preview's sample counts) marks the holes, 0; a hole's colour is 0 whatever the input holds.
-template<bool kMasked>
+template<bool kMasked, bool kViews = false>
 __global__ __launch_bounds__(256) void pt_denoise_prepare_kernel(const float4 *__restrict__ rgba, const float4 *__restrict__ feat, int32_t width, int32_t height,
                                                                  const int32_t *__restrict__ samples, float4 *__restrict__ col, float4 *__restrict__ guide,
                                                                  uint32_t *__restrict__ cls) {
     const int x = blockIdx.x * 16 + threadIdx.x, y = blockIdx.y * 16 + threadIdx.y;
     if(x >= width || y >= height) {
         return;
+    }
+    if constexpr(kViews) {
+        const size_t v0 = view_first_pixel(width, height);
+        rgba += v0;
+        feat += 3 * v0;
+        col += v0;
+        guide += v0;
+        cls += v0;
+        if constexpr(kMasked) {
+            samples += v0;
+        }
     }
     const int p = y * width + x;
     const float4 f0 = feat[3 * p], f1 = feat[3 * p + 1], f2 = feat[3 * p + 2];
@@ -107,13 +130,22 @@ __global__ __launch_bounds__(256) void pt_denoise_prepare_kernel(const float4 *_
 // kTemporal (pt_temporal_run): where the pixel's history is long enough (temporal_variance_px), its variance is that of the integrated
 // luminance moments instead; the spatial estimate is computed as in pt_denoise either way.
 // kMasked: a hole's variance is 0 (not filled yet); its gradient is computed as any pixel's (over neighbours of its class: holes).
-template<bool kTemporal, bool kMasked>
+template<bool kTemporal, bool kMasked, bool kViews = false>
 __global__ __launch_bounds__(256) void pt_denoise_variance_kernel(const float4 *__restrict__ col, const float4 *__restrict__ guide, const uint32_t *__restrict__ cls,
                                                                   int32_t width, int32_t height, float sigma_normal, float sigma_depth, float2 *__restrict__ grad,
                                                                   float *__restrict__ var, PtTemporalPixel tp) {
     const int x = blockIdx.x * 16 + threadIdx.x, y = blockIdx.y * 16 + threadIdx.y;
     if(x >= width || y >= height) {
         return;
+    }
+    if constexpr(kViews) {
+        const size_t v0 = view_first_pixel(width, height);
+        static_assert(!(kViews && kTemporal), "a view batch has no temporal form");
+        col += v0;
+        guide += v0;
+        cls += v0;
+        grad += v0;
+        var += v0;
     }
     const int p = y * width + x;
     const uint32_t cp = cls[p];
@@ -177,7 +209,7 @@ __global__ __launch_bounds__(256) void pt_denoise_variance_kernel(const float4 *
 
 // kTemporal: the luminance sigma is tp.sigma_luminance_temporal at pixels whose variance came from the temporal moments.
 // kMasked: holes are no taps (the variance prefilter included), and a hole is filled (pt_denoise_masked_run).
-template<bool kTemporal, bool kMasked>
+template<bool kTemporal, bool kMasked, bool kViews = false>
 __global__ __launch_bounds__(256) void pt_denoise_atrous_kernel(const float4 *__restrict__ col_in, const float *__restrict__ var_in, const float4 *__restrict__ guide,
                                                                 const uint32_t *__restrict__ cls, const float2 *__restrict__ grad, int32_t width, int32_t height,
                                                                 int32_t step, float sigma_luminance, float sigma_normal, float sigma_depth,
@@ -185,6 +217,17 @@ __global__ __launch_bounds__(256) void pt_denoise_atrous_kernel(const float4 *__
     const int x = blockIdx.x * 16 + threadIdx.x, y = blockIdx.y * 16 + threadIdx.y;
     if(x >= width || y >= height) {
         return;
+    }
+    if constexpr(kViews) {
+        const size_t v0 = view_first_pixel(width, height);
+        static_assert(!(kViews && kTemporal), "a view batch has no temporal form");
+        col_in += v0;
+        var_in += v0;
+        guide += v0;
+        cls += v0;
+        grad += v0;
+        col_out += v0;
+        var_out += v0;
     }
     const int p = y * width + x;
     const uint32_t cp = cls[p];
@@ -435,12 +478,23 @@ __global__ __launch_bounds__(256) void pt_temporal_accumulate_kernel(const float
 
 // (rgba and out may be the same array: no __restrict__ on them)
 // kMasked: a hole that a pass filled has alpha 1, one that none did is (0, 0, 0, 0).
-template<bool kMasked>
+template<bool kMasked, bool kViews = false>
 __global__ __launch_bounds__(256) void pt_denoise_finish_kernel(const float4 *__restrict__ col, const float4 *rgba, const float4 *__restrict__ feat, int32_t width,
                                                                 int32_t height, const uint32_t *__restrict__ cls, const float *__restrict__ var, float4 *out) {
     const int x = blockIdx.x * 16 + threadIdx.x, y = blockIdx.y * 16 + threadIdx.y;
     if(x >= width || y >= height) {
         return;
+    }
+    if constexpr(kViews) {
+        const size_t v0 = view_first_pixel(width, height);
+        col += v0;
+        rgba += v0;
+        feat += 3 * v0;
+        out += v0;
+        if constexpr(kMasked) {
+            cls += v0;
+            var += v0;
+        }
     }
     const int p = y * width + x;
     const float4 f0 = feat[3 * p], f2 = feat[3 * p + 2];
@@ -496,6 +550,63 @@ hipError_t pt_denoise_masked_run(hipStream_t stream, const float4 *rgba, const f
     }
     hipLaunchKernelGGL(pt_denoise_finish_kernel<true>, grid, block, 0, stream, s.col[cur], rgba, features, width, height, s.cls, s.var[cur], out);
     return hipGetLastError();
+}
+
+namespace {
+
+// The kViews launches of `count` views from view `first` on: 3 + iterations launches, the view in blockIdx.z
+template<bool kMasked>
+hipError_t run_views(hipStream_t stream, const float4 *rgba, const float4 *features, const int32_t *samples, int32_t width, int32_t height, size_t first,
+                     uint32_t count, const PtDenoiseParams &params, const PtDenoiseScratch &scratch, float4 *out) {
+    const size_t at = first * (static_cast<size_t>(width) * static_cast<size_t>(height));
+    rgba += at;
+    features += 3 * at;
+    out += at;
+    if(samples != nullptr) {
+        samples += at;
+    }
+    PtDenoiseScratch s = scratch;
+    s.col[0] += at;
+    s.col[1] += at;
+    s.var[0] += at;
+    s.var[1] += at;
+    s.guide += at;
+    s.grad += at;
+    s.cls += at;
+    const dim3 block(16, 16), grid((width + 15) / 16, (height + 15) / 16, count);
+    hipLaunchKernelGGL((pt_denoise_prepare_kernel<kMasked, true>), grid, block, 0, stream, rgba, features, width, height, samples, s.col[0], s.guide, s.cls);
+    hipLaunchKernelGGL((pt_denoise_variance_kernel<false, kMasked, true>), grid, block, 0, stream, s.col[0], s.guide, s.cls, width, height, params.sigma_normal,
+                       params.sigma_depth, s.grad, s.var[0], PtTemporalPixel{});
+    int cur = 0;
+    for(int i = 0; i < params.iterations; i++) {
+        hipLaunchKernelGGL((pt_denoise_atrous_kernel<false, kMasked, true>), grid, block, 0, stream, s.col[cur], s.var[cur], s.guide, s.cls, s.grad, width, height,
+                           1 << i, params.sigma_luminance, params.sigma_normal, params.sigma_depth, s.col[cur ^ 1], s.var[cur ^ 1], PtTemporalPixel{});
+        cur ^= 1;
+    }
+    hipLaunchKernelGGL((pt_denoise_finish_kernel<kMasked, true>), grid, block, 0, stream, s.col[cur], rgba, features, width, height, kMasked ? s.cls : nullptr,
+                       kMasked ? s.var[cur] : nullptr, out);
+    return hipGetLastError();
+}
+
+} // namespace
+
+hipError_t pt_denoise_views_run(hipStream_t stream, const float4 *rgba, const float4 *features, const int32_t *samples, int32_t width, int32_t height,
+                                int32_t n_views, const PtDenoiseParams &params, const PtDenoiseScratch &scratch, float4 *out) {
+    if(n_views == 1) { // the single frame's own launches
+        return samples != nullptr ? pt_denoise_masked_run(stream, rgba, features, samples, width, height, params, scratch, out)
+                                  : pt_denoise_run(stream, rgba, features, width, height, params, scratch, out);
+    }
+    // (a grid has 65535 planes at most: a longer batch takes one set of launches per 65535 views, each on its own part of every array)
+    constexpr size_t kMaxPlanes = 65535;
+    for(size_t first = 0; first < static_cast<size_t>(n_views); first += kMaxPlanes) {
+        const uint32_t count = static_cast<uint32_t>(std::min(kMaxPlanes, static_cast<size_t>(n_views) - first));
+        const hipError_t e = samples != nullptr ? run_views<true>(stream, rgba, features, samples, width, height, first, count, params, scratch, out)
+                                                : run_views<false>(stream, rgba, features, nullptr, width, height, first, count, params, scratch, out);
+        if(e != hipSuccess) {
+            return e;
+        }
+    }
+    return hipSuccess;
 }
 
 hipError_t pt_temporal_run(hipStream_t stream, const float4 *rgba, const float4 *features, int32_t width, int32_t height, const PtTemporalParams &params,

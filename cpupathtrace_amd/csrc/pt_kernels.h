@@ -171,6 +171,10 @@ void pt_launch_closest(hipStream_t stream, const PtDevScene &scene, const float 
 // first-hit features of a width x height frame for the denoiser (pt_feature_kernel): out[3 * pixel + k], k = albedo + coverage, normal + t,
 // position + emission luminance; `camera` must have no aperture sampler.  The walk, its instantiation and cfg.spill are pt_launch_closest's.
 void pt_launch_features(hipStream_t stream, const PtDevScene &scene, const PtDevCamera &camera, int32_t width, int32_t height, float4 *out, const PtPathConfig &cfg);
+// the same for n_views frames of width x height in one launch: out[3 * ((v * height + y) * width + x) + k] is what pt_launch_features gives
+// pixel (x, y) with views[v].cam (a DEVICE table whose cameras have no aperture); cfg.spill holds n_views * width * height walks
+void pt_launch_features_views(hipStream_t stream, const PtDevScene &scene, const PtViewCamera *views, int32_t n_views, int32_t width, int32_t height, float4 *out,
+                              const PtPathConfig &cfg);
 // diagnostic (tools/step_timing.py): stamped walks, `lanes_per_wave` rays per wavefront; out[ray] = (steps, cycles waiting for records, cycles in all, price of a stamp pair)
 void pt_launch_steptime(hipStream_t stream, const PtDevScene &scene, const float *rays6, uint32_t n, uint32_t lanes_per_wave, uint4 *out, uint2 *spill, uint32_t spill_depth, int flags);
 

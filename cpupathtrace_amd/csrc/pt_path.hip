@@ -1608,9 +1608,13 @@ __global__ __launch_bounds__(256) void pt_closest_kernel(PtDevScene sc, const fl
 //   k = 0: albedo rgb (diffuse for Lambertian, specular for glass and mirror, white for no material), fraction of rays that hit
 //   k = 1: shading normal xyz (object_normal), hit distance t
 //   k = 2: hit position xyz (o + d * t), luminance of the material's emission
-template<int STACK_LDS, bool IN_LDS>
+// kViews (pt_render_features_views): `height` is the row count of n views stacked as in a view batch, view_height the rows of one; a pixel's
+// camera is views[row / view_height] (aperture none, as `cam`), read per lane, and its row the one inside its view.  Everything else is the
+// single frame's, so view v is bit for bit the single frame's result for views[v].  The single-frame instantiations read `cam` and have no
+// such test: kViews is a template parameter.
+template<int STACK_LDS, bool IN_LDS, bool kViews>
 __global__ __launch_bounds__(256) void pt_feature_kernel(PtDevScene sc, PtDevCamera cam, int32_t width, int32_t height, float4 *__restrict__ out, uint2 *__restrict__ spill,
-                                                         uint32_t spill_depth) {
+                                                         uint32_t spill_depth, const PtViewCamera *__restrict__ views, int32_t view_height) {
     extern __shared__ __align__(16) unsigned char lds_raw[];
     const int tid = threadIdx.x;
     lds_u2_ptr stack_l = (lds_u2_ptr)reinterpret_cast<uint2 *>(lds_raw) + tid;
@@ -1634,7 +1638,16 @@ __global__ __launch_bounds__(256) void pt_feature_kernel(PtDevScene sc, PtDevCam
     if(gid >= (size_t)width * (size_t)height) {
         return;
     }
-    const int32_t px = (int32_t)(gid % (size_t)width), py = (int32_t)(gid / (size_t)width);
+    const int32_t px = (int32_t)(gid % (size_t)width);
+    int32_t py = (int32_t)(gid / (size_t)width);
+    const PtDevCamera *lane_cam = &cam;
+    int32_t frame_height = height;
+    if constexpr(kViews) {
+        const int32_t view = py / view_height;
+        py -= view * view_height;
+        lane_cam = &views[view].cam;
+        frame_height = view_height;
+    }
     RootBox root;
     root.ref = sc.root_ref;
     for(int k = 0; k < 3; k++) {
@@ -1647,10 +1660,10 @@ __global__ __launch_bounds__(256) void pt_feature_kernel(PtDevScene sc, PtDevCam
         // the camera ray of the path kernel (worker.cpp:166-168) with x + 1/2 + dx in place of x + 1/2
         const float one_half = 1.0f / 2.0f;
         const float x_camera = 2 * (((float)px + one_half + dx) / (float)width - one_half);
-        float y_camera = 2 * (((float)py + one_half + dy) / (float)height - one_half);
+        float y_camera = 2 * (((float)py + one_half + dy) / (float)frame_height - one_half);
         y_camera = -y_camera;
         uint64_t rng = 0; // (drawn from, never used: both offsets are +0 and there is no aperture)
-        const Ray ray = camera_shoot(cam, x_camera, y_camera, 0.0f, 0.0f, rng);
+        const Ray ray = camera_shoot(*lane_cam, x_camera, y_camera, 0.0f, 0.0f, rng);
         Walk w;
         typename Tracer<STACK_LDS, IN_LDS>::Rec rec;
         rec.r0 = rec.r1 = rec.r2 = rec.r3 = (f4v){0.0f, 0.0f, 0.0f, 0.0f};
@@ -1890,12 +1903,20 @@ void launch_closest(hipStream_t stream, const PtDevScene &scene, const float *ra
     hipLaunchKernelGGL((pt_closest_kernel<STACK_LDS, IN_LDS>), dim3((n + 255) / 256), dim3(256), lds, stream, scene, rays6, n, out, cfg.spill, cfg.spill_depth);
 }
 
+// views == nullptr: the frame of `cam`; else the stacked frames of views[0 .. height / view_height)
 template<int STACK_LDS, bool IN_LDS>
-void launch_features(hipStream_t stream, const PtDevScene &scene, const PtDevCamera &cam, int32_t width, int32_t height, float4 *out, const PtPathConfig &cfg) {
+void launch_features(hipStream_t stream, const PtDevScene &scene, const PtDevCamera &cam, int32_t width, int32_t height, float4 *out, const PtPathConfig &cfg,
+                     const PtViewCamera *views = nullptr, int32_t view_height = 0) {
     const size_t lds = (size_t)STACK_LDS * 256 * sizeof(uint2) + (IN_LDS ? ((size_t)scene.n_lds_pairs + scene.pair_base) * 64 : 0);
     const size_t n = (size_t)width * (size_t)height;
-    hipLaunchKernelGGL((pt_feature_kernel<STACK_LDS, IN_LDS>), dim3((unsigned)((n + 255) / 256)), dim3(256), lds, stream, scene, cam, width, height, out, cfg.spill,
-                       cfg.spill_depth);
+    if(views != nullptr) {
+        hipLaunchKernelGGL((pt_feature_kernel<STACK_LDS, IN_LDS, true>), dim3((unsigned)((n + 255) / 256)), dim3(256), lds, stream, scene, cam, width, height, out,
+                           cfg.spill, cfg.spill_depth, views, view_height);
+    }
+    else {
+        hipLaunchKernelGGL((pt_feature_kernel<STACK_LDS, IN_LDS, false>), dim3((unsigned)((n + 255) / 256)), dim3(256), lds, stream, scene, cam, width, height, out,
+                           cfg.spill, cfg.spill_depth, nullptr, 0);
+    }
 }
 
 } // namespace
@@ -1997,6 +2018,24 @@ void pt_launch_features(hipStream_t stream, const PtDevScene &scene, const PtDev
     }
     else {
         launch_features<PT_PATH_STACK_LDS, false>(stream, scene, camera, width, height, out, cfg);
+    }
+}
+
+void pt_launch_features_views(hipStream_t stream, const PtDevScene &scene, const PtViewCamera *views, int32_t n_views, int32_t width, int32_t height, float4 *out,
+                              const PtPathConfig &cfg) {
+    if(width <= 0 || height <= 0 || n_views <= 0) {
+        return;
+    }
+    const PtDevCamera none{}; // (never read: every pixel has its view's camera)
+    const int32_t rows = n_views * height;
+    if(cfg.in_lds && cfg.stack_lds == PT_PATH_STACK_LDS_SMALL) {
+        launch_features<PT_PATH_STACK_LDS_SMALL, true>(stream, scene, none, width, rows, out, cfg, views, height);
+    }
+    else if(cfg.in_lds) {
+        launch_features<PT_PATH_STACK_LDS, true>(stream, scene, none, width, rows, out, cfg, views, height);
+    }
+    else {
+        launch_features<PT_PATH_STACK_LDS, false>(stream, scene, none, width, rows, out, cfg, views, height);
     }
 }
 

@@ -43,6 +43,7 @@ public:
 private:
     friend Image<> processJob(const FrameRenderJob &, RenderControl &, const std::function<void(int, int)> &, int);
     friend class FrameRender; // (PathTrace/frame_render.h: a resumable processJob)
+    friend class ViewBatchRender; // (PathTrace/view_batch_render.h: a resumable processViews)
     pt_render_control ctl_;
     bool cancelled_ = false;
     std::vector<Tile> finished_;

@@ -1,0 +1,55 @@
+// PathTrace/view_batch_render.h -- processViews that can be stopped, continued and previewed (PathTrace/view_batch.h and
+// PathTrace/frame_render.h together).
+#ifndef PATHTRACE_VIEW_BATCH_RENDER_H
+#define PATHTRACE_VIEW_BATCH_RENDER_H
+
+#include <PathTrace/camera.h>
+#include <PathTrace/image/image.h>
+#include <PathTrace/render_control.h>
+#include <PathTrace/scene/scene.h>
+#include <PathTrace/worker.h>
+
+#include "../pt_hip.h"
+
+#include <cstdint>
+#include <functional>
+#include <vector>
+
+// One frame per camera, all in one launch per device replica as processViews renders them, in as many calls as the caller likes: every
+// render() continues where the last one stopped, as FrameRender does for one frame.  The finished images are bit for bit what processViews
+// gives with the same $PATHTRACE_SEED (view v takes the seed base + v; pass `seeds` to choose them) -- without denoising: options.allow_bias
+// is ignored, preview() shows the batch as it stands, denoised if asked.  A denoised preview of the complete batch equals processViews with
+// allow_bias.  The scene must outlive the ViewBatchRender.  Throws std::invalid_argument for an empty camera list, a null camera or a seed
+// list of another length.
+class ViewBatchRender {
+public:
+    ViewBatchRender(const Scene &scene, const std::vector<const Camera *> &cameras, const RenderOptions &options, const std::vector<std::uint64_t> &seeds = {},
+                    int worker_count = 0);
+    ~ViewBatchRender();
+    ViewBatchRender(const ViewBatchRender &) = delete;
+    ViewBatchRender &operator=(const ViewBatchRender &) = delete;
+
+    // As FrameRender::render; the tiles control reports lie in the stacked image: view v's tiles have y in [v * height, (v + 1) * height).
+    bool render(RenderControl &control, const std::function<void(int, int)> &progress_callback = [](int, int) {});
+    // the views so far: finished pixels are final, the others transparent black (0, 0, 0, 0)
+    std::vector<Image<>> images() const;
+    bool complete() const noexcept { return complete_; }
+    pt_frame_info info() const;
+    // As FrameRender::preview, per view: `out` gets one image per view, `samples` (if not null) one count per pixel, [view][y][x].  With
+    // `denoise` a hole is filled from pixels of its own view only.
+    void preview(std::vector<Image<>> &out, std::vector<std::int32_t> *samples = nullptr, const pt_denoise_params *denoise = nullptr) const;
+    const std::vector<std::uint64_t> &seeds() const noexcept { return seeds_; }
+    std::size_t viewCount() const noexcept { return seeds_.size(); }
+
+private:
+    std::vector<Image<>> split(const std::vector<float> &stacked) const;
+
+    int width_ = 0, height_ = 0;
+    std::vector<float> stacked_; // [V][H][W][4]
+    std::vector<pt_tile> tiles_;
+    std::vector<std::uint64_t> seeds_;
+    pt_frame *frame_ = nullptr;
+    bool complete_ = false;
+};
+
+#endif

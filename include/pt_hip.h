@@ -201,7 +201,9 @@ int pt_render_tiles_device(pt_scene *scene, const pt_camera_params *camera, cons
  * seeded from (base_seeds[v], x, y) and equal pt_render_tiles(camera = cameras[v], base_seed = base_seeds[v]) bit for bit; one view is
  * that call.  out_images: [n_views][height][width][4] floats.  The views' tiles are dealt to the replicas as in pt_render_tiles_multi;
  * progress counts the tiles of all views (n_views * pt_job_tiles(width, height)).  PT_ERR_INVALID without a launch for n_views <= 0, null
- * tables, or more than 0x0fffffff pixels in all.  The views share the options; there is no controlled or resumable form. */
+ * tables, or more than 0x0fffffff pixels in all.  The views share the options.  The resumable form of a batch is pt_frame_create_views
+ * (below); one pt_frame_render call of such a frame with a `ctl` is the controlled render of a batch, at the frame path's overhead
+ * (+5.8 % on the metric frame). */
 int pt_render_views(pt_scene *const *scenes, int n_scenes, const pt_camera_params *cameras, const uint64_t *base_seeds, int32_t n_views,
                     const pt_options *options, float *out_images, pt_stats *stats, pt_progress_fn progress, void *user);
 /* Same, one scene, into DEVICE memory (e.g. a [V, H, W, 4] torch tensor's data_ptr), ordered on `stream` as pt_render_tiles_device. */
@@ -272,6 +274,21 @@ typedef struct pt_frame_info {
 } pt_frame_info;
 int pt_frame_create(pt_scene *const *scenes, int n_scenes, const pt_camera_params *camera, const pt_options *options, const pt_tile *tiles,
                     size_t n_tiles, uint64_t base_seed, pt_frame **out);
+/* A resumable frame over a view batch: the job of pt_render_views (same arguments, same tile list -- pt_job_tiles(width, height) of every view,
+ * moved down by v * height, dealt to the replicas as always), behind the same handle.  pt_frame_render, pt_frame_get_info, pt_frame_preview and
+ * pt_frame_destroy work on it with the contracts above; out_image / image / out_rgba are [n_views][height][width][4], out_samples is
+ * [n_views][height][width], tile_done and progress cover n_views * pt_job_tiles(width, height) tiles.  However the calls were sliced, the
+ * finished image equals pt_render_views with the same arguments bit for bit (so view v equals pt_render_tiles(cameras[v], base_seeds[v])).
+ * The frame keeps its own copies of the cameras and seeds, on the host and in device tables of its own: other batches on the same scenes
+ * between two slices do not disturb it.  n_views == 1 is pt_frame_create over pt_job_tiles(width, height) with base_seeds[0].
+ * PT_ERR_INVALID before anything is uploaded: n_views <= 0, null tables, more than 0x0fffffff pixels or more than 2^31 - 1 rows in all;
+ * PT_ERR_NO_DEVICE as pt_frame_create.
+ * Preview of a view frame: per view as described at pt_frame_preview; with `denoise` the features are pt_render_features_views with the frame's
+ * cameras and the filter is the view form of the masked filter, so a hole is filled only from taps of its own view.  One device keeps about
+ * 2^20 streams in flight: a batch of more pixels than that has whole views that are still holes after its first slice (the work list is
+ * view after view). */
+int pt_frame_create_views(pt_scene *const *scenes, int n_scenes, const pt_camera_params *cameras, const uint64_t *base_seeds, int32_t n_views,
+                          const pt_options *options, pt_frame **out);
 int pt_frame_render(pt_frame *frame, float *out_image, pt_stats *stats, pt_progress_fn progress, void *user, pt_render_control *ctl);
 /* (the info of a frame: `pt_frame_info` names the struct, so the function is pt_frame_get_info) */
 int pt_frame_get_info(const pt_frame *frame, pt_frame_info *info);
@@ -329,6 +346,19 @@ int pt_render_features_device(pt_scene *scene, const pt_camera_params *camera, c
 int pt_denoise(int device, const float *rgba, const float *features, int32_t width, int32_t height, const pt_denoise_params *params, float *out_rgba);
 int pt_denoise_device(int device, const float *d_rgba, const float *d_features, int32_t width, int32_t height, const pt_denoise_params *params,
                       float *d_out_rgba, void *stream);
+
+/* The same for a batch of n_views frames of one size (a view batch: pt_render_views, pt_frame_create_views), ONE launch per stage for all
+ * views: 1 feature launch, 3 + iterations filter launches, whatever n_views is.  features: [n_views][height][width][3][4]; rgba and out_rgba:
+ * [n_views][height][width][4].  View v of each result is bit for bit what pt_render_features(cameras[v]) or pt_denoise on view v alone gives:
+ * a neighbour or tap counts only if it lies in the same view, everything else is the same arithmetic in the same order.  n_views == 1 is the
+ * single-frame entry point.  PT_ERR_INVALID as for those, and for n_views <= 0 or more than 0x0fffffff pixels over all views. */
+int pt_render_features_views(pt_scene *scene, const pt_camera_params *cameras, int32_t n_views, const pt_options *options, float *out_features);
+int pt_render_features_views_device(pt_scene *scene, const pt_camera_params *cameras, int32_t n_views, const pt_options *options, float *d_out_features,
+                                    void *stream);
+int pt_denoise_views(int device, const float *rgba, const float *features, int32_t width, int32_t height, int32_t n_views,
+                     const pt_denoise_params *params, float *out_rgba);
+int pt_denoise_views_device(int device, const float *d_rgba, const float *d_features, int32_t width, int32_t height, int32_t n_views,
+                            const pt_denoise_params *params, float *d_out_rgba, void *stream);
 
 /* The frame as it stands: what a viewer shows between two pt_frame_render calls.  `image` is the buffer the caller passes
  * to pt_frame_render (it holds the finished pixels); out_rgba is [height][width][4] floats and may equal `image` only when the caller no

@@ -1,4 +1,5 @@
-// src/host/view_batch.cpp -- processViews of PathTrace/view_batch.h on top of pt_render_views (include/pt_hip.h).
+// src/host/view_batch.cpp -- processViews of PathTrace/view_batch.h on top of pt_render_views, and with allow_bias of
+// pt_render_features_views and pt_denoise_views (include/pt_hip.h).
 #include <PathTrace/denoise.h>
 #include <PathTrace/view_batch.h>
 
@@ -53,11 +54,17 @@ std::vector<Image<>> processViews(const Scene &scene, const std::vector<const Ca
         std::rethrow_exception(forward.failure);
     }
     check(status, "processViews");
+    if(options.allow_bias) {
+        // as processJob denoises its frame, every view bit for bit, but with one launch per stage for the whole batch
+        const DenoiseParams defaults;
+        const pt_denoise_params p{defaults.iterations, defaults.sigma_luminance, defaults.sigma_normal, defaults.sigma_depth};
+        std::vector<float> features(per_view * 12 * cameras.size());
+        check(pt_render_features_views(replicas.front(), params.data(), static_cast<int32_t>(cameras.size()), &opt, features.data()), "processViews (features)");
+        check(pt_denoise_views(sceneDevice(), stacked.data(), features.data(), width, height, static_cast<int32_t>(cameras.size()), &p, stacked.data()),
+              "processViews (denoise)");
+    }
     for(size_t v = 0; v < cameras.size(); v++) {
         std::memcpy(views[v].data(), stacked.data() + v * per_view * 4, per_view * 4 * sizeof(float));
-        if(options.allow_bias) {
-            views[v] = denoise(views[v], scene, *cameras[v], options); // as processJob denoises its frame
-        }
     }
     return views;
 }
