@@ -43,6 +43,8 @@ DENOISE_EXPORTS = ["pt_denoise_params_default", "pt_render_features", "pt_render
 EXPORTS += DENOISE_EXPORTS
 VIEWS_FRAME_EXPORTS = ["pt_frame_create_views", "pt_render_features_views", "pt_render_features_views_device", "pt_denoise_views", "pt_denoise_views_device"]
 EXPORTS += VIEWS_FRAME_EXPORTS
+PROGRESSIVE_EXPORTS = ["pt_frame_set_progressive", "pt_frame_get_progress"]
+EXPORTS += PROGRESSIVE_EXPORTS
 TEMPORAL_EXPORTS = ["pt_temporal_params_default", "pt_temporal_create", "pt_temporal_denoise", "pt_temporal_denoise_device", "pt_temporal_reset",
                     "pt_temporal_destroy"]
 EXPORTS += TEMPORAL_EXPORTS
@@ -274,6 +276,16 @@ class FrameInfo(C.Structure):
     _fields_ = [("streams_total", C.c_uint64), ("streams_finished", C.c_uint64), ("streams_parked", C.c_uint64), ("streams_untouched", C.c_uint64),
                 ("tiles_total", C.c_uint64), ("tiles_done", C.c_uint64), ("samples_carried", C.c_uint64), ("parked_with_candidates", C.c_uint64),
                 ("park_bytes", C.c_uint64), ("launches", C.c_int32), ("status", C.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class FrameProgress(C.Structure):
+    """pt_frame_progress: where a progressive frame stands."""
+    _fields_ = [("quantum", C.c_int32), ("max_passes_per_call", C.c_int32), ("passes_completed", C.c_int32), ("target", C.c_int32),
+                ("pass_in_progress", C.c_int32), ("min_samples", C.c_int32), ("max_samples", C.c_int32), ("streams_at_target", C.c_uint64),
+                ("samples_lost", C.c_uint64)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -621,6 +633,25 @@ class Frame:
         _check(load().pt_frame_get_info(self._h, C.byref(fi)))
         return fi.as_dict()
 
+    def set_progressive(self, quantum, max_passes_per_call=0):
+        """Progressive mode (pt_frame_set_progressive): render() then works in passes, each bringing every unfinished pixel to `quantum`
+        more samples, so the preview has samples everywhere; it returns (status PT_ERR_CANCELLED) after max_passes_per_call passes if that
+        is > 0.  quantum 0 turns the mode off.  Between two render() calls only; the finished image does not depend on it."""
+        if self._h is None:
+            raise ValueError("frame is closed")
+        if quantum < 0:
+            raise ValueError("quantum must be >= 0")
+        _check(load().pt_frame_set_progressive(self._h, C.c_int32(quantum), C.c_int32(max_passes_per_call)))
+
+    def progress(self):
+        """pt_frame_get_progress as a dict: passes_completed, target, pass_in_progress, min_samples / max_samples over the unfinished
+        pixels, streams_at_target, samples_lost (always 0)."""
+        if self._h is None:
+            raise ValueError("frame is closed")
+        fp = FrameProgress()
+        _check(load().pt_frame_get_progress(self._h, C.byref(fp)))
+        return fp.as_dict()
+
     def preview(self, denoise=None):
         """The frame as it stands (pt_frame_preview): (rgba, samples).  rgba (h, w, 4) float32: finished pixels as self.image, parked ones
         the running mean of their samples so far, holes (untouched pixels) 0.  samples (h, w) int32: -1 finished, the samples a parked
@@ -652,10 +683,10 @@ class Frame:
 
 
 class ViewsFrame(Frame):
-    """process_views that can be stopped and continued (pt_frame_create_views): a Frame over a view batch.  render, info, preview, done and
-    close are Frame's; image and the preview are (V, H, W, 4), the preview's sample counts (V, H, W), tile_done covers the tiles of all
-    views (V x job_tiles(W, H), view after view).  The finished images equal process_views / process_views_multi with the same seeds bit
-    for bit, however the calls were sliced.  base_seeds: one int for every view, or V ints."""
+    """process_views that can be stopped and continued (pt_frame_create_views): a Frame over a view batch.  render, info, preview, done,
+    set_progressive, progress and close are Frame's; image and the preview are (V, H, W, 4), the preview's sample counts (V, H, W), tile_done
+    covers the tiles of all views (V x job_tiles(W, H), view after view).  The finished images equal process_views / process_views_multi
+    with the same seeds bit for bit, however the calls were sliced.  base_seeds: one int for every view, or V ints."""
 
     def __init__(self, scenes, cameras, options, base_seeds=1234):
         self._scenes = list(scenes) if isinstance(scenes, (list, tuple)) else [scenes]

@@ -263,6 +263,7 @@ int derive_options(const pt_options *o, PtDevOptions *out) {
     d.image_height = o->image_height;
     d.min_sample_count = o->min_sample_count;
     d.max_sample_count = o->max_sample_count;
+    d.overlap_bound = o->max_sample_count;
     d.epsilon = o->epsilon;
     d.pixel_width = 1.0F / static_cast<float>(o->image_width);
     d.pixel_height = 1.0F / static_cast<float>(o->image_height);
@@ -2115,6 +2116,8 @@ struct pt_frame {
         uint32_t n_streams = 0;
         uint32_t n_todo = 0, n_parked = 0; // the next launch's work list: its length, and the parked streams at its head
         uint64_t samples_carried = 0, with_candidates = 0;
+        uint32_t n_at_target = 0;                 // streams of the list at or above the target of the last progressive pass
+        int32_t min_samples = 0, max_samples = 0; // samples taken, over the list's pixels
         bool ready = false; // the device tables exist
         bool in_order = true; // the work list is every stream of the replica in order (stream i at index i)
         int cur = 0;        // todo[cur] and park[cur] are what the next launch reads
@@ -2149,6 +2152,11 @@ struct pt_frame {
     std::vector<uint8_t> tile_done;
     uint64_t tiles_done = 0, streams_total = 0;
     int32_t launches = 0;
+    // progressive mode (pt_frame_set_progressive): passes of `quantum` samples per pixel; `target` is the sample count of the pass in
+    // progress or last completed, the same for every replica
+    int32_t quantum = 0, max_passes_per_call = 0, passes_completed = 0, target = 0;
+    bool pass_in_progress = false;
+    uint64_t samples_lost = 0;
     int status = PT_OK; // a failed frame returns this (and `error`) from every later call
     std::string error;
     mutable std::mutex mutex; // one call at a time
@@ -2184,7 +2192,7 @@ int frame_prepare(pt_frame::Replica &r) {
     PT_HIP(r.d_blocks.ensure(2 * ((static_cast<size_t>(r.n_streams) + 1023) / 1024)));
     PT_HIP(r.d_park_count.ensure(1));
     PT_HIP(r.d_park[0].ensure(1));
-    PT_HIP(r.d_result.ensure(8));
+    PT_HIP(r.d_result.ensure(16));
     r.ready = true;
     return PT_OK;
 }
@@ -2218,8 +2226,9 @@ struct FrameLaunch {
 };
 
 // One launch of a replica: its work list, under the scene's lock, then the next work list
+// (yield_at > 0: a pass of a progressive frame up to that sample count)
 int frame_launch(pt_frame &f, pt_frame::Replica &r, float *out_image, pt_stats *stats, pt_progress_fn progress, void *progress_user, RenderStop *stop,
-                 FrameLaunch *out) {
+                 FrameLaunch *out, int32_t yield_at) {
     pt_scene *s = r.s;
     std::lock_guard<std::mutex> lock(s->render_mutex);
     PT_HIP(hipSetDevice(s->device));
@@ -2245,14 +2254,19 @@ int frame_launch(pt_frame &f, pt_frame::Replica &r, float *out_image, pt_stats *
     if(rc != PT_OK) {
         return rc;
     }
-    // park storage: one record per slot at most (a stop closes the pool, so a slot drops one stream at most), and never more than the streams left
+    // park storage: one record per slot at most (a stop closes the pool, so a slot drops one stream at most), and never more than the streams left.
+    // A progressive pass keeps the pool open and every stream of the list leaves a record, written by the launch or carried over: one per entry.
     PtPathConfig cfg;
     rc = ensure_path_workspace(s, r.n_todo, &cfg);
     if(rc != PT_OK) {
         return rc;
     }
     const int cur = r.cur, next = cur ^ 1;
-    const uint32_t cap = std::min<uint32_t>(r.n_todo, s->path_slots);
+    const bool progressive = yield_at > 0;
+    const uint32_t cap = progressive ? r.n_todo : std::min<uint32_t>(r.n_todo, s->path_slots);
+    if(progressive) {
+        opt.overlap_bound = std::min(opt.max_sample_count, yield_at); // (the sample that reaches the target ends at a boundary of its own)
+    }
     PT_HIP(r.d_park[next].ensure(cap));
     PT_HIP(hipMemsetAsync(r.d_park_count.ptr, 0, sizeof(uint32_t), s->stream));
     PtStreams T{};
@@ -2281,6 +2295,7 @@ int frame_launch(pt_frame &f, pt_frame::Replica &r, float *out_image, pt_stats *
     T.park_count = r.d_park_count.ptr;
     T.park_cap = cap;
     T.status = r.d_status.ptr;
+    T.yield_at = progressive ? yield_at : 0;
     rc = run_path(s, cam, opt, T, reinterpret_cast<float4 *>(s->image.ptr), stats, progress, progress_user, nullptr, false, stop);
     if(rc != PT_OK) {
         return rc;
@@ -2293,28 +2308,33 @@ int frame_launch(pt_frame &f, pt_frame::Replica &r, float *out_image, pt_stats *
     if(rc != PT_OK) {
         return rc;
     }
-    if(pt_launch_frame_compact(s->stream, r.d_todo[cur].ptr, r.n_todo, r.d_status.ptr, r.d_park[next].ptr, r.d_todo[next].ptr, r.d_blocks.ptr, r.d_result.ptr) != 0) {
+    if(pt_launch_frame_compact(s->stream, r.d_todo[cur].ptr, r.n_todo, r.d_status.ptr, r.d_park[next].ptr, r.d_todo[next].ptr, r.d_blocks.ptr, r.d_result.ptr,
+                               progressive ? yield_at : 0, r.d_park[cur].ptr, r.d_park[next].ptr, r.d_park_count.ptr, cap) != 0) {
         PT_HIP(hipGetLastError());
         return fail(PT_ERR_HIP, "frame: work list kernel failed to launch");
     }
-    unsigned long long res[8];
+    unsigned long long res[16];
     PT_HIP(hipMemcpyAsync(res, r.d_result.ptr, sizeof(res), hipMemcpyDeviceToHost, s->stream));
     std::vector<uint32_t> left(r.tiles.size());
     PT_HIP(hipMemcpyAsync(left.data(), r.d_left.ptr, left.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
     PT_HIP(hipStreamSynchronize(s->stream));
     // every stream of the work list is finished, parked or still to do, and the stop dropped no more than the parked and returned ones
     const StreamTally &t = out->tally;
-    if(t.finished + res[0] + res[1] != r.n_todo || res[0] > t.abandoned || res[0] > cap) {
+    // (res[8]: the records the launch wrote; a progressive pass drops no record: res[9], the samples of records that found no room, is 0)
+    if(t.finished + res[0] + res[1] != r.n_todo || res[8] > t.abandoned || res[7] > cap || (!progressive && res[8] != res[0]) || res[9] != 0) {
         return fail(PT_ERR_HIP, "frame: " + std::to_string(t.finished) + " finished, " + std::to_string(res[0]) + " parked and " + std::to_string(res[1]) +
                                     " left of " + std::to_string(r.n_todo) + " streams (" + std::to_string(t.abandoned) + " dropped)");
     }
     r.n_todo = static_cast<uint32_t>(res[0] + res[1]);
-    r.n_parked = static_cast<uint32_t>(res[0]);
-    r.in_order = r.n_todo == r.n_streams && (r.n_parked == 0 || r.n_parked == r.n_todo); // (parked first, each part in order)
+    r.n_parked = static_cast<uint32_t>(res[7]);
+    r.in_order = r.n_todo == r.n_streams && (r.n_parked == 0 || r.n_parked == r.n_todo) && (!progressive || res[0] == 0 || res[1] == 0); // (each part in order)
     r.samples_carried = res[3];
     r.with_candidates = res[4];
+    r.n_at_target = progressive ? static_cast<uint32_t>(res[1]) : 0;
+    r.min_samples = r.n_todo != 0 ? static_cast<int32_t>(0xffffffffULL - res[5]) : 0;
+    r.max_samples = static_cast<int32_t>(res[6]);
     r.cur = next;
-    out->parked = res[0];
+    out->parked = res[8];
     for(size_t k = 0; k < left.size(); k++) {
         f.tile_done[r.index[k]] = left[k] == 0 ? 1 : 0;
     }
@@ -2475,60 +2495,172 @@ int pt_frame_render(pt_frame *f, float *out_image, pt_stats *stats, pt_progress_
         sh->completed++;
         sh->fn(sh->completed, sh->total, sh->user);
     };
-    std::vector<int> rcs(static_cast<size_t>(n_scenes), PT_OK);
-    std::vector<std::string> errors(static_cast<size_t>(n_scenes));
-    std::vector<FrameLaunch> launched(static_cast<size_t>(n_scenes));
-    std::vector<char> ran(static_cast<size_t>(n_scenes), 0);
-    auto work = [&](int i) {
-        pt_frame::Replica &r = *f->reps[static_cast<size_t>(i)];
-        if(r.n_todo == 0) {
-            return;
-        }
-        ran[static_cast<size_t>(i)] = 1;
-        rcs[static_cast<size_t>(i)] = frame_launch(*f, r, out_image, stats != nullptr ? stats + i : nullptr, progress != nullptr ? static_cast<pt_progress_fn>(trampoline) : nullptr,
-                                                   &shared, &stop, &launched[static_cast<size_t>(i)]);
-        if(rcs[static_cast<size_t>(i)] != PT_OK) {
-            errors[static_cast<size_t>(i)] = g_last_error;
-        }
-    };
-    std::vector<std::thread> threads;
-    for(int i = 1; i < n_scenes; i++) {
-        threads.emplace_back(work, i);
-    }
-    work(0);
-    for(std::thread &t : threads) {
-        t.join();
-    }
-    for(int i = 0; i < n_scenes; i++) {
-        f->launches += ran[static_cast<size_t>(i)];
-    }
-    for(int i = 0; i < n_scenes; i++) {
-        if(rcs[static_cast<size_t>(i)] != PT_OK) {
-            f->status = rcs[static_cast<size_t>(i)];
-            f->error = "frame failed: scene " + std::to_string(i) + ": " + errors[static_cast<size_t>(i)];
-            return fail(f->status, f->error);
-        }
-    }
-    f->tiles_done = static_cast<uint64_t>(std::count(f->tile_done.begin(), f->tile_done.end(), 1));
-    report_tiles();
+    // A plain frame makes one launch per replica that has work.  A progressive frame makes one per pass: every replica runs the pass over its
+    // own tiles up to the frame's target, and the next pass starts when all of them have ended theirs.
     uint64_t left = 0, parked = 0;
-    for(int i = 0; i < n_scenes; i++) {
-        const FrameLaunch &l = launched[static_cast<size_t>(i)];
-        left += f->reps[static_cast<size_t>(i)]->n_todo;
-        parked += l.parked;
+    int passes_this_call = 0;
+    bool pass_limit = false;
+    std::vector<pt_stats> pass_stats(stats != nullptr ? static_cast<size_t>(n_scenes) : 0);
+    for(;;) {
+        int32_t yield_at = 0;
+        if(f->quantum > 0) {
+            if(!f->pass_in_progress) {
+                f->target = f->target > INT32_MAX - f->quantum ? INT32_MAX : f->target + f->quantum;
+                f->pass_in_progress = true;
+            }
+            yield_at = f->target;
+        }
+        std::vector<int> rcs(static_cast<size_t>(n_scenes), PT_OK);
+        std::vector<std::string> errors(static_cast<size_t>(n_scenes));
+        std::vector<FrameLaunch> launched(static_cast<size_t>(n_scenes));
+        std::vector<char> ran(static_cast<size_t>(n_scenes), 0);
+        if(stats != nullptr) {
+            std::memset(pass_stats.data(), 0, sizeof(pt_stats) * pass_stats.size());
+        }
+        auto work = [&](int i) {
+            pt_frame::Replica &r = *f->reps[static_cast<size_t>(i)];
+            if(r.n_todo == 0) {
+                return;
+            }
+            ran[static_cast<size_t>(i)] = 1;
+            rcs[static_cast<size_t>(i)] = frame_launch(*f, r, out_image, stats != nullptr ? &pass_stats[static_cast<size_t>(i)] : nullptr,
+                                                       progress != nullptr ? static_cast<pt_progress_fn>(trampoline) : nullptr, &shared, &stop, &launched[static_cast<size_t>(i)], yield_at);
+            if(rcs[static_cast<size_t>(i)] != PT_OK) {
+                errors[static_cast<size_t>(i)] = g_last_error;
+            }
+        };
+        std::vector<std::thread> threads;
+        for(int i = 1; i < n_scenes; i++) {
+            threads.emplace_back(work, i);
+        }
+        work(0);
+        for(std::thread &t : threads) {
+            t.join();
+        }
+        for(int i = 0; i < n_scenes; i++) {
+            f->launches += ran[static_cast<size_t>(i)];
+        }
+        for(int i = 0; i < n_scenes; i++) {
+            if(rcs[static_cast<size_t>(i)] != PT_OK) {
+                f->status = rcs[static_cast<size_t>(i)];
+                f->error = "frame failed: scene " + std::to_string(i) + ": " + errors[static_cast<size_t>(i)];
+                return fail(f->status, f->error);
+            }
+        }
+        f->tiles_done = static_cast<uint64_t>(std::count(f->tile_done.begin(), f->tile_done.end(), 1));
+        left = 0;
+        parked = 0;
+        uint64_t at_target = 0;
         if(ctl != nullptr) {
-            ctl->streams_finished += l.tally.finished;
-            ctl->streams_abandoned += l.parked;
-            ctl->streams_unclaimed += l.tally.unclaimed + (l.tally.abandoned - l.parked); // (dropped before their first sample: they start afresh)
+            ctl->streams_abandoned = ctl->streams_unclaimed = 0; // (of the call's last launches)
+        }
+        for(int i = 0; i < n_scenes; i++) {
+            const FrameLaunch &l = launched[static_cast<size_t>(i)];
+            left += f->reps[static_cast<size_t>(i)]->n_todo;
+            at_target += f->reps[static_cast<size_t>(i)]->n_at_target;
+            parked += l.parked;
+            if(ctl != nullptr) {
+                ctl->streams_finished += l.tally.finished;
+                ctl->streams_abandoned += l.parked;
+                ctl->streams_unclaimed += l.tally.unclaimed + (l.tally.abandoned - l.parked); // (dropped before their first sample: they start afresh)
+            }
+            if(stats != nullptr) {
+                // the work of all the call's launches; the grid is the last launch's
+                const pt_stats &p = pass_stats[static_cast<size_t>(i)];
+                pt_stats &o = stats[i];
+                o.samples += p.samples;
+                o.rays_traced += p.rays_traced;
+                o.shadow_rays_traced += p.shadow_rays_traced;
+                o.node_visits += p.node_visits;
+                o.leaf_tests += p.leaf_tests;
+                o.vertices += p.vertices;
+                o.launches += p.launches;
+                o.kernel_ms += p.kernel_ms;
+                o.wave_steps += p.wave_steps;
+                o.shading_passes += p.shading_passes;
+                if(p.launches != 0) {
+                    o.wavefronts = p.wavefronts;
+                    o.slot_rows = p.slot_rows;
+                }
+            }
+        }
+        if(yield_at == 0) {
+            break;
+        }
+        // the pass has ended when every stream that is left has its samples (a stop that came too late to drop anything ends it too)
+        const bool pass_done = at_target == left;
+        if(pass_done) {
+            f->pass_in_progress = false;
+            f->passes_completed++;
+            passes_this_call++;
+        }
+        if(left == 0 || !pass_done) {
+            break;
+        }
+        stop.poll();
+        if(stop.requested.load()) {
+            break;
+        }
+        if(f->max_passes_per_call > 0 && passes_this_call >= f->max_passes_per_call) {
+            pass_limit = true;
+            break;
         }
     }
+    report_tiles();
     if(ctl != nullptr) {
         ctl->drain_ms = stop.drain_ms;
     }
     if(left != 0) {
-        return fail(PT_ERR_CANCELLED, "frame stopped (" + std::string(__atomic_load_n(&stop.ctl->cancel, __ATOMIC_ACQUIRE) != 0 ? "cancelled" : "budget spent") + "): " +
-                                          std::to_string(parked) + " streams parked, " + std::to_string(left) + " streams left");
+        const std::string why = pass_limit ? "pass limit reached" : (__atomic_load_n(&stop.ctl->cancel, __ATOMIC_ACQUIRE) != 0 ? "cancelled" : "budget spent");
+        return fail(PT_ERR_CANCELLED, "frame stopped (" + why + "): " + std::to_string(parked) + " streams parked, " + std::to_string(left) + " streams left");
     }
+    return PT_OK;
+}
+
+int pt_frame_set_progressive(pt_frame *f, int32_t quantum, int32_t max_passes_per_call) {
+    if(f == nullptr) {
+        return fail(PT_ERR_INVALID, "null frame");
+    }
+    if(quantum < 0) {
+        return fail(PT_ERR_INVALID, "negative quantum");
+    }
+    std::lock_guard<std::mutex> lock(f->mutex);
+    if(f->status != PT_OK) {
+        return fail(f->status, f->error);
+    }
+    f->quantum = quantum;
+    f->max_passes_per_call = std::max(max_passes_per_call, 0);
+    if(quantum == 0) {
+        f->pass_in_progress = false; // (what an interrupted pass left is a plain frame's work now)
+    }
+    return PT_OK;
+}
+
+int pt_frame_get_progress(const pt_frame *f, pt_frame_progress *out) {
+    if(f == nullptr || out == nullptr) {
+        return fail(PT_ERR_INVALID, "null argument");
+    }
+    std::lock_guard<std::mutex> lock(f->mutex);
+    if(f->status != PT_OK) {
+        return fail(f->status, f->error);
+    }
+    std::memset(out, 0, sizeof(*out));
+    out->quantum = f->quantum;
+    out->max_passes_per_call = f->max_passes_per_call;
+    out->passes_completed = f->passes_completed;
+    out->target = f->target;
+    out->pass_in_progress = f->pass_in_progress ? 1 : 0;
+    bool any = false;
+    for(const auto &r : f->reps) {
+        if(r->n_todo == 0) {
+            continue;
+        }
+        out->min_samples = any ? std::min(out->min_samples, r->min_samples) : r->min_samples;
+        out->max_samples = any ? std::max(out->max_samples, r->max_samples) : r->max_samples;
+        out->streams_at_target += r->n_at_target;
+        any = true;
+    }
+    out->samples_lost = f->samples_lost;
     return PT_OK;
 }
 

@@ -6,6 +6,13 @@
 // counts of the blocks before it).  Parked streams first: the next launch's first round takes them all (it deals out at least as many
 // streams as the launch before could park, one per slot), so no record has to outlive the launch that reads it.
 //
+//
+// A progressive frame (pt_frame_set_progressive) renders in passes: every stream parks when its pixel has the pass's sample count `target`
+// (PtStreams::yield_at), so a launch leaves up to one record per entry of its list.  Its list is split by sample count instead: streams
+// below the target first (what an interrupted pass has left to do), streams at it behind them, each part in the order of the old list.  An
+// entry the launch never claimed keeps its record: the carry kernel copies it from the launch's input records to its output records, behind
+// the ones the launch wrote, so no sample is ever lost.
+//
 // The same work list is what pt_frame_preview shows between two launches: the gather kernels below read it without changing it.
 #include <hip/hip_runtime.h>
 
@@ -17,30 +24,59 @@ constexpr uint32_t kThreads = 256;
 constexpr uint32_t kPerThread = 4;
 constexpr uint32_t kPerBlock = kThreads * kPerThread;
 
-// what became of entry i: 0 = finished, 1 = parked in this launch, 2 = still to do from its seed
-__device__ uint32_t entry_class(const uint2 *todo, const uint32_t *status, uint32_t i) {
-    const uint32_t st = status[todo[i].x];
-    return st == PT_STREAM_FINISHED ? 0u : (st >= PT_STREAM_PARKED ? 1u : 2u);
+// a record of the launch's INPUT buffer that the carry kernel has yet to move: bit 31 of a work-list entry's y (a record index has 28 bits)
+constexpr uint32_t kCarry = 0x80000000u;
+
+// what became of entry i: 0 = finished, 1 = parked in this launch, 2 = still to do from its seed.  In a progressive frame (target > 0):
+// 0 = finished, 1 = its pixel has fewer than `target` samples, 2 = it has them; `samples` is that count and `where` says where the stream's
+// record is: 0 = it has none, 1 = in the launch's output records (index `rec`), 2 = in its input records (index `rec`: never claimed).
+__device__ uint32_t entry_class(const uint2 *todo, const uint32_t *status, uint32_t i, int32_t target, const PtParkRecord *parked, const PtParkRecord *park_in,
+                                uint32_t &where, uint32_t &rec, int32_t &samples) {
+    const uint2 e = todo[i];
+    const uint32_t st = status[e.x];
+    where = 0;
+    rec = PT_NO_PARK;
+    samples = 0;
+    if(target <= 0) {
+        return st == PT_STREAM_FINISHED ? 0u : (st >= PT_STREAM_PARKED ? 1u : 2u);
+    }
+    if(st == PT_STREAM_FINISHED) {
+        return 0u;
+    }
+    if(st >= PT_STREAM_PARKED) {
+        where = 1;
+        rec = st - PT_STREAM_PARKED;
+        samples = parked[rec].est.pixel_sample;
+    }
+    else if(e.y != PT_NO_PARK) {
+        where = 2;
+        rec = e.y;
+        samples = park_in[rec].est.pixel_sample;
+    }
+    return samples < target ? 1u : 2u;
 }
 
 __global__ __launch_bounds__(kThreads) void pt_frame_count_kernel(const uint2 *__restrict__ todo, uint32_t n, const uint32_t *__restrict__ status,
-                                                                  uint32_t *__restrict__ block_counts) {
+                                                                  uint32_t *__restrict__ block_counts, int32_t target, const PtParkRecord *__restrict__ parked,
+                                                                  const PtParkRecord *__restrict__ park_in) {
     __shared__ uint32_t sum[2];
     if(threadIdx.x < 2) {
         sum[threadIdx.x] = 0;
     }
     __syncthreads();
-    uint32_t parked = 0, fresh = 0;
+    uint32_t first = 0, second = 0;
     for(uint32_t k = 0; k < kPerThread; k++) {
         const uint32_t i = blockIdx.x * kPerBlock + threadIdx.x * kPerThread + k;
         if(i < n) {
-            const uint32_t c = entry_class(todo, status, i);
-            parked += c == 1u ? 1u : 0u;
-            fresh += c == 2u ? 1u : 0u;
+            uint32_t where, rec;
+            int32_t samples;
+            const uint32_t c = entry_class(todo, status, i, target, parked, park_in, where, rec, samples);
+            first += c == 1u ? 1u : 0u;
+            second += c == 2u ? 1u : 0u;
         }
     }
-    atomicAdd(&sum[0], parked);
-    atomicAdd(&sum[1], fresh);
+    atomicAdd(&sum[0], first);
+    atomicAdd(&sum[1], second);
     __syncthreads();
     if(threadIdx.x < 2) {
         block_counts[2 * blockIdx.x + threadIdx.x] = sum[threadIdx.x];
@@ -49,9 +85,10 @@ __global__ __launch_bounds__(kThreads) void pt_frame_count_kernel(const uint2 *_
 
 __global__ __launch_bounds__(kThreads) void pt_frame_place_kernel(const uint2 *__restrict__ todo, uint32_t n, uint32_t *__restrict__ status,
                                                                   const uint32_t *__restrict__ block_counts, uint32_t n_blocks, const PtParkRecord *__restrict__ parked,
-                                                                  uint2 *__restrict__ todo_out, unsigned long long *__restrict__ result) {
+                                                                  uint2 *__restrict__ todo_out, unsigned long long *__restrict__ result, int32_t target,
+                                                                  const PtParkRecord *__restrict__ park_in) {
     __shared__ uint32_t scan[kThreads];
-    __shared__ uint32_t before[3]; // parked in earlier blocks, fresh in earlier blocks, parked in all blocks
+    __shared__ uint32_t before[3]; // first class in earlier blocks, second class in earlier blocks, first class in all blocks
     if(threadIdx.x < 3) {
         before[threadIdx.x] = 0;
     }
@@ -70,12 +107,16 @@ __global__ __launch_bounds__(kThreads) void pt_frame_place_kernel(const uint2 *_
         atomicAdd(&before[1], f_before);
         atomicAdd(&before[2], p_all);
     }
-    // the thread's entries, and an inclusive scan of (parked | fresh << 16) over the block's threads in thread order
-    uint32_t cls[kPerThread];
+    // the thread's entries, and an inclusive scan of (first class | second class << 16) over the block's threads in thread order
+    uint32_t cls[kPerThread], where[kPerThread], rec[kPerThread];
+    int32_t samples[kPerThread];
     uint32_t mine = 0;
     for(uint32_t k = 0; k < kPerThread; k++) {
         const uint32_t i = blockIdx.x * kPerBlock + threadIdx.x * kPerThread + k;
-        cls[k] = i < n ? entry_class(todo, status, i) : 0u;
+        where[k] = 0;
+        rec[k] = PT_NO_PARK;
+        samples[k] = 0;
+        cls[k] = i < n ? entry_class(todo, status, i, target, parked, park_in, where[k], rec[k], samples[k]) : 0u;
         mine += cls[k] == 1u ? 1u : (cls[k] == 2u ? 0x10000u : 0u);
     }
     scan[threadIdx.x] = mine;
@@ -87,26 +128,48 @@ __global__ __launch_bounds__(kThreads) void pt_frame_place_kernel(const uint2 *_
         __syncthreads();
     }
     const uint32_t excl = scan[threadIdx.x] - mine;
-    uint32_t at_parked = before[0] + (excl & 0xffffu);
-    uint32_t at_fresh = before[2] + before[1] + (excl >> 16);
-    uint32_t lost = 0, carried = 0, with_candidates = 0;
+    uint32_t at_first = before[0] + (excl & 0xffffu);
+    uint32_t at_second = before[2] + before[1] + (excl >> 16);
+    uint32_t lost = 0, carried = 0, with_candidates = 0, with_record = 0, written = 0, least = 0xffffffffu, most = 0;
     for(uint32_t k = 0; k < kPerThread; k++) {
         const uint32_t i = blockIdx.x * kPerBlock + threadIdx.x * kPerThread + k;
         if(i >= n || cls[k] == 0u) {
             continue;
         }
         const uint2 e = todo[i];
-        if(cls[k] == 1u) {
-            const uint32_t rec = status[e.x] - PT_STREAM_PARKED;
-            todo_out[at_parked++] = make_uint2(e.x, rec);
-            carried += (uint32_t)parked[rec].est.pixel_sample;
-            with_candidates += parked[rec].est.n_candidates > 0 ? 1u : 0u;
+        uint32_t s = 0; // samples the pixel has taken
+        if(target > 0) {
+            // a progressive frame: the record stays with the stream wherever it is (an unclaimed one is moved by the carry kernel)
+            const uint32_t y = where[k] == 1u ? rec[k] : (where[k] == 2u ? (rec[k] | kCarry) : PT_NO_PARK);
+            if(cls[k] == 1u) {
+                todo_out[at_first++] = make_uint2(e.x, y);
+            }
+            else {
+                todo_out[at_second++] = make_uint2(e.x, y);
+            }
+            s = (uint32_t)samples[k];
+            if(where[k] != 0u) {
+                with_record++;
+                written += where[k] == 1u ? 1u : 0u;
+                with_candidates += (where[k] == 1u ? parked[rec[k]] : park_in[rec[k]]).est.n_candidates > 0 ? 1u : 0u;
+            }
+        }
+        else if(cls[k] == 1u) {
+            const uint32_t r = status[e.x] - PT_STREAM_PARKED;
+            todo_out[at_first++] = make_uint2(e.x, r);
+            s = (uint32_t)parked[r].est.pixel_sample;
+            with_candidates += parked[r].est.n_candidates > 0 ? 1u : 0u;
+            with_record++;
+            written++;
         }
         else {
             // (a stream that held a record and was not taken this time starts afresh: the same bits, only its samples are lost)
             lost += e.y != PT_NO_PARK ? 1u : 0u;
-            todo_out[at_fresh++] = make_uint2(e.x, PT_NO_PARK);
+            todo_out[at_second++] = make_uint2(e.x, PT_NO_PARK);
         }
+        carried += s;
+        least = s < least ? s : least;
+        most = s > most ? s : most;
         status[e.x] = PT_STREAM_UNTOUCHED; // (the status describes one launch)
     }
     if(lost != 0) {
@@ -118,9 +181,61 @@ __global__ __launch_bounds__(kThreads) void pt_frame_place_kernel(const uint2 *_
     if(with_candidates != 0) {
         atomicAdd(&result[4], (unsigned long long)with_candidates);
     }
+    if(least != 0xffffffffu) {
+        atomicMax(&result[5], (unsigned long long)(0xffffffffu - least)); // (a minimum over a word that starts at zero)
+        atomicMax(&result[6], (unsigned long long)most);
+    }
+    if(with_record != 0) {
+        atomicAdd(&result[7], (unsigned long long)with_record);
+    }
+    if(written != 0) {
+        atomicAdd(&result[8], (unsigned long long)written);
+    }
     if(blockIdx.x == n_blocks - 1 && threadIdx.x == kThreads - 1) {
         result[0] = before[2];
         result[1] = before[1] + (scan[threadIdx.x] >> 16);
+    }
+}
+
+// A progressive frame: the records of the entries the launch never claimed, from its input records to its output records.  A wavefront
+// takes kCarryPerWave entries of the new work list one after the other; a record is 33 x 16 bytes, copied by 33 neighbouring lanes.  The
+// record's new place is the next free one behind those the launch wrote (park_count goes on counting).  result[9] counts the samples of
+// records that found no room (none: the host sizes the output for every entry of the list).
+constexpr uint32_t kCarryPerWave = 16;
+static_assert(sizeof(PtParkRecord) == 33 * sizeof(uint4), "a park record is 33 x 16 bytes");
+
+__global__ __launch_bounds__(kThreads) void pt_frame_carry_kernel(uint2 *__restrict__ todo_out, const PtParkRecord *__restrict__ park_in, PtParkRecord *__restrict__ park_out,
+                                                                  uint32_t *__restrict__ park_count, uint32_t park_cap, unsigned long long *__restrict__ result) {
+    const uint32_t n = (uint32_t)(result[0] + result[1]); // (the new list's length, left by the place kernel)
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = (blockIdx.x * kThreads + threadIdx.x) / 64u;
+    for(uint32_t k = 0; k < kCarryPerWave; k++) {
+        const uint32_t i = wave * kCarryPerWave + k;
+        if(i >= n) {
+            return;
+        }
+        const uint2 e = todo_out[i];
+        if(e.y == PT_NO_PARK || (e.y & kCarry) == 0u) {
+            continue;
+        }
+        const uint32_t src = e.y & ~kCarry;
+        uint32_t dst = 0;
+        if(lane == 0) {
+            dst = atomicAdd(park_count, 1u);
+        }
+        dst = (uint32_t)__shfl((int)dst, 0);
+        if(dst < park_cap) {
+            if(lane < 33u) {
+                reinterpret_cast<uint4 *>(park_out + dst)[lane] = reinterpret_cast<const uint4 *>(park_in + src)[lane];
+            }
+            if(lane == 0) {
+                todo_out[i].y = dst;
+            }
+        }
+        else if(lane == 0) {
+            todo_out[i].y = PT_NO_PARK;
+            atomicAdd(&result[9], (unsigned long long)park_in[src].est.pixel_sample);
+        }
     }
 }
 
@@ -128,8 +243,8 @@ __global__ __launch_bounds__(kThreads) void pt_frame_place_kernel(const uint2 *_
 // Each replica gathers its work list into compact entries (gather); replica 0's device lays the frame out from the caller's image (base)
 // and writes every replica's entries over it (scatter).
 
-// One thread per entry of a replica's work list todo[0 .. n): entry i < n_parked is a parked stream with its record in `park`, the others
-// are untouched.  Writes the entry's preview colour and (pixel, samples): the running mean pixel_value * (1 / collected_sample_count) and
+// One thread per entry of a replica's work list todo[0 .. n): an entry that names a record is a parked stream with its record in `park`
+// (the first n_parked entries of a plain frame's list; any entry of a progressive frame's), the others are untouched.  Writes the entry's preview colour and (pixel, samples): the running mean pixel_value * (1 / collected_sample_count) and
 // pixel_sample of a parked stream (estimator_finish's first step, pt_shading.h), (0, 0, 0, 0) and 0 samples for an untouched one.  A parked
 // entry reads three fields of its 528-byte record, not the record.
 __global__ __launch_bounds__(kThreads) void pt_frame_gather_kernel(const uint2 *__restrict__ todo, uint32_t n, uint32_t n_parked,
@@ -157,7 +272,7 @@ __global__ __launch_bounds__(kThreads) void pt_frame_gather_kernel(const uint2 *
     const int32_t x = t.x + (int32_t)(k % (uint32_t)t.z), y = t.y + (int32_t)(k / (uint32_t)t.z);
     float4 c = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     int32_t samples = 0;
-    if(i < n_parked) {
+    if(e.y != PT_NO_PARK) {
         const PtEstimator &est = park[e.y].est;
         const float4 pv = *reinterpret_cast<const float4 *>(est.pixel_value);
         const int32_t collected = est.collected_sample_count;
@@ -202,16 +317,20 @@ __global__ __launch_bounds__(kThreads) void pt_frame_scatter_kernel(const float4
 } // namespace
 
 int pt_launch_frame_compact(hipStream_t stream, const uint2 *todo, uint32_t n, uint32_t *status, const PtParkRecord *parked, uint2 *todo_out, uint32_t *block_counts,
-                            unsigned long long *result) {
-    if(hipMemsetAsync(result, 0, 8 * sizeof(unsigned long long), stream) != hipSuccess) {
+                            unsigned long long *result, int32_t target, const PtParkRecord *park_in, PtParkRecord *park_out, uint32_t *park_count, uint32_t park_cap) {
+    if(hipMemsetAsync(result, 0, 16 * sizeof(unsigned long long), stream) != hipSuccess) {
         return 1;
     }
     if(n == 0) {
         return 0;
     }
     const uint32_t n_blocks = (n + kPerBlock - 1) / kPerBlock;
-    pt_frame_count_kernel<<<n_blocks, kThreads, 0, stream>>>(todo, n, status, block_counts);
-    pt_frame_place_kernel<<<n_blocks, kThreads, 0, stream>>>(todo, n, status, block_counts, n_blocks, parked, todo_out, result);
+    pt_frame_count_kernel<<<n_blocks, kThreads, 0, stream>>>(todo, n, status, block_counts, target, parked, park_in);
+    pt_frame_place_kernel<<<n_blocks, kThreads, 0, stream>>>(todo, n, status, block_counts, n_blocks, parked, todo_out, result, target, park_in);
+    if(target > 0) {
+        const uint32_t per_block = (kThreads / 64u) * kCarryPerWave;
+        pt_frame_carry_kernel<<<(n + per_block - 1) / per_block, kThreads, 0, stream>>>(todo_out, park_in, park_out, park_count, park_cap, result);
+    }
     return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 

@@ -84,6 +84,11 @@ struct PtStreams {
     uint32_t *park_count;        // records written to park_out
     uint32_t park_cap;
     uint32_t *status;            // [streams of the frame] or null: PT_STREAM_* of every stream this launch finished or parked
+    // A pass of a progressive frame (pt_frame_set_progressive; 0 = off, and every test of it is wave-uniform): a stream whose pixel has taken
+    // yield_at samples parks at that sample boundary as after a stop request -- exactly yield_at, since PtDevOptions::overlap_bound keeps the
+    // sample that reaches it from being overlapped with its successor -- and frees its slot, which takes the next stream: the pool stays open.
+    // A launch with yield_at may therefore park one stream per entry of its work list (park_cap = n), and counts them in streams_abandoned.
+    int32_t yield_at;
     // A batch of views (pt_render_views): n_views > 1 frames of opt.image_height rows stacked into one tall image, view v = rows
     // [v * H, (v + 1) * H).  A pixel's view is its row / H; it is seeded from (view_seed[view], x, row - view * H) and its camera ray is
     // made by views[view] at that local row.  n_views <= 1: base_seed and the launch's camera, as every other entry point.
@@ -148,12 +153,18 @@ void pt_launch_path(hipStream_t stream, const PtDevScene &scene, const PtDevCame
                     PtLocalQueue queue, const PtPathConfig &cfg, float4 *image, PtDevCounters *counters, PtPathArgs *host_args, PtPathArgs *d_args);
 // the work list of a resumable frame's next launch (pt_frame.hip): the streams of `todo` that `status` does not call finished, parked ones
 // first, each part in the order of `todo` (block_counts: [2 * ceil(n / 1024)]).  result[0..4] = parked streams, untouched ones, untouched ones
-// whose earlier record went unused (0 by construction: such a stream would start afresh), samples the parked streams carry, parked streams
-// with closed candidates.  Returns 0, or 1 when a launch failed.
+// whose earlier record went unused (such a stream starts afresh), samples the streams of the list carry, streams with closed candidates;
+// result[5] = 0xffffffff - the least sample count of an unfinished pixel, [6] = the greatest, [7] = streams that have a record, [8] = records
+// the launch wrote (result: 16 words).
+// target > 0, a progressive frame's pass: the list is split into streams below `target` samples (result[0]) and streams at or above it
+// (result[1]) instead, every stream keeps its record, and those the launch never claimed are copied from park_in (the launch's input
+// records) into park_out behind the park_count records the launch wrote (park_cap: room for every entry); result[2] stays 0 and result[9]
+// counts samples of records that found no room (0 with that room).  target <= 0: park_in, park_out, park_count are not used.
+// Returns 0, or 1 when a launch failed.
 int pt_launch_frame_compact(hipStream_t stream, const uint2 *todo, uint32_t n, uint32_t *status, const PtParkRecord *parked, uint2 *todo_out, uint32_t *block_counts,
-                            unsigned long long *result);
-// The preview of a frame (pt_frame.hip; pt_frame_preview).  gather: one compact entry per entry of a replica's work list todo[0 .. n), the
-// first n_parked parked in `park` -- out_rgba the running mean (0 for an untouched stream), out_at (y * width + x, samples taken).  base: the
+                            unsigned long long *result, int32_t target, const PtParkRecord *park_in, PtParkRecord *park_out, uint32_t *park_count, uint32_t park_cap);
+// The preview of a frame (pt_frame.hip; pt_frame_preview).  gather: one compact entry per entry of a replica's work list todo[0 .. n), those
+// that name a record (the first n_parked of a plain frame) parked in `park` -- out_rgba the running mean (0 for an untouched stream), out_at (y * width + x, samples taken).  base: the
 // view of replica 0's device, which holds the caller's image: samples -1 where cover[p] != 0, else a hole (0, 0, 0, 0) with 0 samples.
 // scatter: the n entries into the view.  Each returns 0, or 1 when the launch failed.
 int pt_launch_frame_gather(hipStream_t stream, const uint2 *todo, uint32_t n, uint32_t n_parked, const PtParkRecord *park, const int4 *tiles,

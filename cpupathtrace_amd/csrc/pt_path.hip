@@ -522,7 +522,7 @@ PT_D void park_stream(const PtStreams &T, const PtSlots &S, uint32_t p, uint32_t
         const PtEstimator *e = S.est + p;
         if(e->pixel_sample > 0 || cursor > 0) {
             const uint32_t k = atomicAdd(T.park_count, 1u);
-            if(k < T.park_cap) { // (always: a launch parks at most one stream per slot, and the host sizes park_out for that)
+            if(k < T.park_cap) { // (always: a launch parks at most one stream per slot -- per stream with yield_at -- and the host sizes park_out for that)
                 PtParkRecord *rec = T.park_out + k;
                 rec->stream = stream;
                 rec->cursor = cursor;
@@ -846,11 +846,14 @@ PT_D void shade_row(const PtDevScene &sc, const PtDevCamera &cam, const PtDevOpt
             have_pixel = true;
             break;
         }
-        if(!have_pixel || stop) {
+        // (a pass of a progressive frame: the pixel has the pass's sample count -- one word of the estimator against a scalar)
+        const bool yield = T.yield_at != 0 && have_pixel && S.est[p].pixel_sample >= T.yield_at;
+        if(!have_pixel || stop || yield) {
             // the stream has rendered its whole rectangle: hand the engine back and free the slot (it takes a new stream in the next pass).
             // After a stop request a stream that has a pixel left is dropped here instead, between two samples, with no ray in flight (a
             // slot is only shaded once all its rays are back): every pixel it finished is exact, its current pixel is never written, and
-            // its slot is freed in the same way -- since the pool is closed, it dies in its next pass.
+            // its slot is freed in the same way -- since the pool is closed, it dies in its next pass.  A stream that yields (PtStreams::yield_at)
+            // leaves in the same way without a stop: the pool is open then, and its slot takes the next stream in its next pass.
             stream_finished = !have_pixel;
             stream_abandoned = have_pixel;
             if(T.status != nullptr) {
@@ -903,7 +906,7 @@ PT_D void shade_row(const PtDevScene &sc, const PtDevCamera &cam, const PtDevOpt
                 atomicAdd(&counters->streams_done, (unsigned long long)__popcll(fin_mask));
             }
         }
-        if(stop) {
+        if(stop || T.yield_at != 0) {
             const unsigned long long drop_mask = __ballot(stream_abandoned);
             if(lane == 0 && drop_mask != 0ULL) {
                 atomicAdd(&counters->streams_abandoned, (unsigned long long)__popcll(drop_mask));

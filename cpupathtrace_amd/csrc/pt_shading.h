@@ -183,7 +183,7 @@ PT_D C4 estimator_finish(PtEstimator &e, PtCandidate *cand, const PtDevOptions &
 PT_D bool estimator_safe_to_overlap(const PtEstimator &e, const PtDevOptions &opt) {
     const bool closes_batch = e.stats_sample_index + 1 == opt.stats_sample_count;
     const int min_needed = opt.min_sample_count > 2 ? opt.min_sample_count : 2;
-    return e.pixel_sample + 1 < opt.max_sample_count && !(closes_batch && e.collected_sample_count + 1 >= min_needed);
+    return e.pixel_sample + 1 < opt.overlap_bound && !(closes_batch && e.collected_sample_count + 1 >= min_needed);
 }
 
 PT_D void estimator_reset(PtEstimator &e, const PtDevOptions &opt) {

@@ -101,6 +101,7 @@ struct PtDevOptions {
     int32_t stats_sample_count;    /* worker.cpp:158 */
     int32_t candidate_batch_count; /* worker.cpp:159 */
     int32_t check_sample_count;    /* worker.cpp:161-164 */
+    int32_t overlap_bound;         /* max_sample_count, or less in a pass of a progressive frame: min(max_sample_count, PtStreams::yield_at) */
 };
 
 // Per-pixel adaptive estimator, the locals of processItem's pixel loop (worker.cpp:172-192); one per stream slot.

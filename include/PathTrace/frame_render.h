@@ -34,6 +34,12 @@ public:
     bool complete() const noexcept { return complete_; }
     // where the frame stands (pt_frame_info: streams finished / parked / untouched, tiles, samples the parked streams carry)
     pt_frame_info info() const;
+    // Progressive mode (pt_frame_set_progressive): render() then works in passes, each bringing every unfinished pixel to `quantum` more
+    // samples, so that a preview between two calls has samples everywhere; max_passes_per_call > 0 makes render() return (not complete)
+    // after that many passes.  quantum 0 turns the mode off.  The finished image does not depend on any of this.  Throws
+    // std::invalid_argument for a negative quantum.  progress(): passes completed, the target, the sample counts of the unfinished pixels.
+    void setProgressive(int quantum, int max_passes_per_call = 0);
+    pt_frame_progress progress() const;
     // The frame as it stands, for a viewer between two render() calls (pt_frame_preview): finished pixels as image(), parked ones the
     // running mean of their samples so far, untouched ones (0, 0, 0, 0).  `samples` (if not null) gets one count per pixel, row-major:
     // -1 finished, the samples taken of a parked pixel, 0 untouched.  With `denoise` the preview is filtered as pt_denoise filters a frame,

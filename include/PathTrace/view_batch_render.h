@@ -35,6 +35,12 @@ public:
     std::vector<Image<>> images() const;
     bool complete() const noexcept { return complete_; }
     pt_frame_info info() const;
+    // Progressive mode (pt_frame_set_progressive): render() then works in passes, each bringing every unfinished pixel to `quantum` more
+    // samples, so that a preview between two calls has samples everywhere; max_passes_per_call > 0 makes render() return (not complete)
+    // after that many passes.  quantum 0 turns the mode off.  The finished image does not depend on any of this.  Throws
+    // std::invalid_argument for a negative quantum.  progress(): passes completed, the target, the sample counts of the unfinished pixels.
+    void setProgressive(int quantum, int max_passes_per_call = 0);
+    pt_frame_progress progress() const;
     // As FrameRender::preview, per view: `out` gets one image per view, `samples` (if not null) one count per pixel, [view][y][x].  With
     // `denoise` a hole is filled from pixels of its own view only.
     void preview(std::vector<Image<>> &out, std::vector<std::int32_t> *samples = nullptr, const pt_denoise_params *denoise = nullptr) const;

@@ -286,10 +286,41 @@ int pt_frame_create(pt_scene *const *scenes, int n_scenes, const pt_camera_param
  * Preview of a view frame: per view as described at pt_frame_preview; with `denoise` the features are pt_render_features_views with the frame's
  * cameras and the filter is the view form of the masked filter, so a hole is filled only from taps of its own view.  One device keeps about
  * 2^20 streams in flight: a batch of more pixels than that has whole views that are still holes after its first slice (the work list is
- * view after view). */
+ * view after view) -- unless the frame is progressive (pt_frame_set_progressive): then every view has its samples after every pass. */
 int pt_frame_create_views(pt_scene *const *scenes, int n_scenes, const pt_camera_params *cameras, const uint64_t *base_seeds, int32_t n_views,
                           const pt_options *options, pt_frame **out);
 int pt_frame_render(pt_frame *frame, float *out_image, pt_stats *stats, pt_progress_fn progress, void *user, pt_render_control *ctl);
+/* Progressive mode of a resumable frame: the frame is rendered in PASSES, and after pass k every unfinished pixel of the
+ * frame has taken exactly target_k = target_(k-1) + quantum samples (target_0 = 0) -- the whole picture refines together, however many
+ * pixels the frame has.  In a pass every unfinished stream is taken once, samples its pixel until the pixel has the target (or its
+ * estimator finishes it first, as always), parks and gives its slot to the next stream of the pass; one pass is one launch per replica.
+ * The finished frame is bit-identical to pt_render_tiles / pt_render_views with the same arguments for every quantum, every change of the
+ * quantum between calls and every placement of stops: each pixel still runs its own engine through the same chain of samples.
+ *   - pt_frame_set_progressive: quantum >= 1 turns the mode on or changes the step of the passes to come (a pass in progress keeps its
+ *     target); 0 turns it off: the frame goes on as a plain resumable frame from the records it has.  max_passes_per_call <= 0 = no limit.
+ *     Only between two pt_frame_render calls (it takes the frame's lock).  PT_ERR_INVALID for a null frame or a negative quantum; a
+ *     failed frame returns its code.  A stream that already has the target's samples when the mode is turned on (a frame sliced before)
+ *     takes none in that pass.
+ *   - pt_frame_render on a progressive frame runs pass after pass until the frame is complete (PT_OK), the budget or pt_render_cancel
+ *     stops it (PT_ERR_CANCELLED, as always), or max_passes_per_call passes have COMPLETED in this call and work is left
+ *     (PT_ERR_CANCELLED as well: stopped, call again).  A pass that a stop cut short is finished by the next call before a new one
+ *     starts, its streams below the target first.  No sample is ever lost: a stream the stopped launch did not reach keeps its record.
+ *     stats sum the call's launches (launches, kernel_ms and the work counters); ctl's streams_finished counts all of them,
+ *     streams_abandoned and streams_unclaimed describe the call's last pass.  Progress, tile_done, replicas and view frames as always.
+ *   - Park storage of a progressive frame: two buffers per replica of one record per stream left (528 bytes each; 2 x 1.1 GB for
+ *     1920 x 1080), allocated by its first passes and reported by pt_frame_get_info's park_bytes.
+ *   - pt_frame_preview between two passes has no holes inside the frame's tiles: every unfinished pixel shows its running mean. */
+int pt_frame_set_progressive(pt_frame *frame, int32_t quantum, int32_t max_passes_per_call);
+typedef struct pt_frame_progress {
+    int32_t quantum, max_passes_per_call;
+    int32_t passes_completed;
+    int32_t target;                 /* of the pass in progress or last completed */
+    int32_t pass_in_progress;       /* 1 = a stop cut the last pass short */
+    int32_t min_samples, max_samples; /* samples taken, over unfinished pixels (0, 0 when there is none) */
+    uint64_t streams_at_target;     /* unfinished streams with at least `target` samples, after a progressive pass */
+    uint64_t samples_lost;          /* always 0: a progressive frame that dropped a record would fail instead */
+} pt_frame_progress;
+int pt_frame_get_progress(const pt_frame *frame, pt_frame_progress *out);
 /* (the info of a frame: `pt_frame_info` names the struct, so the function is pt_frame_get_info) */
 int pt_frame_get_info(const pt_frame *frame, pt_frame_info *info);
 int pt_frame_destroy(pt_frame *frame);

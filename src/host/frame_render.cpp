@@ -68,6 +68,23 @@ pt_frame_info FrameRender::info() const {
     return i;
 }
 
+void FrameRender::setProgressive(int quantum, int max_passes_per_call) {
+    if(quantum < 0) {
+        throw std::invalid_argument("FrameRender::setProgressive: negative quantum");
+    }
+    if(frame_ != nullptr) {
+        check(pt_frame_set_progressive(frame_, quantum, max_passes_per_call), "FrameRender::setProgressive");
+    }
+}
+
+pt_frame_progress FrameRender::progress() const {
+    pt_frame_progress p{};
+    if(frame_ != nullptr) {
+        check(pt_frame_get_progress(frame_, &p), "FrameRender::progress");
+    }
+    return p;
+}
+
 void FrameRender::preview(Image<> &out, std::vector<std::int32_t> *samples, const pt_denoise_params *denoise) const {
     if(out.getWidth() != image_.getWidth() || out.getHeight() != image_.getHeight()) {
         out = Image<>(image_.getWidth(), image_.getHeight());

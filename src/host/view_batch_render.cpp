@@ -109,6 +109,23 @@ pt_frame_info ViewBatchRender::info() const {
     return i;
 }
 
+void ViewBatchRender::setProgressive(int quantum, int max_passes_per_call) {
+    if(quantum < 0) {
+        throw std::invalid_argument("ViewBatchRender::setProgressive: negative quantum");
+    }
+    if(frame_ != nullptr) {
+        check(pt_frame_set_progressive(frame_, quantum, max_passes_per_call), "ViewBatchRender::setProgressive");
+    }
+}
+
+pt_frame_progress ViewBatchRender::progress() const {
+    pt_frame_progress p{};
+    if(frame_ != nullptr) {
+        check(pt_frame_get_progress(frame_, &p), "ViewBatchRender::progress");
+    }
+    return p;
+}
+
 void ViewBatchRender::preview(std::vector<Image<>> &out, std::vector<std::int32_t> *samples, const pt_denoise_params *denoise) const {
     const size_t pixels = static_cast<size_t>(width_) * static_cast<size_t>(height_) * seeds_.size();
     if(samples != nullptr) {

@@ -8,7 +8,7 @@ procedural stand-in mesh, at 1024^2 and 1920x1080 (1024 spp, the metric frame's 
 The kernels alone: run this under rocprofv3 --kernel-trace --stats (pt_frame_gather_kernel, pt_frame_preview_base_kernel,
 pt_frame_scatter_kernel, the masked pt_denoise_* instantiations).
 
-    python tools/preview_probe.py [--mesh-n 1900] [--out FILE]
+    python tools/preview_probe.py [--mesh-n 1900] [--progressive Q] [--cases box,dragon] [--out FILE]
 """
 import argparse
 import os
@@ -26,6 +26,9 @@ def main():
     ap.add_argument("--slice-ms", type=float, default=100.0)
     ap.add_argument("--spp", type=int, default=1024)
     ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--progressive", type=int, default=0, metavar="Q",
+                    help="render the first slice as one progressive pass of Q samples per pixel instead of a budgeted slice (DESIGN.md 4.14)")
+    ap.add_argument("--cases", default="box,dragon", help="comma-separated: box, dragon")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import numpy as np
@@ -69,12 +72,16 @@ def main():
                 down.append(e[1].elapsed_time(e[2]))
         return statistics.median(up), statistics.median(down)
 
-    mesh = scenes.bumpy_sphere_mesh(args.mesh_n, args.mesh_n, scenes.DRAGON_BOX_TRANSFORM)
-    cases = [("box", lambda a: scenes.box_scene(aspect_ratio=a)),
-             ("dragon_standin_%dtri" % len(mesh[0]), lambda a: scenes.dragon_box_scene(*mesh, aspect_ratio=a))]
+    cases = []
+    if "box" in args.cases.split(","):
+        cases.append(("box", lambda a: scenes.box_scene(aspect_ratio=a)))
+    if "dragon" in args.cases.split(","):
+        mesh = scenes.bumpy_sphere_mesh(args.mesh_n, args.mesh_n, scenes.DRAGON_BOX_TRANSFORM)
+        cases.append(("dragon_standin_%dtri" % len(mesh[0]), lambda a: scenes.dragon_box_scene(*mesh, aspect_ratio=a)))
     sizes = [(1024, 1024), (1920, 1080)]
-    say("preview_probe: device %s; %d spp; first slice %.0f ms; preview times: median of %d calls, host clock around the call" % (
-        torch.cuda.get_device_name(0), args.spp, args.slice_ms, args.repeats))
+    first_slice = "one progressive pass of %d samples" % args.progressive if args.progressive > 0 else "%.0f ms" % args.slice_ms
+    say("preview_probe: device %s; %d spp; first slice %s; preview times: median of %d calls, host clock around the call" % (
+        torch.cuda.get_device_name(0), args.spp, first_slice, args.repeats))
     say("%-30s %10s %9s %9s %9s %9s %10s %10s %10s" % ("scene", "size", "covered", "parked", "untouched", "raw ms", "denoise ms",
                                                        "1st dn ms", "features*"))
     for name, make in cases:
@@ -85,7 +92,11 @@ def main():
                 opt = scenes.options(w, h, args.spp, args.spp)
                 frame = binding.Frame(gpu, cam, opt, base_seed=1234)
                 try:
-                    frame.render(budget_ms=args.slice_ms)
+                    if args.progressive > 0:
+                        frame.set_progressive(args.progressive, 1)
+                        frame.render()
+                    else:
+                        frame.render(budget_ms=args.slice_ms)
                     _, samples = frame.preview()
                     fi = frame.info()
                     covered = float((samples != 0).mean())
