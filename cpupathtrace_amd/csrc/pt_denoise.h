@@ -1,4 +1,4 @@
-// pt_denoise.h -- the feature-guided a-trous denoiser (pt_denoise.hip): launch interface for the host side (pt_api.cpp).
+// pt_denoise.h -- the feature-guided a-trous denoiser (pt_denoise.hip): launch interface for the host side (pt_image.cpp, pt_frames.cpp).
 #ifndef PT_DENOISE_H
 #define PT_DENOISE_H
 
@@ -49,7 +49,7 @@ struct PtTemporalParams {
 enum { PT_REPROJECT_NONE = 0, PT_REPROJECT_IDENTICAL = 1, PT_REPROJECT_CAMERA = 2 };
 
 // Where the previous push's camera saw a point: X - origin = a forward + b up + c right, (a, b, c) = row . (X - origin) up to a positive
-// factor (rows of the inverse of [forward up right], times |det|).  Derived on the host (pt_api.cpp).
+// factor (rows of the inverse of [forward up right], times |det|).  Derived on the host (pt_image.cpp).
 struct PtReprojection {
     float origin[3];
     float row[3][3];

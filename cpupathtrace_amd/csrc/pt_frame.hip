@@ -1,4 +1,4 @@
-// pt_frame.hip -- the work list of a resumable frame (pt_frame_render, pt_api.cpp).
+// pt_frame.hip -- the work list of a resumable frame (pt_frame_render, pt_frames.cpp).
 //
 // After a launch the frame's next work list is built from the status every stream of the launch left (PtStreams::status): finished
 // streams leave the list, parked ones come first with their new park record, untouched ones follow without one.  Both parts keep the order
@@ -239,7 +239,7 @@ __global__ __launch_bounds__(kThreads) void pt_frame_carry_kernel(uint2 *__restr
     }
 }
 
-// ---- the preview of a frame (pt_frame_preview, pt_api.cpp) -----------------------------------------------------------------------------
+// ---- the preview of a frame (pt_frame_preview, pt_frames.cpp) ---------------------------------------------------------------------------
 // Each replica gathers its work list into compact entries (gather); replica 0's device lays the frame out from the caller's image (base)
 // and writes every replica's entries over it (scatter).
 

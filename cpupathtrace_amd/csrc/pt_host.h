@@ -1,0 +1,391 @@
+// pt_host.h -- what the host units of libpathtrace_hip.so share: pt_api.cpp (scenes), pt_render.cpp (render calls), pt_frames.cpp
+// (resumable frames) and pt_image.cpp (post-processing, features, denoising).  Internal: not installed, not part of the C ABI.
+// Everything but the ABI's own handle types lives in namespace pth, so that no helper can collide with a pt_* name of include/pt_hip.h.
+#ifndef PT_HOST_H
+#define PT_HOST_H
+
+#include "../../include/pt_hip.h"
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <atomic>
+#include <chrono>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <functional>
+#include <memory>
+#include <mutex>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "pt_build.h"
+#include "pt_bvh.h"
+#include "pt_kernels.h"
+#include "pt_denoise.h"
+#include "pt_post.h"
+
+namespace pth {
+
+// The calling thread's message (pt_last_error).  It has one definition, in pt_api.cpp, and is reached through these two only: a copy
+// per unit would hand pt_last_error() another unit's empty string.
+int fail(int code, const std::string &msg);
+const std::string &last_error();
+
+#define PT_HIP(call)                                                                                               \
+    do {                                                                                                           \
+        hipError_t err_ = (call);                                                                                  \
+        if(err_ != hipSuccess) {                                                                                   \
+            return fail(PT_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(err_));                          \
+        }                                                                                                          \
+    } while(0)
+
+// ... and for a helper that returns a status of its own (it has set the message)
+#define PT_TRY(call)                                                                                               \
+    do {                                                                                                           \
+        const int rc_ = (call);                                                                                    \
+        if(rc_ != PT_OK) {                                                                                         \
+            return rc_;                                                                                            \
+        }                                                                                                          \
+    } while(0)
+
+inline int env_int(const char *name, int fallback) {
+    const char *v = std::getenv(name);
+    return (v != nullptr && *v != '\0') ? std::atoi(v) : fallback;
+}
+
+inline float fmin_std(float a, float b) {
+    return (b < a) ? b : a;
+}
+inline float fmax_std(float a, float b) {
+    return (a < b) ? b : a;
+}
+
+struct Vec3 {
+    float x, y, z;
+};
+inline Vec3 sub(Vec3 a, Vec3 b) {
+    return {a.x - b.x, a.y - b.y, a.z - b.z};
+}
+inline Vec3 scale(Vec3 a, float f) {
+    return {a.x * f, a.y * f, a.z * f};
+}
+inline float dot(Vec3 a, Vec3 b) {
+    float d = 0.0F;
+    d += a.x * b.x;
+    d += a.y * b.y;
+    d += a.z * b.z;
+    return d;
+}
+inline Vec3 cross(Vec3 a, Vec3 b) {
+    return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
+}
+inline Vec3 normalize(Vec3 a) {
+    const float inv = 1.0F / std::sqrt(dot(a, a));
+    return scale(a, inv);
+}
+inline Vec3 ld(const float *p) {
+    return {p[0], p[1], p[2]};
+}
+
+inline uint32_t bits(float f) {
+    uint32_t u;
+    std::memcpy(&u, &f, 4);
+    return u;
+}
+inline float from_bits(uint32_t u) {
+    float f;
+    std::memcpy(&f, &u, 4);
+    return f;
+}
+
+template<typename T>
+struct DevBuf {
+    T *ptr = nullptr;
+    size_t count = 0;
+    ~DevBuf() { release(); }
+    void release() {
+        if(ptr != nullptr) {
+            (void)hipFree(ptr);
+            ptr = nullptr;
+            count = 0;
+        }
+    }
+    hipError_t ensure(size_t n) {
+        if(n <= count && ptr != nullptr) {
+            return hipSuccess;
+        }
+        release();
+        const size_t bytes = std::max<size_t>(n, 1) * sizeof(T);
+        hipError_t e = hipMalloc(reinterpret_cast<void **>(&ptr), bytes);
+        if(e == hipSuccess) {
+            count = std::max<size_t>(n, 1);
+        }
+        return e;
+    }
+    hipError_t upload(const std::vector<T> &host) {
+        hipError_t e = ensure(host.size());
+        if(e != hipSuccess || host.empty()) {
+            return e;
+        }
+        return hipMemcpy(ptr, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice);
+    }
+};
+
+struct F4 {
+    float x, y, z, w;
+};
+
+struct Event {
+    hipEvent_t e = nullptr;
+    hipError_t create(unsigned flags = hipEventDefault) { return hipEventCreateWithFlags(&e, flags); }
+    ~Event() {
+        if(e != nullptr) {
+            (void)hipEventDestroy(e);
+        }
+    }
+};
+
+} // namespace pth
+
+struct pt_scene {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    int cu_count = 256;
+
+    // host copies kept for introspection and for mapping references back to object indices
+    ptb::Tree tree;          // host-built scenes only (PT_BUILD=host or few objects); empty when the device built the tree
+    uint64_t n_nodes = 0;    // 2 * n_objects - 1
+    uint32_t depth = 0;      // levels of the tree (a single leaf has depth 1)
+    bool device_built = false;
+    float build_ms[4] = {0, 0, 0, 0}; // host preparation, upload, device tree construction, emissive registration + rest
+    std::vector<uint32_t> tri_obj;
+    std::vector<uint32_t> sph_obj;
+    uint32_t n_objects = 0;
+    uint32_t n_emissive = 0;
+    std::vector<int32_t> emissive_obj;
+    std::vector<float> emissive_cdf;
+
+    // device scene
+    pth::DevBuf<pth::F4> recs, pairs, tris, tri_shade, spheres, materials, lights, emis; // (pairs and tris only while the scene is being built: linked into recs)
+    pth::DevBuf<uint2> sph_meta;
+    pth::DevBuf<float> emis_cdf;
+    PtDevScene dev{};
+
+    pth::DevBuf<PtDevCounters> counters;
+    pth::DevBuf<pth::F4> image;
+    pth::DevBuf<int4> tiles;
+    pth::DevBuf<uint32_t> tile_offset;
+    pth::DevBuf<float> batch_rays;
+
+    // One render call at a time per scene: the workspace below is shared by every entry point (processItem may be called from several
+    // threads on one const Scene, reference worker.h:66-69 / src/worker.cpp:328-362: such callers are serialised here).
+    std::mutex render_mutex;
+
+    // workspace of the persistent path kernel (pt_path.hip), grown on demand and reused between calls
+    PtPathConfig path_cfg{};
+    int path_blocks_per_cu = 0;
+    uint32_t path_slots = 0, path_waves = 0, path_cap = 0;
+    pth::DevBuf<uint32_t> sl_nee_mask, pull_counter, tile_left;
+    pth::DevBuf<int4> st_rect;
+    pth::DevBuf<uint64_t> st_rng;
+    pth::DevBuf<pth::F4> sl_state, sl_nee, lq_ray_o, lq_ray_d;
+    pth::DevBuf<PtEstimator> sl_est;
+    pth::DevBuf<PtCandidate> sl_cand;
+    pth::DevBuf<uint2> path_spill, closest_out;
+    pth::DevBuf<uint32_t> walk_save;
+    pth::DevBuf<PtPathArgs> path_args;  // the kernel's arguments in device memory
+    PtPathArgs host_path_args{};   // ... and the host copy they are uploaded from
+    pth::DevBuf<unsigned long long> path_wave_counters;
+    uint32_t *host_tiles_done = nullptr; // pinned: tiles finished so far, written by the kernel (progress callback)
+    unsigned long long *host_streams_done = nullptr; // pinned: the launch's count of finished streams, copied behind every launch
+    uint64_t streams_expected = 0;                   // ... and what it must read once the stream has drained (finish_path)
+    // a controlled launch (pt_render_tiles_ctl) also leaves its count of abandoned streams in host_streams_done[1] and its final pull
+    // counter in host_streams_done[2]; finish_path accounts for every stream with them
+    bool streams_controlled = false;
+    uint32_t streams_first_total = 0;
+    uint32_t *host_cancel = nullptr; // pinned, fine-grained: the stop request of a controlled launch (PtStreams::cancel), written by the host
+    uint32_t *dev_cancel = nullptr;  // ... and its address on the device
+    // cost-aware placement (render_tiles_impl): what every stream of the pilot launch cost, and the stream every slot of the main launch starts with
+    pth::DevBuf<uint32_t> sl_cost, stream_cost, place;
+    // a view batch (pt_render_views): the cameras and seeds of its views
+    pth::DevBuf<PtViewCamera> view_cams;
+    pth::DevBuf<uint64_t> view_seeds;
+    // the first-hit features of a frame (pt_render_features*): the frame's features and the walks' spill area
+    pth::DevBuf<pth::F4> features;
+    pth::DevBuf<uint2> feature_spill;
+    pth::DevBuf<PtViewCamera> feature_cams; // pt_render_features_views: the views' cameras, aperture none
+    bool debug_collect_costs = false;                // pt_debug_collect_costs: every launch records them
+    std::vector<uint32_t> debug_place;               // pt_debug_set_place: the next launch starts from this table ...
+    uint32_t debug_place_waves = 0, debug_place_slots = 0; // ... with this many wavefronts and slots in each
+
+    ~pt_scene() {
+        if(host_tiles_done != nullptr) {
+            (void)hipHostFree(host_tiles_done);
+        }
+        if(host_streams_done != nullptr) {
+            (void)hipHostFree(host_streams_done);
+        }
+        if(host_cancel != nullptr) {
+            (void)hipHostFree(host_cancel);
+        }
+        if(stream != nullptr) {
+            (void)hipStreamDestroy(stream);
+        }
+    }
+};
+
+namespace pth {
+
+// ---- pt_api.cpp ------------------------------------------------------------------------------------------------------------------------
+
+int device_count_quiet();
+int check_device(int device); // PT_ERR_NO_DEVICE without a HIP device, or for an index that names none
+PtDevCamera derive_camera(const pt_camera_params *c);
+int derive_options(const pt_options *o, PtDevOptions *out);
+int check_render_args(pt_scene *scene, const pt_camera_params *camera, const pt_options *options);
+
+// ---- pt_render.cpp: the persistent path kernel (pt_path.hip), one launch per render call ----------------------------------------------
+
+// The stop of one controlled call (pt_render_tiles_ctl), shared by the host threads of its replicas.  The stop travels to the device as
+// one word per replica in pinned, fine-grained host memory; the host loop of every launch polls the caller's cancel flag and the deadline,
+// and the first one to see either writes 1 into the word of every replica whose launch is prepared or running.
+struct RenderStop {
+    typedef std::chrono::steady_clock Clock;
+    pt_render_control none{}; // (a call without a control can still be asked to stop by its deadline -- it has none -- or not at all)
+    pt_render_control *ctl;
+    bool has_deadline = false;
+    Clock::time_point deadline;
+    std::atomic<bool> requested{false};
+    std::mutex mutex; // guards what follows
+    Clock::time_point requested_at;
+    std::vector<uint32_t *> words; // the cancel words of the launches prepared or running
+    double drain_ms = 0.0;         // the latest end of a launch after the request
+
+    // The stop of a call that began at `start`: its deadline from ctl->budget_ms (ctl may be null), and a first look at both -- a control
+    // cancelled before the call, or a budget spent already, starts the launches stopped.
+    RenderStop(pt_render_control *ctl, Clock::time_point start);
+    // a launch takes part: its word starts as the stop's state (a request that came before the launch stops it at its first pass)
+    void enlist(uint32_t *word);
+    // ... and has ended (seen by its host loop at `end`): its word may serve another call now
+    void retire(uint32_t *word, Clock::time_point end);
+    void poll();
+};
+
+// What a controlled launch did with its streams (finish_path)
+struct StreamTally {
+    uint64_t finished = 0, abandoned = 0, unclaimed = 0;
+};
+
+struct PathPlan;
+int setup_path(pt_scene *s);
+// Grid and slot rows for n streams, and the buffers they need.
+int ensure_path_workspace(pt_scene *s, uint32_t n, PtPathConfig *out_cfg, const PathPlan *plan = nullptr);
+// Render the streams described by T (device pointers) with one launch on the scene's stream.  With a progress function the host polls
+// the count of finished tiles (pinned memory, written by the kernel) while the launch runs and reports every step from the calling thread.
+// With a RenderStop (controlled launches) the host loop runs whether or not there is a progress function: it forwards a stop request to the
+// launch through the scene's cancel word.
+int run_path(pt_scene *s, const PtDevCamera &cam, const PtDevOptions &opt, PtStreams T, float4 *d_image, pt_stats *stats, pt_progress_fn progress, void *progress_user,
+             RenderStop *stop = nullptr);
+// Wait for the scene's stream and make sure the last launch rendered every stream it was given: a wavefront that left early or a stream
+// lost in the hand-out would otherwise return stale pixels with PT_OK.  Every entry point that synchronises anyway ends with this.  A
+// controlled launch must account for every stream as finished, abandoned or never taken; `tally` (may be null) receives the three.
+int finish_path(pt_scene *s, StreamTally *tally = nullptr);
+
+// A view batch (pt_render_views): n > 1 views of one scene whose frames are stacked into one image of n * image_height rows; view v has the
+// camera cams[v] and the seed seeds[v].  The tiles of such a call lie in the stacked image.
+struct ViewSet {
+    std::vector<PtViewCamera> cams;
+    std::vector<uint64_t> seeds;
+    int32_t rows(const pt_options *options) const { return static_cast<int32_t>(cams.size()) * options->image_height; }
+};
+
+// The arguments every view-batch entry point checks before anything is launched; fills the stacked tile list and, for V > 1, the view set.
+int prepare_views(const pt_camera_params *cameras, const uint64_t *base_seeds, int32_t n_views, const pt_options *options, std::vector<pt_tile> *tiles, ViewSet *views);
+
+// Every tile lies inside the image of `rows` rows and is not empty; with `total`, the tiles' pixels are counted into it and may not be
+// more than 0x0fffffff in one `unit` (the message's last word).
+int check_tiles(const pt_tile *tiles, size_t n_tiles, int32_t width, int32_t rows, uint64_t *total, const char *unit = "call");
+
+// The tile table of a launch, on the host: stream i = pixel i of the tiles laid end to end; the kernel derives rectangle and engine from it.
+struct TileTable {
+    std::vector<int4> rects;
+    std::vector<uint32_t> offsets, left; // the first stream of every tile, and its pixels
+    TileTable(const pt_tile *tiles, size_t n_tiles);
+};
+// The tile and view fields of a launch's streams, from the tables in device memory (the scene's for a render call, a frame's own for its
+// launches); n_views <= 1: no view tables.
+void set_tile_streams(PtStreams *T, uint32_t n, const int4 *d_tiles, const uint32_t *d_offset, size_t n_tiles, uint64_t base_seed, int32_t n_views, int32_t view_height,
+                      const PtViewCamera *d_view_cams, const uint64_t *d_view_seeds);
+// A regular grid of equal tiles (what pt_job_tiles makes of a frame whose sides are multiples of the tile size) lets the kernel spread a
+// wavefront's first rows over the frame's columns as well as over its bands: tiles per grid row, 64-stream chunks per tile (0, 0: no grid).
+void tile_grid(const pt_tile *tiles, size_t n_tiles, uint32_t *tiles_per_row, uint32_t *chunks_per_tile);
+// The replica that renders each tile of a multi-device call (render_tiles_multi_impl, and a frame's tiles for good: pt_frame_create).
+std::vector<int> tile_owners(const pt_tile *tiles, size_t n_tiles, int n_scenes);
+
+// Runs fn(i) for the replicas i = 0 .. n-1 of a multi-device call, replica 0 on the calling thread and every other one on a thread of its
+// own, and waits for all of them.  PT_OK, or the code of the first replica that failed with the message "scene i: " + its thread's message.
+int for_each_replica(int n, const std::function<int(int)> &fn);
+
+// The progress function of a multi-device call: its replicas' launches report through callback() / this, and the caller's function sees
+// one count over all of them, one call at a time (from the replicas' polling threads).
+struct SharedProgress {
+    std::mutex mutex;
+    int completed, total;
+    pt_progress_fn fn;
+    void *user;
+    SharedProgress(pt_progress_fn fn_, void *user_, int completed_, int total_) : completed(completed_), total(total_), fn(fn_), user(user_) {}
+    pt_progress_fn callback() const { return fn != nullptr ? &SharedProgress::step : nullptr; }
+    static void step(int, int, void *shared);
+};
+
+// The rectangles of `tiles` between the caller's image (`width` pixels wide) and the scene's frame in HBM, on the scene's stream; with
+// `skip`, tile k is left out when skip[index[k]] is set.
+int copy_tile_rects(pt_scene *s, const std::vector<pt_tile> &tiles, const std::vector<size_t> &index, const uint8_t *skip, float *image, size_t width, bool to_device);
+
+// The library's stream ordered after the caller's stream (begin), and the caller's later work after the library's (end: not called when
+// the work between them failed to enqueue, so that the caller's stream is not made to wait then)
+struct StreamOrder {
+    Event ev;
+    hipStream_t caller = nullptr, own = nullptr;
+    int begin(void *caller_stream, hipStream_t own_stream) {
+        caller = static_cast<hipStream_t>(caller_stream);
+        own = own_stream;
+        PT_HIP(ev.create(hipEventDisableTiming));
+        PT_HIP(hipEventRecord(ev.e, caller));
+        PT_HIP(hipStreamWaitEvent(own, ev.e, 0));
+        return PT_OK;
+    }
+    int end() {
+        PT_HIP(hipEventRecord(ev.e, own));
+        PT_HIP(hipStreamWaitEvent(caller, ev.e, 0));
+        return PT_OK;
+    }
+};
+
+// ---- pt_image.cpp ----------------------------------------------------------------------------------------------------------------------
+
+// Enqueues the feature pass for the stacked frames of n_views cameras on the scene's stream (render_mutex held), in one launch: into
+// `d_out`, n_views * width * height * 3 float4.
+int features_views_launch(pt_scene *s, const pt_camera_params *cameras, int32_t n_views, const pt_options *options, float4 *d_out);
+
+// The denoiser's scratch buffers: one set per device, grown on demand, one call at a time per device.  They live as long as the process
+// (never freed: a static destructor would run after the HIP runtime has gone).
+struct DenoiseWorkspace {
+    std::mutex mutex;
+    size_t pixels = 0;  // capacity of the per-pixel buffers
+    size_t staged = 0;  // ... and of the host form's upload/download buffers
+    PtDenoiseScratch scratch{};
+    float4 *in_rgba = nullptr, *in_features = nullptr;
+};
+DenoiseWorkspace &denoise_workspace(int device);
+int denoise_ensure(DenoiseWorkspace &ws, size_t n, bool staged);
+// The parameters pt_denoise takes (NULL = the defaults), checked without a device
+int denoise_params_resolve(const pt_denoise_params *params, PtDenoiseParams *resolved);
+
+} // namespace pth
+
+#endif

@@ -1,4 +1,4 @@
-// pt_kernels.h -- launch interface between the host side of libpathtrace_hip.so (pt_api.cpp) and the kernels of pt_path.hip.
+// pt_kernels.h -- launch interface between the host side of libpathtrace_hip.so (pt_render.cpp, pt_frames.cpp, pt_image.cpp) and the kernels of pt_path.hip.
 #ifndef PT_KERNELS_H
 #define PT_KERNELS_H
 

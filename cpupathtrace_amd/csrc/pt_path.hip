@@ -597,7 +597,7 @@ PT_D void shade_row(const PtDevScene &sc, const PtDevCamera &cam, const PtDevOpt
                 base = ctx.first_base + row * 64u;
                 mine = base + lane;
                 if(T.place != nullptr) {
-                    // an explicit first round (cost-aware placement, pt_api.cpp): the table names the stream of every slot, or none
+                    // an explicit first round (cost-aware placement, pt_render.cpp): the table names the stream of every slot, or none
                     base = 0;
                     mine = T.place[ctx.first_base + ls];
                 }

@@ -18,7 +18,7 @@ def tile_owner(tiles, world):
     """Rank of every tile.  Tile k of processJob's row-major list goes to rank k % world; when the grid's rows hold a multiple of
     `world` tiles that would give every rank whole COLUMNS of the frame (with 32 tiles per row and 8 ranks: columns r, r + 8, ...,
     and the ranks' loads differ by what their columns show), so every grid row is then shifted by one more rank: (column + row) % world.
-    Same rule in pt_render_tiles_multi (cpupathtrace_amd/csrc/pt_api.cpp)."""
+    Same rule in pt_render_tiles_multi (cpupathtrace_amd/csrc/pt_render.cpp)."""
     k = np.arange(len(tiles), dtype=np.int64)
     if world <= 1 or len(tiles) == 0:
         return np.zeros(len(tiles), np.int64)

@@ -1,5 +1,5 @@
 """numpy float32 restatement of the temporal denoiser of cpupathtrace_amd/csrc/pt_denoise.hip (pt_temporal_run) and of the
-host-side camera terms pt_api.cpp hands it: the definition the GPU is checked against.  Reprojection and tap validity are only + - * /, one
+host-side camera terms pt_image.cpp hands it: the definition the GPU is checked against.  Reprojection and tap validity are only + - * /, one
 square root and comparisons, all correctly rounded (the library is built with -ffp-contract=off and correctly rounded division and square
 root), so the history lengths agree exactly; the filter itself is tests/denoise_ref.py's.
 
@@ -28,7 +28,7 @@ def params(**kw):
     return p
 
 
-# ---- the camera terms (pt_api.cpp: derive_camera, temporal_camera) ---------------------------------------------------------------------
+# ---- the camera terms (pt_api.cpp: derive_camera; pt_image.cpp: temporal_camera) ---------------------------------------------------------------------
 
 def _dot(a, b):
     d = F(0.0)

@@ -108,3 +108,35 @@ def test_device_libm_matches_glibc(tmp_path, step):
     subprocess.run(["g++", "-O2", "-std=c++20", "-ffp-contract=off", "-o", str(exe), str(src)], check=True)
     n, bad = subprocess.run([str(exe), str(step)], check=True, capture_output=True, text=True).stdout.split()
     assert int(n) > 1000000 and int(bad) == 0
+
+
+_ZERO = (ctypes.c_float * 4)()
+# one cheap argument fault per host unit of cpupathtrace_amd/csrc: (unit, entry point, arguments, message)
+UNIT_FAULTS = [
+    ("pt_api.cpp", "pt_scene_info", (None, None, None, None), b"null scene"),
+    ("pt_render.cpp", "pt_render_cancel", (None,), b"null control"),
+    ("pt_frames.cpp", "pt_frame_destroy", (None,), b"null frame"),
+    ("pt_image.cpp", "pt_denoise", (0, _ZERO, _ZERO, 0, 0, None, _ZERO), b"image size must be positive"),
+    ("pt_image.cpp", "pt_temporal_params_default", (None,), b"null argument"),
+]
+
+
+def _fault_library():
+    build.build()
+    lib = ctypes.CDLL(binding.LIB_PATH)
+    lib.pt_last_error.restype = ctypes.c_char_p
+    return lib
+
+
+def test_a_failing_call_sets_the_message_from_every_host_unit():
+    """The calling thread's message has one definition for all host units: pt_last_error() returns what the failing call of each unit
+    wrote, not an empty string of its own or the message an earlier call of another unit left."""
+    lib = _fault_library()
+    for unit, name, args, message in UNIT_FAULTS:
+        assert getattr(lib, name)(*args) != 0, (unit, name)
+        assert lib.pt_last_error() == message, (unit, name, lib.pt_last_error())
+
+
+@pytest.mark.parametrize("unit,name,args,message", UNIT_FAULTS, ids=[f[1] for f in UNIT_FAULTS])
+def test_argument_faults_are_invalid_before_any_device_is_looked_for(unit, name, args, message):
+    assert getattr(_fault_library(), name)(*args) == 1, (unit, name)  # PT_ERR_INVALID, with or without a GPU

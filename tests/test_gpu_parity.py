@@ -743,7 +743,7 @@ SCHEDULE_STATS = ("wave_steps", "shading_passes", "wavefronts", "slot_rows")
 def _render_with_env(desc, cam, opt, base_seed, **values):
     """process_job of a new scene of `desc` with the given knobs set across scene creation AND the render: the library reads some of its
     knobs when a scene is created (PT_ROWS, PT_REFILL_IDLE, PT_COMPACT, ...) and others at every render call (PT_BURST, PT_LEAF_MIN,
-    PT_FIRST_LANES, PT_SPREAD_WAVES, PT_FIRST_SPREAD, PT_FIRST_SHIFT; pt_api.cpp, ensure_path_workspace / run_path)."""
+    PT_FIRST_LANES, PT_SPREAD_WAVES, PT_FIRST_SPREAD, PT_FIRST_SHIFT; pt_render.cpp, ensure_path_workspace / run_path)."""
     with env(**values):
         scene = binding.Scene(desc)
         try:
