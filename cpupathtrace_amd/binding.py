@@ -48,6 +48,8 @@ EXPORTS += PROGRESSIVE_EXPORTS
 TEMPORAL_EXPORTS = ["pt_temporal_params_default", "pt_temporal_create", "pt_temporal_denoise", "pt_temporal_denoise_device", "pt_temporal_reset",
                     "pt_temporal_destroy"]
 EXPORTS += TEMPORAL_EXPORTS
+# (EXPORTS is what include/pt_hip.h itself declares; these two are declared in include/pt_frame_noise.h, which it includes)
+NOISE_EXPORTS = ["pt_frame_get_noise", "pt_frame_set_noise_target"]
 
 
 
@@ -289,6 +291,42 @@ class FrameProgress(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class FrameNoise(C.Structure):
+    """pt_frame_noise: how noisy the unfinished pixels of a frame are."""
+    _fields_ = [("target_error", C.c_float), ("floor", C.c_float), ("fraction", C.c_float), ("target_reached", C.c_int32), ("streams_total", C.c_uint64),
+                ("streams_finished", C.c_uint64), ("streams_rated", C.c_uint64), ("streams_unrated", C.c_uint64), ("streams_held", C.c_uint64),
+                ("max_error", C.c_float), ("histogram", C.c_uint32 * 64)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_}
+        d["histogram"] = np.array(self.histogram, np.uint32)
+        return NoiseSummary(d)
+
+
+def error_bin(error):
+    """The histogram bin of an error (pixel_error_bin, csrc/pt_noise.h): clamp(exponent of the float32 - 127 + 32, 0, 63), so bin 32 is
+    [1, 2), zero and the denormals fall in bin 0, 2^31 and everything above in bin 63.  Scalar or array."""
+    bits = np.asarray(error, np.float32).view(np.uint32)
+    return np.clip(((bits >> np.uint32(23)) & np.uint32(0xff)).astype(np.int32) - 127 + 32, 0, 63)
+
+
+class NoiseSummary(dict):
+    """Frame.noise(): pt_frame_noise as a dict (histogram: 64 counts as a numpy array), with percentile()."""
+
+    def percentile(self, p):
+        """An upper bound of the error that p percent (0 < p <= 100) of the rated streams do not exceed, from the histogram: the upper
+        edge 2^(bin - 31) of the first bin at which the running count reaches them, or max_error if that is less (0.0 for bin 0 of a
+        frame whose max_error is 0, and when nothing is rated)."""
+        if not 0 < p <= 100:
+            raise ValueError("p must be in (0, 100]")
+        hist = np.asarray(self["histogram"], np.uint64)
+        rated = int(hist.sum())
+        if rated == 0:
+            return 0.0
+        b = int(np.searchsorted(np.cumsum(hist), max(int(np.ceil(rated * p / 100.0)), 1)))
+        return min(float(2.0 ** (b - 31)), float(self["max_error"]))
 
 
 TILE_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("w", "<i4"), ("h", "<i4")])
@@ -652,6 +690,38 @@ class Frame:
         _check(load().pt_frame_get_progress(self._h, C.byref(fp)))
         return fp.as_dict()
 
+    def set_noise_target(self, target_error, floor=1e-5, fraction=1.0):
+        """A noise target (pt_frame_set_noise_target): a progressive frame then holds every pixel rated at or below target_error out of
+        its passes, and render() returns (status PT_ERR_CANCELLED, noise()["target_reached"] 1) once finished + held pixels are `fraction`
+        of the frame.  0 clears the target: render on and the finished image is what it always is.  floor: added to the denominator of
+        the rating, raise it to keep dark pixels from dominating.  Between two render() calls only."""
+        if self._h is None:
+            raise ValueError("frame is closed")
+        if not (np.isfinite(target_error) and target_error >= 0 and np.isfinite(floor) and floor >= 0 and 0 < fraction <= 1):
+            raise ValueError("target_error and floor must be finite and >= 0, fraction in (0, 1]")
+        _check(load().pt_frame_set_noise_target(self._h, C.c_float(target_error), C.c_float(floor), C.c_float(fraction)))
+
+    def _noise(self, error):
+        if self._h is None:
+            raise ValueError("frame is closed")
+        fn = FrameNoise()
+        _check(load().pt_frame_get_noise(self._h, C.byref(fn), _ptr(error)))
+        return fn.as_dict()
+
+    def noise(self):
+        """pt_frame_get_noise as a NoiseSummary: streams_rated / unrated / held / finished / total, max_error, the 64-bin histogram of the
+        rated streams by the exponent of their error (error_bin), target_reached and the target as set; percentile(p) reads the histogram."""
+        return self._noise(None)
+
+    def error_map(self):
+        """One rating per pixel, float32 in the shape of the preview's sample counts: -1 finished, +inf unrated, untouched or in no
+        tile, else the standard error of the pixel's mean relative to 9 * its mean + floor."""
+        if self._h is None:
+            raise ValueError("frame is closed")
+        error = np.empty(self.image.shape[:-1], np.float32)
+        self._noise(error)
+        return error
+
     def preview(self, denoise=None):
         """The frame as it stands (pt_frame_preview): (rgba, samples).  rgba (h, w, 4) float32: finished pixels as self.image, parked ones
         the running mean of their samples so far, holes (untouched pixels) 0.  samples (h, w) int32: -1 finished, the samples a parked
@@ -684,7 +754,7 @@ class Frame:
 
 class ViewsFrame(Frame):
     """process_views that can be stopped and continued (pt_frame_create_views): a Frame over a view batch.  render, info, preview, done,
-    set_progressive, progress and close are Frame's; image and the preview are (V, H, W, 4), the preview's sample counts (V, H, W), tile_done
+    set_progressive, progress, set_noise_target, noise, error_map and close are Frame's (the error map is (V, H, W)); image and the preview are (V, H, W, 4), the preview's sample counts (V, H, W), tile_done
     covers the tiles of all views (V x job_tiles(W, H), view after view).  The finished images equal process_views / process_views_multi
     with the same seeds bit for bit, however the calls were sliced.  base_seeds: one int for every view, or V ints."""
 

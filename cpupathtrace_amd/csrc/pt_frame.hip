@@ -13,10 +13,18 @@
 // entry the launch never claimed keeps its record: the carry kernel copies it from the launch's input records to its output records, behind
 // the ones the launch wrote, so no sample is ever lost.
 //
-// The same work list is what pt_frame_preview shows between two launches: the gather kernels below read it without changing it.
+// A progressive frame with a noise target (pt_frame_set_noise_target; PtNoiseRule::target > 0) has a third part behind those two: the HELD
+// streams, whose pixel is rated (pixel_error, pt_noise.h) at or below the target.  A pass's launch takes the list without that part, so a
+// held stream is never claimed and its record is carried like any unclaimed one.  Whether a stream is held is read from its record every
+// time a list is built and stored nowhere.  Before a pass the host has the list built once more with nothing launched (`resort`): every
+// record stays where it is and only the list is split again, by the pass's sample count and the target as they are now.
+//
+// The same work list is what pt_frame_preview shows between two launches: the gather kernels below read it without changing it, and
+// pt_frame_rate_kernel rates its pixels for pt_frame_get_noise.
 #include <hip/hip_runtime.h>
 
 #include "pt_kernels.h"
+#include "pt_noise.h"
 
 namespace {
 
@@ -30,8 +38,9 @@ constexpr uint32_t kCarry = 0x80000000u;
 // what became of entry i: 0 = finished, 1 = parked in this launch, 2 = still to do from its seed.  In a progressive frame (target > 0):
 // 0 = finished, 1 = its pixel has fewer than `target` samples, 2 = it has them; `samples` is that count and `where` says where the stream's
 // record is: 0 = it has none, 1 = in the launch's output records (index `rec`), 2 = in its input records (index `rec`: never claimed).
+// With a noise target, 3 = held: the stream has a record and its pixel's error is at or below the target (an unrated pixel's is +inf).
 __device__ uint32_t entry_class(const uint2 *todo, const uint32_t *status, uint32_t i, int32_t target, const PtParkRecord *parked, const PtParkRecord *park_in,
-                                uint32_t &where, uint32_t &rec, int32_t &samples) {
+                                const PtNoiseRule &noise, uint32_t &where, uint32_t &rec, int32_t &samples) {
     const uint2 e = todo[i];
     const uint32_t st = status[e.x];
     where = 0;
@@ -53,83 +62,96 @@ __device__ uint32_t entry_class(const uint2 *todo, const uint32_t *status, uint3
         rec = e.y;
         samples = park_in[rec].est.pixel_sample;
     }
+    if(noise.target > 0.0f && where != 0u && pixel_error((where == 1u ? parked : park_in)[rec].est, noise.opt, noise.floor) <= noise.target) {
+        return 3u;
+    }
     return samples < target ? 1u : 2u;
 }
 
 __global__ __launch_bounds__(kThreads) void pt_frame_count_kernel(const uint2 *__restrict__ todo, uint32_t n, const uint32_t *__restrict__ status,
                                                                   uint32_t *__restrict__ block_counts, int32_t target, const PtParkRecord *__restrict__ parked,
-                                                                  const PtParkRecord *__restrict__ park_in) {
-    __shared__ uint32_t sum[2];
-    if(threadIdx.x < 2) {
+                                                                  const PtParkRecord *__restrict__ park_in, PtNoiseRule noise) {
+    __shared__ uint32_t sum[3];
+    if(threadIdx.x < 3) {
         sum[threadIdx.x] = 0;
     }
     __syncthreads();
-    uint32_t first = 0, second = 0;
+    uint32_t first = 0, second = 0, third = 0;
     for(uint32_t k = 0; k < kPerThread; k++) {
         const uint32_t i = blockIdx.x * kPerBlock + threadIdx.x * kPerThread + k;
         if(i < n) {
             uint32_t where, rec;
             int32_t samples;
-            const uint32_t c = entry_class(todo, status, i, target, parked, park_in, where, rec, samples);
+            const uint32_t c = entry_class(todo, status, i, target, parked, park_in, noise, where, rec, samples);
             first += c == 1u ? 1u : 0u;
             second += c == 2u ? 1u : 0u;
+            third += c == 3u ? 1u : 0u;
         }
     }
     atomicAdd(&sum[0], first);
     atomicAdd(&sum[1], second);
+    if(third != 0) {
+        atomicAdd(&sum[2], third);
+    }
     __syncthreads();
-    if(threadIdx.x < 2) {
-        block_counts[2 * blockIdx.x + threadIdx.x] = sum[threadIdx.x];
+    if(threadIdx.x < 3) {
+        block_counts[3 * blockIdx.x + threadIdx.x] = sum[threadIdx.x];
     }
 }
 
 __global__ __launch_bounds__(kThreads) void pt_frame_place_kernel(const uint2 *__restrict__ todo, uint32_t n, uint32_t *__restrict__ status,
                                                                   const uint32_t *__restrict__ block_counts, uint32_t n_blocks, const PtParkRecord *__restrict__ parked,
                                                                   uint2 *__restrict__ todo_out, unsigned long long *__restrict__ result, int32_t target,
-                                                                  const PtParkRecord *__restrict__ park_in) {
-    __shared__ uint32_t scan[kThreads];
-    __shared__ uint32_t before[3]; // first class in earlier blocks, second class in earlier blocks, first class in all blocks
-    if(threadIdx.x < 3) {
+                                                                  const PtParkRecord *__restrict__ park_in, PtNoiseRule noise, int resort) {
+    __shared__ unsigned long long scan[kThreads];
+    // first class in earlier blocks, second class in earlier blocks, first class in all blocks, held in earlier blocks, second class in all blocks
+    __shared__ uint32_t before[5];
+    if(threadIdx.x < 5) {
         before[threadIdx.x] = 0;
     }
     __syncthreads();
     {
-        uint32_t p_before = 0, f_before = 0, p_all = 0;
+        uint32_t p_before = 0, f_before = 0, p_all = 0, h_before = 0, f_all = 0;
         for(uint32_t b = threadIdx.x; b < n_blocks; b += kThreads) {
-            const uint32_t pb = block_counts[2 * b], fb = block_counts[2 * b + 1];
+            const uint32_t pb = block_counts[3 * b], fb = block_counts[3 * b + 1];
             p_all += pb;
+            f_all += fb;
             if(b < blockIdx.x) {
                 p_before += pb;
                 f_before += fb;
+                h_before += block_counts[3 * b + 2];
             }
         }
         atomicAdd(&before[0], p_before);
         atomicAdd(&before[1], f_before);
         atomicAdd(&before[2], p_all);
+        atomicAdd(&before[3], h_before);
+        atomicAdd(&before[4], f_all);
     }
-    // the thread's entries, and an inclusive scan of (first class | second class << 16) over the block's threads in thread order
+    // the thread's entries, and an inclusive scan of (first class | second class << 21 | held << 42) over the block's threads in thread order
     uint32_t cls[kPerThread], where[kPerThread], rec[kPerThread];
     int32_t samples[kPerThread];
-    uint32_t mine = 0;
+    unsigned long long mine = 0;
     for(uint32_t k = 0; k < kPerThread; k++) {
         const uint32_t i = blockIdx.x * kPerBlock + threadIdx.x * kPerThread + k;
         where[k] = 0;
         rec[k] = PT_NO_PARK;
         samples[k] = 0;
-        cls[k] = i < n ? entry_class(todo, status, i, target, parked, park_in, where[k], rec[k], samples[k]) : 0u;
-        mine += cls[k] == 1u ? 1u : (cls[k] == 2u ? 0x10000u : 0u);
+        cls[k] = i < n ? entry_class(todo, status, i, target, parked, park_in, noise, where[k], rec[k], samples[k]) : 0u;
+        mine += cls[k] == 1u ? 1ull : (cls[k] == 2u ? 1ull << 21 : (cls[k] == 3u ? 1ull << 42 : 0ull));
     }
     scan[threadIdx.x] = mine;
     __syncthreads();
     for(uint32_t d = 1; d < kThreads; d <<= 1) {
-        const uint32_t add = threadIdx.x >= d ? scan[threadIdx.x - d] : 0u;
+        const unsigned long long add = threadIdx.x >= d ? scan[threadIdx.x - d] : 0ull;
         __syncthreads();
         scan[threadIdx.x] += add;
         __syncthreads();
     }
-    const uint32_t excl = scan[threadIdx.x] - mine;
-    uint32_t at_first = before[0] + (excl & 0xffffu);
-    uint32_t at_second = before[2] + before[1] + (excl >> 16);
+    const unsigned long long excl = scan[threadIdx.x] - mine;
+    uint32_t at_first = before[0] + (uint32_t)(excl & 0x1fffffu);
+    uint32_t at_second = before[2] + before[1] + (uint32_t)((excl >> 21) & 0x1fffffu);
+    uint32_t at_held = before[2] + before[4] + before[3] + (uint32_t)(excl >> 42);
     uint32_t lost = 0, carried = 0, with_candidates = 0, with_record = 0, written = 0, least = 0xffffffffu, most = 0;
     for(uint32_t k = 0; k < kPerThread; k++) {
         const uint32_t i = blockIdx.x * kPerBlock + threadIdx.x * kPerThread + k;
@@ -139,13 +161,17 @@ __global__ __launch_bounds__(kThreads) void pt_frame_place_kernel(const uint2 *_
         const uint2 e = todo[i];
         uint32_t s = 0; // samples the pixel has taken
         if(target > 0) {
-            // a progressive frame: the record stays with the stream wherever it is (an unclaimed one is moved by the carry kernel)
-            const uint32_t y = where[k] == 1u ? rec[k] : (where[k] == 2u ? (rec[k] | kCarry) : PT_NO_PARK);
+            // a progressive frame: the record stays with the stream wherever it is (an unclaimed one is moved by the carry kernel,
+            // unless the list is only split again: then the input records stay the frame's records)
+            const uint32_t y = where[k] == 1u ? rec[k] : (where[k] == 2u ? (resort != 0 ? rec[k] : (rec[k] | kCarry)) : PT_NO_PARK);
             if(cls[k] == 1u) {
                 todo_out[at_first++] = make_uint2(e.x, y);
             }
-            else {
+            else if(cls[k] == 2u) {
                 todo_out[at_second++] = make_uint2(e.x, y);
+            }
+            else {
+                todo_out[at_held++] = make_uint2(e.x, y);
             }
             s = (uint32_t)samples[k];
             if(where[k] != 0u) {
@@ -193,7 +219,8 @@ __global__ __launch_bounds__(kThreads) void pt_frame_place_kernel(const uint2 *_
     }
     if(blockIdx.x == n_blocks - 1 && threadIdx.x == kThreads - 1) {
         result[0] = before[2];
-        result[1] = before[1] + (scan[threadIdx.x] >> 16);
+        result[1] = before[4];
+        result[10] = before[3] + (uint32_t)(scan[threadIdx.x] >> 42);
     }
 }
 
@@ -206,7 +233,7 @@ static_assert(sizeof(PtParkRecord) == 33 * sizeof(uint4), "a park record is 33 x
 
 __global__ __launch_bounds__(kThreads) void pt_frame_carry_kernel(uint2 *__restrict__ todo_out, const PtParkRecord *__restrict__ park_in, PtParkRecord *__restrict__ park_out,
                                                                   uint32_t *__restrict__ park_count, uint32_t park_cap, unsigned long long *__restrict__ result) {
-    const uint32_t n = (uint32_t)(result[0] + result[1]); // (the new list's length, left by the place kernel)
+    const uint32_t n = (uint32_t)(result[0] + result[1] + result[10]); // (the new list's length, left by the place kernel)
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = (blockIdx.x * kThreads + threadIdx.x) / 64u;
     for(uint32_t k = 0; k < kCarryPerWave; k++) {
@@ -243,6 +270,24 @@ __global__ __launch_bounds__(kThreads) void pt_frame_carry_kernel(uint2 *__restr
 // Each replica gathers its work list into compact entries (gather); replica 0's device lays the frame out from the caller's image (base)
 // and writes every replica's entries over it (scatter).
 
+// The pixel of stream `stream` of a replica, as tile_stream (pt_path.hip) finds it: the last tile whose first stream is not behind it
+__device__ int32_t stream_pixel(uint32_t stream, const int4 *tiles, const uint32_t *tile_offset, uint32_t n_tiles, int32_t width) {
+    uint32_t lo = 0, hi = n_tiles;
+    while(hi - lo > 1) {
+        const uint32_t mid = (lo + hi) / 2;
+        if(tile_offset[mid] <= stream) {
+            lo = mid;
+        }
+        else {
+            hi = mid;
+        }
+    }
+    const int4 t = tiles[lo];
+    const uint32_t k = stream - tile_offset[lo];
+    const int32_t x = t.x + (int32_t)(k % (uint32_t)t.z), y = t.y + (int32_t)(k / (uint32_t)t.z);
+    return y * width + x;
+}
+
 // One thread per entry of a replica's work list todo[0 .. n): an entry that names a record is a parked stream with its record in `park`
 // (the first n_parked entries of a plain frame's list; any entry of a progressive frame's), the others are untouched.  Writes the entry's preview colour and (pixel, samples): the running mean pixel_value * (1 / collected_sample_count) and
 // pixel_sample of a parked stream (estimator_finish's first step, pt_shading.h), (0, 0, 0, 0) and 0 samples for an untouched one.  A parked
@@ -256,20 +301,6 @@ __global__ __launch_bounds__(kThreads) void pt_frame_gather_kernel(const uint2 *
         return;
     }
     const uint2 e = todo[i];
-    // the stream's pixel, as tile_stream (pt_path.hip) finds it: the last tile whose first stream is not behind it
-    uint32_t lo = 0, hi = n_tiles;
-    while(hi - lo > 1) {
-        const uint32_t mid = (lo + hi) / 2;
-        if(tile_offset[mid] <= e.x) {
-            lo = mid;
-        }
-        else {
-            hi = mid;
-        }
-    }
-    const int4 t = tiles[lo];
-    const uint32_t k = e.x - tile_offset[lo];
-    const int32_t x = t.x + (int32_t)(k % (uint32_t)t.z), y = t.y + (int32_t)(k / (uint32_t)t.z);
     float4 c = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     int32_t samples = 0;
     if(e.y != PT_NO_PARK) {
@@ -283,7 +314,7 @@ __global__ __launch_bounds__(kThreads) void pt_frame_gather_kernel(const uint2 *
         }
     }
     out_rgba[i] = c;
-    out_at[i] = make_int2(y * width + x, samples);
+    out_at[i] = make_int2(stream_pixel(e.x, tiles, tile_offset, n_tiles, width), samples);
 }
 
 // One thread per pixel: a pixel of some tile keeps the caller's colour and is finished (-1) until a scatter says otherwise; a pixel of
@@ -314,10 +345,104 @@ __global__ __launch_bounds__(kThreads) void pt_frame_scatter_kernel(const float4
     samples[a.x] = a.y;
 }
 
+// ---- the rating of a frame (pt_frame_get_noise, pt_frames.cpp) --------------------------------------------------------------------------
+// One thread per entry of a replica's work list, as the gather kernel: out[i] = (pixel, bits of its error), +inf for an entry without a
+// record or with fewer than two batch means (unrated).  Reads the estimator's fields pixel_error needs, not the record.  The summary is
+// reduced with integer atomics only, per block in LDS and then once per block: summary[0..2] = rated, unrated and held entries (held:
+// rated, and error <= noise.target > 0), [3] = the bits of the largest error of a rated entry (errors are never negative, so their bits
+// order as they do), [4 .. 67] = rated entries by pixel_error_bin.
+__global__ __launch_bounds__(kThreads) void pt_frame_rate_kernel(const uint2 *__restrict__ todo, uint32_t n, const PtParkRecord *__restrict__ park,
+                                                                 const int4 *__restrict__ tiles, const uint32_t *__restrict__ tile_offset, uint32_t n_tiles,
+                                                                 int32_t width, PtNoiseRule noise, uint2 *__restrict__ out, uint32_t *__restrict__ summary) {
+    __shared__ uint32_t part[PT_NOISE_SUMMARY_WORDS];
+    if(threadIdx.x < PT_NOISE_SUMMARY_WORDS) {
+        part[threadIdx.x] = 0;
+    }
+    __syncthreads();
+    const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
+    if(i < n) {
+        const uint2 e = todo[i];
+        float error = __builtin_inff();
+        bool rated = false;
+        if(e.y != PT_NO_PARK) {
+            const PtEstimator &est = park[e.y].est;
+            rated = pixel_batches(est, noise.opt) >= 2;
+            error = pixel_error(est, noise.opt, noise.floor);
+        }
+        out[i] = make_uint2((uint32_t)stream_pixel(e.x, tiles, tile_offset, n_tiles, width), __float_as_uint(error));
+        if(rated) {
+            atomicAdd(&part[0], 1u);
+            if(noise.target > 0.0f && error <= noise.target) {
+                atomicAdd(&part[2], 1u);
+            }
+            atomicMax(&part[3], __float_as_uint(error));
+            atomicAdd(&part[4 + pixel_error_bin(error)], 1u);
+        }
+        else {
+            atomicAdd(&part[1], 1u);
+        }
+    }
+    __syncthreads();
+    if(threadIdx.x < PT_NOISE_SUMMARY_WORDS && part[threadIdx.x] != 0) {
+        if(threadIdx.x == 3) {
+            atomicMax(&summary[3], part[3]);
+        }
+        else {
+            atomicAdd(&summary[threadIdx.x], part[threadIdx.x]);
+        }
+    }
+}
+
+// The error map on replica 0's device, one thread per pixel: -1 (finished) where a tile of a replica that has rendered covers the pixel,
+// until a scatter says otherwise; +inf elsewhere.
+__global__ __launch_bounds__(kThreads) void pt_frame_noise_base_kernel(float *__restrict__ map, const uint8_t *__restrict__ cover, uint32_t n_pixels) {
+    const uint32_t p = blockIdx.x * kThreads + threadIdx.x;
+    if(p < n_pixels) {
+        map[p] = cover[p] != 0 ? -1.0f : __builtin_inff();
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void pt_frame_noise_scatter_kernel(const uint2 *__restrict__ rated, uint32_t n, float *__restrict__ map) {
+    const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
+    if(i < n) {
+        const uint2 a = rated[i];
+        map[a.x] = __uint_as_float(a.y);
+    }
+}
+
 } // namespace
 
+int pt_launch_frame_rate(hipStream_t stream, const uint2 *todo, uint32_t n, const PtParkRecord *park, const int4 *tiles, const uint32_t *tile_offset, uint32_t n_tiles,
+                         int32_t width, const PtNoiseRule &noise, uint2 *out, uint32_t *summary) {
+    if(hipMemsetAsync(summary, 0, PT_NOISE_SUMMARY_WORDS * sizeof(uint32_t), stream) != hipSuccess) {
+        return 1;
+    }
+    if(n == 0) {
+        return 0;
+    }
+    pt_frame_rate_kernel<<<(n + kThreads - 1) / kThreads, kThreads, 0, stream>>>(todo, n, park, tiles, tile_offset, n_tiles, width, noise, out, summary);
+    return hipGetLastError() == hipSuccess ? 0 : 1;
+}
+
+int pt_launch_frame_noise_base(hipStream_t stream, float *map, const uint8_t *cover, uint32_t n_pixels) {
+    if(n_pixels == 0) {
+        return 0;
+    }
+    pt_frame_noise_base_kernel<<<(n_pixels + kThreads - 1) / kThreads, kThreads, 0, stream>>>(map, cover, n_pixels);
+    return hipGetLastError() == hipSuccess ? 0 : 1;
+}
+
+int pt_launch_frame_noise_scatter(hipStream_t stream, const uint2 *rated, uint32_t n, float *map) {
+    if(n == 0) {
+        return 0;
+    }
+    pt_frame_noise_scatter_kernel<<<(n + kThreads - 1) / kThreads, kThreads, 0, stream>>>(rated, n, map);
+    return hipGetLastError() == hipSuccess ? 0 : 1;
+}
+
 int pt_launch_frame_compact(hipStream_t stream, const uint2 *todo, uint32_t n, uint32_t *status, const PtParkRecord *parked, uint2 *todo_out, uint32_t *block_counts,
-                            unsigned long long *result, int32_t target, const PtParkRecord *park_in, PtParkRecord *park_out, uint32_t *park_count, uint32_t park_cap) {
+                            unsigned long long *result, int32_t target, const PtParkRecord *park_in, PtParkRecord *park_out, uint32_t *park_count, uint32_t park_cap,
+                            const PtNoiseRule &noise, int resort) {
     if(hipMemsetAsync(result, 0, 16 * sizeof(unsigned long long), stream) != hipSuccess) {
         return 1;
     }
@@ -325,9 +450,9 @@ int pt_launch_frame_compact(hipStream_t stream, const uint2 *todo, uint32_t n, u
         return 0;
     }
     const uint32_t n_blocks = (n + kPerBlock - 1) / kPerBlock;
-    pt_frame_count_kernel<<<n_blocks, kThreads, 0, stream>>>(todo, n, status, block_counts, target, parked, park_in);
-    pt_frame_place_kernel<<<n_blocks, kThreads, 0, stream>>>(todo, n, status, block_counts, n_blocks, parked, todo_out, result, target, park_in);
-    if(target > 0) {
+    pt_frame_count_kernel<<<n_blocks, kThreads, 0, stream>>>(todo, n, status, block_counts, target, parked, park_in, noise);
+    pt_frame_place_kernel<<<n_blocks, kThreads, 0, stream>>>(todo, n, status, block_counts, n_blocks, parked, todo_out, result, target, park_in, noise, resort);
+    if(target > 0 && resort == 0) {
         const uint32_t per_block = (kThreads / 64u) * kCarryPerWave;
         pt_frame_carry_kernel<<<(n + per_block - 1) / per_block, kThreads, 0, stream>>>(todo_out, park_in, park_out, park_count, park_cap, result);
     }

@@ -2,6 +2,8 @@
 // preview of an unfinished frame (pt_frame_preview) and the frame's queries.
 #include "pt_host.h"
 
+#include <limits>
+
 using namespace pth;
 
 // ---- resumable frames (pt_frame_*) -----------------------------------------------------------------------------------------------
@@ -19,10 +21,11 @@ struct pt_frame {
         uint32_t n_todo = 0, n_parked = 0; // the next launch's work list: its length, and the parked streams at its head
         uint64_t samples_carried = 0, with_candidates = 0;
         uint32_t n_at_target = 0;                 // streams of the list at or above the target of the last progressive pass
+        uint32_t n_held = 0;                      // streams at the list's end that the noise target holds (0 without one)
         int32_t min_samples = 0, max_samples = 0; // samples taken, over the list's pixels
         bool ready = false; // the device tables exist
         bool in_order = true; // the work list is every stream of the replica in order (stream i at index i)
-        int cur = 0;        // todo[cur] and park[cur] are what the next launch reads
+        int cur = 0, pcur = 0; // todo[cur] and park[pcur] are what the next launch reads
         DevBuf<int4> d_tiles;
         DevBuf<uint32_t> d_offset, d_left, d_status, d_blocks, d_park_count;
         DevBuf<uint2> d_todo[2];
@@ -38,6 +41,13 @@ struct pt_frame {
         DevBuf<uint8_t> pv_cover;
         bool pv_cover_ready = false, pv_features_ready = false;
         bool previewed = false; // device buffers of the preview exist
+        // pt_frame_get_noise: the replica's rated work list and its summary; on replica 0 also the error map, which pixels the tiles of
+        // the replicas that have rendered cover (and how many such replicas that is) and the other replicas' entries on their way in
+        DevBuf<uint2> nz_rated, nz_stage;
+        DevBuf<uint32_t> nz_summary;
+        DevBuf<float> nz_map;
+        DevBuf<uint8_t> nz_cover;
+        size_t nz_cover_ready = 0;
     };
     pt_camera_params camera{};
     pt_options options{};
@@ -59,6 +69,19 @@ struct pt_frame {
     int32_t quantum = 0, max_passes_per_call = 0, passes_completed = 0, target = 0;
     bool pass_in_progress = false;
     uint64_t samples_lost = 0;
+    // the noise target (pt_frame_set_noise_target): a progressive frame holds the streams rated at or below noise_target (0 = none);
+    // target_reached: the last pt_frame_render found enough of them held, and nothing has changed since
+    float noise_target = 0.0f, noise_floor = 1E-5f, noise_fraction = 1.0f;
+    bool target_reached = false;
+    double noise_rate_ms = 0.0; // device time of the rating kernels of the last pt_frame_get_noise, all replicas (tools/noise_probe.py)
+    PtNoiseRule noise_rule(const PtDevOptions &opt, bool holding) const {
+        PtNoiseRule rule;
+        rule.opt = opt;
+        rule.target = holding ? noise_target : 0.0f;
+        rule.floor = noise_floor;
+        return rule;
+    }
+    bool holding() const { return quantum > 0 && noise_target > 0.0f; }
     int status = PT_OK; // a failed frame returns this (and `error`) from every later call
     std::string error;
     mutable std::mutex mutex; // one call at a time
@@ -81,7 +104,7 @@ int frame_prepare(pt_frame::Replica &r) {
     PT_HIP(r.d_todo[1].ensure(r.n_streams));
     PT_HIP(r.d_status.ensure(r.n_streams));
     PT_HIP(hipMemset(r.d_status.ptr, 0, static_cast<size_t>(r.n_streams) * sizeof(uint32_t)));
-    PT_HIP(r.d_blocks.ensure(2 * ((static_cast<size_t>(r.n_streams) + 1023) / 1024)));
+    PT_HIP(r.d_blocks.ensure(3 * ((static_cast<size_t>(r.n_streams) + 1023) / 1024)));
     PT_HIP(r.d_park_count.ensure(1));
     PT_HIP(r.d_park[0].ensure(1));
     PT_HIP(r.d_result.ensure(16));
@@ -117,18 +140,20 @@ int frame_launch(pt_frame &f, pt_frame::Replica &r, float *out_image, pt_stats *
     PT_TRY(copy_tile_rects(s, r.tiles, r.index, f.tile_done.data(), out_image, static_cast<size_t>(f.options.image_width), true));
     // park storage: one record per slot at most (a stop closes the pool, so a slot drops one stream at most), and never more than the streams left.
     // A progressive pass keeps the pool open and every stream of the list leaves a record, written by the launch or carried over: one per entry.
-    PtPathConfig cfg;
-    PT_TRY(ensure_path_workspace(s, r.n_todo, &cfg));
-    const int cur = r.cur, next = cur ^ 1;
+    // (the streams a noise target holds are the end of the list: the launch does not see them, the next list keeps them)
     const bool progressive = yield_at > 0;
+    const uint32_t n_launch = r.n_todo - (progressive ? r.n_held : 0u);
+    PtPathConfig cfg;
+    PT_TRY(ensure_path_workspace(s, n_launch, &cfg));
+    const int cur = r.cur, next = cur ^ 1, pcur = r.pcur, pnext = pcur ^ 1;
     const uint32_t cap = progressive ? r.n_todo : std::min<uint32_t>(r.n_todo, s->path_slots);
     if(progressive) {
         opt.overlap_bound = std::min(opt.max_sample_count, yield_at); // (the sample that reaches the target ends at a boundary of its own)
     }
-    PT_HIP(r.d_park[next].ensure(cap));
+    PT_HIP(r.d_park[pnext].ensure(cap));
     PT_HIP(hipMemsetAsync(r.d_park_count.ptr, 0, sizeof(uint32_t), s->stream));
     PtStreams T{};
-    set_tile_streams(&T, r.n_todo, r.d_tiles.ptr, r.d_offset.ptr, r.tiles.size(), f.base_seed, f.n_views, f.options.image_height, r.d_view_cams.ptr, r.d_view_seeds.ptr);
+    set_tile_streams(&T, n_launch, r.d_tiles.ptr, r.d_offset.ptr, r.tiles.size(), f.base_seed, f.n_views, f.options.image_height, r.d_view_cams.ptr, r.d_view_seeds.ptr);
     // The first round is spread over the work list.  The first launch's list is every stream in order, so it is spread over the tile grid
     // as pt_render_tiles spreads it (an uninterrupted frame is scheduled exactly like one); a later list is no tile grid.
     T.tiles_per_row = 0;
@@ -138,8 +163,8 @@ int frame_launch(pt_frame &f, pt_frame::Replica &r, float *out_image, pt_stats *
     }
     T.tile_left = r.d_left.ptr;
     T.todo = r.d_todo[cur].ptr;
-    T.park_in = r.d_park[cur].ptr;
-    T.park_out = r.d_park[next].ptr;
+    T.park_in = r.d_park[pcur].ptr;
+    T.park_out = r.d_park[pnext].ptr;
     T.park_count = r.d_park_count.ptr;
     T.park_cap = cap;
     T.status = r.d_status.ptr;
@@ -147,8 +172,8 @@ int frame_launch(pt_frame &f, pt_frame::Replica &r, float *out_image, pt_stats *
     PT_TRY(run_path(s, cam, opt, T, reinterpret_cast<float4 *>(s->image.ptr), stats, progress, progress_user, stop));
     PT_TRY(copy_tile_rects(s, r.tiles, r.index, f.tile_done.data(), out_image, static_cast<size_t>(f.options.image_width), false));
     PT_TRY(finish_path(s, &out->tally));
-    if(pt_launch_frame_compact(s->stream, r.d_todo[cur].ptr, r.n_todo, r.d_status.ptr, r.d_park[next].ptr, r.d_todo[next].ptr, r.d_blocks.ptr, r.d_result.ptr,
-                               progressive ? yield_at : 0, r.d_park[cur].ptr, r.d_park[next].ptr, r.d_park_count.ptr, cap) != 0) {
+    if(pt_launch_frame_compact(s->stream, r.d_todo[cur].ptr, r.n_todo, r.d_status.ptr, r.d_park[pnext].ptr, r.d_todo[next].ptr, r.d_blocks.ptr, r.d_result.ptr,
+                               progressive ? yield_at : 0, r.d_park[pcur].ptr, r.d_park[pnext].ptr, r.d_park_count.ptr, cap, f.noise_rule(opt, f.holding()), 0) != 0) {
         PT_HIP(hipGetLastError());
         return fail(PT_ERR_HIP, "frame: work list kernel failed to launch");
     }
@@ -160,19 +185,22 @@ int frame_launch(pt_frame &f, pt_frame::Replica &r, float *out_image, pt_stats *
     // every stream of the work list is finished, parked or still to do, and the stop dropped no more than the parked and returned ones
     const StreamTally &t = out->tally;
     // (res[8]: the records the launch wrote; a progressive pass drops no record: res[9], the samples of records that found no room, is 0)
-    if(t.finished + res[0] + res[1] != r.n_todo || res[8] > t.abandoned || res[7] > cap || (!progressive && res[8] != res[0]) || res[9] != 0) {
+    // (res[10]: the streams the noise target holds, launched or not)
+    if(t.finished + res[0] + res[1] + res[10] != r.n_todo || res[8] > t.abandoned || res[7] > cap || (!progressive && res[8] != res[0]) || res[9] != 0) {
         return fail(PT_ERR_HIP, "frame: " + std::to_string(t.finished) + " finished, " + std::to_string(res[0]) + " parked and " + std::to_string(res[1]) +
-                                    " left of " + std::to_string(r.n_todo) + " streams (" + std::to_string(t.abandoned) + " dropped)");
+                                    " left of " + std::to_string(r.n_todo) + " streams (" + std::to_string(t.abandoned) + " dropped, " + std::to_string(res[10]) + " held)");
     }
-    r.n_todo = static_cast<uint32_t>(res[0] + res[1]);
+    r.n_todo = static_cast<uint32_t>(res[0] + res[1] + res[10]);
     r.n_parked = static_cast<uint32_t>(res[7]);
-    r.in_order = r.n_todo == r.n_streams && (r.n_parked == 0 || r.n_parked == r.n_todo) && (!progressive || res[0] == 0 || res[1] == 0); // (each part in order)
+    r.n_held = static_cast<uint32_t>(res[10]);
+    r.in_order = r.n_todo == r.n_streams && (r.n_parked == 0 || r.n_parked == r.n_todo) && (!progressive || std::max({res[0], res[1], res[10]}) == r.n_todo); // (each part in order)
     r.samples_carried = res[3];
     r.with_candidates = res[4];
     r.n_at_target = progressive ? static_cast<uint32_t>(res[1]) : 0;
     r.min_samples = r.n_todo != 0 ? static_cast<int32_t>(0xffffffffULL - res[5]) : 0;
     r.max_samples = static_cast<int32_t>(res[6]);
     r.cur = next;
+    r.pcur = pnext;
     out->parked = res[8];
     for(size_t k = 0; k < left.size(); k++) {
         f.tile_done[r.index[k]] = left[k] == 0 ? 1 : 0;
@@ -180,9 +208,40 @@ int frame_launch(pt_frame &f, pt_frame::Replica &r, float *out_image, pt_stats *
     return PT_OK;
 }
 
+// A progressive frame with a noise target, before a pass to `yield_at` samples: the replica's list split again by that sample count and
+// the target as they are now -- streams below the count, streams at it, held streams -- with nothing launched and no record moved.
+int frame_resort(pt_frame &f, pt_frame::Replica &r, int32_t yield_at) {
+    if(!r.ready || r.n_todo == 0) {
+        r.n_held = 0; // (no records yet: nothing is rated)
+        return PT_OK;
+    }
+    pt_scene *s = r.s;
+    std::lock_guard<std::mutex> lock(s->render_mutex);
+    PT_HIP(hipSetDevice(s->device));
+    PtDevOptions opt;
+    PT_TRY(derive_options(&f.options, &opt));
+    const int cur = r.cur, next = cur ^ 1;
+    if(pt_launch_frame_compact(s->stream, r.d_todo[cur].ptr, r.n_todo, r.d_status.ptr, r.d_park[r.pcur].ptr, r.d_todo[next].ptr, r.d_blocks.ptr, r.d_result.ptr,
+                               yield_at, r.d_park[r.pcur].ptr, nullptr, nullptr, 0, f.noise_rule(opt, true), 1) != 0) {
+        PT_HIP(hipGetLastError());
+        return fail(PT_ERR_HIP, "frame: work list kernel failed to launch");
+    }
+    unsigned long long res[16];
+    PT_HIP(hipMemcpyAsync(res, r.d_result.ptr, sizeof(res), hipMemcpyDeviceToHost, s->stream));
+    PT_HIP(hipStreamSynchronize(s->stream));
+    if(res[0] + res[1] + res[10] != r.n_todo) {
+        return fail(PT_ERR_HIP, "frame: " + std::to_string(res[0] + res[1]) + " streams to do and " + std::to_string(res[10]) + " held of " + std::to_string(r.n_todo));
+    }
+    r.in_order = r.in_order && std::max({res[0], res[1], res[10]}) == r.n_todo;
+    r.n_at_target = static_cast<uint32_t>(res[1]);
+    r.n_held = static_cast<uint32_t>(res[10]);
+    r.cur = next;
+    return PT_OK;
+}
+
 // What one round of launches left of the frame
 struct FrameRound {
-    uint64_t left = 0, parked = 0, at_target = 0; // streams still to do, parked by this round, at the target of a progressive pass
+    uint64_t left = 0, parked = 0, at_target = 0, held = 0; // streams still to do, parked by this round, at the target of a progressive pass, held by the noise target
 };
 
 // the work of all of a call's launches; the grid is the last launch's
@@ -212,8 +271,8 @@ int frame_round(pt_frame *f, float *out_image, pt_stats *stats, SharedProgress *
     std::vector<pt_stats> pass_stats(stats != nullptr ? n_scenes : 0, pt_stats{});
     const int rc = for_each_replica(static_cast<int>(n_scenes), [&](int i) -> int {
         pt_frame::Replica &r = *f->reps[static_cast<size_t>(i)];
-        if(r.n_todo == 0) {
-            return PT_OK;
+        if(r.n_todo - (yield_at > 0 ? r.n_held : 0u) == 0) {
+            return PT_OK; // (nothing left, or every stream left is held)
         }
         ran[static_cast<size_t>(i)] = 1;
         return frame_launch(*f, r, out_image, stats != nullptr ? &pass_stats[static_cast<size_t>(i)] : nullptr, shared->callback(), shared, stop, &launched[static_cast<size_t>(i)], yield_at);
@@ -235,6 +294,7 @@ int frame_round(pt_frame *f, float *out_image, pt_stats *stats, SharedProgress *
         const FrameLaunch &l = launched[i];
         round->left += f->reps[i]->n_todo;
         round->at_target += f->reps[i]->n_at_target;
+        round->held += f->reps[i]->n_held;
         round->parked += l.parked;
         if(ctl != nullptr) {
             ctl->streams_finished += l.tally.finished;
@@ -246,6 +306,10 @@ int frame_round(pt_frame *f, float *out_image, pt_stats *stats, SharedProgress *
         }
     }
     return PT_OK;
+}
+
+std::string noise_reached_message(uint64_t held, uint64_t left) {
+    return "frame stopped (noise target reached): " + std::to_string(held) + " streams held, " + std::to_string(left) + " streams left";
 }
 
 } // namespace
@@ -362,6 +426,15 @@ int pt_frame_render(pt_frame *f, float *out_image, pt_stats *stats, pt_progress_
     if(out_image == nullptr) {
         return fail(PT_ERR_INVALID, "null image");
     }
+    if(f->holding() && f->target_reached) {
+        report_tiles();
+        uint64_t left = 0, held = 0;
+        for(const auto &r : f->reps) {
+            left += r->n_todo;
+            held += r->n_held;
+        }
+        return fail(PT_ERR_CANCELLED, noise_reached_message(held, left));
+    }
     RenderStop stop(ctl, start);
     // progress over the whole frame, serialised over the replicas (as pt_render_tiles_multi)
     SharedProgress shared(progress, progress_user, static_cast<int>(f->tiles_done), static_cast<int>(f->tiles.size()));
@@ -370,21 +443,48 @@ int pt_frame_render(pt_frame *f, float *out_image, pt_stats *stats, pt_progress_
     FrameRound round;
     int passes_this_call = 0;
     bool pass_limit = false;
+    uint64_t noise_held = 0, noise_left = 0;
     for(;;) {
         int32_t yield_at = 0;
         if(f->quantum > 0) {
-            if(!f->pass_in_progress) {
-                f->target = f->target > INT32_MAX - f->quantum ? INT32_MAX : f->target + f->quantum;
-                f->pass_in_progress = true;
+            yield_at = f->pass_in_progress ? f->target : (f->target > INT32_MAX - f->quantum ? INT32_MAX : f->target + f->quantum);
+        }
+        if(f->holding()) {
+            // what the target holds now, from the records: out of this pass, and a new pass does not start once enough of the frame is
+            // finished or held
+            uint64_t left = 0, held = 0;
+            for(auto &r : f->reps) {
+                const int rc = frame_resort(*f, *r, yield_at);
+                if(rc != PT_OK) {
+                    f->status = rc;
+                    f->error = "frame failed: " + last_error();
+                    return fail(f->status, f->error);
+                }
+                left += r->n_todo;
+                held += r->n_held;
             }
-            yield_at = f->target;
+            if(!f->pass_in_progress && static_cast<double>(f->streams_total - left + held) >= static_cast<double>(f->noise_fraction) * static_cast<double>(f->streams_total)) {
+                f->target_reached = true;
+                noise_held = held;
+                noise_left = left;
+                break;
+            }
+        }
+        else {
+            for(auto &r : f->reps) {
+                r->n_held = 0;
+            }
+        }
+        if(f->quantum > 0) {
+            f->target = yield_at;
+            f->pass_in_progress = true;
         }
         PT_TRY(frame_round(f, out_image, stats, &shared, &stop, ctl, yield_at, &round));
         if(yield_at == 0) {
             break;
         }
-        // the pass has ended when every stream that is left has its samples (a stop that came too late to drop anything ends it too)
-        const bool pass_done = round.at_target == round.left;
+        // the pass has ended when every stream that is left has its samples or is held (a stop that came too late to drop anything ends it too)
+        const bool pass_done = round.at_target + round.held == round.left;
         if(pass_done) {
             f->pass_in_progress = false;
             f->passes_completed++;
@@ -406,6 +506,9 @@ int pt_frame_render(pt_frame *f, float *out_image, pt_stats *stats, pt_progress_
     if(ctl != nullptr) {
         ctl->drain_ms = stop.drain_ms;
     }
+    if(f->target_reached) {
+        return fail(PT_ERR_CANCELLED, noise_reached_message(noise_held, noise_left));
+    }
     if(round.left != 0) {
         const std::string why = pass_limit ? "pass limit reached" : (__atomic_load_n(&stop.ctl->cancel, __ATOMIC_ACQUIRE) != 0 ? "cancelled" : "budget spent");
         return fail(PT_ERR_CANCELLED, "frame stopped (" + why + "): " + std::to_string(round.parked) + " streams parked, " + std::to_string(round.left) + " streams left");
@@ -426,6 +529,7 @@ int pt_frame_set_progressive(pt_frame *f, int32_t quantum, int32_t max_passes_pe
     }
     f->quantum = quantum;
     f->max_passes_per_call = std::max(max_passes_per_call, 0);
+    f->target_reached = false;
     if(quantum == 0) {
         f->pass_in_progress = false; // (what an interrupted pass left is a plain frame's work now)
     }
@@ -518,7 +622,7 @@ static int preview_gather(pt_frame *f, std::vector<std::vector<F4>> &far_rgba, s
         r.previewed = true;
         PT_HIP(r.pv_rgba.ensure(r.n_todo));
         PT_HIP(r.pv_at.ensure(r.n_todo));
-        if(pt_launch_frame_gather(s->stream, r.d_todo[r.cur].ptr, r.n_todo, r.n_parked, r.d_park[r.cur].ptr, r.d_tiles.ptr, r.d_offset.ptr,
+        if(pt_launch_frame_gather(s->stream, r.d_todo[r.cur].ptr, r.n_todo, r.n_parked, r.d_park[r.pcur].ptr, r.d_tiles.ptr, r.d_offset.ptr,
                                   static_cast<uint32_t>(r.tiles.size()), width, reinterpret_cast<float4 *>(r.pv_rgba.ptr), r.pv_at.ptr) != 0) {
             PT_HIP(hipGetLastError());
             return fail(PT_ERR_HIP, "preview: gather kernel failed to launch");
@@ -650,5 +754,189 @@ extern "C" int pt_frame_preview(pt_frame *f, const float *image, const pt_denois
         PT_HIP(hipMemcpyAsync(out_samples, r0.pv_samples.ptr, n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     }
     PT_HIP(hipStreamSynchronize(st));
+    return PT_OK;
+}
+
+// ---- the noise of a frame (pt_frame_get_noise, pt_frame_set_noise_target; include/pt_frame_noise.h) -------------------------------------
+
+extern "C" int pt_frame_set_noise_target(pt_frame *f, float target_error, float floor, float fraction) {
+    if(f == nullptr) {
+        return fail(PT_ERR_INVALID, "null frame");
+    }
+    if(!std::isfinite(target_error) || target_error < 0.0f) {
+        return fail(PT_ERR_INVALID, "the target error must be finite and not negative");
+    }
+    if(!std::isfinite(floor) || floor < 0.0f) {
+        return fail(PT_ERR_INVALID, "the floor must be finite and not negative");
+    }
+    if(!(fraction > 0.0f && fraction <= 1.0f)) {
+        return fail(PT_ERR_INVALID, "the fraction must be in (0, 1]");
+    }
+    std::lock_guard<std::mutex> lock(f->mutex);
+    if(f->status != PT_OK) {
+        return fail(f->status, f->error);
+    }
+    f->noise_target = target_error;
+    f->noise_floor = floor;
+    f->noise_fraction = fraction;
+    f->target_reached = false;
+    return PT_OK;
+}
+
+// pt_frame_get_noise, step 1: every replica that has rendered rates its work list on its own device; the summaries, and the other
+// replicas' entries when a map is wanted, come to the host
+static int noise_rate(pt_frame *f, const PtNoiseRule &rule, bool want_map, std::vector<std::vector<uint32_t>> &summary, std::vector<std::vector<uint2>> &far) {
+    f->noise_rate_ms = 0.0;
+    for(size_t i = 0; i < f->reps.size(); i++) {
+        pt_frame::Replica &r = *f->reps[i];
+        if(!r.ready || r.n_todo == 0) {
+            continue;
+        }
+        pt_scene *s = r.s;
+        std::lock_guard<std::mutex> lock(s->render_mutex);
+        PT_HIP(hipSetDevice(s->device));
+        PT_HIP(r.nz_rated.ensure(r.n_todo));
+        PT_HIP(r.nz_summary.ensure(PT_NOISE_SUMMARY_WORDS));
+        Event begin, end;
+        PT_HIP(begin.create());
+        PT_HIP(end.create());
+        PT_HIP(hipEventRecord(begin.e, s->stream));
+        if(pt_launch_frame_rate(s->stream, r.d_todo[r.cur].ptr, r.n_todo, r.d_park[r.pcur].ptr, r.d_tiles.ptr, r.d_offset.ptr, static_cast<uint32_t>(r.tiles.size()),
+                                f->options.image_width, rule, r.nz_rated.ptr, r.nz_summary.ptr) != 0) {
+            PT_HIP(hipGetLastError());
+            return fail(PT_ERR_HIP, "noise: rating kernel failed to launch");
+        }
+        PT_HIP(hipEventRecord(end.e, s->stream));
+        summary[i].resize(PT_NOISE_SUMMARY_WORDS);
+        PT_HIP(hipMemcpyAsync(summary[i].data(), r.nz_summary.ptr, PT_NOISE_SUMMARY_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
+        if(want_map && i != 0) {
+            far[i].resize(r.n_todo);
+            PT_HIP(hipMemcpyAsync(far[i].data(), r.nz_rated.ptr, r.n_todo * sizeof(uint2), hipMemcpyDeviceToHost, s->stream));
+        }
+        PT_HIP(hipStreamSynchronize(s->stream));
+        float ms = 0.0f;
+        PT_HIP(hipEventElapsedTime(&ms, begin.e, end.e));
+        f->noise_rate_ms += ms;
+    }
+    return PT_OK;
+}
+
+// pt_frame_get_noise, step 2, on replica 0's device (its render_mutex held), as preview_compose: finished (-1) where a tile of a replica
+// that has rendered covers the pixel, +inf elsewhere, every replica's entries over them -- the map of n pixels in r0.nz_map
+static int noise_compose(pt_frame *f, size_t n, const std::vector<std::vector<uint2>> &far) {
+    pt_frame::Replica &r0 = *f->reps[0];
+    hipStream_t st = r0.s->stream;
+    const int32_t width = f->options.image_width;
+    r0.previewed = true; // (replica 0's device holds buffers of the frame now, whether or not the replica has rendered)
+    PT_HIP(r0.nz_map.ensure(n));
+    size_t ready = 0;
+    for(const auto &r : f->reps) {
+        ready += r->ready ? 1 : 0;
+    }
+    if(r0.nz_cover_ready != ready) {
+        std::vector<uint8_t> cover(n, 0);
+        for(const auto &r : f->reps) {
+            for(const pt_tile &t : r->tiles) {
+                for(int32_t y = t.y; r->ready && y < t.y + t.h; y++) {
+                    std::memset(cover.data() + static_cast<size_t>(y) * width + t.x, 1, static_cast<size_t>(t.w));
+                }
+            }
+        }
+        PT_HIP(r0.nz_cover.upload(cover));
+        r0.nz_cover_ready = ready;
+    }
+    if(pt_launch_frame_noise_base(st, r0.nz_map.ptr, r0.nz_cover.ptr, static_cast<uint32_t>(n)) != 0) {
+        PT_HIP(hipGetLastError());
+        return fail(PT_ERR_HIP, "noise: base kernel failed to launch");
+    }
+    for(size_t i = 0; i < f->reps.size(); i++) {
+        const pt_frame::Replica &r = *f->reps[i];
+        if(!r.ready || r.n_todo == 0) {
+            continue;
+        }
+        const uint2 *rated = r0.nz_rated.ptr;
+        if(i != 0) {
+            PT_HIP(r0.nz_stage.ensure(r.n_todo));
+            PT_HIP(hipMemcpyAsync(r0.nz_stage.ptr, far[i].data(), r.n_todo * sizeof(uint2), hipMemcpyHostToDevice, st));
+            rated = r0.nz_stage.ptr;
+        }
+        if(pt_launch_frame_noise_scatter(st, rated, r.n_todo, r0.nz_map.ptr) != 0) {
+            PT_HIP(hipGetLastError());
+            return fail(PT_ERR_HIP, "noise: scatter kernel failed to launch");
+        }
+    }
+    return PT_OK;
+}
+
+extern "C" int pt_frame_get_noise(pt_frame *f, pt_frame_noise *out, float *out_error) {
+    if(f == nullptr || out == nullptr) {
+        return fail(PT_ERR_INVALID, "null argument");
+    }
+    const size_t n = static_cast<size_t>(f->options.image_width) * static_cast<size_t>(f->rows());
+    if(n > 0x0fffffffULL) {
+        return fail(PT_ERR_INVALID, "more than 0x0fffffff pixels");
+    }
+    std::lock_guard<std::mutex> frame_lock(f->mutex);
+    if(f->status != PT_OK) {
+        return fail(f->status, f->error);
+    }
+    PtDevOptions opt;
+    PT_TRY(derive_options(&f->options, &opt));
+    std::vector<std::vector<uint32_t>> summary(f->reps.size());
+    std::vector<std::vector<uint2>> far(f->reps.size());
+    PT_TRY(noise_rate(f, f->noise_rule(opt, true), out_error != nullptr, summary, far));
+    std::memset(out, 0, sizeof(*out));
+    out->target_error = f->noise_target;
+    out->floor = f->noise_floor;
+    out->fraction = f->noise_fraction;
+    out->streams_total = f->streams_total;
+    uint32_t max_bits = 0;
+    uint64_t left = 0;
+    bool any_ready = false;
+    for(size_t i = 0; i < f->reps.size(); i++) {
+        const pt_frame::Replica &r = *f->reps[i];
+        left += r.n_todo;
+        any_ready = any_ready || r.ready;
+        if(summary[i].empty()) {
+            out->streams_unrated += r.n_todo; // (no launch yet: its streams are untouched)
+            continue;
+        }
+        out->streams_rated += summary[i][0];
+        out->streams_unrated += summary[i][1];
+        out->streams_held += summary[i][2];
+        max_bits = std::max(max_bits, summary[i][3]);
+        for(int b = 0; b < 64; b++) {
+            out->histogram[b] += summary[i][4 + b];
+        }
+    }
+    out->streams_finished = f->streams_total - left;
+    out->max_error = from_bits(max_bits);
+    out->target_reached = f->noise_target > 0.0f && static_cast<double>(out->streams_finished + out->streams_held) >=
+                                                       static_cast<double>(f->noise_fraction) * static_cast<double>(f->streams_total)
+                            ? 1
+                            : 0;
+    if(out_error == nullptr) {
+        return PT_OK;
+    }
+    if(!any_ready) {
+        std::fill(out_error, out_error + n, std::numeric_limits<float>::infinity()); // (before the first pt_frame_render every pixel is untouched)
+        return PT_OK;
+    }
+    pt_scene *s0 = f->reps[0]->s;
+    std::lock_guard<std::mutex> lock(s0->render_mutex);
+    PT_HIP(hipSetDevice(s0->device));
+    PT_TRY(noise_compose(f, n, far));
+    PT_HIP(hipMemcpyAsync(out_error, f->reps[0]->nz_map.ptr, n * sizeof(float), hipMemcpyDeviceToHost, s0->stream));
+    PT_HIP(hipStreamSynchronize(s0->stream));
+    return PT_OK;
+}
+
+// diagnostic (tools/noise_probe.py): the device time of the rating kernels of the frame's last pt_frame_get_noise, all replicas
+extern "C" int pt_debug_frame_noise_ms(pt_frame *f, double *out_ms) {
+    if(f == nullptr || out_ms == nullptr) {
+        return fail(PT_ERR_INVALID, "null argument");
+    }
+    std::lock_guard<std::mutex> lock(f->mutex);
+    *out_ms = f->noise_rate_ms;
     return PT_OK;
 }

@@ -152,7 +152,7 @@ struct PtPathArgs {
 void pt_launch_path(hipStream_t stream, const PtDevScene &scene, const PtDevCamera &camera, const PtDevOptions &options, PtSlots slots, PtStreams streams,
                     PtLocalQueue queue, const PtPathConfig &cfg, float4 *image, PtDevCounters *counters, PtPathArgs *host_args, PtPathArgs *d_args);
 // the work list of a resumable frame's next launch (pt_frame.hip): the streams of `todo` that `status` does not call finished, parked ones
-// first, each part in the order of `todo` (block_counts: [2 * ceil(n / 1024)]).  result[0..4] = parked streams, untouched ones, untouched ones
+// first, each part in the order of `todo`.  result[0..4] = parked streams, untouched ones, untouched ones
 // whose earlier record went unused (such a stream starts afresh), samples the streams of the list carry, streams with closed candidates;
 // result[5] = 0xffffffff - the least sample count of an unfinished pixel, [6] = the greatest, [7] = streams that have a record, [8] = records
 // the launch wrote (result: 16 words).
@@ -160,9 +160,26 @@ void pt_launch_path(hipStream_t stream, const PtDevScene &scene, const PtDevCame
 // (result[1]) instead, every stream keeps its record, and those the launch never claimed are copied from park_in (the launch's input
 // records) into park_out behind the park_count records the launch wrote (park_cap: room for every entry); result[2] stays 0 and result[9]
 // counts samples of records that found no room (0 with that room).  target <= 0: park_in, park_out, park_count are not used.
-// Returns 0, or 1 when a launch failed.
+// noise.target > 0 (a progressive frame with a noise target, pt_frame_set_noise_target): a third part behind those two, the HELD streams
+// (result[10]): those with a record whose pixel_error (pt_noise.h) is at or below noise.target.  resort != 0: nothing was launched (every
+// status is untouched) and the list is only split again -- no record moves, park_in stays the frame's records, park_out is not used.
+// block_counts: [3 * ceil(n / 1024)].  Returns 0, or 1 when a launch failed.
+struct PtNoiseRule {
+    PtDevOptions opt; // (its stats_sample_count: the samples of a batch mean)
+    float target;     // 0 = none: nothing is held
+    float floor;
+};
 int pt_launch_frame_compact(hipStream_t stream, const uint2 *todo, uint32_t n, uint32_t *status, const PtParkRecord *parked, uint2 *todo_out, uint32_t *block_counts,
-                            unsigned long long *result, int32_t target, const PtParkRecord *park_in, PtParkRecord *park_out, uint32_t *park_count, uint32_t park_cap);
+                            unsigned long long *result, int32_t target, const PtParkRecord *park_in, PtParkRecord *park_out, uint32_t *park_count, uint32_t park_cap,
+                            const PtNoiseRule &noise, int resort);
+// The rating of a frame (pt_frame.hip; pt_frame_get_noise).  rate: out[i] = (pixel, bits of pixel_error) per entry of a replica's work list
+// and the summary of PT_NOISE_SUMMARY_WORDS words (zeroed first): rated, unrated, held entries, bits of the largest error, 64 bins by
+// exponent.  base: the map of replica 0's device, -1 where cover[p] != 0, else +inf.  scatter: n entries into the map.
+#define PT_NOISE_SUMMARY_WORDS 68
+int pt_launch_frame_rate(hipStream_t stream, const uint2 *todo, uint32_t n, const PtParkRecord *park, const int4 *tiles, const uint32_t *tile_offset, uint32_t n_tiles,
+                         int32_t width, const PtNoiseRule &noise, uint2 *out, uint32_t *summary);
+int pt_launch_frame_noise_base(hipStream_t stream, float *map, const uint8_t *cover, uint32_t n_pixels);
+int pt_launch_frame_noise_scatter(hipStream_t stream, const uint2 *rated, uint32_t n, float *map);
 // The preview of a frame (pt_frame.hip; pt_frame_preview).  gather: one compact entry per entry of a replica's work list todo[0 .. n), those
 // that name a record (the first n_parked of a plain frame) parked in `park` -- out_rgba the running mean (0 for an untouched stream), out_at (y * width + x, samples taken).  base: the
 // view of replica 0's device, which holds the caller's image: samples -1 where cover[p] != 0, else a hole (0, 0, 0, 0) with 0 samples.

@@ -40,6 +40,16 @@ public:
     // std::invalid_argument for a negative quantum.  progress(): passes completed, the target, the sample counts of the unfinished pixels.
     void setProgressive(int quantum, int max_passes_per_call = 0);
     pt_frame_progress progress() const;
+    // A noise target (pt_frame_set_noise_target, include/pt_frame_noise.h): every unfinished pixel is rated by the standard error of its
+    // mean, and a progressive frame holds the pixels rated at or below `target` out of its passes; render() returns (not complete) once
+    // finished + held pixels are `fraction` of the frame, and noiseTargetReached() is true then.  target 0 clears it: render on, and the
+    // finished image is what it always is.  floor keeps dark pixels from dominating (the reference's own is 1E-5).  Throws
+    // std::invalid_argument for a negative or non-finite target or floor or a fraction outside (0, 1].  noise(): the summary of the frame as
+    // it stands; errorMap(): one rating per pixel, row-major -- -1 finished, +inf unrated or untouched.
+    void setNoiseTarget(float target, float floor = 1E-5f, float fraction = 1.0f);
+    pt_frame_noise noise() const;
+    std::vector<float> errorMap() const;
+    bool noiseTargetReached() const;
     // The frame as it stands, for a viewer between two render() calls (pt_frame_preview): finished pixels as image(), parked ones the
     // running mean of their samples so far, untouched ones (0, 0, 0, 0).  `samples` (if not null) gets one count per pixel, row-major:
     // -1 finished, the samples taken of a parked pixel, 0 untouched.  With `denoise` the preview is filtered as pt_denoise filters a frame,

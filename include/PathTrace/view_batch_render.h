@@ -41,6 +41,16 @@ public:
     // std::invalid_argument for a negative quantum.  progress(): passes completed, the target, the sample counts of the unfinished pixels.
     void setProgressive(int quantum, int max_passes_per_call = 0);
     pt_frame_progress progress() const;
+    // A noise target (pt_frame_set_noise_target, include/pt_frame_noise.h): every unfinished pixel is rated by the standard error of its
+    // mean, and a progressive frame holds the pixels rated at or below `target` out of its passes; render() returns (not complete) once
+    // finished + held pixels are `fraction` of the frame, and noiseTargetReached() is true then.  target 0 clears it: render on, and the
+    // finished image is what it always is.  floor keeps dark pixels from dominating (the reference's own is 1E-5).  Throws
+    // std::invalid_argument for a negative or non-finite target or floor or a fraction outside (0, 1].  noise(): the summary of the frame as
+    // it stands; errorMap(): one rating per pixel, [view][y][x] -- -1 finished, +inf unrated or untouched.
+    void setNoiseTarget(float target, float floor = 1E-5f, float fraction = 1.0f);
+    pt_frame_noise noise() const;
+    std::vector<float> errorMap() const;
+    bool noiseTargetReached() const;
     // As FrameRender::preview, per view: `out` gets one image per view, `samples` (if not null) one count per pixel, [view][y][x].  With
     // `denoise` a hole is filled from pixels of its own view only.
     void preview(std::vector<Image<>> &out, std::vector<std::int32_t> *samples = nullptr, const pt_denoise_params *denoise = nullptr) const;

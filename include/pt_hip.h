@@ -324,6 +324,10 @@ int pt_frame_get_progress(const pt_frame *frame, pt_frame_progress *out);
 /* (the info of a frame: `pt_frame_info` names the struct, so the function is pt_frame_get_info) */
 int pt_frame_get_info(const pt_frame *frame, pt_frame_info *info);
 int pt_frame_destroy(pt_frame *frame);
+/* The noise of a frame and its noise target: every unfinished pixel rated by the standard error of its mean, a summary and a map of the
+ * ratings, and a progressive frame that holds the pixels at or below a target and stops once enough of them are.  The
+ * struct pt_frame_noise and the two entry points that take it and set the target are declared, with their contracts, in: */
+#include "pt_frame_noise.h"
 
 /* The tile list processJob builds (worker.cpp:398-414): tile_size = clamp(min(w, h) / 4, 1, 32), row-major, edge tiles clipped.
  * Returns the tile count; fills at most `capacity` entries. */

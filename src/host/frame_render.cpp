@@ -5,6 +5,7 @@
 #include "job_params.h"
 
 #include <algorithm>
+#include <cmath>
 #include <exception>
 #include <stdexcept>
 #include <vector>
@@ -83,6 +84,36 @@ pt_frame_progress FrameRender::progress() const {
         check(pt_frame_get_progress(frame_, &p), "FrameRender::progress");
     }
     return p;
+}
+
+void FrameRender::setNoiseTarget(float target, float floor, float fraction) {
+    if(!std::isfinite(target) || target < 0.0f || !std::isfinite(floor) || floor < 0.0f || !(fraction > 0.0f && fraction <= 1.0f)) {
+        throw std::invalid_argument("FrameRender::setNoiseTarget: target and floor must be finite and not negative, fraction in (0, 1]");
+    }
+    if(frame_ != nullptr) {
+        check(pt_frame_set_noise_target(frame_, target, floor, fraction), "FrameRender::setNoiseTarget");
+    }
+}
+
+pt_frame_noise FrameRender::noise() const {
+    pt_frame_noise n{};
+    if(frame_ != nullptr) {
+        check(pt_frame_get_noise(frame_, &n, nullptr), "FrameRender::noise");
+    }
+    return n;
+}
+
+std::vector<float> FrameRender::errorMap() const {
+    std::vector<float> map(static_cast<size_t>(image_.getWidth()) * static_cast<size_t>(image_.getHeight()), -1.0f); // (a frame without pixels to render is finished)
+    if(frame_ != nullptr) {
+        pt_frame_noise n{};
+        check(pt_frame_get_noise(frame_, &n, map.data()), "FrameRender::errorMap");
+    }
+    return map;
+}
+
+bool FrameRender::noiseTargetReached() const {
+    return noise().target_reached != 0;
 }
 
 void FrameRender::preview(Image<> &out, std::vector<std::int32_t> *samples, const pt_denoise_params *denoise) const {

@@ -5,6 +5,7 @@
 #include "job_params.h"
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <exception>
 #include <stdexcept>
@@ -124,6 +125,36 @@ pt_frame_progress ViewBatchRender::progress() const {
         check(pt_frame_get_progress(frame_, &p), "ViewBatchRender::progress");
     }
     return p;
+}
+
+void ViewBatchRender::setNoiseTarget(float target, float floor, float fraction) {
+    if(!std::isfinite(target) || target < 0.0f || !std::isfinite(floor) || floor < 0.0f || !(fraction > 0.0f && fraction <= 1.0f)) {
+        throw std::invalid_argument("ViewBatchRender::setNoiseTarget: target and floor must be finite and not negative, fraction in (0, 1]");
+    }
+    if(frame_ != nullptr) {
+        check(pt_frame_set_noise_target(frame_, target, floor, fraction), "ViewBatchRender::setNoiseTarget");
+    }
+}
+
+pt_frame_noise ViewBatchRender::noise() const {
+    pt_frame_noise n{};
+    if(frame_ != nullptr) {
+        check(pt_frame_get_noise(frame_, &n, nullptr), "ViewBatchRender::noise");
+    }
+    return n;
+}
+
+std::vector<float> ViewBatchRender::errorMap() const {
+    std::vector<float> map(static_cast<size_t>(width_) * static_cast<size_t>(height_) * seeds_.size(), -1.0f); // (a frame without pixels to render is finished)
+    if(frame_ != nullptr) {
+        pt_frame_noise n{};
+        check(pt_frame_get_noise(frame_, &n, map.data()), "ViewBatchRender::errorMap");
+    }
+    return map;
+}
+
+bool ViewBatchRender::noiseTargetReached() const {
+    return noise().target_reached != 0;
 }
 
 void ViewBatchRender::preview(std::vector<Image<>> &out, std::vector<std::int32_t> *samples, const pt_denoise_params *denoise) const {
