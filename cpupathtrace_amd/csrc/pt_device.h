@@ -167,6 +167,24 @@ PT_D float slab_test(V3 lo, V3 hi, V3 o, V3 inv) {
     return t;
 }
 
+// slab test of the device walk: bounding_box.cpp:38-73 with std::min/std::max replaced by v_min_f32/v_max_f32.
+// The two differ only for NaN operands (the reference asserts there are none, bounding_box.cpp:60-61) and in the sign of a
+// zero result, and every use of the returned distance is an ordered comparison, for which -0 and +0 are the same value.
+PT_D float slab_walk(V3 lo, V3 hi, V3 o, V3 inv) {
+    const float t1 = (lo.x - o.x) * inv.x;
+    const float t2 = (hi.x - o.x) * inv.x;
+    const float t3 = (lo.y - o.y) * inv.y;
+    const float t4 = (hi.y - o.y) * inv.y;
+    const float t5 = (lo.z - o.z) * inv.z;
+    const float t6 = (hi.z - o.z) * inv.z;
+    const float t_min = __builtin_fmaxf(__builtin_fmaxf(__builtin_fminf(t1, t2), __builtin_fminf(t3, t4)), __builtin_fminf(t5, t6));
+    const float t_max = __builtin_fminf(__builtin_fminf(__builtin_fmaxf(t1, t2), __builtin_fmaxf(t3, t4)), __builtin_fmaxf(t5, t6));
+    if(t_max < 0.0f || t_min > t_max) {
+        return -1.0f;
+    }
+    return t_min < 0.0f ? 0.0f : t_min; // origin inside: t_min < 0 <= t_max (bounding_box.cpp:68-70)
+}
+
 // ---- a-6: Triangle::getIntersection, src/scene/object.cpp:146-182 -------------------------------------------------------
 
 PT_D float tri_intersect(V3 a, V3 ab, V3 ac, bool cull, V3 o, V3 d) {
