@@ -76,13 +76,15 @@ __device__ __forceinline__ float normal_weight(float4 gp, float4 gq, float sigma
     return powf(fmaxf(0.0f, d), sigma_normal);
 }
 
-// |t_p - t_q| over the depth change the gradient predicts for the offset, floored relative to t_p (0 when the term is off)
+// |t_p - t_q| over the depth change the gradient predicts for the offset, floored relative to t_p (0 when the term is off, and 0 for
+// equal distances whatever the scale: at t_p = 0 on a flat gradient the scale is 0, and 0 / 0 would make every weight NaN)
 __device__ __forceinline__ float depth_arg(float tp, float tq, float2 g, float ox, float oy, float sigma_depth) {
     if(sigma_depth == 0.0f) {
         return 0.0f;
     }
     const float scale = sigma_depth * (fabsf(g.x * ox + g.y * oy) + kDepthRel * tp);
-    return fabsf(tp - tq) / scale;
+    const float d = fabsf(tp - tq);
+    return d == 0.0f ? 0.0f : d / scale;
 }
 
 // kMasked: `samples` (the preview's sample counts) marks the holes, 0; a hole's colour is 0 whatever the input holds.
@@ -189,7 +191,7 @@ __global__ __launch_bounds__(256) void pt_denoise_variance_kernel(const float4 *
                 w = normal_weight(gp, gq, sigma_normal) * expf(-depth_arg(gp.w, gq.w, gr, (float)dx, (float)dy, sigma_depth));
             }
             else {
-                w = 0.0f;
+                continue; // (a zero weight: adds nothing, whatever the tap holds)
             }
             sw = sw + w;
             m1 = m1 + w * lq;

@@ -2,6 +2,10 @@
 filter is checked against.  Every array operation is the fp32 operation the kernels perform, in the same order; only expf, powf and the
 per-tap accumulation order of numpy's vectorised passes (the same order as the kernel's loops) are shared, so the two agree to a few ulp.
 
+Non-finite values: the kernels' fmaxf returns the operand that is no NaN, so the three places that use it (the normal
+weight, the albedo floor, the variance clamp) are np.fmax here; and a tap whose weight is zero by class or image bounds is not read, so
+it adds nothing whatever it holds.
+
 Inputs: rgba (H, W, 4) and features (H, W, 3, 4) as pt_render_features writes them:
   F0 = (albedo rgb, coverage), F1 = (normal xyz, mean t), F2 = (position xyz, luminance of the mean emission).
 """
@@ -47,7 +51,7 @@ def prepare(rgba, features):
     emissive = f2[..., 3] > 0
     cls = np.where(covered, CLS_COVERED, 0) | np.where(emissive, CLS_EMISSIVE, 0)
     demod = covered & ~emissive
-    factor = np.where(demod[..., None], np.maximum(f0[..., :3], ALBEDO_MIN), F(1.0)).astype(F)
+    factor = np.where(demod[..., None], np.fmax(f0[..., :3], ALBEDO_MIN), F(1.0)).astype(F)
     c = np.where(demod[..., None], rgba[..., :3] / factor, rgba[..., :3]).astype(F)
     return c, lum(c).astype(F), f1.copy(), cls.astype(np.int32), factor
 
@@ -56,13 +60,14 @@ def _depth_arg(t_p, t_q, gx, gy, ox, oy, sigma_depth):
     if sigma_depth == 0:
         return np.zeros_like(t_p)
     scale = F(sigma_depth) * (np.abs(gx * F(ox) + gy * F(oy)) + DEPTH_REL * t_p)
+    d = np.abs(t_p - t_q)
     with np.errstate(divide="ignore", invalid="ignore"):
-        return np.abs(t_p - t_q) / scale
+        return np.where(d == 0, F(0.0), d / scale).astype(F)  # (equal distances: 0 whatever the scale, also a scale of 0)
 
 
 def _normal_w(g_p, g_q, sigma_normal):
     d = (g_p[..., 0] * g_q[..., 0] + g_p[..., 1] * g_q[..., 1]) + g_p[..., 2] * g_q[..., 2]
-    return np.power(np.maximum(F(0.0), d), F(sigma_normal)).astype(F)
+    return np.power(np.fmax(F(0.0), d), F(sigma_normal)).astype(F)
 
 
 def gradient(guide, cls):
@@ -100,11 +105,14 @@ def variance(l, guide, cls, gx, gy, sigma_normal, sigma_depth):
                 with np.errstate(invalid="ignore", over="ignore"):
                     w = _normal_w(guide, gq, sigma_normal) * np.exp(-_depth_arg(t, gq[..., 3], gx, gy, dx, dy, sigma_depth)).astype(F)
                 w = np.where(ok, w, F(0.0)).astype(F)
+                lq = np.where(ok, lq, F(0.0))  # (a tap of weight zero by class or bounds is not read)
             sw = sw + w
-            m1 = m1 + w * lq
-            m2 = m2 + w * (lq * lq)
-    mean = m1 / sw
-    return np.maximum(F(0.0), m2 / sw - mean * mean).astype(F)
+            with np.errstate(invalid="ignore", over="ignore"):
+                m1 = m1 + w * lq
+                m2 = m2 + w * (lq * lq)
+    with np.errstate(invalid="ignore", over="ignore"):
+        mean = m1 / sw
+        return np.fmax(F(0.0), m2 / sw - mean * mean).astype(F)
 
 
 def atrous(c, l, var, guide, cls, gx, gy, step, sigma_luminance, sigma_normal, sigma_depth):
@@ -120,8 +128,9 @@ def atrous(c, l, var, guide, cls, gx, gy, step, sigma_luminance, sigma_normal, s
             k = np.where(m, G3[dy + 1] * G3[dx + 1], F(0.0)).astype(F)
             g = g + k * vq
             gs = gs + k
-    g = g / gs
-    lum_scale = F(sigma_luminance) * np.sqrt(g) + LUM_EPS
+    with np.errstate(invalid="ignore", over="ignore"):
+        g = g / gs
+        lum_scale = F(sigma_luminance) * np.sqrt(g) + LUM_EPS
     sw = np.zeros_like(var)
     sc = np.zeros_like(c)
     sv = np.zeros_like(var)
@@ -144,11 +153,15 @@ def atrous(c, l, var, guide, cls, gx, gy, step, sigma_luminance, sigma_normal, s
                         a = a + np.abs(l - lq) / lum_scale
                     w = (h * _normal_w(guide, gq, sigma_normal)) * np.exp(-a).astype(F)
                 w = np.where(ok, w, F(0.0)).astype(F)
-            sw = sw + w
-            sc = sc + w[..., None] * cq
-            sv = sv + (w * w) * vq
-    c_out = (sc / sw[..., None]).astype(F)
-    v_out = (sv / (sw * sw)).astype(F)
+                cq = np.where(ok[..., None], cq, F(0.0))  # (a tap of weight zero by class or bounds is not read)
+                vq = np.where(ok, vq, F(0.0))
+            with np.errstate(invalid="ignore", over="ignore"):
+                sw = sw + w
+                sc = sc + w[..., None] * cq
+                sv = sv + (w * w) * vq
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        c_out = (sc / sw[..., None]).astype(F)
+        v_out = (sv / (sw * sw)).astype(F)
     c_out = np.where(covered[..., None], c_out, c)
     v_out = np.where(covered, v_out, var)
     return c_out, lum(c_out).astype(F), v_out

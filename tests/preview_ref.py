@@ -107,13 +107,17 @@ def atrous(c, l, var, guide, cls, gx, gy, step, sigma_luminance, sigma_normal, s
                     nw = dr._normal_w(guide, gq, sigma_normal)
                     w = (h * nw) * np.exp(-a).astype(F)
                     wh = np.where(covered, (h * nw) * np.exp(-d).astype(F), h).astype(F)
+                okh = m & hole & (clq == (cls & ~CLS_HOLE))
                 w = np.where(ok, w, F(0.0)).astype(F)
-                wh = np.where(m & hole & (clq == (cls & ~CLS_HOLE)), wh, F(0.0)).astype(F)
-            sw = sw + w
-            sc = sc + w[..., None] * cq
-            sv = sv + (w * w) * vq
-            hw = hw + wh
-            hc = hc + wh[..., None] * cq
+                wh = np.where(okh, wh, F(0.0)).astype(F)
+                cq = np.where((ok | okh)[..., None], cq, F(0.0))  # (a tap of weight zero by class or bounds is not read)
+                vq = np.where(ok, vq, F(0.0))
+            with np.errstate(invalid="ignore", over="ignore"):
+                sw = sw + w
+                sc = sc + w[..., None] * cq
+                sv = sv + (w * w) * vq
+                hw = hw + wh
+                hc = hc + wh[..., None] * cq
     with np.errstate(divide="ignore", invalid="ignore"):
         c_out = (sc / sw[..., None]).astype(F)
         v_out = (sv / (sw * sw)).astype(F)

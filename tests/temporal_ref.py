@@ -190,8 +190,8 @@ def accumulate(c, l, cls, features, cam, prev, p):
     if blend.any():
         with np.errstate(divide="ignore", invalid="ignore"):
             inv_n = (F(1.0) / n.astype(F)).astype(F)
-            ac = np.maximum(inv_n, F(p["alpha_color"]))[..., None]
-            am = np.maximum(inv_n, F(p["alpha_moments"]))[..., None]
+            ac = np.fmax(inv_n, F(p["alpha_color"]))[..., None]
+            am = np.fmax(inv_n, F(p["alpha_moments"]))[..., None]
             hc = sc / sw[..., None]
             hm = sm / sw[..., None]
             bc = ((F(1.0) - ac) * hc + ac * c).astype(F)
@@ -211,7 +211,7 @@ def push(state, rgba, features, cam, p=None):
     gx, gy = dr.gradient(guide, cls)
     var = dr.variance(l, guide, cls, gx, gy, sp["sigma_normal"], sp["sigma_depth"])
     temporal = (n >= p["moments_min_history"]) & (n >= 2)
-    var = np.where(temporal, np.maximum(F(0.0), mom[..., 1] - mom[..., 0] * mom[..., 0]), var).astype(F)
+    var = np.where(temporal, np.fmax(F(0.0), mom[..., 1] - mom[..., 0] * mom[..., 0]), var).astype(F)
     hist = col
     for i in range(sp["iterations"]):
         # each pixel's output depends on its own sigma only: the spatial and the temporal pass, chosen per pixel
