@@ -50,6 +50,8 @@ TEMPORAL_EXPORTS = ["pt_temporal_params_default", "pt_temporal_create", "pt_temp
 EXPORTS += TEMPORAL_EXPORTS
 # (EXPORTS is what include/pt_hip.h itself declares; these two are declared in include/pt_frame_noise.h, which it includes)
 NOISE_EXPORTS = ["pt_frame_get_noise", "pt_frame_set_noise_target"]
+# (... and these in include/pt_frame_variance.h)
+VARIANCE_EXPORTS = ["pt_denoise_measured_params_default", "pt_frame_get_variance", "pt_denoise_measured", "pt_denoise_measured_device", "pt_frame_preview_measured"]
 
 
 
@@ -138,6 +140,67 @@ def denoise_views_device(d_rgba_ptr, d_features_ptr, width, height, n_views, d_o
     """pt_denoise_views_device on device memory: as denoise_device, every array holding n_views frames."""
     _check(load().pt_denoise_views_device(C.c_int(device), C.c_void_p(d_rgba_ptr), C.c_void_p(d_features_ptr), C.c_int32(width), C.c_int32(height),
                                           C.c_int32(n_views), _denoise_params(params), C.c_void_p(d_out_ptr), C.c_void_p(stream_ptr)))
+
+
+class DenoiseMeasuredParams(C.Structure):
+    """pt_denoise_measured_params: DenoiseParams and the luminance sigma of the pixels whose variance is measured."""
+    _fields_ = [("base", DenoiseParams), ("sigma_measured", C.c_float)]
+
+    def as_dict(self):
+        d = self.base.as_dict()
+        d["sigma_measured"] = self.sigma_measured
+        return d
+
+
+def denoise_measured_params_default():
+    """The library's default parameters of the measured form (pt_denoise_measured_params_default) as a flat dict: DenoiseParams' fields
+    and sigma_measured."""
+    p = DenoiseMeasuredParams()
+    _check(load().pt_denoise_measured_params_default(C.byref(p)))
+    return p.as_dict()
+
+
+def _denoise_measured_params(params):
+    """None = the library's defaults (a NULL pointer); otherwise a flat dict whose missing keys take the defaults."""
+    if params is None:
+        return None
+    unknown = set(params) - {k for k, _ in DenoiseParams._fields_} - {"sigma_measured"}
+    if unknown:
+        raise ValueError("unknown denoise parameters: %s" % ", ".join(sorted(unknown)))
+    p = DenoiseMeasuredParams()
+    _check(load().pt_denoise_measured_params_default(C.byref(p)))
+    for k, v in params.items():
+        setattr(p if k == "sigma_measured" else p.base, k, v)
+    return C.byref(p)
+
+
+def denoise_measured(image, features, variance, mask=None, params=None, device=0):
+    """denoise with a plane of measured variances (pt_denoise_measured): variance (h, w, 4) float32 as Frame.variance() gives it -- the
+    variance of the mean of r, g, b and the batch means B; a pixel with B >= 2 filters with that variance and sigma_measured, the others as
+    denoise does.  mask: None, or (h, w) int32 sample counts whose zeros are holes, as Frame.preview's.  Returns a new array."""
+    img = np.ascontiguousarray(image, dtype=np.float32)
+    feat = np.ascontiguousarray(features, dtype=np.float32)
+    var = np.ascontiguousarray(variance, dtype=np.float32)
+    if img.ndim != 3 or img.shape[2] != 4 or feat.shape != img.shape[:2] + (3, 4) or var.shape != img.shape:
+        raise ValueError("image and variance must be (h, w, 4) and features (h, w, 3, 4)")
+    m = None
+    if mask is not None:
+        m = np.ascontiguousarray(mask, dtype=np.int32)
+        if m.shape != img.shape[:2]:
+            raise ValueError("mask must be (h, w)")
+    out = np.empty_like(img)
+    h, w = img.shape[:2]
+    _check(load().pt_denoise_measured(C.c_int(device), _ptr(img), _ptr(feat), _ptr(var), _ptr(m), C.c_int32(w), C.c_int32(h), _denoise_measured_params(params),
+                                      _ptr(out)))
+    return out
+
+
+def denoise_measured_device(d_rgba_ptr, d_features_ptr, d_variance_ptr, width, height, d_out_ptr, d_mask_ptr=0, stream_ptr=0, params=None, device=0):
+    """pt_denoise_measured_device on device memory: as denoise_device, with the variance plane (width*height*4 floats) and an optional mask
+    (width*height int32, 0 = none)."""
+    _check(load().pt_denoise_measured_device(C.c_int(device), C.c_void_p(d_rgba_ptr), C.c_void_p(d_features_ptr), C.c_void_p(d_variance_ptr),
+                                             C.c_void_p(d_mask_ptr or None), C.c_int32(width), C.c_int32(height), _denoise_measured_params(params),
+                                             C.c_void_p(d_out_ptr), C.c_void_p(stream_ptr)))
 
 
 class TemporalParams(C.Structure):
@@ -733,6 +796,26 @@ class Frame:
         samples = np.empty(self.image.shape[:2], np.int32)
         params = None if denoise is None or denoise is False else _denoise_params({} if denoise is True else denoise)
         _check(load().pt_frame_preview(self._h, _ptr(self.image), params, _ptr(rgba), _ptr(samples)))
+        return rgba, samples
+
+    def variance(self):
+        """The measured variance of the unfinished pixels (pt_frame_get_variance): float32 in the shape of self.image -- the variance of the
+        mean of r, g, b from the estimator's batch statistics and the batch means B, (0, 0, 0, 0) for a pixel that is finished, untouched,
+        in no tile or has B < 2."""
+        if self._h is None:
+            raise ValueError("frame is closed")
+        var = np.empty_like(self.image)
+        _check(load().pt_frame_get_variance(self._h, _ptr(var)))
+        return var
+
+    def preview_measured(self, params=None):
+        """preview(denoise=...) with each rated pixel's measured variance in place of the filter's 3x3 estimate (pt_frame_preview_measured):
+        (rgba, samples).  params: None = defaults, or a flat dict of DenoiseParams fields and sigma_measured.  Not for a ViewsFrame."""
+        if self._h is None:
+            raise ValueError("frame is closed")
+        rgba = np.empty_like(self.image)
+        samples = np.empty(self.image.shape[:-1], np.int32)
+        _check(load().pt_frame_preview_measured(self._h, _ptr(self.image), _denoise_measured_params(params), _ptr(rgba), _ptr(samples)))
         return rgba, samples
 
     @property

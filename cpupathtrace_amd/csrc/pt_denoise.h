@@ -37,6 +37,14 @@ hipError_t pt_denoise_masked_run(hipStream_t stream, const float4 *rgba, const f
 hipError_t pt_denoise_views_run(hipStream_t stream, const float4 *rgba, const float4 *features, const int32_t *samples, int32_t width, int32_t height,
                                 int32_t n_views, const PtDenoiseParams &params, const PtDenoiseScratch &scratch, float4 *out);
 
+// pt_denoise_run (samples == nullptr) or pt_denoise_masked_run with a plane of measured variances, `variance`: width * height float4
+// (v_r, v_g, v_b, B), the variance of the mean of every channel of `rgba` and the batch means behind it (pt_frame_get_variance).  Where
+// B >= 2 and every v_c is finite and not negative, the variance stage writes (0.2126 s_r + 0.7152 s_g + 0.0722 s_b)^2 with
+// s_c = sqrtf(v_c) / max(albedo_c, 0.01) on the pixels prepare demodulates, sqrtf(v_c) elsewhere, in place of its 3x3 estimate, and the
+// pixel's luminance sigma is sigma_measured.  A plane that rates no pixel gives the other run's result bit for bit.  `out` may equal rgba.
+hipError_t pt_denoise_measured_run(hipStream_t stream, const float4 *rgba, const float4 *features, const float4 *variance, const int32_t *samples, int32_t width,
+                                   int32_t height, const PtDenoiseParams &params, float sigma_measured, const PtDenoiseScratch &scratch, float4 *out);
+
 // ---- the temporal form (pt_temporal_*): one push of a frame of a sequence ----------------------------------------------------------
 
 struct PtTemporalParams {

@@ -25,6 +25,12 @@
 // anything is read.  From there on the kernel is the single frame's, bounds tests included, so no tap crosses a view border and view v is
 // bit for bit what the single-frame run gives on view v alone.  kViews is a template parameter: the single-frame instantiations are untouched.
 //
+// pt_denoise_measured_run, the preview of a frame with its own measured variance (pt_denoise_measured, pt_frame_preview_measured; DESIGN.md
+// 4.16; tests/denoise_measured_ref.py), runs the plain or the kMasked stages in their kMeasured form: a plane of (v_r, v_g, v_b, B) per pixel
+// gives the variance of the mean of every pixel it rates (B >= 2), which replaces the 3x3 estimate there, and such a pixel filters with
+// sigma_measured.  kMeasured is a parameter of the stage functions: the other kernels instantiate them without it, and with a plane
+// that rates no pixel the kMeasured kernels compute what those do, operation for operation.
+//
 // One thread per pixel in 16 x 16 workgroups, float4 loads, fp32, no atomics: the result does not depend on the launch.  Every tap is
 // read from global memory (L1/L2 serve the overlap of neighbouring workgroups); no tile is staged in LDS.
 #include "pt_denoise.h"
@@ -55,6 +61,19 @@ struct PtTemporalPixel {
 __device__ __forceinline__ bool temporal_variance_px(const PtTemporalPixel &tp, int p) {
     const int32_t n = tp.len[p];
     return n >= tp.min_history && n >= 2;
+}
+
+// What the measured form (pt_denoise_measured_run) adds to the variance and a-trous stages; unused (null) in every other instantiation.
+struct PtMeasuredPixel {
+    const float4 *plane;   // per pixel (v_r, v_g, v_b, B): the measured variance of the pixel's mean and its batch means (pt_frame_get_variance)
+    const float4 *feat;    // the frame's features: the albedo prepare divided by
+    float sigma_measured;  // the luminance sigma of a rated pixel
+};
+
+// the pixel's variance is the measured one: two batch means and more, every v_c finite and not negative (false for NaN)
+__device__ __forceinline__ bool measured_variance_px(float4 m) {
+    const float top = 3.402823466e+38f;
+    return m.w >= 2.0f && m.x >= 0.0f && m.x <= top && m.y >= 0.0f && m.y <= top && m.z >= 0.0f && m.z <= top;
 }
 
 // kViews: the first pixel of the workgroup's view in the stacked arrays
@@ -132,10 +151,13 @@ __global__ __launch_bounds__(256) void pt_denoise_prepare_kernel(const float4 *_
 // kTemporal (pt_temporal_run): where the pixel's history is long enough (temporal_variance_px), its variance is that of the integrated
 // luminance moments instead; the spatial estimate is computed as in pt_denoise either way.
 // kMasked: a hole's variance is 0 (not filled yet); its gradient is computed as any pixel's (over neighbours of its class: holes).
-template<bool kTemporal, bool kMasked, bool kViews = false>
-__global__ __launch_bounds__(256) void pt_denoise_variance_kernel(const float4 *__restrict__ col, const float4 *__restrict__ guide, const uint32_t *__restrict__ cls,
-                                                                  int32_t width, int32_t height, float sigma_normal, float sigma_depth, float2 *__restrict__ grad,
-                                                                  float *__restrict__ var, PtTemporalPixel tp) {
+// kMeasured (pt_denoise_measured_run): where the plane rates the pixel (measured_variance_px), its variance is the measured one instead:
+// the standard deviation of every channel's mean in the unit of c (over the albedo floor prepare divided by, on the pixels it divided),
+// their luminance -- the channels taken as fully correlated, DESIGN.md 4.16 -- squared.  The spatial estimate is computed either way.
+template<bool kTemporal, bool kMasked, bool kViews, bool kMeasured>
+__device__ __forceinline__ void denoise_variance_stage(const float4 *__restrict__ col, const float4 *__restrict__ guide, const uint32_t *__restrict__ cls,
+                                                       int32_t width, int32_t height, float sigma_normal, float sigma_depth, float2 *__restrict__ grad,
+                                                       float *__restrict__ var, const PtTemporalPixel &tp, const PtMeasuredPixel &mp) {
     const int x = blockIdx.x * 16 + threadIdx.x, y = blockIdx.y * 16 + threadIdx.y;
     if(x >= width || y >= height) {
         return;
@@ -206,16 +228,46 @@ __global__ __launch_bounds__(256) void pt_denoise_variance_kernel(const float4 *
             v = fmaxf(0.0f, m.y - m.x * m.x);
         }
     }
+    if constexpr(kMeasured) {
+        const float4 m = mp.plane[p];
+        if(measured_variance_px(m)) {
+            float sr = sqrtf(m.x), sg = sqrtf(m.y), sb = sqrtf(m.z);
+            if((cp & PTDN_COVERED) && !(cp & PTDN_EMISSIVE)) {
+                const float4 f0 = mp.feat[3 * p];
+                sr = sr / fmaxf(f0.x, kAlbedoMin);
+                sg = sg / fmaxf(f0.y, kAlbedoMin);
+                sb = sb / fmaxf(f0.z, kAlbedoMin);
+            }
+            const float s = lum_of(sr, sg, sb);
+            v = s * s;
+        }
+    }
     var[p] = v;
+}
+
+template<bool kTemporal, bool kMasked, bool kViews = false>
+__global__ __launch_bounds__(256) void pt_denoise_variance_kernel(const float4 *__restrict__ col, const float4 *__restrict__ guide, const uint32_t *__restrict__ cls,
+                                                                  int32_t width, int32_t height, float sigma_normal, float sigma_depth, float2 *__restrict__ grad,
+                                                                  float *__restrict__ var, PtTemporalPixel tp) {
+    denoise_variance_stage<kTemporal, kMasked, kViews, false>(col, guide, cls, width, height, sigma_normal, sigma_depth, grad, var, tp, PtMeasuredPixel{});
+}
+
+template<bool kMasked>
+__global__ __launch_bounds__(256) void pt_denoise_variance_measured_kernel(const float4 *__restrict__ col, const float4 *__restrict__ guide,
+                                                                           const uint32_t *__restrict__ cls, int32_t width, int32_t height, float sigma_normal,
+                                                                           float sigma_depth, float2 *__restrict__ grad, float *__restrict__ var, PtMeasuredPixel mp) {
+    denoise_variance_stage<false, kMasked, false, true>(col, guide, cls, width, height, sigma_normal, sigma_depth, grad, var, PtTemporalPixel{}, mp);
 }
 
 // kTemporal: the luminance sigma is tp.sigma_luminance_temporal at pixels whose variance came from the temporal moments.
 // kMasked: holes are no taps (the variance prefilter included), and a hole is filled (pt_denoise_masked_run).
-template<bool kTemporal, bool kMasked, bool kViews = false>
-__global__ __launch_bounds__(256) void pt_denoise_atrous_kernel(const float4 *__restrict__ col_in, const float *__restrict__ var_in, const float4 *__restrict__ guide,
-                                                                const uint32_t *__restrict__ cls, const float2 *__restrict__ grad, int32_t width, int32_t height,
-                                                                int32_t step, float sigma_luminance, float sigma_normal, float sigma_depth,
-                                                                float4 *__restrict__ col_out, float *__restrict__ var_out, PtTemporalPixel tp) {
+// kMeasured: the luminance sigma is mp.sigma_measured at pixels whose variance is the measured one.
+template<bool kTemporal, bool kMasked, bool kViews, bool kMeasured>
+__device__ __forceinline__ void denoise_atrous_stage(const float4 *__restrict__ col_in, const float *__restrict__ var_in, const float4 *__restrict__ guide,
+                                                     const uint32_t *__restrict__ cls, const float2 *__restrict__ grad, int32_t width, int32_t height,
+                                                     int32_t step, float sigma_luminance, float sigma_normal, float sigma_depth,
+                                                     float4 *__restrict__ col_out, float *__restrict__ var_out, const PtTemporalPixel &tp,
+                                                     const PtMeasuredPixel &mp) {
     const int x = blockIdx.x * 16 + threadIdx.x, y = blockIdx.y * 16 + threadIdx.y;
     if(x >= width || y >= height) {
         return;
@@ -305,6 +357,11 @@ __global__ __launch_bounds__(256) void pt_denoise_atrous_kernel(const float4 *__
             sl = tp.sigma_luminance_temporal;
         }
     }
+    if constexpr(kMeasured) {
+        if(measured_variance_px(mp.plane[p])) {
+            sl = mp.sigma_measured;
+        }
+    }
     const float lum_scale = sl * sqrtf(g) + kLumEps;
     const float4 gp = guide[p];
     const float2 gr = grad[p];
@@ -345,6 +402,25 @@ __global__ __launch_bounds__(256) void pt_denoise_atrous_kernel(const float4 *__
     const float r = sr / sw, gg = sg / sw, b = sb / sw;
     col_out[p] = make_float4(r, gg, b, lum_of(r, gg, b));
     var_out[p] = sv / (sw * sw);
+}
+
+template<bool kTemporal, bool kMasked, bool kViews = false>
+__global__ __launch_bounds__(256) void pt_denoise_atrous_kernel(const float4 *__restrict__ col_in, const float *__restrict__ var_in, const float4 *__restrict__ guide,
+                                                                const uint32_t *__restrict__ cls, const float2 *__restrict__ grad, int32_t width, int32_t height,
+                                                                int32_t step, float sigma_luminance, float sigma_normal, float sigma_depth,
+                                                                float4 *__restrict__ col_out, float *__restrict__ var_out, PtTemporalPixel tp) {
+    denoise_atrous_stage<kTemporal, kMasked, kViews, false>(col_in, var_in, guide, cls, grad, width, height, step, sigma_luminance, sigma_normal, sigma_depth, col_out,
+                                                            var_out, tp, PtMeasuredPixel{});
+}
+
+template<bool kMasked>
+__global__ __launch_bounds__(256) void pt_denoise_atrous_measured_kernel(const float4 *__restrict__ col_in, const float *__restrict__ var_in,
+                                                                         const float4 *__restrict__ guide, const uint32_t *__restrict__ cls,
+                                                                         const float2 *__restrict__ grad, int32_t width, int32_t height, int32_t step,
+                                                                         float sigma_luminance, float sigma_normal, float sigma_depth, float4 *__restrict__ col_out,
+                                                                         float *__restrict__ var_out, PtMeasuredPixel mp) {
+    denoise_atrous_stage<false, kMasked, false, true>(col_in, var_in, guide, cls, grad, width, height, step, sigma_luminance, sigma_normal, sigma_depth, col_out,
+                                                      var_out, PtTemporalPixel{}, mp);
 }
 
 // the previous push's history, as the temporal step reads it
@@ -552,6 +628,35 @@ hipError_t pt_denoise_masked_run(hipStream_t stream, const float4 *rgba, const f
     }
     hipLaunchKernelGGL(pt_denoise_finish_kernel<true>, grid, block, 0, stream, s.col[cur], rgba, features, width, height, s.cls, s.var[cur], out);
     return hipGetLastError();
+}
+
+namespace {
+
+template<bool kMasked>
+hipError_t run_measured(hipStream_t stream, const float4 *rgba, const float4 *features, const float4 *variance, const int32_t *samples, int32_t width, int32_t height,
+                        const PtDenoiseParams &params, float sigma_measured, const PtDenoiseScratch &s, float4 *out) {
+    const dim3 block(16, 16), grid((width + 15) / 16, (height + 15) / 16);
+    const PtMeasuredPixel mp{variance, features, sigma_measured};
+    hipLaunchKernelGGL(pt_denoise_prepare_kernel<kMasked>, grid, block, 0, stream, rgba, features, width, height, samples, s.col[0], s.guide, s.cls);
+    hipLaunchKernelGGL(pt_denoise_variance_measured_kernel<kMasked>, grid, block, 0, stream, s.col[0], s.guide, s.cls, width, height, params.sigma_normal,
+                       params.sigma_depth, s.grad, s.var[0], mp);
+    int cur = 0;
+    for(int i = 0; i < params.iterations; i++) {
+        hipLaunchKernelGGL(pt_denoise_atrous_measured_kernel<kMasked>, grid, block, 0, stream, s.col[cur], s.var[cur], s.guide, s.cls, s.grad, width, height, 1 << i,
+                           params.sigma_luminance, params.sigma_normal, params.sigma_depth, s.col[cur ^ 1], s.var[cur ^ 1], mp);
+        cur ^= 1;
+    }
+    hipLaunchKernelGGL(pt_denoise_finish_kernel<kMasked>, grid, block, 0, stream, s.col[cur], rgba, features, width, height, kMasked ? s.cls : nullptr,
+                       kMasked ? s.var[cur] : nullptr, out);
+    return hipGetLastError();
+}
+
+} // namespace
+
+hipError_t pt_denoise_measured_run(hipStream_t stream, const float4 *rgba, const float4 *features, const float4 *variance, const int32_t *samples, int32_t width,
+                                   int32_t height, const PtDenoiseParams &params, float sigma_measured, const PtDenoiseScratch &scratch, float4 *out) {
+    return samples != nullptr ? run_measured<true>(stream, rgba, features, variance, samples, width, height, params, sigma_measured, scratch, out)
+                              : run_measured<false>(stream, rgba, features, variance, nullptr, width, height, params, sigma_measured, scratch, out);
 }
 
 namespace {

@@ -20,7 +20,8 @@
 // record stays where it is and only the list is split again, by the pass's sample count and the target as they are now.
 //
 // The same work list is what pt_frame_preview shows between two launches: the gather kernels below read it without changing it, and
-// pt_frame_rate_kernel rates its pixels for pt_frame_get_noise.
+// pt_frame_rate_kernel rates its pixels for pt_frame_get_noise, pt_frame_variance_kernel gives their measured variance for
+// pt_frame_get_variance.
 #include <hip/hip_runtime.h>
 
 #include "pt_kernels.h"
@@ -410,6 +411,34 @@ __global__ __launch_bounds__(kThreads) void pt_frame_noise_scatter_kernel(const 
     }
 }
 
+// ---- the variance map of a frame (pt_frame_get_variance, pt_frames.cpp) -----------------------------------------------------------------
+// One thread per entry of a replica's work list, as the rating kernel: out_var[i] = pixel_variance of the entry's record, (0, 0, 0, 0)
+// for an entry without one, and out_at[i] its pixel.  Reads the estimator's M2 and sample count, not the record.
+__global__ __launch_bounds__(kThreads) void pt_frame_variance_kernel(const uint2 *__restrict__ todo, uint32_t n, const PtParkRecord *__restrict__ park,
+                                                                     const int4 *__restrict__ tiles, const uint32_t *__restrict__ tile_offset, uint32_t n_tiles,
+                                                                     int32_t width, PtDevOptions opt, float4 *__restrict__ out_var, int32_t *__restrict__ out_at) {
+    const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
+    if(i >= n) {
+        return;
+    }
+    const uint2 e = todo[i];
+    float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if(e.y != PT_NO_PARK) {
+        v = pixel_variance(park[e.y].est, opt);
+    }
+    out_var[i] = v;
+    out_at[i] = stream_pixel(e.x, tiles, tile_offset, n_tiles, width);
+}
+
+// (the map on replica 0's device starts as zeros: finished, untouched and uncovered pixels stay (0, 0, 0, 0))
+__global__ __launch_bounds__(kThreads) void pt_frame_variance_scatter_kernel(const float4 *__restrict__ var, const int32_t *__restrict__ at, uint32_t n,
+                                                                             float4 *__restrict__ map) {
+    const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
+    if(i < n) {
+        map[at[i]] = var[i];
+    }
+}
+
 } // namespace
 
 int pt_launch_frame_rate(hipStream_t stream, const uint2 *todo, uint32_t n, const PtParkRecord *park, const int4 *tiles, const uint32_t *tile_offset, uint32_t n_tiles,
@@ -481,5 +510,22 @@ int pt_launch_frame_scatter(hipStream_t stream, const float4 *rgba, const int2 *
         return 0;
     }
     pt_frame_scatter_kernel<<<(n + kThreads - 1) / kThreads, kThreads, 0, stream>>>(rgba, at, n, view, samples);
+    return hipGetLastError() == hipSuccess ? 0 : 1;
+}
+
+int pt_launch_frame_variance(hipStream_t stream, const uint2 *todo, uint32_t n, const PtParkRecord *park, const int4 *tiles, const uint32_t *tile_offset,
+                             uint32_t n_tiles, int32_t width, const PtDevOptions &opt, float4 *out_var, int32_t *out_at) {
+    if(n == 0) {
+        return 0;
+    }
+    pt_frame_variance_kernel<<<(n + kThreads - 1) / kThreads, kThreads, 0, stream>>>(todo, n, park, tiles, tile_offset, n_tiles, width, opt, out_var, out_at);
+    return hipGetLastError() == hipSuccess ? 0 : 1;
+}
+
+int pt_launch_frame_variance_scatter(hipStream_t stream, const float4 *var, const int32_t *at, uint32_t n, float4 *map) {
+    if(n == 0) {
+        return 0;
+    }
+    pt_frame_variance_scatter_kernel<<<(n + kThreads - 1) / kThreads, kThreads, 0, stream>>>(var, at, n, map);
     return hipGetLastError() == hipSuccess ? 0 : 1;
 }

@@ -48,6 +48,10 @@ struct pt_frame {
         DevBuf<float> nz_map;
         DevBuf<uint8_t> nz_cover;
         size_t nz_cover_ready = 0;
+        // pt_frame_get_variance: the replica's gathered variances and their pixels; on replica 0 also the map and the other replicas'
+        // entries on their way in
+        DevBuf<F4> vr_var, vr_stage_var, vr_map;
+        DevBuf<int32_t> vr_at, vr_stage_at;
     };
     pt_camera_params camera{};
     pt_options options{};
@@ -74,6 +78,9 @@ struct pt_frame {
     float noise_target = 0.0f, noise_floor = 1E-5f, noise_fraction = 1.0f;
     bool target_reached = false;
     double noise_rate_ms = 0.0; // device time of the rating kernels of the last pt_frame_get_noise, all replicas (tools/noise_probe.py)
+    // device time of the gather kernels of the last variance map, all replicas, and of the filter of the last denoised preview
+    // (tools/measured_probe.py)
+    double variance_gather_ms = 0.0, preview_filter_ms = 0.0;
     PtNoiseRule noise_rule(const PtDevOptions &opt, bool holding) const {
         PtNoiseRule rule;
         rule.opt = opt;
@@ -695,14 +702,12 @@ static int preview_compose(pt_frame *f, const float *image, size_t n, const std:
     return PT_OK;
 }
 
-extern "C" int pt_frame_preview(pt_frame *f, const float *image, const pt_denoise_params *denoise, float *out_rgba, int32_t *out_samples) {
-    if(f == nullptr || image == nullptr || out_rgba == nullptr) {
-        return fail(PT_ERR_INVALID, "null argument");
-    }
-    PtDenoiseParams dp{};
-    if(denoise != nullptr) {
-        PT_TRY(denoise_params_resolve(denoise, &dp));
-    }
+static int variance_gather(pt_frame *f, const PtDevOptions &opt, std::vector<std::vector<F4>> &far_var, std::vector<std::vector<int32_t>> &far_at);
+static int variance_compose(pt_frame *f, size_t n, const std::vector<std::vector<F4>> &far_var, const std::vector<std::vector<int32_t>> &far_at);
+
+// pt_frame_preview (sigma_measured == nullptr) and pt_frame_preview_measured: `dp` is the filter's parameters when `denoise`
+static int frame_preview(pt_frame *f, const float *image, bool denoise, const PtDenoiseParams &dp, const float *sigma_measured, float *out_rgba,
+                         int32_t *out_samples) {
     // (a view frame's image is its views stacked: every step below but the features and the filter sees one frame of rows() rows)
     const int32_t width = f->options.image_width, height = f->options.image_height;
     const size_t n = static_cast<size_t>(width) * static_cast<size_t>(f->rows());
@@ -728,6 +733,13 @@ extern "C" int pt_frame_preview(pt_frame *f, const float *image, const pt_denois
     std::vector<std::vector<F4>> far_rgba(f->reps.size());
     std::vector<std::vector<int2>> far_at(f->reps.size());
     PT_TRY(preview_gather(f, far_rgba, far_at));
+    std::vector<std::vector<F4>> far_var(f->reps.size());
+    std::vector<std::vector<int32_t>> far_var_at(f->reps.size());
+    if(sigma_measured != nullptr) {
+        PtDevOptions opt;
+        PT_TRY(derive_options(&f->options, &opt));
+        PT_TRY(variance_gather(f, opt, far_var, far_var_at));
+    }
     pt_frame::Replica &r0 = *f->reps[0];
     pt_scene *s0 = r0.s;
     std::lock_guard<std::mutex> lock(s0->render_mutex);
@@ -737,7 +749,8 @@ extern "C" int pt_frame_preview(pt_frame *f, const float *image, const pt_denois
     float4 *view = reinterpret_cast<float4 *>(r0.pv_view.ptr);
     // 3. the filter, and the view back to the caller
     std::unique_lock<std::mutex> ws_lock;
-    if(denoise != nullptr) {
+    Event begin, end;
+    if(denoise) {
         if(!r0.pv_features_ready) {
             PT_HIP(r0.pv_features.ensure(3 * n));
             PT_TRY(features_views_launch(s0, f->n_views > 1 ? f->cameras.data() : &f->camera, f->n_views, &f->options, reinterpret_cast<float4 *>(r0.pv_features.ptr)));
@@ -747,14 +760,43 @@ extern "C" int pt_frame_preview(pt_frame *f, const float *image, const pt_denois
         ws_lock = std::unique_lock<std::mutex>(ws.mutex); // (held until the stream has been synchronised below)
         PT_TRY(denoise_ensure(ws, n, false));
         // (one view: pt_denoise_masked_run itself; more: its view form, a hole filled from its own view only)
-        PT_HIP(pt_denoise_views_run(st, view, reinterpret_cast<const float4 *>(r0.pv_features.ptr), r0.pv_samples.ptr, width, height, f->n_views, dp, ws.scratch, view));
+        if(sigma_measured != nullptr) {
+            PT_TRY(variance_compose(f, n, far_var, far_var_at));
+        }
+        PT_HIP(begin.create());
+        PT_HIP(end.create());
+        PT_HIP(hipEventRecord(begin.e, st));
+        if(sigma_measured != nullptr) {
+            PT_HIP(pt_denoise_measured_run(st, view, reinterpret_cast<const float4 *>(r0.pv_features.ptr), reinterpret_cast<const float4 *>(r0.vr_map.ptr),
+                                           r0.pv_samples.ptr, width, height, dp, *sigma_measured, ws.scratch, view));
+        }
+        else {
+            PT_HIP(pt_denoise_views_run(st, view, reinterpret_cast<const float4 *>(r0.pv_features.ptr), r0.pv_samples.ptr, width, height, f->n_views, dp, ws.scratch, view));
+        }
+        PT_HIP(hipEventRecord(end.e, st));
     }
     PT_HIP(hipMemcpyAsync(out_rgba, view, n * sizeof(F4), hipMemcpyDeviceToHost, st));
     if(out_samples != nullptr) {
         PT_HIP(hipMemcpyAsync(out_samples, r0.pv_samples.ptr, n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     }
     PT_HIP(hipStreamSynchronize(st));
+    if(denoise) {
+        float ms = 0.0f;
+        PT_HIP(hipEventElapsedTime(&ms, begin.e, end.e));
+        f->preview_filter_ms = ms;
+    }
     return PT_OK;
+}
+
+extern "C" int pt_frame_preview(pt_frame *f, const float *image, const pt_denoise_params *denoise, float *out_rgba, int32_t *out_samples) {
+    if(f == nullptr || image == nullptr || out_rgba == nullptr) {
+        return fail(PT_ERR_INVALID, "null argument");
+    }
+    PtDenoiseParams dp{};
+    if(denoise != nullptr) {
+        PT_TRY(denoise_params_resolve(denoise, &dp));
+    }
+    return frame_preview(f, image, denoise != nullptr, dp, nullptr, out_rgba, out_samples);
 }
 
 // ---- the noise of a frame (pt_frame_get_noise, pt_frame_set_noise_target; include/pt_frame_noise.h) -------------------------------------
@@ -938,5 +980,140 @@ extern "C" int pt_debug_frame_noise_ms(pt_frame *f, double *out_ms) {
     }
     std::lock_guard<std::mutex> lock(f->mutex);
     *out_ms = f->noise_rate_ms;
+    return PT_OK;
+}
+
+// ---- the variance map of a frame (pt_frame_get_variance, pt_frame_preview_measured; include/pt_frame_variance.h) -------------------------
+
+// step 1: every replica that has rendered gathers the measured variance of its work list on its own device; the other replicas'
+// entries come to the host
+static int variance_gather(pt_frame *f, const PtDevOptions &opt, std::vector<std::vector<F4>> &far_var, std::vector<std::vector<int32_t>> &far_at) {
+    f->variance_gather_ms = 0.0;
+    for(size_t i = 0; i < f->reps.size(); i++) {
+        pt_frame::Replica &r = *f->reps[i];
+        if(!r.ready || r.n_todo == 0) {
+            continue;
+        }
+        pt_scene *s = r.s;
+        std::lock_guard<std::mutex> lock(s->render_mutex);
+        PT_HIP(hipSetDevice(s->device));
+        r.previewed = true;
+        PT_HIP(r.vr_var.ensure(r.n_todo));
+        PT_HIP(r.vr_at.ensure(r.n_todo));
+        Event begin, end;
+        PT_HIP(begin.create());
+        PT_HIP(end.create());
+        PT_HIP(hipEventRecord(begin.e, s->stream));
+        if(pt_launch_frame_variance(s->stream, r.d_todo[r.cur].ptr, r.n_todo, r.d_park[r.pcur].ptr, r.d_tiles.ptr, r.d_offset.ptr, static_cast<uint32_t>(r.tiles.size()),
+                                    f->options.image_width, opt, reinterpret_cast<float4 *>(r.vr_var.ptr), r.vr_at.ptr) != 0) {
+            PT_HIP(hipGetLastError());
+            return fail(PT_ERR_HIP, "variance: gather kernel failed to launch");
+        }
+        PT_HIP(hipEventRecord(end.e, s->stream));
+        if(i != 0) {
+            far_var[i].resize(r.n_todo);
+            far_at[i].resize(r.n_todo);
+            PT_HIP(hipMemcpyAsync(far_var[i].data(), r.vr_var.ptr, r.n_todo * sizeof(F4), hipMemcpyDeviceToHost, s->stream));
+            PT_HIP(hipMemcpyAsync(far_at[i].data(), r.vr_at.ptr, r.n_todo * sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
+        }
+        PT_HIP(hipStreamSynchronize(s->stream));
+        float ms = 0.0f;
+        PT_HIP(hipEventElapsedTime(&ms, begin.e, end.e));
+        f->variance_gather_ms += ms;
+    }
+    return PT_OK;
+}
+
+// step 2, on replica 0's device (its render_mutex held), as preview_compose: zeros, every replica's entries over them -- the map of n
+// pixels in r0.vr_map
+static int variance_compose(pt_frame *f, size_t n, const std::vector<std::vector<F4>> &far_var, const std::vector<std::vector<int32_t>> &far_at) {
+    pt_frame::Replica &r0 = *f->reps[0];
+    hipStream_t st = r0.s->stream;
+    r0.previewed = true;
+    PT_HIP(r0.vr_map.ensure(n));
+    PT_HIP(hipMemsetAsync(r0.vr_map.ptr, 0, n * sizeof(F4), st)); // (the base: finished, untouched and uncovered pixels are (0, 0, 0, 0))
+    for(size_t i = 0; i < f->reps.size(); i++) {
+        const pt_frame::Replica &r = *f->reps[i];
+        if(!r.ready || r.n_todo == 0) {
+            continue;
+        }
+        const float4 *var = reinterpret_cast<const float4 *>(r0.vr_var.ptr);
+        const int32_t *at = r0.vr_at.ptr;
+        if(i != 0) {
+            PT_HIP(r0.vr_stage_var.ensure(r.n_todo));
+            PT_HIP(r0.vr_stage_at.ensure(r.n_todo));
+            PT_HIP(hipMemcpyAsync(r0.vr_stage_var.ptr, far_var[i].data(), r.n_todo * sizeof(F4), hipMemcpyHostToDevice, st));
+            PT_HIP(hipMemcpyAsync(r0.vr_stage_at.ptr, far_at[i].data(), r.n_todo * sizeof(int32_t), hipMemcpyHostToDevice, st));
+            var = reinterpret_cast<const float4 *>(r0.vr_stage_var.ptr);
+            at = r0.vr_stage_at.ptr;
+        }
+        if(pt_launch_frame_variance_scatter(st, var, at, r.n_todo, reinterpret_cast<float4 *>(r0.vr_map.ptr)) != 0) {
+            PT_HIP(hipGetLastError());
+            return fail(PT_ERR_HIP, "variance: scatter kernel failed to launch");
+        }
+    }
+    return PT_OK;
+}
+
+extern "C" int pt_frame_get_variance(pt_frame *f, float *out_var) {
+    if(f == nullptr || out_var == nullptr) {
+        return fail(PT_ERR_INVALID, "null argument");
+    }
+    const size_t n = static_cast<size_t>(f->options.image_width) * static_cast<size_t>(f->rows());
+    if(n > 0x0fffffffULL) {
+        return fail(PT_ERR_INVALID, "more than 0x0fffffff pixels");
+    }
+    std::lock_guard<std::mutex> frame_lock(f->mutex);
+    if(f->status != PT_OK) {
+        return fail(f->status, f->error);
+    }
+    bool any_ready = false;
+    for(const auto &r : f->reps) {
+        any_ready = any_ready || r->ready;
+    }
+    if(!any_ready) {
+        std::memset(out_var, 0, n * sizeof(F4)); // (before the first pt_frame_render every pixel is untouched)
+        return PT_OK;
+    }
+    PtDevOptions opt;
+    PT_TRY(derive_options(&f->options, &opt));
+    std::vector<std::vector<F4>> far_var(f->reps.size());
+    std::vector<std::vector<int32_t>> far_at(f->reps.size());
+    PT_TRY(variance_gather(f, opt, far_var, far_at));
+    pt_scene *s0 = f->reps[0]->s;
+    std::lock_guard<std::mutex> lock(s0->render_mutex);
+    PT_HIP(hipSetDevice(s0->device));
+    PT_TRY(variance_compose(f, n, far_var, far_at));
+    PT_HIP(hipMemcpyAsync(out_var, f->reps[0]->vr_map.ptr, n * sizeof(F4), hipMemcpyDeviceToHost, s0->stream));
+    PT_HIP(hipStreamSynchronize(s0->stream));
+    return PT_OK;
+}
+
+extern "C" int pt_frame_preview_measured(pt_frame *f, const float *image, const pt_denoise_measured_params *params, float *out_rgba, int32_t *out_samples) {
+    if(f == nullptr || image == nullptr || out_rgba == nullptr) {
+        return fail(PT_ERR_INVALID, "null argument");
+    }
+    PtDenoiseParams dp{};
+    float sigma_measured = 0.0f;
+    PT_TRY(denoise_measured_params_resolve(params, &dp, &sigma_measured));
+    if(f->n_views > 1) {
+        return fail(PT_ERR_UNSUPPORTED, "a view frame has no measured preview");
+    }
+    return frame_preview(f, image, true, dp, &sigma_measured, out_rgba, out_samples);
+}
+
+// diagnostic (tools/measured_probe.py): the device time of the gather kernels of the frame's last variance map, all replicas, and of the
+// filter of its last denoised preview (either may be NULL)
+extern "C" int pt_debug_frame_measured_ms(pt_frame *f, double *out_gather_ms, double *out_filter_ms) {
+    if(f == nullptr) {
+        return fail(PT_ERR_INVALID, "null argument");
+    }
+    std::lock_guard<std::mutex> lock(f->mutex);
+    if(out_gather_ms != nullptr) {
+        *out_gather_ms = f->variance_gather_ms;
+    }
+    if(out_filter_ms != nullptr) {
+        *out_filter_ms = f->preview_filter_ms;
+    }
     return PT_OK;
 }

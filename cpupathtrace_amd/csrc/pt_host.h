@@ -380,11 +380,15 @@ struct DenoiseWorkspace {
     size_t staged = 0;  // ... and of the host form's upload/download buffers
     PtDenoiseScratch scratch{};
     float4 *in_rgba = nullptr, *in_features = nullptr;
+    size_t staged_variance = 0; // ... and of pt_denoise_measured's upload buffer
+    float4 *in_variance = nullptr;
 };
 DenoiseWorkspace &denoise_workspace(int device);
 int denoise_ensure(DenoiseWorkspace &ws, size_t n, bool staged);
 // The parameters pt_denoise takes (NULL = the defaults), checked without a device
 int denoise_params_resolve(const pt_denoise_params *params, PtDenoiseParams *resolved);
+// The same for pt_denoise_measured and pt_frame_preview_measured (NULL = pt_denoise_measured_params_default)
+int denoise_measured_params_resolve(const pt_denoise_measured_params *params, PtDenoiseParams *resolved, float *sigma_measured);
 
 } // namespace pth
 

@@ -169,6 +169,20 @@ int denoise_params_resolve(const pt_denoise_params *params, PtDenoiseParams *res
     return PT_OK;
 }
 
+int denoise_measured_params_resolve(const pt_denoise_measured_params *params, PtDenoiseParams *resolved, float *sigma_measured) {
+    pt_denoise_measured_params p{};
+    pt_denoise_measured_params_default(&p);
+    if(params != nullptr) {
+        p = *params;
+    }
+    PT_TRY(denoise_params_resolve(&p.base, resolved));
+    if(!std::isfinite(p.sigma_measured) || p.sigma_measured < 0.0F) {
+        return fail(PT_ERR_INVALID, "sigmas must be finite and not negative");
+    }
+    *sigma_measured = p.sigma_measured;
+    return PT_OK;
+}
+
 } // namespace pth
 
 // The arguments of the denoise entry points, checked without a device but for its index at the end
@@ -280,6 +294,79 @@ int pt_denoise_views(int device, const float *rgba, const float *features, int32
     PT_HIP(hipMemcpy(ws.in_features, features, 3 * n * sizeof(F4), hipMemcpyHostToDevice));
     // in place: the last kernel reads a pixel's alpha before it writes that pixel, and no kernel reads another pixel of the input
     PT_HIP(pt_denoise_views_run(nullptr, ws.in_rgba, ws.in_features, nullptr, width, height, n_views, p, ws.scratch, ws.in_rgba));
+    PT_HIP(hipMemcpy(out_rgba, ws.in_rgba, n * sizeof(F4), hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
+// The filter with a plane of measured variances (pt_denoise_measured_run; include/pt_frame_variance.h): mask NULL = the plain filter
+static int denoise_measured_check(int device, const void *rgba, const void *features, const void *variance, int32_t width, int32_t height,
+                                  const pt_denoise_measured_params *params, const void *out, PtDenoiseParams *resolved, float *sigma_measured) {
+    if(rgba == nullptr || features == nullptr || variance == nullptr || out == nullptr) {
+        return fail(PT_ERR_INVALID, "null argument");
+    }
+    if(width <= 0 || height <= 0) {
+        return fail(PT_ERR_INVALID, "image size must be positive");
+    }
+    if(static_cast<uint64_t>(width) * static_cast<uint64_t>(height) > 0x0fffffffULL) {
+        return fail(PT_ERR_INVALID, "more than 0x0fffffff pixels");
+    }
+    PT_TRY(denoise_measured_params_resolve(params, resolved, sigma_measured));
+    return check_device(device);
+}
+
+int pt_denoise_measured_params_default(pt_denoise_measured_params *out) {
+    if(out == nullptr) {
+        return fail(PT_ERR_INVALID, "null argument");
+    }
+    pt_denoise_params_default(&out->base);
+    out->sigma_measured = 16.0F;
+    return PT_OK;
+}
+
+int pt_denoise_measured_device(int device, const float *d_rgba, const float *d_features, const float *d_variance, const int32_t *d_mask, int32_t width,
+                               int32_t height, const pt_denoise_measured_params *params, float *d_out_rgba, void *stream) {
+    PtDenoiseParams p{};
+    float sigma_measured = 0.0F;
+    PT_TRY(denoise_measured_check(device, d_rgba, d_features, d_variance, width, height, params, d_out_rgba, &p, &sigma_measured));
+    const size_t n = static_cast<size_t>(width) * static_cast<size_t>(height);
+    DenoiseWorkspace &ws = denoise_workspace(device);
+    std::lock_guard<std::mutex> lock(ws.mutex);
+    PT_HIP(hipSetDevice(device));
+    PT_TRY(denoise_ensure(ws, n, false));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    PT_HIP(pt_denoise_measured_run(st, reinterpret_cast<const float4 *>(d_rgba), reinterpret_cast<const float4 *>(d_features),
+                                   reinterpret_cast<const float4 *>(d_variance), d_mask, width, height, p, sigma_measured, ws.scratch,
+                                   reinterpret_cast<float4 *>(d_out_rgba)));
+    PT_HIP(hipStreamSynchronize(st)); // the scratch buffers are the device's: the next call may reuse them
+    return PT_OK;
+}
+
+int pt_denoise_measured(int device, const float *rgba, const float *features, const float *variance, const int32_t *mask, int32_t width, int32_t height,
+                        const pt_denoise_measured_params *params, float *out_rgba) {
+    PtDenoiseParams p{};
+    float sigma_measured = 0.0F;
+    PT_TRY(denoise_measured_check(device, rgba, features, variance, width, height, params, out_rgba, &p, &sigma_measured));
+    const size_t n = static_cast<size_t>(width) * static_cast<size_t>(height);
+    DenoiseWorkspace &ws = denoise_workspace(device);
+    std::lock_guard<std::mutex> lock(ws.mutex);
+    PT_HIP(hipSetDevice(device));
+    PT_TRY(denoise_ensure(ws, n, true));
+    if(n > ws.staged_variance) {
+        ws.staged_variance = 0;
+        PT_HIP(regrow(&ws.in_variance, n));
+        ws.staged_variance = n;
+    }
+    DevBuf<int32_t> d_mask;
+    if(mask != nullptr) {
+        PT_HIP(d_mask.ensure(n));
+        PT_HIP(hipMemcpy(d_mask.ptr, mask, n * sizeof(int32_t), hipMemcpyHostToDevice));
+    }
+    PT_HIP(hipMemcpy(ws.in_rgba, rgba, n * sizeof(F4), hipMemcpyHostToDevice));
+    PT_HIP(hipMemcpy(ws.in_features, features, 3 * n * sizeof(F4), hipMemcpyHostToDevice));
+    PT_HIP(hipMemcpy(ws.in_variance, variance, n * sizeof(F4), hipMemcpyHostToDevice));
+    // in place, as pt_denoise
+    PT_HIP(pt_denoise_measured_run(nullptr, ws.in_rgba, ws.in_features, ws.in_variance, mask != nullptr ? d_mask.ptr : nullptr, width, height, p, sigma_measured,
+                                   ws.scratch, ws.in_rgba));
     PT_HIP(hipMemcpy(out_rgba, ws.in_rgba, n * sizeof(F4), hipMemcpyDeviceToHost));
     return PT_OK;
 }

@@ -180,6 +180,12 @@ int pt_launch_frame_rate(hipStream_t stream, const uint2 *todo, uint32_t n, cons
                          int32_t width, const PtNoiseRule &noise, uint2 *out, uint32_t *summary);
 int pt_launch_frame_noise_base(hipStream_t stream, float *map, const uint8_t *cover, uint32_t n_pixels);
 int pt_launch_frame_noise_scatter(hipStream_t stream, const uint2 *rated, uint32_t n, float *map);
+// The variance map of a frame (pt_frame.hip; pt_frame_get_variance).  variance: out_var[i] = pixel_variance (pt_noise.h) per entry of a
+// replica's work list, (0, 0, 0, 0) for an entry without a record, and out_at[i] its pixel.  scatter: n entries into the map of replica 0's
+// device, which starts as zeros.  Each returns 0, or 1 when the launch failed.
+int pt_launch_frame_variance(hipStream_t stream, const uint2 *todo, uint32_t n, const PtParkRecord *park, const int4 *tiles, const uint32_t *tile_offset,
+                             uint32_t n_tiles, int32_t width, const PtDevOptions &opt, float4 *out_var, int32_t *out_at);
+int pt_launch_frame_variance_scatter(hipStream_t stream, const float4 *var, const int32_t *at, uint32_t n, float4 *map);
 // The preview of a frame (pt_frame.hip; pt_frame_preview).  gather: one compact entry per entry of a replica's work list todo[0 .. n), those
 // that name a record (the first n_parked of a plain frame) parked in `park` -- out_rgba the running mean (0 for an untouched stream), out_at (y * width + x, samples taken).  base: the
 // view of replica 0's device, which holds the caller's image: samples -1 where cover[p] != 0, else a hole (0, 0, 0, 0) with 0 samples.

@@ -1,5 +1,5 @@
-// pt_noise.h -- the rating of an unfinished pixel of a resumable frame (pt_frame_get_noise, pt_frame_set_noise_target),
-// defined once for the kernels of pt_frame.hip.  Every operation is a correctly rounded fp32 operation in the order written here
+// pt_noise.h -- the rating of an unfinished pixel of a resumable frame (pt_frame_get_noise, pt_frame_set_noise_target)
+// and the measured variance of its mean (pt_frame_get_variance), defined once for the kernels of pt_frame.hip.  Every operation is a correctly rounded fp32 operation in the order written here
 // (tests/noise_ref.py restates it).
 #ifndef PT_NOISE_H
 #define PT_NOISE_H
@@ -27,6 +27,24 @@ __device__ inline float pixel_error(const PtEstimator &e, const PtDevOptions &op
     const float contribution = (e.contribution_mean[0] + e.contribution_mean[1] + e.contribution_mean[2]) / 3.0f; // get_contribution
     const float ratio = stddev / (9.0f * contribution + floor);
     return ratio / __builtin_sqrtf((float)batches);
+}
+
+// The measured variance of the pixel's mean, per channel, and the batch means behind it (pt_frame_get_variance): the sample
+// variance of the B batch means over B, (v_r, v_g, v_b, (float)B).  A batch mean is the mean of stats_sample_count collected
+// contributions, so v is in the unit of the preview colour pixel_value / collected_sample_count squared.  (0, 0, 0, 0) for a pixel with
+// fewer than two batch means, or with a v_c that is negative, NaN or infinite: it is unrated.
+__device__ inline float4 pixel_variance(const PtEstimator &e, const PtDevOptions &opt) {
+    const int32_t batches = pixel_batches(e, opt);
+    if(batches < 2) {
+        return make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    }
+    const float d = (float)(batches - 1), n = (float)batches;
+    const float r = (e.contribution_m2[0] / d) / n, g = (e.contribution_m2[1] / d) / n, b = (e.contribution_m2[2] / d) / n;
+    const float top = 3.402823466e+38f;
+    if(!(r >= 0.0f && r <= top && g >= 0.0f && g <= top && b >= 0.0f && b <= top)) {
+        return make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    }
+    return make_float4(r, g, b, n);
 }
 
 // the bin of an error in the 64-bin histogram by exponent: bin 32 = [1, 2), zero and the denormals in bin 0, 2^31 and above in bin 63

@@ -55,6 +55,12 @@ public:
     // -1 finished, the samples taken of a parked pixel, 0 untouched.  With `denoise` the preview is filtered as pt_denoise filters a frame,
     // holes filled from their neighbours.  out is resized to the frame.  Changes nothing the frame will do.  Throws std::runtime_error on failure.
     void preview(Image<> &out, std::vector<std::int32_t> *samples = nullptr, const pt_denoise_params *denoise = nullptr) const;
+    // The measured variance of the unfinished pixels (pt_frame_get_variance, include/pt_frame_variance.h): four floats per pixel, row-major
+    // -- the variance of the mean of r, g and b from the estimator's batch statistics and the number of batch means, (0, 0, 0, 0) for a
+    // pixel that is finished, untouched or has fewer than two batch means.  previewMeasured(): preview() denoised with each rated pixel's
+    // measured variance in place of the filter's 3x3 estimate (pt_frame_preview_measured; params null = pt_denoise_measured_params_default).
+    std::vector<float> variance() const;
+    void previewMeasured(Image<> &out, std::vector<std::int32_t> *samples = nullptr, const pt_denoise_measured_params *params = nullptr) const;
     std::uint64_t seed() const noexcept { return seed_; }
 
 private:

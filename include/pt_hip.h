@@ -414,6 +414,9 @@ int pt_denoise_views_device(int device, const float *d_rgba, const float *d_feat
  * PT_ERR_INVALID before any device is touched: null frame, image or out_rgba, or denoise parameters pt_denoise refuses; a failed
  * frame returns its stored status. */
 int pt_frame_preview(pt_frame *frame, const float *image, const pt_denoise_params *denoise, float *out_rgba, int32_t *out_samples);
+/* The measured variance of a frame's unfinished pixels (pt_frame_get_variance) and the filter fed with it (pt_denoise_measured,
+ * pt_frame_preview_measured): struct pt_denoise_measured_params and those entry points are declared, with their contracts, in: */
+#include "pt_frame_variance.h"
 
 /* Temporal denoising of a sequence of frames of one static scene (a camera path, a turntable): the temporal half of SVGF (Schied et al. 2017)
  * in front of pt_denoise's spatial filter.  A pt_temporal handle keeps the history of the frames pushed so far, on its own

@@ -130,3 +130,26 @@ void FrameRender::preview(Image<> &out, std::vector<std::int32_t> *samples, cons
                            samples != nullptr ? samples->data() : nullptr),
           "FrameRender::preview");
 }
+
+std::vector<float> FrameRender::variance() const {
+    std::vector<float> map(4 * static_cast<size_t>(image_.getWidth()) * static_cast<size_t>(image_.getHeight()), 0.0f);
+    if(frame_ != nullptr) {
+        check(pt_frame_get_variance(frame_, map.data()), "FrameRender::variance");
+    }
+    return map;
+}
+
+void FrameRender::previewMeasured(Image<> &out, std::vector<std::int32_t> *samples, const pt_denoise_measured_params *params) const {
+    if(out.getWidth() != image_.getWidth() || out.getHeight() != image_.getHeight()) {
+        out = Image<>(image_.getWidth(), image_.getHeight());
+    }
+    if(samples != nullptr) {
+        samples->assign(static_cast<size_t>(image_.getWidth()) * static_cast<size_t>(image_.getHeight()), 0);
+    }
+    if(frame_ == nullptr) {
+        return;
+    }
+    check(pt_frame_preview_measured(frame_, reinterpret_cast<const float *>(image_.data()), params, reinterpret_cast<float *>(out.data()),
+                                    samples != nullptr ? samples->data() : nullptr),
+          "FrameRender::previewMeasured");
+}
