@@ -82,13 +82,15 @@ int derive_options(const pt_options *o, PtDevOptions *out) {
     d.candidate_batch_count = std::max(std::max(o->min_sample_count, o->max_sample_count / 4) / d.stats_sample_count, 2);
     d.check_sample_count =
       std::min(std::max({o->min_sample_count / 2, (o->max_sample_count - o->min_sample_count) / 8, 8, d.stats_sample_count}), 1024) / d.stats_sample_count;
-    // closed candidates a pixel can accumulate (worker.cpp:214-222).  A candidate closes after candidate_batch_count >= max / (4 S) batches
-    // and a pixel has at most max / S of them, so at most 4 candidates ever close: the check below is a guard against a change of the
-    // formulas above, not a limit a caller can reach (PT_MAX_CANDIDATES = 8).
+    // closed candidates a pixel can accumulate (worker.cpp:214-222).  A candidate closes after candidate_batch_count batches and a pixel
+    // has at most max / S of them.  candidate_batch_count is about max / (4 S), which would give 4, but both divisions truncate: max = 11
+    // with min <= 2 gives batches of 1 sample, 2 batches per candidate and 11 batches, so 5 candidates close.  That is the most any pair
+    // of options reaches (tests/test_shading_cases_cpu.py sweeps 0 <= min, max <= 4096), so the check below is a guard against a change of
+    // the formulas above, not a limit a caller can reach (PT_MAX_CANDIDATES = 8).
     const int batches = std::max(o->max_sample_count, 0) / d.stats_sample_count;
     const int closed = batches > 0 ? (batches - 1) / d.candidate_batch_count : 0;
     if(closed > PT_MAX_CANDIDATES) {
-        return fail(PT_ERR_UNSUPPORTED, "internal: the estimator's constants allow more than 8 closed candidates per pixel (worker.cpp:158-164 give at most 4)");
+        return fail(PT_ERR_UNSUPPORTED, "internal: the estimator's constants allow more than 8 closed candidates per pixel (worker.cpp:158-164 give at most 5)");
     }
     *out = d;
     return PT_OK;

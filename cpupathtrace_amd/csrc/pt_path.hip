@@ -47,10 +47,8 @@ using namespace ptd;
 
 namespace {
 
-typedef float f4v __attribute__((ext_vector_type(4)));
 typedef float f2v __attribute__((ext_vector_type(2)));
 typedef unsigned int u2v __attribute__((ext_vector_type(2)));
-typedef const f4v __attribute__((address_space(3))) *lds_f4_cptr;
 typedef const f4v __attribute__((address_space(1))) *glb_f4_cptr;
 typedef u2v __attribute__((address_space(3))) *lds_u2_ptr;
 typedef u2v __attribute__((address_space(1))) *glb_u2_ptr;
@@ -65,10 +63,6 @@ template<>
 struct RecPtr<true> {
     typedef lds_f4_cptr type;
 };
-
-PT_D float4 to_f4(f4v v) {
-    return make_float4(v.x, v.y, v.z, v.w);
-}
 
 // The root of the tree: its box is tested before anything else (Scene::getIntersection, scene.cpp:211-219)
 struct RootBox {
@@ -461,18 +455,8 @@ PT_D void tile_stream(const PtStreams &T, uint32_t i, int4 &rect, uint64_t &rng,
     tile = lo;
 }
 
-// The small tables of the shading pass in LDS (PT_LDS_TABLE_MAX entries at most each; larger ones are read from global memory)
-struct EmisLds {
-    const float __attribute__((address_space(3))) *cdf_l;
-    lds_f4_cptr rec_l;   // [4 * n_emis]
-    lds_f4_cptr light_l; // [6 * n_emis]: the shading record of an emissive triangle (unused for spheres)
-    PT_D float cdf(int i) const { return cdf_l[i]; }
-    PT_D float4 rec(int i, int k) const { return to_f4(rec_l[4 * i + k]); }
-    PT_D V3 tri_normal_at(int i, uint32_t, V3 pos) const {
-        uint32_t mat_unused;
-        return tri_shade_normal(light_l + 6 * i, pos, mat_unused);
-    }
-};
+// The small tables of the shading pass in LDS (PT_LDS_TABLE_MAX entries at most each; larger ones are read from global memory): the emitters'
+// (EmisLds, pt_shading.h) and the materials
 struct ShadeTables {
     EmisLds emis;
     lds_f4_cptr materials_l;

@@ -218,6 +218,26 @@ struct EmisGlobal {
     }
 };
 
+// ... and as the path kernel holds them in LDS when the scene has at most PT_LDS_TABLE_MAX emitters (pt_kernels.h)
+typedef float f4v __attribute__((ext_vector_type(4)));
+typedef const f4v __attribute__((address_space(3))) *lds_f4_cptr;
+
+PT_D float4 to_f4(f4v v) {
+    return make_float4(v.x, v.y, v.z, v.w);
+}
+
+struct EmisLds {
+    const float __attribute__((address_space(3))) *cdf_l;
+    lds_f4_cptr rec_l;   // [4 * n_emis]
+    lds_f4_cptr light_l; // [6 * n_emis]: the shading record of an emissive triangle (unused for spheres)
+    PT_D float cdf(int i) const { return cdf_l[i]; }
+    PT_D float4 rec(int i, int k) const { return to_f4(rec_l[4 * i + k]); }
+    PT_D V3 tri_normal_at(int i, uint32_t, V3 pos) const {
+        uint32_t mat_unused;
+        return tri_shade_normal(light_l + 6 * i, pos, mat_unused);
+    }
+};
+
 template<typename Tables>
 PT_D bool sample_emissive(const PtDevScene &sc, const Tables &tb, V3 pos, uint64_t &rng, V3 &light_pos, C4 &spectrum, float &pd) {
     const float r = rng_uniform01(rng);

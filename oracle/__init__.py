@@ -75,7 +75,8 @@ def _f32(a, shape=None):
 
 
 def build():
-    """Compile the checkers (oracle always; oracle/_ref only where /root/reference exists)."""
+    """Compile the checkers (oracle always; oracle/_ref only where /root/reference exists).  The Makefile rebuilds a library whenever the
+    content of its sources or its command line differs from what the library was made from (oracle/Makefile: `built`)."""
     subprocess.run(["make", "-s", "-C", HERE], check=True)
 
 
@@ -276,6 +277,26 @@ class Checker:
                                  C.c_void_p(_ptr(states)), C.c_void_p(_ptr(rays)), C.c_void_p(_ptr(st)))
         return rays, st
 
+    # ---- per-pixel estimator (oracle only: the compiled reference's processItem takes no contribution sequence) ----
+    def estimator_run(self, min_sample_count, max_sample_count, stop_bound, contrib, collected, cand_cap=8):
+        """n sequences under one pair of options; contrib [n][len][4], collected [n][len].  Returns a dict: value [n][4], accepted [n],
+        consumed [n], est_f [n][24] and est_i [n][8] (the estimator's fields in PtEstimator's order; est_i[:, 6] = samples consumed),
+        cand_f [n][cand_cap][8] and cand_count [n][cand_cap] (the closed candidates, zero behind them)."""
+        contrib = _f32(contrib)
+        n, length = contrib.shape[0], contrib.shape[1]
+        assert contrib.shape == (n, length, 4)
+        collected = np.ascontiguousarray(collected, dtype=np.uint8)
+        assert collected.shape == (n, length)
+        out = {"value": np.empty((n, 4), np.float32), "accepted": np.empty(n, np.uint8), "consumed": np.empty(n, np.int32),
+               "est_f": np.empty((n, 24), np.float32), "est_i": np.empty((n, 8), np.int32),
+               "cand_f": np.empty((n, cand_cap, 8), np.float32), "cand_count": np.empty((n, cand_cap), np.int32)}
+        self._fn("estimator_run")(C.c_int(min_sample_count), C.c_int(max_sample_count), C.c_int(stop_bound), C.c_uint64(n), C.c_int(length),
+                                  C.c_void_p(_ptr(contrib)), C.c_void_p(_ptr(collected)), C.c_void_p(_ptr(out["value"])),
+                                  C.c_void_p(_ptr(out["accepted"])), C.c_void_p(_ptr(out["consumed"])), C.c_void_p(_ptr(out["est_f"])),
+                                  C.c_void_p(_ptr(out["est_i"])), C.c_int(cand_cap), C.c_void_p(_ptr(out["cand_f"])),
+                                  C.c_void_p(_ptr(out["cand_count"])))
+        return out
+
     # ---- post-processing ----
     def post_process(self, image, steps=3, gamma=1.8):
         """steps: 1 = toneMap, 2 = gammaCorrect(gamma), 3 = postProcess (post_processing.h:14,22,30); returns a new (h, w, 4) array."""
@@ -330,6 +351,28 @@ class SceneHandle:
                                           C.c_void_p(_ptr(cnt)), C.c_void_p(_ptr(lp)), C.c_void_p(_ptr(rgba)), C.c_void_p(_ptr(pd)),
                                           C.c_void_p(_ptr(st)))
         return cnt, lp, rgba, pd, st
+
+    def emissive(self):
+        """The emissive registry (oracle only): object indices in registration order and the normalised CDF."""
+        cap = max(len(self.scene["obj_kind"]), 1)
+        obj, cdf = np.empty(cap, np.int32), np.empty(cap, np.float32)
+        n = self.c._fn("scene_emissive", C.c_uint64)(self.h, C.c_void_p(_ptr(obj)), C.c_void_p(_ptr(cdf)), C.c_uint64(cap))
+        return obj[:n], cdf[:n]
+
+    def normal(self, obj, pos):
+        """The surface normal of object obj[i] (construction index) at pos[i], and the object's material index (NO_MATERIAL: default;
+        the compiled reference has no index to give and returns None for it)."""
+        obj = np.ascontiguousarray(obj, dtype=np.int32)
+        pos = _f32(pos, (-1, 3))
+        assert len(obj) == len(pos)
+        nrm = np.empty((len(pos), 3), np.float32)
+        if self.c.which == "ref":
+            self.c._fn("scene_normal")(self.h, C.c_uint64(len(pos)), C.c_void_p(_ptr(obj)), C.c_void_p(_ptr(pos)), C.c_void_p(_ptr(nrm)))
+            return nrm, None
+        mat = np.empty(len(pos), np.uint32)
+        self.c._fn("scene_normal")(self.h, C.c_uint64(len(pos)), C.c_void_p(_ptr(obj)), C.c_void_p(_ptr(pos)), C.c_void_p(_ptr(nrm)),
+                                   C.c_void_p(_ptr(mat)))
+        return nrm, mat
 
     def get_sample(self, cam, opt, xy_camera, states):
         xy = _f32(xy_camera, (-1, 2))

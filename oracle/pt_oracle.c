@@ -1231,19 +1231,203 @@ typedef struct {
 
 static const c4 C4_ZERO = {{0.0F, 0.0F, 0.0F, 0.0F}};
 
+/* The constants processItem derives from the options once per item (worker.cpp:158-164). */
+typedef struct {
+    int min_sc, max_sc;
+    int stats_sample_count, candidate_batch_count, check_sample_count;
+} est_consts_t;
+
+static est_consts_t est_consts(int min_sc, int max_sc) {
+    est_consts_t k;
+    k.min_sc = min_sc;
+    k.max_sc = max_sc;
+    k.stats_sample_count = i_min(i_max(min_sc / 4, 1), 64);
+    k.candidate_batch_count = i_max(i_max(min_sc, max_sc / 4) / k.stats_sample_count, 2);
+    k.check_sample_count = i_min(i_max(i_max(i_max(min_sc / 2, (max_sc - min_sc) / 8), 8), k.stats_sample_count), 1024) / k.stats_sample_count;
+    return k;
+}
+
+/* The locals of processItem's pixel loop (worker.cpp:172-192) and the two vectors the candidates are kept in. */
+typedef struct {
+    c4 pixel_value;
+    int collected_sample_count;
+    c4 contribution_mean, contribution_m2;
+    int contribution_count;
+    int stats_sample_index;
+    c4 sample_aggregate;
+    size_t n_candidates; /* closed candidates */
+    c4 candidate_mean, candidate_m2;
+    int candidate_count;
+    int remaining_checks;
+    size_t cand_cap;
+    candidate_t *candidates;
+    pixel_candidate_t *pixel_candidates;
+} estimator_t;
+
+static void estimator_init(estimator_t *e) {
+    e->cand_cap = 16;
+    e->candidates = (candidate_t *)malloc(sizeof(candidate_t) * e->cand_cap);
+    e->pixel_candidates = (pixel_candidate_t *)malloc(sizeof(pixel_candidate_t) * e->cand_cap);
+}
+
+static void estimator_free(estimator_t *e) {
+    free(e->candidates);
+    free(e->pixel_candidates);
+}
+
+/* worker.cpp:172-192 */
+static void estimator_reset(estimator_t *e, const est_consts_t *k) {
+    e->pixel_value = C4_ZERO;
+    e->collected_sample_count = 0;
+    e->contribution_mean = C4_ZERO;
+    e->contribution_m2 = C4_ZERO;
+    e->contribution_count = 0;
+    e->stats_sample_index = 0;
+    e->sample_aggregate = C4_ZERO;
+    e->n_candidates = 0;
+    e->candidate_mean = C4_ZERO;
+    e->candidate_m2 = C4_ZERO;
+    e->candidate_count = 0;
+    e->remaining_checks = k->check_sample_count;
+}
+
+/* One collected sample, worker.cpp:196-260; returns 1 where the loop breaks with accepted_candidate. */
+static int estimator_add(estimator_t *e, const est_consts_t *k, c4 color_contribution) {
+    e->contribution_count++;
+    e->stats_sample_index++;
+    e->sample_aggregate = c4_add(e->sample_aggregate, color_contribution);
+
+    if(e->stats_sample_index == k->stats_sample_count) {
+        e->sample_aggregate = c4_div(e->sample_aggregate, (float)k->stats_sample_count);
+
+        c4 delta = c4_sub(e->sample_aggregate, e->contribution_mean);
+        e->contribution_mean = c4_add(e->contribution_mean, c4_div(delta, (float)(e->contribution_count / k->stats_sample_count)));
+        c4 delta2 = c4_sub(e->sample_aggregate, e->contribution_mean);
+        e->contribution_m2 = c4_add(e->contribution_m2, c4_mul(delta, delta2));
+
+        if(e->candidate_count == k->candidate_batch_count) {
+            if(e->n_candidates + 1 >= e->cand_cap) {
+                e->cand_cap *= 2;
+                e->candidates = (candidate_t *)realloc(e->candidates, sizeof(candidate_t) * e->cand_cap);
+                e->pixel_candidates = (pixel_candidate_t *)realloc(e->pixel_candidates, sizeof(pixel_candidate_t) * e->cand_cap);
+            }
+            e->candidates[e->n_candidates].mean = e->candidate_mean;
+            e->candidates[e->n_candidates].m2 = e->candidate_m2;
+            e->candidates[e->n_candidates].count = e->candidate_count;
+            e->n_candidates++;
+            e->candidate_mean = C4_ZERO;
+            e->candidate_m2 = C4_ZERO;
+            e->candidate_count = 0;
+        }
+
+        e->candidate_count++;
+        c4 candidate_delta = c4_sub(e->sample_aggregate, e->candidate_mean);
+        e->candidate_mean = c4_add(e->candidate_mean, c4_div(candidate_delta, (float)e->candidate_count));
+        c4 candidate_delta2 = c4_sub(e->sample_aggregate, e->candidate_mean);
+        e->candidate_m2 = c4_add(e->candidate_m2, c4_mul(candidate_delta, candidate_delta2));
+
+        e->stats_sample_index = 0;
+        e->sample_aggregate = C4_ZERO;
+    }
+
+    e->pixel_value = c4_add(e->pixel_value, color_contribution);
+    e->collected_sample_count++;
+
+    if(e->stats_sample_index == 0 && e->collected_sample_count >= i_max(k->min_sc, 2)) {
+        int passed_check = 0;
+        if(e->contribution_count / k->stats_sample_count >= 2) {
+            c4 m2_weighted = c4_div(e->contribution_m2, (float)(e->contribution_count / k->stats_sample_count - 1));
+            float stddev = sqrtf(m2_weighted.e[0] + m2_weighted.e[1] + m2_weighted.e[2]);
+            /* worker.cpp:245: the ratio is evaluated in double because of the 1E-5 literal */
+            if(stddev < 1E-4F || (double)stddev / ((double)(3 * 3 * get_contribution(e->contribution_mean)) + 1E-5) < (double)0.2F) {
+                passed_check = 1;
+                e->remaining_checks--;
+                if(e->remaining_checks <= 0) {
+                    return 1;
+                }
+            }
+        }
+        if(!passed_check) {
+            e->remaining_checks = k->check_sample_count;
+        }
+    }
+    return 0;
+}
+
+/* After the sample loop, worker.cpp:263-319; returns the pixel's value.  The estimator's fields are left as the loop left them
+ * (the open candidate is appended behind the n_candidates closed ones without counting it). */
+static c4 estimator_finish(estimator_t *e, const est_consts_t *k, int accepted_candidate) {
+    c4 pixel_value = e->pixel_value;
+    if(e->collected_sample_count > 0) {
+        pixel_value = c4_scale(pixel_value, 1.0F / (float)e->collected_sample_count);
+    }
+
+    candidate_t *candidates = e->candidates;
+    pixel_candidate_t *pixel_candidates = e->pixel_candidates;
+    size_t n_candidates = e->n_candidates;
+    if(e->candidate_count > 0) {
+        candidates[n_candidates].mean = e->candidate_mean;
+        candidates[n_candidates].m2 = e->candidate_m2;
+        candidates[n_candidates].count = e->candidate_count;
+        n_candidates++;
+    }
+
+    if(!accepted_candidate) {
+        size_t n_pc = 0;
+        for(size_t i = 0; i < n_candidates; i++) {
+            if(candidates[i].count < i_max((k->candidate_batch_count * 3) / 4, 2)) {
+                continue;
+            }
+            c4 m2_weighted = c4_div(candidates[i].m2, (float)candidates[i].count);
+            float stddev = sqrtf(m2_weighted.e[0] + m2_weighted.e[1] + m2_weighted.e[2]);
+            pixel_candidates[n_pc].color = candidates[i].mean;
+            pixel_candidates[n_pc].stddev = stddev;
+            n_pc++;
+        }
+
+        if(n_pc > 0) {
+            /* std::sort on <= 16 elements is libstdc++'s insertion sort (bits/stl_algo.h __insertion_sort):
+             * an element smaller than the first is rotated to the front, otherwise it is inserted linearly. */
+            for(size_t i = 1; i < n_pc; i++) {
+                pixel_candidate_t val = pixel_candidates[i];
+                if(val.stddev < pixel_candidates[0].stddev) {
+                    memmove(&pixel_candidates[1], &pixel_candidates[0], sizeof(pixel_candidate_t) * i);
+                    pixel_candidates[0] = val;
+                }
+                else {
+                    size_t j = i;
+                    while(val.stddev < pixel_candidates[j - 1].stddev) {
+                        pixel_candidates[j] = pixel_candidates[j - 1];
+                        j--;
+                    }
+                    pixel_candidates[j] = val;
+                }
+            }
+
+            pixel_value = pixel_candidates[0].color;
+            float stddev = pixel_candidates[0].stddev;
+            for(size_t i = 1; i < n_pc; i++) {
+                float stddev_other = pixel_candidates[i].stddev;
+                c4 color_other = pixel_candidates[i].color;
+                if(stddev_other < f_max(stddev + 0.005F, stddev * 1.01F)) {
+                    pixel_value = c4_add(pixel_value, c4_div(c4_sub(color_other, pixel_value), (float)(i + 1)));
+                    stddev = stddev_other;
+                }
+                else {
+                    break;
+                }
+            }
+        }
+    }
+    return pixel_value;
+}
+
 static void process_item(const scene_t *s, const camera_t *cam, const pto_options *opt, const pto_stream *item, rng_t *re, float *out_image,
                          oracle_counters *cnt) {
     const float one_half = 1.0F / 2.0F;
-    const int min_sc = opt->min_sample_count;
-    const int max_sc = opt->max_sample_count;
-
-    int stats_sample_count = i_min(i_max(min_sc / 4, 1), 64);
-    int candidate_batch_count = i_max(i_max(min_sc, max_sc / 4) / stats_sample_count, 2);
-    int check_sample_count = i_min(i_max(i_max(i_max(min_sc / 2, (max_sc - min_sc) / 8), 8), stats_sample_count), 1024) / stats_sample_count;
-
-    size_t cand_cap = 16;
-    candidate_t *candidates = (candidate_t *)malloc(sizeof(candidate_t) * cand_cap);
-    pixel_candidate_t *pixel_candidates = (pixel_candidate_t *)malloc(sizeof(pixel_candidate_t) * cand_cap);
+    const est_consts_t k = est_consts(opt->min_sample_count, opt->max_sample_count);
+    estimator_t e;
+    estimator_init(&e);
 
     for(int y = item->y; y < item->y + item->h; y++) {
         for(int x = item->x; x < item->x + item->w; x++) {
@@ -1251,145 +1435,22 @@ static void process_item(const scene_t *s, const camera_t *cam, const pto_option
             float y_camera = 2 * (((float)y + one_half) / (float)opt->image_height - one_half);
             y_camera = -y_camera;
 
-            c4 pixel_value = C4_ZERO;
-            int collected_sample_count = 0;
-            c4 contribution_mean = C4_ZERO;
-            c4 contribution_m2 = C4_ZERO;
-            int contribution_count = 0;
-            int stats_sample_index = 0;
-            c4 sample_aggregate = C4_ZERO;
-            size_t n_candidates = 0;
-            c4 candidate_mean = C4_ZERO;
-            c4 candidate_m2 = C4_ZERO;
-            int candidate_count = 0;
-            int remaining_checks = check_sample_count;
+            estimator_reset(&e, &k);
             int accepted_candidate = 0;
 
-            for(int pixel_sample = 0; pixel_sample < max_sc; pixel_sample++) {
+            for(int pixel_sample = 0; pixel_sample < k.max_sc; pixel_sample++) {
                 int sample_collected;
                 c4 color_contribution = get_sample(s, cam, opt, x_camera, y_camera, re, &sample_collected, cnt);
                 if(!sample_collected) {
                     continue;
                 }
-                contribution_count++;
-                stats_sample_index++;
-                sample_aggregate = c4_add(sample_aggregate, color_contribution);
-
-                if(stats_sample_index == stats_sample_count) {
-                    sample_aggregate = c4_div(sample_aggregate, (float)stats_sample_count);
-
-                    c4 delta = c4_sub(sample_aggregate, contribution_mean);
-                    contribution_mean = c4_add(contribution_mean, c4_div(delta, (float)(contribution_count / stats_sample_count)));
-                    c4 delta2 = c4_sub(sample_aggregate, contribution_mean);
-                    contribution_m2 = c4_add(contribution_m2, c4_mul(delta, delta2));
-
-                    if(candidate_count == candidate_batch_count) {
-                        if(n_candidates + 1 >= cand_cap) {
-                            cand_cap *= 2;
-                            candidates = (candidate_t *)realloc(candidates, sizeof(candidate_t) * cand_cap);
-                            pixel_candidates = (pixel_candidate_t *)realloc(pixel_candidates, sizeof(pixel_candidate_t) * cand_cap);
-                        }
-                        candidates[n_candidates].mean = candidate_mean;
-                        candidates[n_candidates].m2 = candidate_m2;
-                        candidates[n_candidates].count = candidate_count;
-                        n_candidates++;
-                        candidate_mean = C4_ZERO;
-                        candidate_m2 = C4_ZERO;
-                        candidate_count = 0;
-                    }
-
-                    candidate_count++;
-                    c4 candidate_delta = c4_sub(sample_aggregate, candidate_mean);
-                    candidate_mean = c4_add(candidate_mean, c4_div(candidate_delta, (float)candidate_count));
-                    c4 candidate_delta2 = c4_sub(sample_aggregate, candidate_mean);
-                    candidate_m2 = c4_add(candidate_m2, c4_mul(candidate_delta, candidate_delta2));
-
-                    stats_sample_index = 0;
-                    sample_aggregate = C4_ZERO;
-                }
-
-                pixel_value = c4_add(pixel_value, color_contribution);
-                collected_sample_count++;
-
-                if(stats_sample_index == 0 && collected_sample_count >= i_max(min_sc, 2)) {
-                    int passed_check = 0;
-                    if(contribution_count / stats_sample_count >= 2) {
-                        c4 m2_weighted = c4_div(contribution_m2, (float)(contribution_count / stats_sample_count - 1));
-                        float stddev = sqrtf(m2_weighted.e[0] + m2_weighted.e[1] + m2_weighted.e[2]);
-                        /* worker.cpp:245: the ratio is evaluated in double because of the 1E-5 literal */
-                        if(stddev < 1E-4F || (double)stddev / ((double)(3 * 3 * get_contribution(contribution_mean)) + 1E-5) < (double)0.2F) {
-                            passed_check = 1;
-                            remaining_checks--;
-                            if(remaining_checks <= 0) {
-                                accepted_candidate = 1;
-                                break;
-                            }
-                        }
-                    }
-                    if(!passed_check) {
-                        remaining_checks = check_sample_count;
-                    }
+                if(estimator_add(&e, &k, color_contribution)) {
+                    accepted_candidate = 1;
+                    break;
                 }
             }
 
-            if(collected_sample_count > 0) {
-                pixel_value = c4_scale(pixel_value, 1.0F / (float)collected_sample_count);
-            }
-
-            if(candidate_count > 0) {
-                candidates[n_candidates].mean = candidate_mean;
-                candidates[n_candidates].m2 = candidate_m2;
-                candidates[n_candidates].count = candidate_count;
-                n_candidates++;
-            }
-
-            if(!accepted_candidate) {
-                size_t n_pc = 0;
-                for(size_t i = 0; i < n_candidates; i++) {
-                    if(candidates[i].count < i_max((candidate_batch_count * 3) / 4, 2)) {
-                        continue;
-                    }
-                    c4 m2_weighted = c4_div(candidates[i].m2, (float)candidates[i].count);
-                    float stddev = sqrtf(m2_weighted.e[0] + m2_weighted.e[1] + m2_weighted.e[2]);
-                    pixel_candidates[n_pc].color = candidates[i].mean;
-                    pixel_candidates[n_pc].stddev = stddev;
-                    n_pc++;
-                }
-
-                if(n_pc > 0) {
-                    /* std::sort on <= 16 elements is libstdc++'s insertion sort (bits/stl_algo.h __insertion_sort):
-                     * an element smaller than the first is rotated to the front, otherwise it is inserted linearly. */
-                    for(size_t i = 1; i < n_pc; i++) {
-                        pixel_candidate_t val = pixel_candidates[i];
-                        if(val.stddev < pixel_candidates[0].stddev) {
-                            memmove(&pixel_candidates[1], &pixel_candidates[0], sizeof(pixel_candidate_t) * i);
-                            pixel_candidates[0] = val;
-                        }
-                        else {
-                            size_t j = i;
-                            while(val.stddev < pixel_candidates[j - 1].stddev) {
-                                pixel_candidates[j] = pixel_candidates[j - 1];
-                                j--;
-                            }
-                            pixel_candidates[j] = val;
-                        }
-                    }
-
-                    pixel_value = pixel_candidates[0].color;
-                    float stddev = pixel_candidates[0].stddev;
-                    for(size_t i = 1; i < n_pc; i++) {
-                        float stddev_other = pixel_candidates[i].stddev;
-                        c4 color_other = pixel_candidates[i].color;
-                        if(stddev_other < f_max(stddev + 0.005F, stddev * 1.01F)) {
-                            pixel_value = c4_add(pixel_value, c4_div(c4_sub(color_other, pixel_value), (float)(i + 1)));
-                            stddev = stddev_other;
-                        }
-                        else {
-                            break;
-                        }
-                    }
-                }
-            }
+            c4 pixel_value = estimator_finish(&e, &k, accepted_candidate);
 
             float *o = out_image + 4 * ((size_t)y * (size_t)opt->image_width + (size_t)x);
             o[0] = pixel_value.e[0];
@@ -1398,8 +1459,7 @@ static void process_item(const scene_t *s, const camera_t *cam, const pto_option
             o[3] = pixel_value.e[3];
         }
     }
-    free(candidates);
-    free(pixel_candidates);
+    estimator_free(&e);
 }
 
 /* ------------------------------------------------------------------------------------------------------------------ */
@@ -1609,6 +1669,88 @@ void oracle_scene_sample_lights(void *h, uint64_t n, const float *pos, const uin
         }
         out_states[i] = re.s;
     }
+}
+
+/* The emissive registry: object indices in registration order and the normalised CDF (scene.cpp:167-208); returns their number. */
+uint64_t oracle_scene_emissive(void *h, int32_t *out_obj, float *out_cdf, uint64_t cap) {
+    scene_t *s = (scene_t *)h;
+    for(int i = 0; i < s->n_emissive && (uint64_t)i < cap; i++) {
+        out_obj[i] = s->emissive[i];
+        out_cdf[i] = s->cdf[i];
+    }
+    return (uint64_t)s->n_emissive;
+}
+
+/* obj_normal at chosen positions, and the object's material index (0xFFFFFFFF: the default material) */
+void oracle_scene_normal(void *h, uint64_t n, const int32_t *obj, const float *pos, float *out_n, uint32_t *out_material) {
+    scene_t *s = (scene_t *)h;
+    for(uint64_t i = 0; i < n; i++) {
+        v3_st(out_n + 3 * i, obj_normal(s, obj[i], v3_ld(pos + 3 * i)));
+        out_material[i] = s->kind[obj[i]] == PTO_OBJ_TRIANGLE ? s->tri_mat[s->kidx[obj[i]]] : s->sph_mat[s->kidx[obj[i]]];
+    }
+}
+
+/* The per-pixel estimator of process_item driven with chosen contributions: n sequences of `len` samples ([n][len][4], flags [n][len]),
+ * all under one pair of options.  The sample loop is processItem's (worker.cpp:193-261) with the contribution read instead of traced.
+ * stop_bound is the progressive pass's bound on the overlap flags (PtDevOptions::overlap_bound); the reference has no such flag and the
+ * oracle ignores it -- the argument keeps the list equal to the device probe's.
+ * out_est_f [n][24]: pixel_value, contribution_mean, contribution_m2, sample_aggregate, candidate_mean, candidate_m2 as the loop left them;
+ * out_est_i [n][8]: collected_sample_count, contribution_count, stats_sample_index, candidate_count, remaining_checks, n_candidates
+ * (closed), samples consumed, 0.  out_cand_f [n][cand_cap][8] (mean, m2) and out_cand_count [n][cand_cap]: the first
+ * min(n_candidates, cand_cap) closed candidates, zero behind them. */
+void oracle_estimator_run(int min_sample_count, int max_sample_count, int stop_bound, uint64_t n, int len, const float *contrib,
+                          const uint8_t *collected, float *out_value, uint8_t *out_accepted, int32_t *out_consumed, float *out_est_f,
+                          int32_t *out_est_i, int cand_cap, float *out_cand_f, int32_t *out_cand_count) {
+    (void)stop_bound;
+    const est_consts_t k = est_consts(min_sample_count, max_sample_count);
+    estimator_t e;
+    estimator_init(&e);
+    for(uint64_t i = 0; i < n; i++) {
+        estimator_reset(&e, &k);
+        int accepted_candidate = 0;
+        int pixel_sample;
+        for(pixel_sample = 0; pixel_sample < k.max_sc && pixel_sample < len; pixel_sample++) {
+            size_t at = (size_t)i * (size_t)len + (size_t)pixel_sample;
+            if(!collected[at]) {
+                continue;
+            }
+            if(estimator_add(&e, &k, c4_ld(contrib + 4 * at))) {
+                accepted_candidate = 1;
+                pixel_sample++; /* the accepting sample was consumed */
+                break;
+            }
+        }
+        c4 value = estimator_finish(&e, &k, accepted_candidate);
+        memcpy(out_value + 4 * i, value.e, 16);
+        out_accepted[i] = (uint8_t)accepted_candidate;
+        out_consumed[i] = pixel_sample;
+        const c4 *f[6] = {&e.pixel_value, &e.contribution_mean, &e.contribution_m2, &e.sample_aggregate, &e.candidate_mean, &e.candidate_m2};
+        for(int j = 0; j < 6; j++) {
+            memcpy(out_est_f + 24 * i + 4 * j, f[j]->e, 16);
+        }
+        int32_t *ei = out_est_i + 8 * i;
+        ei[0] = e.collected_sample_count;
+        ei[1] = e.contribution_count;
+        ei[2] = e.stats_sample_index;
+        ei[3] = e.candidate_count;
+        ei[4] = e.remaining_checks;
+        ei[5] = (int32_t)e.n_candidates;
+        ei[6] = pixel_sample;
+        ei[7] = 0;
+        for(int j = 0; j < cand_cap; j++) {
+            size_t o = (size_t)i * (size_t)cand_cap + (size_t)j;
+            if((size_t)j < e.n_candidates) {
+                memcpy(out_cand_f + 8 * o, e.candidates[j].mean.e, 16);
+                memcpy(out_cand_f + 8 * o + 4, e.candidates[j].m2.e, 16);
+                out_cand_count[o] = e.candidates[j].count;
+            }
+            else {
+                memset(out_cand_f + 8 * o, 0, 32);
+                out_cand_count[o] = 0;
+            }
+        }
+    }
+    estimator_free(&e);
 }
 
 static void dump_bvh(const scene_t *s, int node, int32_t *out_obj, float *out_box, size_t *pos) {

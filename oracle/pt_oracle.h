@@ -54,12 +54,20 @@ void oracle_scene_destroy(void *h);
 void oracle_scene_intersect(void *h, uint64_t n, const float *rays, float *out_t, int32_t *out_obj);
 void oracle_scene_sample_lights(void *h, uint64_t n, const float *pos, const uint64_t *states, int max_lights, int32_t *out_count, float *out_pos,
                                 float *out_rgba, float *out_pd, uint64_t *out_states);
+uint64_t oracle_scene_emissive(void *h, int32_t *out_obj, float *out_cdf, uint64_t cap);
+void oracle_scene_normal(void *h, uint64_t n, const int32_t *obj, const float *pos, float *out_n, uint32_t *out_material);
 uint64_t oracle_bvh_dump(const pto_scene_desc *d, int32_t *out_obj, float *out_box);
 
 void oracle_get_sample(void *h, const pto_camera_params *cp, const pto_options *op, uint64_t n, const float *xy_camera, const uint64_t *states,
                        float *out_rgba, uint8_t *out_collected, uint64_t *out_states);
 void oracle_render_streams(void *h, const pto_camera_params *cp, const pto_options *op, const pto_stream *streams, uint64_t n, float *out_image,
                            uint64_t *out_states, int n_threads);
+
+/* The per-pixel estimator on chosen contribution sequences (see pt_oracle.c); no counterpart in ref_shim.cpp: the compiled reference's
+ * processItem cannot be handed a contribution sequence. */
+void oracle_estimator_run(int min_sample_count, int max_sample_count, int stop_bound, uint64_t n, int len, const float *contrib,
+                          const uint8_t *collected, float *out_value, uint8_t *out_accepted, int32_t *out_consumed, float *out_est_f,
+                          int32_t *out_est_i, int cand_cap, float *out_cand_f, int32_t *out_cand_count);
 
 /* Counters accumulated by oracle_get_sample / oracle_render_streams / oracle_scene_intersect on this scene since the last reset. */
 void oracle_counters_reset(void *h);

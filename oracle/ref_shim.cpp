@@ -444,6 +444,21 @@ void ref_scene_sample_lights(void *h, uint64_t n, const float *pos, const uint64
     }
 }
 
+// Object::getSurfaceNormal of the scene's objects, by construction index, at chosen positions.
+void ref_scene_normal(void *h, uint64_t n, const int32_t *obj, const float *pos, float *out_n) {
+    auto *rs = static_cast<RefScene *>(h);
+    std::vector<const Object *> by_index(rs->index.size(), nullptr);
+    for(const auto &[object, i] : rs->index) {
+        by_index[static_cast<size_t>(i)] = object;
+    }
+    for(uint64_t i = 0; i < n; i++) {
+        auto nn = by_index[static_cast<size_t>(obj[i])]->getSurfaceNormal(v3(pos + 3 * i));
+        for(int k = 0; k < 3; k++) {
+            out_n[3 * i + k] = nn[k];
+        }
+    }
+}
+
 // Pre-order dump of impl::constructBVH over the same leaves Scene::Scene builds (scene.cpp:156-162).
 // out_obj[i] = object index for a leaf, -1 for an inner node; out_box[i] = low xyz, high xyz.  Returns node count.
 uint64_t ref_bvh_dump(const pto_scene_desc *d, int32_t *out_obj, float *out_box) {

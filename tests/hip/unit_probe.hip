@@ -3,7 +3,8 @@
 // Built by tests/unit_probe.py into tests/hip/libunit_probe.so with the product's compiler flags; not part of libpathtrace_hip.so.
 // The product headers are included unchanged.  Every entry point ptu_* takes the arrays of the matching method of oracle.Checker
 // (oracle/__init__.py), copies them to device 0, runs a one-thread-per-case kernel (256-thread workgroups, guarded tail), copies the
-// results back and returns the HIP error code (0 = hipSuccess).  The libm entries also evaluate the same PT_HD function on the host and
+// results back and returns the HIP error code (0 = hipSuccess).  ptu_estimator_run (the per-pixel estimator of pt_shading.h) keeps its
+// outputs between guard bands (guard_band.h) and returns PT_GUARD_TOUCHED + the buffer's number when one was written.  The libm entries also evaluate the same PT_HD function on the host and
 // return the number of inputs whose results differ and the first 16 of them.
 #include <hip/hip_runtime.h>
 
@@ -14,7 +15,9 @@
 #include <vector>
 
 #include "../../cpupathtrace_amd/csrc/pt_device.h"
+#include "../../cpupathtrace_amd/csrc/pt_shading.h"
 #include "../../include/pt_hip.h"
+#include "guard_band.h"
 
 using namespace ptd;
 
@@ -24,18 +27,9 @@ constexpr unsigned WG = 256;
 
 // ---- plumbing ------------------------------------------------------------------------------------------------------
 
-// The first HIP error of an entry point; every later step is skipped once it is set.
-struct Status {
-    hipError_t err = hipSuccess;
-    bool ok() const {
-        return err == hipSuccess;
-    }
-    void operator()(hipError_t e) {
-        if(err == hipSuccess && e != hipSuccess) {
-            err = e;
-        }
-    }
-};
+// The first HIP error of an entry point; every later step is skipped once it is set (guard_band.h; the guard part is used by the entries
+// that keep their outputs between guard bands).
+using Status = GuardStatus;
 
 // A device array of n elements of T, filled from `src` when given; freed when it goes out of scope.
 template<typename T>
@@ -286,6 +280,40 @@ PtDevCamera probe_camera(const pt_camera_params *c) {
     return cam;
 }
 
+// ---- kernels: estimator -------------------------------------------------------------------------------------------------
+
+// One sequence per thread through the loop of the path kernel's finished-sample branch (pt_path.hip): estimator_reset; per sample the
+// overlap question, estimator_add if the sample was collected, pixel_sample++; estimator_finish on acceptance or at max_sample_count.
+// The estimator and its closed candidates lie in global memory, as PtSlots::est / cand do.
+__global__ void k_estimator_run(PtDevOptions opt, uint64_t n, int len, const float *contrib, const uint8_t *collected, PtEstimator *est,
+                                PtCandidate *cand_all, float *out_value, uint8_t *out_accepted, uint8_t *out_overlap) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if(i >= n) {
+        return;
+    }
+    PtCandidate *cand = cand_all + i * PT_MAX_CANDIDATES;
+    estimator_reset(est[i], opt);
+    for(;;) {
+        PtEstimator e = est[i];
+        if(e.pixel_sample >= len) {
+            break; // (the host refuses len < max_sample_count; this keeps every read inside the arrays regardless)
+        }
+        const uint64_t at = i * (uint64_t)len + (uint64_t)e.pixel_sample;
+        out_overlap[at] = estimator_safe_to_overlap(e, opt) ? 1 : 0;
+        bool accepted = false;
+        if(collected[at] != 0) {
+            accepted = estimator_add(e, cand, opt, ld4(contrib + 4 * at));
+        }
+        e.pixel_sample++;
+        est[i] = e;
+        if(accepted || e.pixel_sample >= opt.max_sample_count) {
+            st4(out_value + 4 * i, estimator_finish(e, cand, opt, accepted));
+            out_accepted[i] = accepted ? 1 : 0;
+            break;
+        }
+    }
+}
+
 // ---- kernels: libm ---------------------------------------------------------------------------------------------------------
 
 // out[4 * i ..]: sinf, cosf, and the two results of sincosf
@@ -395,7 +423,7 @@ int ptu_device_count(void) {
 }
 
 const char *ptu_error_string(int code) {
-    return hipGetErrorString(static_cast<hipError_t>(code));
+    return code >= PT_GUARD_TOUCHED ? "a guard band was written" : hipGetErrorString(static_cast<hipError_t>(code));
 }
 
 // ---- engine --------------------------------------------------------------------------------------------------------------
@@ -558,6 +586,80 @@ int ptu_camera_shoot(const pt_camera_params *cp, uint64_t n, const float *xy, fl
 int ptu_camera_shoot_lane(const pt_camera_params *cp, uint64_t n, const float *xy, float pixel_width, float pixel_height, const uint64_t *states,
                           float *out_ray, uint64_t *out_states) {
     return camera_entry(true, cp, n, xy, pixel_width, pixel_height, states, out_ray, out_states);
+}
+
+// ---- estimator ---------------------------------------------------------------------------------------------------------------
+
+// The arguments and results of oracle_estimator_run (oracle/pt_oracle.h; cand_cap is PT_MAX_CANDIDATES here) plus out_overlap [n][len]:
+// estimator_safe_to_overlap before every consumed sample, 0 behind the last one.  The options are derived as derive_options of pt_api.cpp
+// derives them (worker.cpp:158-164); overlap_bound = stop_bound.
+int ptu_estimator_run(int min_sample_count, int max_sample_count, int stop_bound, uint64_t n, int len, const float *contrib,
+                      const uint8_t *collected, float *out_value, uint8_t *out_accepted, int32_t *out_consumed, float *out_est_f,
+                      int32_t *out_est_i, float *out_cand_f, int32_t *out_cand_count, uint8_t *out_overlap) {
+    static_assert(sizeof(PtEstimator) == 128 && sizeof(PtCandidate) == 48, "the probe splits these records into float and int parts");
+    if(len < max_sample_count || len < 1 || max_sample_count < 1) {
+        return static_cast<int>(hipErrorInvalidValue);
+    }
+    PtDevOptions d{};
+    d.image_width = 1;
+    d.image_height = 1;
+    d.min_sample_count = min_sample_count;
+    d.max_sample_count = max_sample_count;
+    d.overlap_bound = stop_bound;
+    d.pixel_width = 1.0f;
+    d.pixel_height = 1.0f;
+    d.stats_sample_count = std::min(std::max(min_sample_count / 4, 1), 64);
+    d.candidate_batch_count = std::max(std::max(min_sample_count, max_sample_count / 4) / d.stats_sample_count, 2);
+    d.check_sample_count =
+      std::min(std::max({min_sample_count / 2, (max_sample_count - min_sample_count) / 8, 8, d.stats_sample_count}), 1024) / d.stats_sample_count;
+
+    Status st;
+    const size_t g = WG + 64, steps = (size_t)n * (size_t)len;
+    Dev<float> d_contrib(st, 4 * steps, contrib);
+    Dev<uint8_t> d_collected(st, steps, collected);
+    Guarded<PtEstimator> d_est(st, n, g);
+    Guarded<PtCandidate> d_cand(st, n * PT_MAX_CANDIDATES, g);
+    Guarded<float> d_value(st, 4 * n, g);
+    Guarded<uint8_t> d_accepted(st, n, g), d_overlap(st, steps, g);
+    if(st.ok()) {
+        k_estimator_run<<<grid_for(n), dim3(WG)>>>(d, n, len, d_contrib.p, d_collected.p, d_est.p(), d_cand.p(), d_value.p(), d_accepted.p(),
+                                                   d_overlap.p());
+        st(hipGetLastError());
+        st(hipDeviceSynchronize());
+    }
+    std::vector<PtEstimator> est(n);
+    std::vector<PtCandidate> cand(n * PT_MAX_CANDIDATES);
+    d_est.get(est.data());
+    d_cand.get(cand.data());
+    d_value.get(out_value);
+    d_accepted.get(out_accepted);
+    d_overlap.get(out_overlap);
+    const int rc = finish(st);
+    if(rc != 0) {
+        return rc;
+    }
+    for(uint64_t i = 0; i < n; i++) {
+        const PtEstimator &e = est[i];
+        const float *f[6] = {e.pixel_value, e.contribution_mean, e.contribution_m2, e.sample_aggregate, e.candidate_mean, e.candidate_m2};
+        for(int j = 0; j < 6; j++) {
+            std::copy(f[j], f[j] + 4, out_est_f + 24 * i + 4 * j);
+        }
+        const int32_t v[8] = {e.collected_sample_count, e.contribution_count, e.stats_sample_index, e.candidate_count,
+                              e.remaining_checks,       e.n_candidates,       e.pixel_sample,       e.pad};
+        std::copy(v, v + 8, out_est_i + 8 * i);
+        out_consumed[i] = e.pixel_sample;
+        for(int j = 0; j < PT_MAX_CANDIDATES; j++) {
+            const PtCandidate &c = cand[i * PT_MAX_CANDIDATES + j];
+            std::copy(c.mean, c.mean + 4, out_cand_f + 8 * (i * PT_MAX_CANDIDATES + j));
+            std::copy(c.m2, c.m2 + 4, out_cand_f + 8 * (i * PT_MAX_CANDIDATES + j) + 4);
+            out_cand_count[i * PT_MAX_CANDIDATES + j] = c.count;
+        }
+    }
+    return st.code();
+}
+
+int ptu_max_candidates(void) {
+    return PT_MAX_CANDIDATES;
 }
 
 // ---- libm: device header against the same header compiled for the host ------------------------------------------------------

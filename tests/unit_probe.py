@@ -18,14 +18,14 @@ from oracle import _f32, _ptr, camera_params
 HERE = os.path.dirname(os.path.abspath(__file__))
 SOURCE = os.path.join(HERE, "hip", "unit_probe.hip")
 LIB = os.path.join(HERE, "hip", "libunit_probe.so")
-HEADERS = ["pt_device.h", "pt_libm.h", "pt_types.h", os.path.join("..", "..", "include", "pt_hip.h"), os.path.join("..", "..", "include", "pt_frame_noise.h")]
+HEADERS = ["pt_device.h", "pt_shading.h", "pt_kernels.h", "pt_libm.h", "pt_types.h", os.path.join("..", "..", "include", "pt_hip.h"), os.path.join("..", "..", "include", "pt_frame_noise.h")]
 
 
 def up_to_date(lib=LIB):
     if not os.path.exists(lib):
         return False
     t = os.path.getmtime(lib)
-    deps = [SOURCE, os.path.abspath(__file__), os.path.abspath(product.__file__)] + [os.path.join(product.CSRC, h) for h in HEADERS]
+    deps = [SOURCE, os.path.join(HERE, "hip", "guard_band.h"), os.path.abspath(__file__), os.path.abspath(product.__file__)] + [os.path.join(product.CSRC, h) for h in HEADERS]
     return all(os.path.getmtime(d) <= t for d in deps)
 
 
@@ -172,6 +172,29 @@ class Probe:
 
     def camera_shoot_lane(self, cam, xy, pixel_width, pixel_height, states):
         return self._camera("camera_shoot_lane", cam, xy, pixel_width, pixel_height, states)
+
+    # ---- per-pixel estimator (pt_shading.h) ----
+    def max_candidates(self):
+        return int(self.lib.ptu_max_candidates())
+
+    def estimator_run(self, min_sample_count, max_sample_count, stop_bound, contrib, collected):
+        """oracle.Checker.estimator_run on the device (cand_cap = PT_MAX_CANDIDATES), plus "overlap" [n][len]: estimator_safe_to_overlap
+        before every consumed sample."""
+        contrib = _f32(contrib)
+        n, length = contrib.shape[0], contrib.shape[1]
+        assert contrib.shape == (n, length, 4)
+        collected = np.ascontiguousarray(collected, dtype=np.uint8)
+        assert collected.shape == (n, length)
+        cap = self.max_candidates()
+        out = {"value": np.empty((n, 4), np.float32), "accepted": np.empty(n, np.uint8), "consumed": np.empty(n, np.int32),
+               "est_f": np.empty((n, 24), np.float32), "est_i": np.empty((n, 8), np.int32),
+               "cand_f": np.empty((n, cap, 8), np.float32), "cand_count": np.empty((n, cap), np.int32),
+               "overlap": np.empty((n, length), np.uint8)}
+        self._call("estimator_run", C.c_int(min_sample_count), C.c_int(max_sample_count), C.c_int(stop_bound), C.c_uint64(n), C.c_int(length),
+                   C.c_void_p(_ptr(contrib)), C.c_void_p(_ptr(collected)), C.c_void_p(_ptr(out["value"])), C.c_void_p(_ptr(out["accepted"])),
+                   C.c_void_p(_ptr(out["consumed"])), C.c_void_p(_ptr(out["est_f"])), C.c_void_p(_ptr(out["est_i"])),
+                   C.c_void_p(_ptr(out["cand_f"])), C.c_void_p(_ptr(out["cand_count"])), C.c_void_p(_ptr(out["overlap"])))
+        return out
 
     # ---- libm: device header against the same header compiled for the host: (mismatch count, first mismatching inputs, count of inputs
     # on which the host compile differs from the running C library) ----
