@@ -52,6 +52,9 @@ EXPORTS += TEMPORAL_EXPORTS
 NOISE_EXPORTS = ["pt_frame_get_noise", "pt_frame_set_noise_target"]
 # (... and these in include/pt_frame_variance.h)
 VARIANCE_EXPORTS = ["pt_denoise_measured_params_default", "pt_frame_get_variance", "pt_denoise_measured", "pt_denoise_measured_device", "pt_frame_preview_measured"]
+# (... and these in include/pt_features.h)
+FEATURES_EXPORTS = ["pt_feature_params_default", "pt_render_features_followed", "pt_render_features_followed_device", "pt_render_features_followed_views",
+                    "pt_render_features_followed_views_device", "pt_frame_set_feature_params"]
 
 
 
@@ -140,6 +143,35 @@ def denoise_views_device(d_rgba_ptr, d_features_ptr, width, height, n_views, d_o
     """pt_denoise_views_device on device memory: as denoise_device, every array holding n_views frames."""
     _check(load().pt_denoise_views_device(C.c_int(device), C.c_void_p(d_rgba_ptr), C.c_void_p(d_features_ptr), C.c_int32(width), C.c_int32(height),
                                           C.c_int32(n_views), _denoise_params(params), C.c_void_p(d_out_ptr), C.c_void_p(stream_ptr)))
+
+
+class FeatureParams(C.Structure):
+    """pt_feature_params: how far a followed feature ray goes through mirrors and glass (max_bounces, 0..32); flags must be 0."""
+    _fields_ = [("max_bounces", C.c_int32), ("flags", C.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+def feature_params_default():
+    """The library's default parameters of the followed features (pt_feature_params_default) as a dict."""
+    p = FeatureParams()
+    _check(load().pt_feature_params_default(C.byref(p)))
+    return p.as_dict()
+
+
+def _feature_params(params):
+    """A FeatureParams as it is; otherwise a dict whose missing keys take the library's defaults."""
+    if isinstance(params, FeatureParams):
+        return params
+    unknown = set(params) - {k for k, _ in FeatureParams._fields_}
+    if unknown:
+        raise ValueError("unknown feature parameters: %s" % ", ".join(sorted(unknown)))
+    p = FeatureParams()
+    _check(load().pt_feature_params_default(C.byref(p)))
+    for k, v in params.items():
+        setattr(p, k, v)
+    return p
 
 
 class DenoiseMeasuredParams(C.Structure):
@@ -558,11 +590,17 @@ class Scene:
             image = denoise(image, self.render_features(camera, options), device=self.device)
         return (image, st.as_dict()) if want_stats else image
 
-    def render_features(self, camera, options):
+    def render_features(self, camera, options, followed=None):
         """First-hit features of the frame (pt_render_features): an (H, W, 3, 4) float32 array, the mean over 4 deterministic primary rays
-        per pixel of [albedo rgb, coverage], [normal xyz, t], [position xyz, emission luminance]."""
+        per pixel of [albedo rgb, coverage], [normal xyz, t], [position xyz, emission luminance].  followed: a FeatureParams or a dict of
+        its fields ({} = the defaults) makes the rays go on through mirrors and glass to the first diffuse hit
+        (pt_render_features_followed; options' epsilon is read too); None = first-hit."""
         out = np.empty((options["image_height"], options["image_width"], 3, 4), np.float32)
         cp, op = _camera(camera), _options(options)
+        if followed is not None:
+            fp = _feature_params(followed)
+            _check(load().pt_render_features_followed(self._h, C.byref(cp), C.byref(op), C.byref(fp), _ptr(out)))
+            return out
         _check(load().pt_render_features(self._h, C.byref(cp), C.byref(op), _ptr(out)))
         return out
 
@@ -578,24 +616,37 @@ class Scene:
                 out[v], _ = t.denoise(frames[v], self.render_features(cam, options), cam)
         return out
 
-    def render_features_views(self, cameras, options):
+    def render_features_views(self, cameras, options, followed=None):
         """render_features for V cameras in one launch (pt_render_features_views): a (V, H, W, 3, 4) float32 array whose view v equals
-        render_features(cameras[v], options) bit for bit."""
+        render_features(cameras[v], options) bit for bit.  followed: as in render_features (pt_render_features_followed_views)."""
         cams, _ = _view_tables(cameras, 0)
         out = np.empty((len(cams), options["image_height"], options["image_width"], 3, 4), np.float32)
         op = _options(options)
+        if followed is not None:
+            fp = _feature_params(followed)
+            _check(load().pt_render_features_followed_views(self._h, cams, C.c_int32(len(cams)), C.byref(op), C.byref(fp), _ptr(out)))
+            return out
         _check(load().pt_render_features_views(self._h, cams, C.c_int32(len(cams)), C.byref(op), _ptr(out)))
         return out
 
-    def render_features_views_device(self, cameras, options, d_features_ptr, stream_ptr=0):
+    def render_features_views_device(self, cameras, options, d_features_ptr, stream_ptr=0, followed=None):
         """render_features_views into device memory (d_features_ptr: device address of V*H*W*12 floats), ordered on stream_ptr."""
         cams, _ = _view_tables(cameras, 0)
         op = _options(options)
+        if followed is not None:
+            fp = _feature_params(followed)
+            _check(load().pt_render_features_followed_views_device(self._h, cams, C.c_int32(len(cams)), C.byref(op), C.byref(fp), C.c_void_p(d_features_ptr),
+                                                                   C.c_void_p(stream_ptr)))
+            return
         _check(load().pt_render_features_views_device(self._h, cams, C.c_int32(len(cams)), C.byref(op), C.c_void_p(d_features_ptr), C.c_void_p(stream_ptr)))
 
-    def render_features_device(self, camera, options, d_features_ptr, stream_ptr=0):
+    def render_features_device(self, camera, options, d_features_ptr, stream_ptr=0, followed=None):
         """render_features into device memory (d_features_ptr: device address of H*W*12 floats, e.g. an (H, W, 3, 4) tensor), ordered on stream_ptr."""
         cp, op = _camera(camera), _options(options)
+        if followed is not None:
+            fp = _feature_params(followed)
+            _check(load().pt_render_features_followed_device(self._h, C.byref(cp), C.byref(op), C.byref(fp), C.c_void_p(d_features_ptr), C.c_void_p(stream_ptr)))
+            return
         _check(load().pt_render_features_device(self._h, C.byref(cp), C.byref(op), C.c_void_p(d_features_ptr), C.c_void_p(stream_ptr)))
 
     def process_work_item(self, camera, options, x, y, w, h, rng_state, want_stats=False):
@@ -733,6 +784,15 @@ class Frame:
         fi = FrameInfo()
         _check(load().pt_frame_get_info(self._h, C.byref(fi)))
         return fi.as_dict()
+
+    def set_feature_params(self, params):
+        """pt_frame_set_feature_params: the frame's denoised previews use followed features (a FeatureParams or a dict of its fields);
+        None restores the first-hit features.  The cached features are dropped either way."""
+        if params is None:
+            _check(load().pt_frame_set_feature_params(self._h, None))
+            return
+        fp = _feature_params(params)
+        _check(load().pt_frame_set_feature_params(self._h, C.byref(fp)))
 
     def set_progressive(self, quantum, max_passes_per_call=0):
         """Progressive mode (pt_frame_set_progressive): render() then works in passes, each bringing every unfinished pixel to `quantum`

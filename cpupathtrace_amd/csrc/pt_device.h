@@ -414,6 +414,54 @@ PT_D Ray bsdf_propagate(const Material &m, V3 ray_d, V3 pos, V3 normal, float ep
     return out;
 }
 
+// The deterministic continuation of a followed feature ray (pt_path.hip: pt_follow_kernel; include/pt_features.h) through glass or a
+// mirror -- never called for a Lambertian material.  No draw is made.  Glass: the reflection branch of bsdf_propagate where
+// sin_theta_t >= 1 (its Bernoulli has p = 1 there), the refraction branch everywhere else; a mirror: the ray bsdf_propagate returns, the
+// one-way pass-through included.  Each branch is bsdf_propagate's arithmetic, operation for operation.  `reflected`: the ray stays
+// on the side it came from.
+PT_D Ray bsdf_follow(const Material &m, V3 ray_d, V3 pos, V3 normal, float epsilon, bool &reflected) {
+    Ray out;
+    if(m.bsdf == 1) {
+        float ray_dot = -dot(ray_d, normal);
+        float ri_leaving = ray_dot >= 0 ? 1.0f : m.ior;
+        float ri_entering = ray_dot >= 0 ? m.ior : 1.0f;
+        float rd = __builtin_fabsf(ray_dot);
+        float sin_theta_i = __builtin_sqrtf(fmax_std(1.0f - rd * rd, 0.0f));
+        float sin_theta_t = ri_leaving / ri_entering * sin_theta_i;
+        if(sin_theta_t >= 1.0f) {
+            V3 dir = reflect(ray_d, normal * (ray_dot < 0.0f ? -1.0f : 1.0f));
+            out.o = pos + dir * epsilon;
+            out.d = dir;
+            reflected = true;
+            return out;
+        }
+        float cos_theta_t = __builtin_sqrtf(fmax_std(1.0f - sin_theta_t * sin_theta_t, 0.0f));
+        float ri_ratio = ri_leaving / ri_entering;
+        V3 out_dir = ray_d * ri_ratio + (normal * (ri_ratio * rd - cos_theta_t)) * (ray_dot < 0.0f ? -1.0f : 1.0f);
+        out_dir = normalize(out_dir);
+        out.o = pos + out_dir * epsilon;
+        out.d = out_dir;
+        reflected = false;
+        return out;
+    }
+    bool unaligned = dot(ray_d, normal) > 0.0f;
+    if(m.one_way && unaligned) {
+        out.o = pos + ray_d * epsilon;
+        out.d = ray_d;
+        reflected = false;
+        return out;
+    }
+    V3 normal_dir = normal;
+    if(!m.one_way && unaligned) {
+        normal_dir = normal_dir * -1.0f;
+    }
+    V3 dir = reflect(ray_d, normal_dir);
+    out.o = pos + dir * epsilon;
+    out.d = dir;
+    reflected = true;
+    return out;
+}
+
 // BSDF::getSpectrum (propagation.cpp:107-116, 162-176, 206-217)
 PT_D C4 bsdf_spectrum(const Material &m, V3 from_dir, V3 to_dir, V3 normal, C4 light, bool synthetic, float &shade, float &p) {
     if(m.bsdf == 0) {

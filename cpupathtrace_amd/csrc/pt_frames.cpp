@@ -81,6 +81,9 @@ struct pt_frame {
     // device time of the gather kernels of the last variance map, all replicas, and of the filter of the last denoised preview
     // (tools/measured_probe.py)
     double variance_gather_ms = 0.0, preview_filter_ms = 0.0;
+    // pt_frame_set_feature_params: the denoised previews take followed features (include/pt_features.h) with these parameters
+    bool follow_features = false;
+    pt_feature_params feature_params{};
     PtNoiseRule noise_rule(const PtDevOptions &opt, bool holding) const {
         PtNoiseRule rule;
         rule.opt = opt;
@@ -543,6 +546,26 @@ int pt_frame_set_progressive(pt_frame *f, int32_t quantum, int32_t max_passes_pe
     return PT_OK;
 }
 
+int pt_frame_set_feature_params(pt_frame *f, const pt_feature_params *params) {
+    if(f == nullptr) {
+        return fail(PT_ERR_INVALID, "null frame");
+    }
+    pt_feature_params follow{};
+    if(params != nullptr) {
+        PT_TRY(feature_params_resolve(params, &f->options, &follow)); // (the options of a frame never change)
+    }
+    std::lock_guard<std::mutex> lock(f->mutex);
+    if(f->status != PT_OK) {
+        return fail(f->status, f->error);
+    }
+    f->follow_features = params != nullptr;
+    f->feature_params = follow;
+    for(auto &r : f->reps) {
+        r->pv_features_ready = false; // the next denoised preview computes its features again
+    }
+    return PT_OK;
+}
+
 int pt_frame_get_progress(const pt_frame *f, pt_frame_progress *out) {
     if(f == nullptr || out == nullptr) {
         return fail(PT_ERR_INVALID, "null argument");
@@ -753,7 +776,8 @@ static int frame_preview(pt_frame *f, const float *image, bool denoise, const Pt
     if(denoise) {
         if(!r0.pv_features_ready) {
             PT_HIP(r0.pv_features.ensure(3 * n));
-            PT_TRY(features_views_launch(s0, f->n_views > 1 ? f->cameras.data() : &f->camera, f->n_views, &f->options, reinterpret_cast<float4 *>(r0.pv_features.ptr)));
+            PT_TRY(features_views_launch(s0, f->n_views > 1 ? f->cameras.data() : &f->camera, f->n_views, &f->options, reinterpret_cast<float4 *>(r0.pv_features.ptr),
+                                         f->follow_features ? &f->feature_params : nullptr));
             r0.pv_features_ready = true;
         }
         DenoiseWorkspace &ws = denoise_workspace(s0->device);

@@ -369,8 +369,12 @@ struct StreamOrder {
 // ---- pt_image.cpp ----------------------------------------------------------------------------------------------------------------------
 
 // Enqueues the feature pass for the stacked frames of n_views cameras on the scene's stream (render_mutex held), in one launch: into
-// `d_out`, n_views * width * height * 3 float4.
-int features_views_launch(pt_scene *s, const pt_camera_params *cameras, int32_t n_views, const pt_options *options, float4 *d_out);
+// `d_out`, n_views * width * height * 3 float4.  follow == nullptr: first-hit features (pt_feature_kernel); else the followed ones
+// (pt_follow_kernel; include/pt_features.h) with parameters that feature_params_resolve has passed and options->epsilon.
+int features_views_launch(pt_scene *s, const pt_camera_params *cameras, int32_t n_views, const pt_options *options, float4 *d_out,
+                          const pt_feature_params *follow = nullptr);
+// The parameters of the followed feature entries (NULL = pt_feature_params_default) and the epsilon they read, checked without a device
+int feature_params_resolve(const pt_feature_params *params, const pt_options *options, pt_feature_params *resolved);
 
 // The denoiser's scratch buffers: one set per device, grown on demand, one call at a time per device.  They live as long as the process
 // (never freed: a static destructor would run after the HIP runtime has gone).

@@ -50,7 +50,7 @@ int pt_post_process(int device, float *rgba, int32_t width, int32_t height, uint
 // ---- feature-guided denoising (pt_path.hip: pt_feature_kernel; pt_denoise.hip) -------------------------------------------------------
 
 // Enqueues the feature pass on the scene's stream (render_mutex held): into `d_out`, width * height * 3 float4.
-static int features_launch(pt_scene *s, const pt_camera_params *camera, const pt_options *options, float4 *d_out) {
+static int features_launch(pt_scene *s, const pt_camera_params *camera, const pt_options *options, float4 *d_out, const pt_feature_params *follow) {
     PT_TRY(setup_path(s));
     PtDevCamera cam = derive_camera(camera);
     cam.aperture_kind = PT_APERTURE_NONE; // the rays are a pure function of camera and pixel
@@ -58,7 +58,12 @@ static int features_launch(pt_scene *s, const pt_camera_params *camera, const pt
     const size_t n = static_cast<size_t>(options->image_width) * static_cast<size_t>(options->image_height);
     PT_HIP(s->feature_spill.ensure(((n + 255) / 256) * 256 * cfg.spill_depth));
     cfg.spill = s->feature_spill.ptr;
-    pt_launch_features(s->stream, s->dev, cam, options->image_width, options->image_height, d_out, cfg);
+    if(follow != nullptr) {
+        pt_launch_features_followed(s->stream, s->dev, cam, options->image_width, options->image_height, d_out, cfg, follow->max_bounces, options->epsilon);
+    }
+    else {
+        pt_launch_features(s->stream, s->dev, cam, options->image_width, options->image_height, d_out, cfg);
+    }
     PT_HIP(hipGetLastError());
     return PT_OK;
 }
@@ -79,9 +84,29 @@ static int features_views_check(pt_scene *s, const pt_camera_params *cameras, in
     return PT_OK;
 }
 
-int pth::features_views_launch(pt_scene *s, const pt_camera_params *cameras, int32_t n_views, const pt_options *options, float4 *d_out) {
+int pth::feature_params_resolve(const pt_feature_params *params, const pt_options *options, pt_feature_params *resolved) {
+    pt_feature_params p{};
+    pt_feature_params_default(&p);
+    if(params != nullptr) {
+        p = *params;
+    }
+    if(p.max_bounces < 0 || p.max_bounces > 32) {
+        return fail(PT_ERR_INVALID, "max_bounces must be 0..32");
+    }
+    if(p.flags != 0) {
+        return fail(PT_ERR_INVALID, "flags must be 0");
+    }
+    if(options != nullptr && !(std::isfinite(options->epsilon) && options->epsilon >= 0.0F)) {
+        return fail(PT_ERR_INVALID, "epsilon must be finite and not negative");
+    }
+    *resolved = p;
+    return PT_OK;
+}
+
+int pth::features_views_launch(pt_scene *s, const pt_camera_params *cameras, int32_t n_views, const pt_options *options, float4 *d_out,
+                               const pt_feature_params *follow) {
     if(n_views == 1) {
-        return features_launch(s, cameras, options, d_out);
+        return features_launch(s, cameras, options, d_out, follow);
     }
     PT_TRY(setup_path(s));
     std::vector<PtViewCamera> table(static_cast<size_t>(n_views));
@@ -96,7 +121,13 @@ int pth::features_views_launch(pt_scene *s, const pt_camera_params *cameras, int
     const size_t n = static_cast<size_t>(n_views) * static_cast<size_t>(options->image_width) * static_cast<size_t>(options->image_height);
     PT_HIP(s->feature_spill.ensure(((n + 255) / 256) * 256 * cfg.spill_depth));
     cfg.spill = s->feature_spill.ptr;
-    pt_launch_features_views(s->stream, s->dev, s->feature_cams.ptr, n_views, options->image_width, options->image_height, d_out, cfg);
+    if(follow != nullptr) {
+        pt_launch_features_followed_views(s->stream, s->dev, s->feature_cams.ptr, n_views, options->image_width, options->image_height, d_out, cfg, follow->max_bounces,
+                                          options->epsilon);
+    }
+    else {
+        pt_launch_features_views(s->stream, s->dev, s->feature_cams.ptr, n_views, options->image_width, options->image_height, d_out, cfg);
+    }
     PT_HIP(hipGetLastError());
     return PT_OK;
 }
@@ -228,31 +259,78 @@ int pt_render_features_device(pt_scene *s, const pt_camera_params *camera, const
     return pt_render_features_views_device(s, camera, 1, options, d_out_features, stream);
 }
 
-int pt_render_features_views(pt_scene *s, const pt_camera_params *cameras, int32_t n_views, const pt_options *options, float *out_features) {
-    PT_TRY(features_views_check(s, cameras, n_views, options, out_features));
+// pt_render_features_views and its followed form (follow != nullptr: parameters already resolved)
+static int render_features_views(pt_scene *s, const pt_camera_params *cameras, int32_t n_views, const pt_options *options, const pt_feature_params *follow,
+                                 float *out_features) {
     const size_t n = static_cast<size_t>(n_views) * static_cast<size_t>(options->image_width) * static_cast<size_t>(options->image_height);
     std::lock_guard<std::mutex> lock(s->render_mutex);
     PT_HIP(hipSetDevice(s->device));
     PT_HIP(s->features.ensure(3 * n));
-    PT_TRY(features_views_launch(s, cameras, n_views, options, reinterpret_cast<float4 *>(s->features.ptr)));
+    PT_TRY(features_views_launch(s, cameras, n_views, options, reinterpret_cast<float4 *>(s->features.ptr), follow));
     PT_HIP(hipMemcpyAsync(out_features, s->features.ptr, 3 * n * sizeof(F4), hipMemcpyDeviceToHost, s->stream));
     PT_HIP(hipStreamSynchronize(s->stream));
     return PT_OK;
 }
 
-int pt_render_features_views_device(pt_scene *s, const pt_camera_params *cameras, int32_t n_views, const pt_options *options, float *d_out_features, void *stream) {
-    PT_TRY(features_views_check(s, cameras, n_views, options, d_out_features));
+static int render_features_views_device(pt_scene *s, const pt_camera_params *cameras, int32_t n_views, const pt_options *options, const pt_feature_params *follow,
+                                        float *d_out_features, void *stream) {
     std::lock_guard<std::mutex> lock(s->render_mutex);
     PT_HIP(hipSetDevice(s->device));
     // order after the caller's stream, trace on the library's stream, then make the caller's stream wait for it
     StreamOrder order;
     PT_TRY(order.begin(stream, s->stream));
-    PT_TRY(features_views_launch(s, cameras, n_views, options, reinterpret_cast<float4 *>(d_out_features)));
+    PT_TRY(features_views_launch(s, cameras, n_views, options, reinterpret_cast<float4 *>(d_out_features), follow));
     PT_TRY(order.end());
     if(order.caller == nullptr) {
         PT_HIP(hipStreamSynchronize(s->stream));
     }
     return PT_OK;
+}
+
+int pt_render_features_views(pt_scene *s, const pt_camera_params *cameras, int32_t n_views, const pt_options *options, float *out_features) {
+    PT_TRY(features_views_check(s, cameras, n_views, options, out_features));
+    return render_features_views(s, cameras, n_views, options, nullptr, out_features);
+}
+
+int pt_render_features_views_device(pt_scene *s, const pt_camera_params *cameras, int32_t n_views, const pt_options *options, float *d_out_features, void *stream) {
+    PT_TRY(features_views_check(s, cameras, n_views, options, d_out_features));
+    return render_features_views_device(s, cameras, n_views, options, nullptr, d_out_features, stream);
+}
+
+// ---- followed features (include/pt_features.h; pt_path.hip: pt_follow_kernel) ------------------------------------------------------
+
+int pt_feature_params_default(pt_feature_params *out) {
+    if(out == nullptr) {
+        return fail(PT_ERR_INVALID, "null argument");
+    }
+    out->max_bounces = 8;
+    out->flags = 0;
+    return PT_OK;
+}
+
+int pt_render_features_followed(pt_scene *s, const pt_camera_params *camera, const pt_options *options, const pt_feature_params *params, float *out_features) {
+    return pt_render_features_followed_views(s, camera, 1, options, params, out_features);
+}
+
+int pt_render_features_followed_device(pt_scene *s, const pt_camera_params *camera, const pt_options *options, const pt_feature_params *params, float *d_out_features,
+                                       void *stream) {
+    return pt_render_features_followed_views_device(s, camera, 1, options, params, d_out_features, stream);
+}
+
+int pt_render_features_followed_views(pt_scene *s, const pt_camera_params *cameras, int32_t n_views, const pt_options *options, const pt_feature_params *params,
+                                      float *out_features) {
+    PT_TRY(features_views_check(s, cameras, n_views, options, out_features));
+    pt_feature_params follow{};
+    PT_TRY(feature_params_resolve(params, options, &follow));
+    return render_features_views(s, cameras, n_views, options, &follow, out_features);
+}
+
+int pt_render_features_followed_views_device(pt_scene *s, const pt_camera_params *cameras, int32_t n_views, const pt_options *options, const pt_feature_params *params,
+                                             float *d_out_features, void *stream) {
+    PT_TRY(features_views_check(s, cameras, n_views, options, d_out_features));
+    pt_feature_params follow{};
+    PT_TRY(feature_params_resolve(params, options, &follow));
+    return render_features_views_device(s, cameras, n_views, options, &follow, d_out_features, stream);
 }
 
 int pt_denoise_device(int device, const float *d_rgba, const float *d_features, int32_t width, int32_t height, const pt_denoise_params *params, float *d_out_rgba,

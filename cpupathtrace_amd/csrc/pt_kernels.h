@@ -209,6 +209,12 @@ void pt_launch_features(hipStream_t stream, const PtDevScene &scene, const PtDev
 // pixel (x, y) with views[v].cam (a DEVICE table whose cameras have no aperture); cfg.spill holds n_views * width * height walks
 void pt_launch_features_views(hipStream_t stream, const PtDevScene &scene, const PtViewCamera *views, int32_t n_views, int32_t width, int32_t height, float4 *out,
                               const PtPathConfig &cfg);
+// followed features (pt_follow_kernel; include/pt_features.h): the two launchers above with rays that go on through glass and mirrors for
+// at most max_bounces bounces (0: the bits of the first-hit launchers); epsilon is pt_options'
+void pt_launch_features_followed(hipStream_t stream, const PtDevScene &scene, const PtDevCamera &camera, int32_t width, int32_t height, float4 *out, const PtPathConfig &cfg,
+                                 int32_t max_bounces, float epsilon);
+void pt_launch_features_followed_views(hipStream_t stream, const PtDevScene &scene, const PtViewCamera *views, int32_t n_views, int32_t width, int32_t height, float4 *out,
+                                       const PtPathConfig &cfg, int32_t max_bounces, float epsilon);
 // diagnostic (tools/step_timing.py): stamped walks, `lanes_per_wave` rays per wavefront; out[ray] = (steps, cycles waiting for records, cycles in all, price of a stamp pair)
 void pt_launch_steptime(hipStream_t stream, const PtDevScene &scene, const float *rays6, uint32_t n, uint32_t lanes_per_wave, uint4 *out, uint2 *spill, uint32_t spill_depth, int flags);
 

@@ -1666,6 +1666,137 @@ __global__ __launch_bounds__(256) void pt_feature_kernel(PtDevScene sc, PtDevCam
     o[2] = make_float4(acc2.x * q, acc2.y * q, acc2.z * q, (0.2126f * er + 0.7152f * eg) + 0.0722f * eb);
 }
 
+// Followed features (include/pt_features.h): the rays, the layout and the order of pt_feature_kernel, but a ray that
+// hits glass or a mirror goes on -- bsdf_follow's deterministic branch, tinted by bsdf_spectrum as the path kernel's bounce tints -- to the
+// first Lambertian (or material-less) hit or to bounce `max_bounces`, and contributes there: albedo T * albedo, that hit's normal, the
+// summed length L of its segments, the unfolded position o0 + d0 * L and T * emission.  A miss at any bounce contributes what a first-hit
+// miss does: nothing.  With max_bounces = 0 every operation is pt_feature_kernel's (T = 1 and L = 0 + t are exact): the same bits.
+//
+// ONE loop of walks per lane, one tr.start / tr.step site: a lane's state is (sub-pixel ray k, bounce b, T, L, o0, d0, the accumulators),
+// and a lane whose chain ends starts the chain of its next sub-pixel ray in the same turn of the loop, while its neighbours bounce.  A lane
+// accumulates in ray order whatever its neighbours do, so the result does not depend on the wavefront.  The loop is bounded by
+// construction: a chain is at most max_bounces + 1 walks, so a lane makes at most 4 * (max_bounces + 1) of them, and that count -- not the
+// geometry -- ends the loop; a NaN direction fails the root box's test and its chain ends as a miss.
+template<int STACK_LDS, bool IN_LDS, bool kViews>
+__global__ __launch_bounds__(256) void pt_follow_kernel(PtDevScene sc, PtDevCamera cam, int32_t width, int32_t height, float4 *__restrict__ out, uint2 *__restrict__ spill,
+                                                        uint32_t spill_depth, const PtViewCamera *__restrict__ views, int32_t view_height, int32_t max_bounces,
+                                                        float epsilon) {
+    extern __shared__ __align__(16) unsigned char lds_raw[];
+    const int tid = threadIdx.x;
+    lds_u2_ptr stack_l = (lds_u2_ptr)reinterpret_cast<uint2 *>(lds_raw) + tid;
+    float4 *lds_recs = reinterpret_cast<float4 *>(lds_raw + (size_t)STACK_LDS * 256 * sizeof(uint2));
+    if(IN_LDS) {
+        for(uint32_t i = tid; i < 4u * (sc.pair_base + sc.n_pairs); i += 256) {
+            lds_recs[i] = sc.recs[i];
+        }
+        __syncthreads();
+    }
+    Tracer<STACK_LDS, IN_LDS> tr;
+    if(IN_LDS) {
+        tr.recs = (typename RecPtr<IN_LDS>::type)(lds_f4_cptr)lds_recs;
+    }
+    else {
+        tr.recs = (typename RecPtr<IN_LDS>::type)(glb_f4_cptr)sc.recs;
+    }
+    tr.stack_l = stack_l;
+    const size_t gid = (size_t)blockIdx.x * 256 + tid;
+    tr.my_spill = (glb_u2_ptr)(spill + gid * spill_depth);
+    if(gid >= (size_t)width * (size_t)height) {
+        return;
+    }
+    const int32_t px = (int32_t)(gid % (size_t)width);
+    int32_t py = (int32_t)(gid / (size_t)width);
+    const PtDevCamera *lane_cam = &cam;
+    int32_t frame_height = height;
+    if constexpr(kViews) {
+        const int32_t view = py / view_height;
+        py -= view * view_height;
+        lane_cam = &views[view].cam;
+        frame_height = view_height;
+    }
+    RootBox root;
+    root.ref = sc.root_ref;
+    for(int k = 0; k < 3; k++) {
+        root.lo[k] = sc.root_lo[k];
+        root.hi[k] = sc.root_hi[k];
+    }
+    // the primary ray of sub-pixel k: pt_feature_kernel's
+    auto primary = [&](int k) {
+        const float dx = (k & 1) ? 0.25f : -0.25f, dy = (k & 2) ? 0.25f : -0.25f;
+        const float one_half = 1.0f / 2.0f;
+        const float x_camera = 2 * (((float)px + one_half + dx) / (float)width - one_half);
+        float y_camera = 2 * (((float)py + one_half + dy) / (float)frame_height - one_half);
+        y_camera = -y_camera;
+        uint64_t rng = 0; // (drawn from, never used: both offsets are +0 and there is no aperture)
+        return camera_shoot(*lane_cam, x_camera, y_camera, 0.0f, 0.0f, rng);
+    };
+    float4 acc0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), acc1 = acc0, acc2 = acc0, emis = acc0;
+    int k = 0, b = 0;
+    Ray ray = primary(0);
+    V3 o0 = ray.o, d0 = ray.d, T = v3(1.0f, 1.0f, 1.0f);
+    float L = 0.0f;
+    const int max_walks = 4 * (max_bounces + 1);
+    for(int walk = 0; walk < max_walks && k < 4; walk++) {
+        Walk w;
+        typename Tracer<STACK_LDS, IN_LDS>::Rec rec;
+        rec.r0 = rec.r1 = rec.r2 = rec.r3 = (f4v){0.0f, 0.0f, 0.0f, 0.0f};
+        tr.start(w, rec, root, make_float4(ray.o.x, ray.o.y, ray.o.z, 0.0f), make_float4(ray.d.x, ray.d.y, ray.d.z, __uint_as_float(0u)));
+        uint32_t n_nodes = 0, n_leaves = 0;
+        while(tr.step(w, rec, 1, n_nodes, n_leaves)) {
+        }
+        float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), n4 = a, p4 = a, e4 = a;
+        bool chain_ends = true;
+        if(w.best_ref != PT_REF_NONE) {
+            const float t = w.best_t;
+            L = L + t;
+            const V3 pos = ray.o + ray.d * t;
+            uint32_t material_index;
+            const V3 n = object_normal(sc, w.best_ref, pos, material_index);
+            const Material mat = material_load(sc.materials, material_index);
+            const bool lambertian = mat.bsdf == 0; // PT_BSDF_LAMBERTIAN (a hit without a material loads as one)
+            if(lambertian || b == max_bounces) {
+                const V3 virt = o0 + d0 * L;
+                a = make_float4(T.x * (lambertian ? mat.diffuse.r : mat.specular.r), T.y * (lambertian ? mat.diffuse.g : mat.specular.g),
+                                T.z * (lambertian ? mat.diffuse.b : mat.specular.b), 1.0f);
+                n4 = make_float4(n.x, n.y, n.z, L);
+                p4 = make_float4(virt.x, virt.y, virt.z, 0.0f);
+                e4 = make_float4(T.x * mat.emission.r, T.y * mat.emission.g, T.z * mat.emission.b, 0.0f);
+            }
+            else {
+                bool reflected;
+                const Ray next = bsdf_follow(mat, ray.d, pos, n, epsilon, reflected);
+                float shading_factor, shading_pd;
+                const C4 tint = bsdf_spectrum(mat, ray.d, next.d, n, c4(1.0f, 1.0f, 1.0f, 1.0f), false, shading_factor, shading_pd);
+                T = v3(T.x * tint.r, T.y * tint.g, T.z * tint.b);
+                b += 1;
+                ray = next;
+                chain_ends = false;
+            }
+        }
+        if(chain_ends) {
+            acc0 = make_float4(acc0.x + a.x, acc0.y + a.y, acc0.z + a.z, acc0.w + a.w);
+            acc1 = make_float4(acc1.x + n4.x, acc1.y + n4.y, acc1.z + n4.z, acc1.w + n4.w);
+            acc2 = make_float4(acc2.x + p4.x, acc2.y + p4.y, acc2.z + p4.z, 0.0f);
+            emis = make_float4(emis.x + e4.x, emis.y + e4.y, emis.z + e4.z, 0.0f);
+            k += 1;
+            if(k < 4) {
+                ray = primary(k);
+                o0 = ray.o;
+                d0 = ray.d;
+                T = v3(1.0f, 1.0f, 1.0f);
+                L = 0.0f;
+                b = 0;
+            }
+        }
+    }
+    const float q = 0.25f;
+    const float er = emis.x * q, eg = emis.y * q, eb = emis.z * q;
+    float4 *o = out + 3 * gid;
+    o[0] = make_float4(acc0.x * q, acc0.y * q, acc0.z * q, acc0.w * q);
+    o[1] = make_float4(acc1.x * q, acc1.y * q, acc1.z * q, acc1.w * q);
+    o[2] = make_float4(acc2.x * q, acc2.y * q, acc2.z * q, (0.2126f * er + 0.7152f * eg) + 0.0722f * eb);
+}
+
 // ---- diagnostic: where the cycles of a traversal step go -------------------------------------------------------------------------------
 // One walk per lane as in pt_closest_kernel, but only the first `lanes_per_wave` lanes of every wavefront get a ray, and every step is
 // stamped (s_memtime): cycles spent waiting for the record that was requested at the end of the previous step, and everything else.
@@ -1888,6 +2019,22 @@ void launch_features(hipStream_t stream, const PtDevScene &scene, const PtDevCam
     }
 }
 
+// the followed form of launch_features (pt_follow_kernel): the same grid, LDS and spill area
+template<int STACK_LDS, bool IN_LDS>
+void launch_follow(hipStream_t stream, const PtDevScene &scene, const PtDevCamera &cam, int32_t width, int32_t height, float4 *out, const PtPathConfig &cfg,
+                   int32_t max_bounces, float epsilon, const PtViewCamera *views = nullptr, int32_t view_height = 0) {
+    const size_t lds = (size_t)STACK_LDS * 256 * sizeof(uint2) + (IN_LDS ? ((size_t)scene.n_lds_pairs + scene.pair_base) * 64 : 0);
+    const size_t n = (size_t)width * (size_t)height;
+    if(views != nullptr) {
+        hipLaunchKernelGGL((pt_follow_kernel<STACK_LDS, IN_LDS, true>), dim3((unsigned)((n + 255) / 256)), dim3(256), lds, stream, scene, cam, width, height, out,
+                           cfg.spill, cfg.spill_depth, views, view_height, max_bounces, epsilon);
+    }
+    else {
+        hipLaunchKernelGGL((pt_follow_kernel<STACK_LDS, IN_LDS, false>), dim3((unsigned)((n + 255) / 256)), dim3(256), lds, stream, scene, cam, width, height, out,
+                           cfg.spill, cfg.spill_depth, nullptr, 0, max_bounces, epsilon);
+    }
+}
+
 } // namespace
 
 // the instantiations of the path kernel: slot word (compact | wide) x records (HBM | LDS) x stack window (8 entries; 4 for scenes in LDS that need the room)
@@ -2005,6 +2152,40 @@ void pt_launch_features_views(hipStream_t stream, const PtDevScene &scene, const
     }
     else {
         launch_features<PT_PATH_STACK_LDS, false>(stream, scene, none, width, rows, out, cfg, views, height);
+    }
+}
+
+void pt_launch_features_followed(hipStream_t stream, const PtDevScene &scene, const PtDevCamera &camera, int32_t width, int32_t height, float4 *out, const PtPathConfig &cfg,
+                                 int32_t max_bounces, float epsilon) {
+    if(width <= 0 || height <= 0) {
+        return;
+    }
+    if(cfg.in_lds && cfg.stack_lds == PT_PATH_STACK_LDS_SMALL) {
+        launch_follow<PT_PATH_STACK_LDS_SMALL, true>(stream, scene, camera, width, height, out, cfg, max_bounces, epsilon);
+    }
+    else if(cfg.in_lds) {
+        launch_follow<PT_PATH_STACK_LDS, true>(stream, scene, camera, width, height, out, cfg, max_bounces, epsilon);
+    }
+    else {
+        launch_follow<PT_PATH_STACK_LDS, false>(stream, scene, camera, width, height, out, cfg, max_bounces, epsilon);
+    }
+}
+
+void pt_launch_features_followed_views(hipStream_t stream, const PtDevScene &scene, const PtViewCamera *views, int32_t n_views, int32_t width, int32_t height, float4 *out,
+                                       const PtPathConfig &cfg, int32_t max_bounces, float epsilon) {
+    if(width <= 0 || height <= 0 || n_views <= 0) {
+        return;
+    }
+    const PtDevCamera none{}; // (never read: every pixel has its view's camera)
+    const int32_t rows = n_views * height;
+    if(cfg.in_lds && cfg.stack_lds == PT_PATH_STACK_LDS_SMALL) {
+        launch_follow<PT_PATH_STACK_LDS_SMALL, true>(stream, scene, none, width, rows, out, cfg, max_bounces, epsilon, views, height);
+    }
+    else if(cfg.in_lds) {
+        launch_follow<PT_PATH_STACK_LDS, true>(stream, scene, none, width, rows, out, cfg, max_bounces, epsilon, views, height);
+    }
+    else {
+        launch_follow<PT_PATH_STACK_LDS, false>(stream, scene, none, width, rows, out, cfg, max_bounces, epsilon, views, height);
     }
 }
 

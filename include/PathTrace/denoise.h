@@ -23,4 +23,17 @@ struct DenoiseParams {
 // their range, std::runtime_error if the device fails.
 Image<> denoise(const Image<> &frame, const Scene &scene, const Camera &camera, const RenderOptions &options, const DenoiseParams &params = {});
 
+// Features that follow mirrors and glass to the first diffuse hit (pt_feature_params of pt_features.h): a feature ray
+// that hits a mirror or glass goes on -- deterministically: a mirror's reflection, glass's refraction, or its reflection where that is
+// total -- for at most max_bounces bounces, and describes what is seen in the mirror or through the glass.
+struct FeatureParams {
+    int max_bounces = 8; // 0..32; 0 gives the first-hit features
+};
+
+// denoise with followed features: the same filter, guided by what the mirrors and the glass show.  options.epsilon is read as well (the
+// offset of a continued ray's origin).  processJob / processViews with allow_bias keep the first-hit features.  Throws as denoise does,
+// and std::invalid_argument for max_bounces outside 0..32 or an epsilon that is negative or not finite.
+Image<> denoise(const Image<> &frame, const Scene &scene, const Camera &camera, const RenderOptions &options, const DenoiseParams &params,
+                const FeatureParams &features);
+
 #endif

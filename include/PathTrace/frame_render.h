@@ -47,6 +47,10 @@ public:
     // std::invalid_argument for a negative or non-finite target or floor or a fraction outside (0, 1].  noise(): the summary of the frame as
     // it stands; errorMap(): one rating per pixel, row-major -- -1 finished, +inf unrated or untouched.
     void setNoiseTarget(float target, float floor = 1E-5f, float fraction = 1.0f);
+    // The features of the denoised previews (pt_frame_set_feature_params, include/pt_features.h): with parameters they follow mirrors and
+    // glass to the first diffuse hit (max_bounces 0..32, flags 0), with null they are the first-hit features again, which is how a frame
+    // starts.  The next denoised preview computes its features anew.  Throws std::invalid_argument for parameters outside their range.
+    void setFeatureParams(const pt_feature_params *params);
     pt_frame_noise noise() const;
     std::vector<float> errorMap() const;
     bool noiseTargetReached() const;

@@ -86,6 +86,15 @@ pt_frame_progress FrameRender::progress() const {
     return p;
 }
 
+void FrameRender::setFeatureParams(const pt_feature_params *params) {
+    if(params != nullptr && (params->max_bounces < 0 || params->max_bounces > 32 || params->flags != 0)) {
+        throw std::invalid_argument("FrameRender::setFeatureParams: max_bounces must be 0..32 and flags 0");
+    }
+    if(frame_ != nullptr) {
+        check(pt_frame_set_feature_params(frame_, params), "FrameRender::setFeatureParams");
+    }
+}
+
 void FrameRender::setNoiseTarget(float target, float floor, float fraction) {
     if(!std::isfinite(target) || target < 0.0f || !std::isfinite(floor) || floor < 0.0f || !(fraction > 0.0f && fraction <= 1.0f)) {
         throw std::invalid_argument("FrameRender::setNoiseTarget: target and floor must be finite and not negative, fraction in (0, 1]");
