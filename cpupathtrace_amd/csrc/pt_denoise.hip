@@ -1,5 +1,5 @@
 // pt_denoise.hip -- feature-guided denoising of a finished frame (RenderOptions::allow_bias): the spatial part of SVGF (Schied et al. 2017)
-// on the features of pt_feature_kernel (pt_path.hip).  DESIGN.md 4.10 has the algorithm, its constants and its measured cost;
+// on the features of pt_feature_kernel (pt_walks.hip).  DESIGN.md 4.10 has the algorithm, its constants and its measured cost;
 // tests/denoise_ref.py restates every kernel below in numpy, operation for operation.
 //
 //   prepare   c = rgb / max(albedo, 0.01) on covered, non-emissive pixels (rgb elsewhere), its luminance, the guide (n, t), the class

@@ -414,7 +414,7 @@ PT_D Ray bsdf_propagate(const Material &m, V3 ray_d, V3 pos, V3 normal, float ep
     return out;
 }
 
-// The deterministic continuation of a followed feature ray (pt_path.hip: pt_follow_kernel; include/pt_features.h) through glass or a
+// The deterministic continuation of a followed feature ray (pt_walks.hip: pt_follow_kernel; include/pt_features.h) through glass or a
 // mirror -- never called for a Lambertian material.  No draw is made.  Glass: the reflection branch of bsdf_propagate where
 // sin_theta_t >= 1 (its Bernoulli has p = 1 there), the refraction branch everywhere else; a mirror: the ray bsdf_propagate returns, the
 // one-way pass-through included.  Each branch is bsdf_propagate's arithmetic, operation for operation.  `reflected`: the ray stays

@@ -1,5 +1,5 @@
 // pt_image.cpp -- what the C ABI (include/pt_hip.h) does to a finished image: post-processing (pt_post.hip), the first-hit features of a
-// frame (pt_path.hip: pt_feature_kernel), feature-guided denoising and its temporal form (pt_denoise.hip).  A single frame is the batch
+// frame (pt_walks.hip: pt_feature_kernel), feature-guided denoising and its temporal form (pt_denoise.hip).  A single frame is the batch
 // of one view: the single-frame entry points call the view forms with n_views = 1, which issue the single frame's launches.
 #include "pt_host.h"
 
@@ -47,26 +47,7 @@ int pt_post_process(int device, float *rgba, int32_t width, int32_t height, uint
 
 } // extern "C"
 
-// ---- feature-guided denoising (pt_path.hip: pt_feature_kernel; pt_denoise.hip) -------------------------------------------------------
-
-// Enqueues the feature pass on the scene's stream (render_mutex held): into `d_out`, width * height * 3 float4.
-static int features_launch(pt_scene *s, const pt_camera_params *camera, const pt_options *options, float4 *d_out, const pt_feature_params *follow) {
-    PT_TRY(setup_path(s));
-    PtDevCamera cam = derive_camera(camera);
-    cam.aperture_kind = PT_APERTURE_NONE; // the rays are a pure function of camera and pixel
-    PtPathConfig cfg = s->path_cfg;
-    const size_t n = static_cast<size_t>(options->image_width) * static_cast<size_t>(options->image_height);
-    PT_HIP(s->feature_spill.ensure(((n + 255) / 256) * 256 * cfg.spill_depth));
-    cfg.spill = s->feature_spill.ptr;
-    if(follow != nullptr) {
-        pt_launch_features_followed(s->stream, s->dev, cam, options->image_width, options->image_height, d_out, cfg, follow->max_bounces, options->epsilon);
-    }
-    else {
-        pt_launch_features(s->stream, s->dev, cam, options->image_width, options->image_height, d_out, cfg);
-    }
-    PT_HIP(hipGetLastError());
-    return PT_OK;
-}
+// ---- feature-guided denoising (pt_walks.hip: pt_feature_kernel; pt_denoise.hip) -------------------------------------------------------
 
 // The arguments of the feature entry points, checked without a device
 static int features_views_check(pt_scene *s, const pt_camera_params *cameras, int32_t n_views, const pt_options *options, const float *out) {
@@ -103,31 +84,29 @@ int pth::feature_params_resolve(const pt_feature_params *params, const pt_option
     return PT_OK;
 }
 
+// Enqueues the feature pass on the scene's stream (render_mutex held): into `d_out`, n_views * width * height * 3 float4.  A single frame's
+// camera travels in the kernel's arguments; a batch's cameras go through a device table, which costs an upload and a wait for it.
 int pth::features_views_launch(pt_scene *s, const pt_camera_params *cameras, int32_t n_views, const pt_options *options, float4 *d_out,
                                const pt_feature_params *follow) {
-    if(n_views == 1) {
-        return features_launch(s, cameras, options, d_out, follow);
-    }
     PT_TRY(setup_path(s));
     std::vector<PtViewCamera> table(static_cast<size_t>(n_views));
     for(int32_t v = 0; v < n_views; v++) {
         table[static_cast<size_t>(v)] = PtViewCamera{derive_camera(cameras + v), {0, 0, 0}};
         table[static_cast<size_t>(v)].cam.aperture_kind = PT_APERTURE_NONE; // the rays are a pure function of camera and pixel
     }
-    PT_HIP(s->feature_cams.ensure(table.size()));
-    PT_HIP(hipMemcpyAsync(s->feature_cams.ptr, table.data(), table.size() * sizeof(PtViewCamera), hipMemcpyHostToDevice, s->stream));
-    PT_HIP(hipStreamSynchronize(s->stream)); // the table is this function's vector
+    const PtViewCamera *d_views = nullptr;
+    if(n_views > 1) {
+        PT_HIP(s->feature_cams.ensure(table.size()));
+        PT_HIP(hipMemcpyAsync(s->feature_cams.ptr, table.data(), table.size() * sizeof(PtViewCamera), hipMemcpyHostToDevice, s->stream));
+        PT_HIP(hipStreamSynchronize(s->stream)); // the table is this function's vector
+        d_views = s->feature_cams.ptr;
+    }
     PtPathConfig cfg = s->path_cfg;
     const size_t n = static_cast<size_t>(n_views) * static_cast<size_t>(options->image_width) * static_cast<size_t>(options->image_height);
     PT_HIP(s->feature_spill.ensure(((n + 255) / 256) * 256 * cfg.spill_depth));
     cfg.spill = s->feature_spill.ptr;
-    if(follow != nullptr) {
-        pt_launch_features_followed_views(s->stream, s->dev, s->feature_cams.ptr, n_views, options->image_width, options->image_height, d_out, cfg, follow->max_bounces,
-                                          options->epsilon);
-    }
-    else {
-        pt_launch_features_views(s->stream, s->dev, s->feature_cams.ptr, n_views, options->image_width, options->image_height, d_out, cfg);
-    }
+    const PtFollow followed = {follow != nullptr ? follow->max_bounces : 0, options->epsilon};
+    pt_launch_features(s->stream, s->dev, table[0].cam, d_views, n_views, options->image_width, options->image_height, d_out, cfg, follow != nullptr ? &followed : nullptr);
     PT_HIP(hipGetLastError());
     return PT_OK;
 }
@@ -297,7 +276,7 @@ int pt_render_features_views_device(pt_scene *s, const pt_camera_params *cameras
     return render_features_views_device(s, cameras, n_views, options, nullptr, d_out_features, stream);
 }
 
-// ---- followed features (include/pt_features.h; pt_path.hip: pt_follow_kernel) ------------------------------------------------------
+// ---- followed features (include/pt_features.h; pt_walks.hip: pt_follow_kernel) ------------------------------------------------------
 
 int pt_feature_params_default(pt_feature_params *out) {
     if(out == nullptr) {

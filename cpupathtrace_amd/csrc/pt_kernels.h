@@ -1,4 +1,4 @@
-// pt_kernels.h -- launch interface between the host side of libpathtrace_hip.so (pt_render.cpp, pt_frames.cpp, pt_image.cpp) and the kernels of pt_path.hip.
+// pt_kernels.h -- launch interface between the host side of libpathtrace_hip.so (pt_render.cpp, pt_frames.cpp, pt_image.cpp) and the kernels of pt_path.hip and pt_walks.hip.
 #ifndef PT_KERNELS_H
 #define PT_KERNELS_H
 
@@ -197,24 +197,25 @@ int pt_launch_frame_scatter(hipStream_t stream, const float4 *rgba, const int2 *
 int pt_path_blocks_per_cu(const PtPathConfig &cfg); // resident workgroups per CU of the instantiation cfg selects (wide, in_lds, stack_lds) with cfg.lds_bytes
 size_t pt_path_lds_bytes(int wide, int rows, int stack_lds, uint32_t n_lds_pairs, uint32_t n_lds_leaf_records); // leaf records: triangles + 1 spare + spheres, 0 = scene not in LDS
 int pt_path_stack_lds(int in_lds, size_t lds_bytes_with_default_window); // entries of the stack window: 8, or 4 for a scene in LDS that would not leave room for four workgroups per CU
-// Scene::getIntersection for n rays (6 floats each): out[i] = (bits t, ref)
+// ---- one walk per lane (pt_walks.hip) -----------------------------------------------------------------------------------------------
 // diagnostic (tools/replay_probe.py): the traversal alone over the rays a render left in its rings; returns the resident workgroups per CU
 int pt_launch_replay(hipStream_t stream, const PtDevScene &scene, const PtLocalQueue &Q, uint32_t n_logs, uint32_t parts, int waves_per_simd, const PtPathConfig &cfg,
                      uint2 *spill, unsigned long long *out);
+// Scene::getIntersection for n rays (6 floats each): out[i] = (bits t, ref)
 void pt_launch_closest(hipStream_t stream, const PtDevScene &scene, const float *rays6, uint32_t n, uint2 *out, const PtPathConfig &cfg);
-// first-hit features of a width x height frame for the denoiser (pt_feature_kernel): out[3 * pixel + k], k = albedo + coverage, normal + t,
-// position + emission luminance; `camera` must have no aperture sampler.  The walk, its instantiation and cfg.spill are pt_launch_closest's.
-void pt_launch_features(hipStream_t stream, const PtDevScene &scene, const PtDevCamera &camera, int32_t width, int32_t height, float4 *out, const PtPathConfig &cfg);
-// the same for n_views frames of width x height in one launch: out[3 * ((v * height + y) * width + x) + k] is what pt_launch_features gives
-// pixel (x, y) with views[v].cam (a DEVICE table whose cameras have no aperture); cfg.spill holds n_views * width * height walks
-void pt_launch_features_views(hipStream_t stream, const PtDevScene &scene, const PtViewCamera *views, int32_t n_views, int32_t width, int32_t height, float4 *out,
-                              const PtPathConfig &cfg);
-// followed features (pt_follow_kernel; include/pt_features.h): the two launchers above with rays that go on through glass and mirrors for
-// at most max_bounces bounces (0: the bits of the first-hit launchers); epsilon is pt_options'
-void pt_launch_features_followed(hipStream_t stream, const PtDevScene &scene, const PtDevCamera &camera, int32_t width, int32_t height, float4 *out, const PtPathConfig &cfg,
-                                 int32_t max_bounces, float epsilon);
-void pt_launch_features_followed_views(hipStream_t stream, const PtDevScene &scene, const PtViewCamera *views, int32_t n_views, int32_t width, int32_t height, float4 *out,
-                                       const PtPathConfig &cfg, int32_t max_bounces, float epsilon);
+// Features of a width x height frame for the denoiser (pt_walks.hip): out[3 * pixel + k], k = albedo + coverage, normal + t, position +
+// emission luminance.  views == nullptr: the frame of `camera`, which travels in the kernel's arguments and must have no aperture sampler.
+// Otherwise n_views frames in one launch: out[3 * ((v * height + y) * width + x) + k] is what the single frame gives pixel (x, y) with
+// views[v].cam (a DEVICE table whose cameras have no aperture; `camera` is not read).  follow == nullptr: first hits (pt_feature_kernel).
+// Otherwise rays that go on through glass and mirrors for at most max_bounces bounces (pt_follow_kernel; include/pt_features.h; 0: the
+// bits of the first-hit pass), epsilon being pt_options'.  The walk and its instantiation are pt_launch_closest's; cfg.spill holds one
+// walk per pixel of every view.
+struct PtFollow {
+    int32_t max_bounces;
+    float epsilon;
+};
+void pt_launch_features(hipStream_t stream, const PtDevScene &scene, const PtDevCamera &camera, const PtViewCamera *views, int32_t n_views, int32_t width, int32_t height,
+                        float4 *out, const PtPathConfig &cfg, const PtFollow *follow);
 // diagnostic (tools/step_timing.py): stamped walks, `lanes_per_wave` rays per wavefront; out[ray] = (steps, cycles waiting for records, cycles in all, price of a stamp pair)
 void pt_launch_steptime(hipStream_t stream, const PtDevScene &scene, const float *rays6, uint32_t n, uint32_t lanes_per_wave, uint4 *out, uint2 *spill, uint32_t spill_depth, int flags);
 

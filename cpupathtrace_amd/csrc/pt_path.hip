@@ -42,335 +42,11 @@
 #include "pt_device.h"
 #include "pt_kernels.h"
 #include "pt_shading.h"
+#include "pt_trace.h"
 
 using namespace ptd;
 
 namespace {
-
-typedef float f2v __attribute__((ext_vector_type(2)));
-typedef unsigned int u2v __attribute__((ext_vector_type(2)));
-typedef const f4v __attribute__((address_space(1))) *glb_f4_cptr;
-typedef u2v __attribute__((address_space(3))) *lds_u2_ptr;
-typedef u2v __attribute__((address_space(1))) *glb_u2_ptr;
-typedef unsigned int __attribute__((address_space(3))) *lds_u32_ptr;
-typedef const PtPathArgs __attribute__((address_space(4))) *args_c4;
-
-template<bool IN_LDS>
-struct RecPtr {
-    typedef glb_f4_cptr type;
-};
-template<>
-struct RecPtr<true> {
-    typedef lds_f4_cptr type;
-};
-
-// The root of the tree: its box is tested before anything else (Scene::getIntersection, scene.cpp:211-219)
-struct RootBox {
-    float lo[3], hi[3];
-    uint32_t ref;
-};
-
-// One walk (one ray) in a lane.
-//
-// `cur` is where the walk stands: the reference of an inner node (bits 31, 30 = 00) or of a leaf (bit 31 set, pt_types.h), PT_REF_NONE when
-// the walk is over, or PT_REF_POPPING when it has to return to a parked node but the entry on top of its stack has already been
-// discarded (see Tracer::node_step).  The stack of parked nodes has a SENTINEL as entry 0 -- (PT_REF_NONE, -1) -- so "the stack is
-// empty" needs no test anywhere: popping the sentinel ends the walk, and its distance passes every pruning test.
-#define PT_REF_POPPING 0xfffffffeu
-struct Walk {
-    V3 o, d, inv;
-    f2v o_xy, o_zx, o_yz, i_xy, i_zx, i_yz; // origin and inverse direction again, as the register pairs of the packed slab arithmetic
-    float thr;       // shadow threshold |to_light| - epsilon (worker.cpp:86)
-    uint32_t dest;   // destination word of the ray
-    float best_t;
-    uint32_t best_ref;
-    float t_max;     // pruning distance: the smallest hit distance so far (scene.cpp:124,137)
-    float t_lim;     // the largest float below t_max: x < t_max  <=>  x <= t_lim, which lets min() fold the pruning test into the box test
-    uint32_t cur;
-    uint32_t sp;     // entries on the stack, the sentinel included
-    bool occluded;   // shadow ray: a leaf closer than the light was found
-
-    PT_D void pack() {
-        o_xy = (f2v){o.x, o.y};
-        o_zx = (f2v){o.z, o.x};
-        o_yz = (f2v){o.y, o.z};
-        i_xy = (f2v){inv.x, inv.y};
-        i_zx = (f2v){inv.z, inv.x};
-        i_yz = (f2v){inv.y, inv.z};
-    }
-    // t_max is never negative (hit distances are >= 0; it may be -0): below zero there is nothing, and every entry distance is >= 0
-    PT_D void set_t_max(float t) {
-        t_max = t;
-        t_lim = t > 0.0f ? __uint_as_float(__float_as_uint(t) - 1u) : -1.0f;
-    }
-};
-
-// The traversal machinery of one lane: record arrays (LDS or HBM), the stack window in LDS and its HBM spill area.
-//
-// What a step costs on this chip (tools/issue_probe.hip, profiles/r03_issue_probe.txt): a wavefront that is alone on its SIMD issues one
-// instruction per 4.5 cycles whatever the instruction; a taken branch costs 22 cycles, a not-taken one 13, a wave-uniform branch on a
-// ballot (v_cmp into an SGPR pair, s_cmp, s_cbranch) 35-52, a lane mask that goes through the scalar unit on its way to a v_cndmask
-// 16 more than one that stays in vcc, an LDS round trip 55, an L1 hit 112.  A stream's samples are sequential, so at the end of every
-// launch -- and for the whole of a strong-scaling share -- the frame time is the length of a few such lonely chains.  Hence:
-//   * node_step is STRAIGHT-LINE code for all 64 lanes, no branch and no exec mask but the one around the record loads.  Conditions
-//     never meet in scalar registers: a child that is not entered gets the entry distance +inf, and min / max / compare-with-inf on
-//     the two distances yield near child, far child, "both" and "none" (each v_cmp feeds the v_cndmask or the add-with-carry behind
-//     it through vcc).  The far child is written ABOVE the top of the stack by every lane (it only becomes an entry where the stack
-//     pointer moves) and the top entry is read by every lane ahead of the arithmetic, so the first pop of the recursion's return
-//     (scene.cpp:137) costs no trip to LDS;
-//   * everything rare -- leaves, a popped entry that fails the distance test, a stack deeper than its LDS window -- is left to
-//     slow_step, which the traversal loop enters through ONE wave-uniform branch per step.
-// Diagnostic build (-DPT_STEP_STAMPS, tools/step_timing.py): s_memtime stamps inside the step; segment k collects the cycles from the
-// previous stamp to stamp k, each inflated by the round trip of the previous stamp itself (segment 7 = two stamps back to back: that price)
-#ifdef PT_STEP_STAMPS
-#define PT_STAMP(k)                                                      \
-    do {                                                                 \
-        const unsigned long long now_ = __builtin_amdgcn_s_memtime();     \
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");               \
-        stamp_acc[k] += now_ - stamp_last;                               \
-        stamp_last = now_;                                               \
-    } while(0)
-#else
-#define PT_STAMP(k) do { } while(0)
-#endif
-
-template<int STACK_LDS, bool IN_LDS>
-struct Tracer {
-    static_assert((STACK_LDS & (STACK_LDS - 1)) == 0, "the stack window is indexed with a mask");
-#ifdef PT_STEP_STAMPS
-    mutable unsigned long long stamp_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, stamp_last = 0;
-#endif
-    typedef typename RecPtr<IN_LDS>::type rec_ptr;
-    rec_ptr recs;         // the 64-byte records the tree's references index: leaves, then pairs (pt_types.h)
-    lds_u2_ptr stack_l;   // this thread's column: entry e at stack_l[(e mod STACK_LDS) * 256]
-    glb_u2_ptr my_spill;  // entries that have left the window: entry e at my_spill[e]
-
-    // The 64-byte record a walk stands on, requested as soon as the walk knows where it goes next: a node's pair of child boxes, a
-    // triangle, or a sphere's (origin, radius).  A reference's low 30 bits ARE the record's index: one mask, one shift-add.
-    struct Rec {
-        f4v r0, r1, r2, r3;
-    };
-    PT_D void fetch(uint32_t cur, Rec &R) const {
-        rec_ptr p = recs + 4 * (size_t)(cur & PT_REF_INDEX);
-        R.r0 = p[0];
-        R.r1 = p[1];
-        R.r2 = p[2];
-        R.r3 = p[3];
-    }
-    // Registers that a load fills and nobody reads (the last two words of a record) become the compiler's scratch registers, and their
-    // first use then has to wait for the load: a full memory latency at the end of every step.  Every consumer of a record calls this.
-    static PT_D void whole(const Rec &R) {
-        asm volatile("" ::"v"(R.r0), "v"(R.r1), "v"(R.r2), "v"(R.r3));
-    }
-
-    // Where a walk stands, classified with one comparison each: a reference below 2^30 = an inner node (node_step moves it); at or above,
-    // except PT_REF_NONE = it waits for slow_step (a leaf, or a walk that has to go on popping).
-    static PT_D unsigned long long node_lanes(uint32_t cur) { return __builtin_amdgcn_uicmp(cur, 0x40000000u, 36); }       // cur < 2^30
-    static PT_D unsigned long long slow_lanes(uint32_t cur) { return __builtin_amdgcn_uicmp(cur + 1u, 0x40000000u, 34); }  // 2^30 <= cur < NONE
-
-    // Start a walk: Scene::getIntersection tests the root box first (scene.cpp:211-219).
-    PT_D void start(Walk &w, Rec &R, const RootBox &root, float4 ro, float4 rd) const {
-        w.o = v3(ro.x, ro.y, ro.z);
-        w.d = v3(rd.x, rd.y, rd.z);
-        w.thr = ro.w;
-        w.dest = __float_as_uint(rd.w);
-        w.inv = slab_inverse(w.d);
-        w.pack();
-        w.best_ref = PT_REF_NONE;
-        w.best_t = -1.0f;
-        // A shadow ray is a closest-hit query like any other in the reference (worker.cpp:83-86) and must be pruned like one: starting it
-        // with the light's distance as pruning distance is NOT the same thing in floating point.  The sampled point lies on an emitter,
-        // the ray starts epsilon in front of the vertex and the threshold is |to_light| - epsilon: the emitter's own hit distance and
-        // the threshold are the same number up to rounding, and the reference finds "occluded" whenever the hit comes out an ulp
-        // below.  A box around a flat, axis-aligned emitter is entered at that very distance (again up to rounding, of the slab test
-        // this time), so pruning at the threshold skipped the emitter in cases where the reference tested it and found t < threshold.
-        // The walk still ends at the first hit below the threshold (the closest hit can only be nearer).
-        w.set_t_max(FLT_MAX);
-        // (the sentinel pair is made where it is stored: as a constant it was hoisted out of the path kernel's loops and kept in scratch)
-        uint32_t sent_ref, sent_t;
-        asm volatile("v_mov_b32 %0, -1\n\tv_mov_b32 %1, -1.0" : "=v"(sent_ref), "=v"(sent_t)); // PT_REF_NONE, bits of -1.0f
-        const u2v sentinel = {sent_ref, sent_t};
-        stack_l[0] = sentinel;
-        w.sp = 1;
-        w.occluded = false;
-        w.cur = PT_REF_NONE;
-        if(root.ref != PT_REF_NONE) {
-            const float t_root = slab_walk(ld3(root.lo), ld3(root.hi), w.o, w.inv);
-            if(t_root >= 0.0f) {
-                w.cur = root.ref;
-                fetch(w.cur, R);
-            }
-        }
-    }
-
-    // One step of every walk that stands on an inner node (`node_mask`); the record of where a walk stands next is requested.
-    // AABB::getIntersection of both children (bounding_box.cpp:38-73): a box is hit iff t_max >= 0 and t_min <= t_max -- the
-    // same as max(t_min, 0) <= t_max -- and its entry distance is max(t_min, 0) (0 = origin inside, :68-70).
-    // impl::getChildIntersection (scene.cpp:113-146): a child is entered iff it is hit and its entry distance is below the pruning
-    // distance (entry < t_max <=> entry <= t_lim, so both tests are ONE comparison with min(box exit, t_lim)); with both entered the
-    // nearer one comes first -- on equal distances the RIGHT one (scene.cpp:120-121): "left first" is a strict less-than -- and the other
-    // is parked with its entry distance; with none entered the walk returns to the node on top of its stack if that one's entry
-    // distance is still below the pruning distance (scene.cpp:137), and goes on popping in slow_step otherwise.
-    // The stack: the top STACK_LDS entries of a lane live in LDS (slot = index mod STACK_LDS), older ones in the lane's HBM spill area.
-    // `deep_mask`: the lanes whose stack has left the window -- for them a push first moves the entry it overwrites to the spill area and
-    // a pop brings the entry that left the window last back into the slot that has become free; if there is no such lane (one scalar
-    // branch) the far child is simply written ABOVE the top of the stack by every lane: it only becomes an entry where the pointer moves.
-    PT_D void node_step(Walk &w, Rec &R, unsigned long long node_mask, unsigned long long deep_mask) const {
-        if(!__builtin_amdgcn_inverse_ballot_w64(node_mask)) {
-            return; // (the one exec mask of the step; the caller knows the mask is not empty)
-        }
-#ifdef PT_STEP_STAMPS
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-        PT_STAMP(2); // waiting for the record
-        whole(R);
-        const f4v q0 = R.r0, q1 = R.r1, q2 = R.r2;
-        const uint32_t sp = w.sp;
-        const u2v top = stack_l[((sp - 1u) & (uint32_t)(STACK_LDS - 1)) * 256u]; // read ahead of the arithmetic that decides whether it is needed
-        // twelve differences and products, two per instruction (v_pk_add_f32 with a negated operand is the IEEE subtraction,
-        // v_pk_mul_f32 the IEEE product: nothing is fused, every result is the reference's)
-        const f2v a0 = ((f2v){q0.x, q0.y} - w.o_xy) * w.i_xy; // L.lo.x, L.lo.y
-        const f2v a1 = ((f2v){q0.z, q0.w} - w.o_zx) * w.i_zx; // L.lo.z, L.hi.x
-        const f2v a2 = ((f2v){q1.x, q1.y} - w.o_yz) * w.i_yz; // L.hi.y, L.hi.z
-        const f2v a3 = ((f2v){q1.z, q1.w} - w.o_xy) * w.i_xy; // R.lo.x, R.lo.y
-        const f2v a4 = ((f2v){q2.x, q2.y} - w.o_zx) * w.i_zx; // R.lo.z, R.hi.x
-        const f2v a5 = ((f2v){q2.z, q2.w} - w.o_yz) * w.i_yz; // R.hi.y, R.hi.z
-        const float l1 = a0.x, l2 = a1.y, l3 = a0.y, l4 = a2.x, l5 = a1.x, l6 = a2.y;
-        const float r1 = a3.x, r2 = a4.y, r3 = a3.y, r4 = a5.x, r5 = a4.x, r6 = a5.y;
-        const float l_min = __builtin_fmaxf(__builtin_fmaxf(__builtin_fminf(l1, l2), __builtin_fminf(l3, l4)), __builtin_fminf(l5, l6));
-        const float l_max = __builtin_fminf(__builtin_fminf(__builtin_fmaxf(l1, l2), __builtin_fmaxf(l3, l4)), __builtin_fmaxf(l5, l6));
-        const float r_min = __builtin_fmaxf(__builtin_fmaxf(__builtin_fminf(r1, r2), __builtin_fminf(r3, r4)), __builtin_fminf(r5, r6));
-        const float r_max = __builtin_fminf(__builtin_fminf(__builtin_fmaxf(r1, r2), __builtin_fmaxf(r3, r4)), __builtin_fmaxf(r5, r6));
-        const float left_t = __builtin_fmaxf(l_min, 0.0f), right_t = __builtin_fmaxf(r_min, 0.0f);
-        const float inf = __builtin_inff();
-        const float t_lim = w.t_lim;
-        const float tl = left_t <= __builtin_fminf(l_max, t_lim) ? left_t : inf;   // entry distance of a child that is entered, else +inf
-        const float tr = right_t <= __builtin_fminf(r_max, t_lim) ? right_t : inf;
-        const bool left_first = tl < tr;
-        const uint32_t left_ref = __float_as_uint(R.r3.x), right_ref = __float_as_uint(R.r3.y);
-        const uint32_t near_ref = left_first ? left_ref : right_ref;
-        const float near_t = __builtin_fminf(tl, tr), far_t = __builtin_fmaxf(tl, tr);
-        const u2v far = {left_first ? right_ref : left_ref, __float_as_uint(far_t)};
-        const bool both = far_t < inf, entered = near_t < inf;
-        const uint32_t slot = (sp & (uint32_t)(STACK_LDS - 1)) * 256u;
-        if(deep_mask == 0ULL) {
-            stack_l[slot] = far;
-        }
-        else if(both) {
-            if(sp >= (uint32_t)STACK_LDS) {
-                my_spill[sp - STACK_LDS] = stack_l[slot];
-            }
-            stack_l[slot] = far;
-        }
-        const uint32_t popped = __uint_as_float(top.y) <= t_lim ? top.x : PT_REF_POPPING;
-        const uint32_t next = entered ? near_ref : popped;
-        w.sp = entered ? sp + (both ? 1u : 0u) : sp - 1u;
-        w.cur = next;
-        asm volatile("" ::"v"(w.sp), "v"(w.cur)); // (the walk's new state is complete before the record is requested: nothing is left to do behind the loads)
-        PT_STAMP(3); // slab tests, decision, stack
-        // the lanes that moved onto a record (not the ones whose walk ended or that go on popping: the two codes at the top)
-        if(next < PT_REF_POPPING) {
-            fetch(next, R);
-        }
-        if(deep_mask != 0ULL) {
-            if(!entered & (sp - 1u >= (uint32_t)STACK_LDS)) {
-                stack_l[((sp - 1u) & (uint32_t)(STACK_LDS - 1)) * 256u] = my_spill[sp - 1u - STACK_LDS]; // the window moves down
-            }
-        }
-        PT_STAMP(4); // address and request of the next record
-    }
-
-    // Everything that is not the common step: the leaves in `leaf_mask` (Object::getIntersection) and the walks that must (go on) pop(ping).
-    // n_leaves counts visits for the whole wavefront (the same value in every lane).
-    PT_D void slow_step(Walk &w, Rec &R, unsigned long long leaf_mask, uint32_t &n_leaves) const {
-        uint32_t cur = w.cur;
-        bool need_pop = cur == PT_REF_POPPING;
-        bool moved = false;
-        if(leaf_mask != 0ULL) {
-            n_leaves += (uint32_t)__popcll(leaf_mask);
-            if(__builtin_amdgcn_inverse_ballot_w64(leaf_mask)) {
-                // a leaf reports Object::getIntersection unconditionally (scene.cpp:105-109); among the non-negative hits the smallest wins and a
-                // later-visited leaf wins ties (scene.cpp:141-146); a shadow walk ends at its first hit below the threshold (worker.cpp:86)
-                const float4 q0 = to_f4(R.r0), q1 = to_f4(R.r1), q2 = to_f4(R.r2);
-                float t_leaf;
-                if(cur & PT_REF_SPHERE) {
-                    t_leaf = sphere_intersect(v3(q0.x, q0.y, q0.z), q0.w, w.o, w.d);
-                }
-                else {
-                    const TriRec tr = tri_unpack(q0, q1, q2);
-                    t_leaf = tri_intersect(tr.a, tr.ab, tr.ac, (tr.obj_cull >> 31) != 0, w.o, w.d);
-                }
-                need_pop = true;
-                if(t_leaf >= 0.0f) {
-                    if((w.dest & PT_DEST_SHADOW) && t_leaf < w.thr) {
-                        w.occluded = true;
-                        need_pop = false;
-                    }
-                    else {
-                        if(w.best_ref == PT_REF_NONE || !(w.best_t < t_leaf)) {
-                            w.best_t = t_leaf;
-                            w.best_ref = cur;
-                        }
-                        w.set_t_max(fmin_std(w.t_max, t_leaf));
-                    }
-                }
-                cur = PT_REF_NONE;
-            }
-        }
-        // pop: the first parked node whose entry distance is still below t_max (scene.cpp:137: re-tested against the then-current distance);
-        // the sentinel at the bottom passes the test and ends the walk
-        if(__ballot(need_pop) != 0ULL) {
-            uint32_t sp = w.sp;
-            const float t_max = w.t_max;
-            while(__ballot(need_pop) != 0ULL) {
-                if(need_pop) {
-                    sp--;
-                    const uint32_t slot = (sp & (uint32_t)(STACK_LDS - 1)) * 256u;
-                    const u2v e = stack_l[slot];
-                    if(sp >= (uint32_t)STACK_LDS) {
-                        stack_l[slot] = my_spill[sp - STACK_LDS]; // the window moves down: the entry that left it last comes back
-                    }
-                    if(__uint_as_float(e.y) < t_max) {
-                        cur = e.x;
-                        need_pop = false;
-                        moved = true;
-                    }
-                }
-            }
-            w.sp = sp;
-        }
-        w.cur = cur;
-        if(moved & (cur != PT_REF_NONE)) {
-            fetch(cur, R);
-        }
-    }
-
-    // One step of the wavefront: the common step for the lanes on inner nodes; then, if no lane is left on one or `leaf_min` lanes wait for
-    // it, the rare one.  Returns false when no lane of the wavefront stands anywhere any more.
-    PT_D bool step(Walk &w, Rec &R, int leaf_min, uint32_t &n_nodes, uint32_t &n_leaves) const {
-        PT_STAMP(0); // loop back, the caller's code between two steps
-        PT_STAMP(7); // (nothing: what a stamp costs)
-        const unsigned long long nodes = node_lanes(w.cur), slow = slow_lanes(w.cur);
-        if((nodes | slow) == 0ULL) {
-            return false;
-        }
-        PT_STAMP(1); // classification
-        if(nodes != 0ULL) {
-            n_nodes += (uint32_t)__popcll(nodes);
-            node_step(w, R, nodes, nodes & __builtin_amdgcn_uicmp(w.sp, (uint32_t)STACK_LDS, 35));
-        }
-        PT_STAMP(5); // leaving the common step
-        // The rare step, for the leaves and the walks that have to go on popping: its code is long (a triangle test is 100 instructions,
-        // a division among them), so the waiting lanes share it -- not before `leaf_min` of them wait, unless no lane stands on a node any
-        // more.  (Serving the popping walks at once instead of letting them wait with the leaves: 422 against 430 Msamples/s.)
-        if(slow != 0ULL && (nodes == 0ULL || __popcll(slow) >= leaf_min)) {
-            // (slow was taken before the common step: a lane that has just reached a leaf is not in it, its record is on its way)
-            slow_step(w, R, slow & __builtin_amdgcn_uicmp(w.cur, PT_REF_POPPING, 36), n_leaves);
-        }
-        PT_STAMP(6); // the rare step (or the test for it)
-        return true;
-    }
-};
 
 // ---- the per-slot word in LDS -----------------------------------------------------------------------------------------------------------
 // What the lanes that finish a slot's rays and the shading pass tell each other:
@@ -1085,11 +761,6 @@ PT_D void shade_row(const PtDevScene &sc, const PtDevCamera &cam, const PtDevOpt
 
 // ---- the kernel -------------------------------------------------------------------------------------------------------------------------
 
-#define PT_PATH_STACK_LDS 8 /* entries of a lane's traversal stack kept in LDS (16 KB per workgroup: four workgroups share a CU); deeper ones spill to HBM */
-// A scene staged in LDS whose records leave no room for four workgroups per CU beside an 8-entry window gets a 4-entry one (its tree has at most
-// 384 records: few walks go deeper, and those spill as on any tree).  176 / 98 / 72 triangles in the benchmark's box: 600 -> 757, 855 -> 949, 802 -> 862
-// Msamples/s; where four workgroups fit anyway the small window costs 2-4 % (Cornell 718 -> 705), and on trees in HBM 9 % (profiles/r03_stack_window_ab.txt).
-#define PT_PATH_STACK_LDS_SMALL 4
 #ifndef PT_COST_LDS_BYTES
 #define PT_COST_LDS_BYTES 1024 /* one word per lane: the wave step at which its walk began (stream cost diagnostics); 0 in builds that need the LDS */
 #endif
@@ -1526,465 +1197,6 @@ __global__ __launch_bounds__(256, PT_PATH_WAVES) void pt_path_kernel(const PtPat
     }
 }
 
-// Scene::getIntersection for a batch of rays: one walk per lane, the same traversal machinery
-template<int STACK_LDS, bool IN_LDS>
-__global__ __launch_bounds__(256) void pt_closest_kernel(PtDevScene sc, const float *__restrict__ rays6, uint32_t n, uint2 *__restrict__ out, uint2 *__restrict__ spill,
-                                                         uint32_t spill_depth) {
-    extern __shared__ __align__(16) unsigned char lds_raw[];
-    const int tid = threadIdx.x;
-    lds_u2_ptr stack_l = (lds_u2_ptr)reinterpret_cast<uint2 *>(lds_raw) + tid;
-    float4 *lds_recs = reinterpret_cast<float4 *>(lds_raw + (size_t)STACK_LDS * 256 * sizeof(uint2));
-    if(IN_LDS) {
-        for(uint32_t i = tid; i < 4u * (sc.pair_base + sc.n_pairs); i += 256) {
-            lds_recs[i] = sc.recs[i];
-        }
-        __syncthreads();
-    }
-    Tracer<STACK_LDS, IN_LDS> tr;
-    if(IN_LDS) {
-        tr.recs = (typename RecPtr<IN_LDS>::type)(lds_f4_cptr)lds_recs;
-    }
-    else {
-        tr.recs = (typename RecPtr<IN_LDS>::type)(glb_f4_cptr)sc.recs;
-    }
-    tr.stack_l = stack_l;
-    const size_t gid = (size_t)blockIdx.x * 256 + tid;
-    tr.my_spill = (glb_u2_ptr)(spill + gid * spill_depth);
-    if(gid >= n) {
-        return;
-    }
-    const float *r = rays6 + 6 * gid;
-    Walk w;
-    typename Tracer<STACK_LDS, IN_LDS>::Rec rec;
-    rec.r0 = rec.r1 = rec.r2 = rec.r3 = (f4v){0.0f, 0.0f, 0.0f, 0.0f};
-    RootBox root;
-    root.ref = sc.root_ref;
-    for(int k = 0; k < 3; k++) {
-        root.lo[k] = sc.root_lo[k];
-        root.hi[k] = sc.root_hi[k];
-    }
-    tr.start(w, rec, root, make_float4(r[0], r[1], r[2], 0.0f), make_float4(r[3], r[4], r[5], __uint_as_float(0u)));
-    uint32_t n_nodes = 0, n_leaves = 0;
-    while(tr.step(w, rec, 1, n_nodes, n_leaves)) {
-    }
-    out[gid] = make_uint2(__float_as_uint(w.best_ref == PT_REF_NONE ? -1.0f : w.best_t), w.best_ref);
-}
-
-// First-hit features of a frame for the denoiser (pt_denoise.hip): each pixel traces K = 4 primary rays at the sub-pixel offsets
-// (-1/4, -1/4), (+1/4, -1/4), (-1/4, +1/4), (+1/4, +1/4) through a camera without aperture sampling and without pixel jitter (the caller
-// passes aperture_kind = none; pixel_width = pixel_height = 0 make camera_shoot's two offsets +0), so the rays are a pure function of
-// camera and pixel.  The walk is pt_closest_kernel's.  out[3 p + k], the mean over the rays (summed in ray order, then * 0.25f; a miss adds 0):
-//   k = 0: albedo rgb (diffuse for Lambertian, specular for glass and mirror, white for no material), fraction of rays that hit
-//   k = 1: shading normal xyz (object_normal), hit distance t
-//   k = 2: hit position xyz (o + d * t), luminance of the material's emission
-// kViews (pt_render_features_views): `height` is the row count of n views stacked as in a view batch, view_height the rows of one; a pixel's
-// camera is views[row / view_height] (aperture none, as `cam`), read per lane, and its row the one inside its view.  Everything else is the
-// single frame's, so view v is bit for bit the single frame's result for views[v].  The single-frame instantiations read `cam` and have no
-// such test: kViews is a template parameter.
-template<int STACK_LDS, bool IN_LDS, bool kViews>
-__global__ __launch_bounds__(256) void pt_feature_kernel(PtDevScene sc, PtDevCamera cam, int32_t width, int32_t height, float4 *__restrict__ out, uint2 *__restrict__ spill,
-                                                         uint32_t spill_depth, const PtViewCamera *__restrict__ views, int32_t view_height) {
-    extern __shared__ __align__(16) unsigned char lds_raw[];
-    const int tid = threadIdx.x;
-    lds_u2_ptr stack_l = (lds_u2_ptr)reinterpret_cast<uint2 *>(lds_raw) + tid;
-    float4 *lds_recs = reinterpret_cast<float4 *>(lds_raw + (size_t)STACK_LDS * 256 * sizeof(uint2));
-    if(IN_LDS) {
-        for(uint32_t i = tid; i < 4u * (sc.pair_base + sc.n_pairs); i += 256) {
-            lds_recs[i] = sc.recs[i];
-        }
-        __syncthreads();
-    }
-    Tracer<STACK_LDS, IN_LDS> tr;
-    if(IN_LDS) {
-        tr.recs = (typename RecPtr<IN_LDS>::type)(lds_f4_cptr)lds_recs;
-    }
-    else {
-        tr.recs = (typename RecPtr<IN_LDS>::type)(glb_f4_cptr)sc.recs;
-    }
-    tr.stack_l = stack_l;
-    const size_t gid = (size_t)blockIdx.x * 256 + tid;
-    tr.my_spill = (glb_u2_ptr)(spill + gid * spill_depth);
-    if(gid >= (size_t)width * (size_t)height) {
-        return;
-    }
-    const int32_t px = (int32_t)(gid % (size_t)width);
-    int32_t py = (int32_t)(gid / (size_t)width);
-    const PtDevCamera *lane_cam = &cam;
-    int32_t frame_height = height;
-    if constexpr(kViews) {
-        const int32_t view = py / view_height;
-        py -= view * view_height;
-        lane_cam = &views[view].cam;
-        frame_height = view_height;
-    }
-    RootBox root;
-    root.ref = sc.root_ref;
-    for(int k = 0; k < 3; k++) {
-        root.lo[k] = sc.root_lo[k];
-        root.hi[k] = sc.root_hi[k];
-    }
-    float4 acc0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), acc1 = acc0, acc2 = acc0, emis = acc0;
-    for(int k = 0; k < 4; k++) {
-        const float dx = (k & 1) ? 0.25f : -0.25f, dy = (k & 2) ? 0.25f : -0.25f;
-        // the camera ray of the path kernel (worker.cpp:166-168) with x + 1/2 + dx in place of x + 1/2
-        const float one_half = 1.0f / 2.0f;
-        const float x_camera = 2 * (((float)px + one_half + dx) / (float)width - one_half);
-        float y_camera = 2 * (((float)py + one_half + dy) / (float)frame_height - one_half);
-        y_camera = -y_camera;
-        uint64_t rng = 0; // (drawn from, never used: both offsets are +0 and there is no aperture)
-        const Ray ray = camera_shoot(*lane_cam, x_camera, y_camera, 0.0f, 0.0f, rng);
-        Walk w;
-        typename Tracer<STACK_LDS, IN_LDS>::Rec rec;
-        rec.r0 = rec.r1 = rec.r2 = rec.r3 = (f4v){0.0f, 0.0f, 0.0f, 0.0f};
-        tr.start(w, rec, root, make_float4(ray.o.x, ray.o.y, ray.o.z, 0.0f), make_float4(ray.d.x, ray.d.y, ray.d.z, __uint_as_float(0u)));
-        uint32_t n_nodes = 0, n_leaves = 0;
-        while(tr.step(w, rec, 1, n_nodes, n_leaves)) {
-        }
-        float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), n4 = a, p4 = a, e4 = a;
-        if(w.best_ref != PT_REF_NONE) {
-            const float t = w.best_t;
-            const V3 pos = ray.o + ray.d * t;
-            uint32_t material_index;
-            const V3 n = object_normal(sc, w.best_ref, pos, material_index);
-            const Material mat = material_load(sc.materials, material_index);
-            const bool lambertian = mat.bsdf == 0; // PT_BSDF_LAMBERTIAN
-            a = make_float4(lambertian ? mat.diffuse.r : mat.specular.r, lambertian ? mat.diffuse.g : mat.specular.g, lambertian ? mat.diffuse.b : mat.specular.b, 1.0f);
-            n4 = make_float4(n.x, n.y, n.z, t);
-            p4 = make_float4(pos.x, pos.y, pos.z, 0.0f);
-            e4 = make_float4(mat.emission.r, mat.emission.g, mat.emission.b, 0.0f);
-        }
-        acc0 = make_float4(acc0.x + a.x, acc0.y + a.y, acc0.z + a.z, acc0.w + a.w);
-        acc1 = make_float4(acc1.x + n4.x, acc1.y + n4.y, acc1.z + n4.z, acc1.w + n4.w);
-        acc2 = make_float4(acc2.x + p4.x, acc2.y + p4.y, acc2.z + p4.z, 0.0f);
-        emis = make_float4(emis.x + e4.x, emis.y + e4.y, emis.z + e4.z, 0.0f);
-    }
-    const float q = 0.25f;
-    const float er = emis.x * q, eg = emis.y * q, eb = emis.z * q;
-    float4 *o = out + 3 * gid;
-    o[0] = make_float4(acc0.x * q, acc0.y * q, acc0.z * q, acc0.w * q);
-    o[1] = make_float4(acc1.x * q, acc1.y * q, acc1.z * q, acc1.w * q);
-    o[2] = make_float4(acc2.x * q, acc2.y * q, acc2.z * q, (0.2126f * er + 0.7152f * eg) + 0.0722f * eb);
-}
-
-// Followed features (include/pt_features.h): the rays, the layout and the order of pt_feature_kernel, but a ray that
-// hits glass or a mirror goes on -- bsdf_follow's deterministic branch, tinted by bsdf_spectrum as the path kernel's bounce tints -- to the
-// first Lambertian (or material-less) hit or to bounce `max_bounces`, and contributes there: albedo T * albedo, that hit's normal, the
-// summed length L of its segments, the unfolded position o0 + d0 * L and T * emission.  A miss at any bounce contributes what a first-hit
-// miss does: nothing.  With max_bounces = 0 every operation is pt_feature_kernel's (T = 1 and L = 0 + t are exact): the same bits.
-//
-// ONE loop of walks per lane, one tr.start / tr.step site: a lane's state is (sub-pixel ray k, bounce b, T, L, o0, d0, the accumulators),
-// and a lane whose chain ends starts the chain of its next sub-pixel ray in the same turn of the loop, while its neighbours bounce.  A lane
-// accumulates in ray order whatever its neighbours do, so the result does not depend on the wavefront.  The loop is bounded by
-// construction: a chain is at most max_bounces + 1 walks, so a lane makes at most 4 * (max_bounces + 1) of them, and that count -- not the
-// geometry -- ends the loop; a NaN direction fails the root box's test and its chain ends as a miss.
-template<int STACK_LDS, bool IN_LDS, bool kViews>
-__global__ __launch_bounds__(256) void pt_follow_kernel(PtDevScene sc, PtDevCamera cam, int32_t width, int32_t height, float4 *__restrict__ out, uint2 *__restrict__ spill,
-                                                        uint32_t spill_depth, const PtViewCamera *__restrict__ views, int32_t view_height, int32_t max_bounces,
-                                                        float epsilon) {
-    extern __shared__ __align__(16) unsigned char lds_raw[];
-    const int tid = threadIdx.x;
-    lds_u2_ptr stack_l = (lds_u2_ptr)reinterpret_cast<uint2 *>(lds_raw) + tid;
-    float4 *lds_recs = reinterpret_cast<float4 *>(lds_raw + (size_t)STACK_LDS * 256 * sizeof(uint2));
-    if(IN_LDS) {
-        for(uint32_t i = tid; i < 4u * (sc.pair_base + sc.n_pairs); i += 256) {
-            lds_recs[i] = sc.recs[i];
-        }
-        __syncthreads();
-    }
-    Tracer<STACK_LDS, IN_LDS> tr;
-    if(IN_LDS) {
-        tr.recs = (typename RecPtr<IN_LDS>::type)(lds_f4_cptr)lds_recs;
-    }
-    else {
-        tr.recs = (typename RecPtr<IN_LDS>::type)(glb_f4_cptr)sc.recs;
-    }
-    tr.stack_l = stack_l;
-    const size_t gid = (size_t)blockIdx.x * 256 + tid;
-    tr.my_spill = (glb_u2_ptr)(spill + gid * spill_depth);
-    if(gid >= (size_t)width * (size_t)height) {
-        return;
-    }
-    const int32_t px = (int32_t)(gid % (size_t)width);
-    int32_t py = (int32_t)(gid / (size_t)width);
-    const PtDevCamera *lane_cam = &cam;
-    int32_t frame_height = height;
-    if constexpr(kViews) {
-        const int32_t view = py / view_height;
-        py -= view * view_height;
-        lane_cam = &views[view].cam;
-        frame_height = view_height;
-    }
-    RootBox root;
-    root.ref = sc.root_ref;
-    for(int k = 0; k < 3; k++) {
-        root.lo[k] = sc.root_lo[k];
-        root.hi[k] = sc.root_hi[k];
-    }
-    // the primary ray of sub-pixel k: pt_feature_kernel's
-    auto primary = [&](int k) {
-        const float dx = (k & 1) ? 0.25f : -0.25f, dy = (k & 2) ? 0.25f : -0.25f;
-        const float one_half = 1.0f / 2.0f;
-        const float x_camera = 2 * (((float)px + one_half + dx) / (float)width - one_half);
-        float y_camera = 2 * (((float)py + one_half + dy) / (float)frame_height - one_half);
-        y_camera = -y_camera;
-        uint64_t rng = 0; // (drawn from, never used: both offsets are +0 and there is no aperture)
-        return camera_shoot(*lane_cam, x_camera, y_camera, 0.0f, 0.0f, rng);
-    };
-    float4 acc0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), acc1 = acc0, acc2 = acc0, emis = acc0;
-    int k = 0, b = 0;
-    Ray ray = primary(0);
-    V3 o0 = ray.o, d0 = ray.d, T = v3(1.0f, 1.0f, 1.0f);
-    float L = 0.0f;
-    const int max_walks = 4 * (max_bounces + 1);
-    for(int walk = 0; walk < max_walks && k < 4; walk++) {
-        Walk w;
-        typename Tracer<STACK_LDS, IN_LDS>::Rec rec;
-        rec.r0 = rec.r1 = rec.r2 = rec.r3 = (f4v){0.0f, 0.0f, 0.0f, 0.0f};
-        tr.start(w, rec, root, make_float4(ray.o.x, ray.o.y, ray.o.z, 0.0f), make_float4(ray.d.x, ray.d.y, ray.d.z, __uint_as_float(0u)));
-        uint32_t n_nodes = 0, n_leaves = 0;
-        while(tr.step(w, rec, 1, n_nodes, n_leaves)) {
-        }
-        float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), n4 = a, p4 = a, e4 = a;
-        bool chain_ends = true;
-        if(w.best_ref != PT_REF_NONE) {
-            const float t = w.best_t;
-            L = L + t;
-            const V3 pos = ray.o + ray.d * t;
-            uint32_t material_index;
-            const V3 n = object_normal(sc, w.best_ref, pos, material_index);
-            const Material mat = material_load(sc.materials, material_index);
-            const bool lambertian = mat.bsdf == 0; // PT_BSDF_LAMBERTIAN (a hit without a material loads as one)
-            if(lambertian || b == max_bounces) {
-                const V3 virt = o0 + d0 * L;
-                a = make_float4(T.x * (lambertian ? mat.diffuse.r : mat.specular.r), T.y * (lambertian ? mat.diffuse.g : mat.specular.g),
-                                T.z * (lambertian ? mat.diffuse.b : mat.specular.b), 1.0f);
-                n4 = make_float4(n.x, n.y, n.z, L);
-                p4 = make_float4(virt.x, virt.y, virt.z, 0.0f);
-                e4 = make_float4(T.x * mat.emission.r, T.y * mat.emission.g, T.z * mat.emission.b, 0.0f);
-            }
-            else {
-                bool reflected;
-                const Ray next = bsdf_follow(mat, ray.d, pos, n, epsilon, reflected);
-                float shading_factor, shading_pd;
-                const C4 tint = bsdf_spectrum(mat, ray.d, next.d, n, c4(1.0f, 1.0f, 1.0f, 1.0f), false, shading_factor, shading_pd);
-                T = v3(T.x * tint.r, T.y * tint.g, T.z * tint.b);
-                b += 1;
-                ray = next;
-                chain_ends = false;
-            }
-        }
-        if(chain_ends) {
-            acc0 = make_float4(acc0.x + a.x, acc0.y + a.y, acc0.z + a.z, acc0.w + a.w);
-            acc1 = make_float4(acc1.x + n4.x, acc1.y + n4.y, acc1.z + n4.z, acc1.w + n4.w);
-            acc2 = make_float4(acc2.x + p4.x, acc2.y + p4.y, acc2.z + p4.z, 0.0f);
-            emis = make_float4(emis.x + e4.x, emis.y + e4.y, emis.z + e4.z, 0.0f);
-            k += 1;
-            if(k < 4) {
-                ray = primary(k);
-                o0 = ray.o;
-                d0 = ray.d;
-                T = v3(1.0f, 1.0f, 1.0f);
-                L = 0.0f;
-                b = 0;
-            }
-        }
-    }
-    const float q = 0.25f;
-    const float er = emis.x * q, eg = emis.y * q, eb = emis.z * q;
-    float4 *o = out + 3 * gid;
-    o[0] = make_float4(acc0.x * q, acc0.y * q, acc0.z * q, acc0.w * q);
-    o[1] = make_float4(acc1.x * q, acc1.y * q, acc1.z * q, acc1.w * q);
-    o[2] = make_float4(acc2.x * q, acc2.y * q, acc2.z * q, (0.2126f * er + 0.7152f * eg) + 0.0722f * eb);
-}
-
-// ---- diagnostic: where the cycles of a traversal step go -------------------------------------------------------------------------------
-// One walk per lane as in pt_closest_kernel, but only the first `lanes_per_wave` lanes of every wavefront get a ray, and every step is
-// stamped (s_memtime): cycles spent waiting for the record that was requested at the end of the previous step, and everything else.
-// out[ray] = (steps, cycles waiting for records, cycles of the whole walk, cycles of two back-to-back stamps = the stamps' own price).
-template<int STACK_LDS, bool STAMP>
-__global__ __launch_bounds__(256) void pt_steptime_kernel(PtDevScene sc, const float *__restrict__ rays6, uint32_t n, uint32_t lanes_per_wave, uint4 *__restrict__ out,
-                                                          uint2 *__restrict__ spill, uint32_t spill_depth) {
-    extern __shared__ __align__(16) unsigned char lds_raw[];
-    const int tid = threadIdx.x;
-    const uint32_t lane = (uint32_t)tid & 63u;
-    const uint32_t wave = blockIdx.x * 4u + ((uint32_t)tid >> 6);
-    Tracer<STACK_LDS, false> tr;
-    tr.recs = (glb_f4_cptr)sc.recs;
-    tr.stack_l = (lds_u2_ptr)reinterpret_cast<uint2 *>(lds_raw) + tid;
-    const size_t gid = (size_t)blockIdx.x * 256 + tid;
-    tr.my_spill = (glb_u2_ptr)(spill + gid * spill_depth);
-    const uint32_t ray = wave * lanes_per_wave + lane;
-    if(lane >= lanes_per_wave || ray >= n) {
-        return;
-    }
-    const float *r = rays6 + 6 * (size_t)ray;
-    Walk w;
-    typename Tracer<STACK_LDS, false>::Rec rec;
-    rec.r0 = rec.r1 = rec.r2 = rec.r3 = (f4v){0.0f, 0.0f, 0.0f, 0.0f};
-    RootBox root;
-    root.ref = sc.root_ref;
-    for(int k = 0; k < 3; k++) {
-        root.lo[k] = sc.root_lo[k];
-        root.hi[k] = sc.root_hi[k];
-    }
-    const unsigned long long t_begin = __builtin_amdgcn_s_memtime();
-    const unsigned long long t_again = __builtin_amdgcn_s_memtime();
-#ifdef PT_STEP_STAMPS
-    tr.stamp_last = t_again;
-#endif
-    tr.start(w, rec, root, make_float4(r[0], r[1], r[2], 0.0f), make_float4(r[3], r[4], r[5], __uint_as_float(0u)));
-    uint32_t n_nodes = 0, n_leaves = 0, steps = 0;
-    unsigned long long waiting = 0;
-    for(;;) {
-        if(STAMP) {
-            const unsigned long long t1 = __builtin_amdgcn_s_memtime();
-            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-            const unsigned long long t2 = __builtin_amdgcn_s_memtime();
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            waiting += t2 - t1;
-        }
-        if(!tr.step(w, rec, 1, n_nodes, n_leaves)) {
-            break;
-        }
-        steps += 1u;
-    }
-    const unsigned long long t_end = __builtin_amdgcn_s_memtime();
-    out[ray] = make_uint4(steps, (uint32_t)waiting, (uint32_t)(t_end - t_begin), (uint32_t)(t_again - t_begin));
-#ifdef PT_STEP_STAMPS
-    // (the stamped build reports its segments behind the n results: 8 x 8 bytes per ray)
-    unsigned long long *seg = reinterpret_cast<unsigned long long *>(out + n) + 8 * (size_t)ray;
-    for(int k = 0; k < 8; k++) {
-        seg[k] = tr.stamp_acc[k];
-    }
-#endif
-}
-
-// ---- diagnostic: the traversal alone on the rays of a finished render ----------------------------------------------------------------
-// With PT_RING_LOG_RAYS set, the wavefronts' rings are long enough never to wrap, so after a render they hold every ray of the frame
-// in the order the wavefront traced them.  This kernel replays them: the same hand-out / burst / leaf-batching loop as the path
-// kernel, no shading, results folded into a checksum -- at WAVES wavefronts per SIMD, which the path kernel cannot choose freely
-// (the shading code's registers cap it at four).  It answers what a tracer that is not tied to the shading code would deliver.
-// Wavefront v replays part (v / n_logs) of `parts` equal parts of ring (v % n_logs).
-template<int STACK_LDS, int WAVES>
-__global__ __launch_bounds__(256, WAVES) void pt_replay_kernel(PtDevScene sc, PtLocalQueue Q, uint32_t n_logs, uint32_t parts, int refill_idle, int burst_steps,
-                                                                int leaf_min, uint2 *__restrict__ spill, uint32_t spill_depth,
-                                                                unsigned long long *__restrict__ out) {
-    extern __shared__ __align__(16) unsigned char lds_raw[];
-    const int tid = threadIdx.x;
-    const uint32_t lane = (uint32_t)tid & 63u;
-    const uint32_t wave = blockIdx.x * 4u + ((uint32_t)tid >> 6);
-    if(wave >= n_logs * parts) {
-        return;
-    }
-    Tracer<STACK_LDS, false> tr;
-    tr.recs = (glb_f4_cptr)sc.recs;
-    tr.stack_l = (lds_u2_ptr)reinterpret_cast<uint2 *>(lds_raw) + tid;
-    tr.my_spill = (glb_u2_ptr)(spill + ((size_t)wave * 64 + lane) * spill_depth);
-    RootBox root;
-    root.ref = sc.root_ref;
-    for(int k = 0; k < 3; k++) {
-        root.lo[k] = sc.root_lo[k];
-        root.hi[k] = sc.root_hi[k];
-    }
-    const size_t base = (size_t)(wave % n_logs) * Q.cap;
-    // rays written: the prefix of the ring whose direction words are not the 0xff fill
-    uint32_t lo = 0, hi = Q.cap;
-    while(lo < hi) {
-        const uint32_t mid = (lo + hi) / 2;
-        if(__float_as_uint(Q.ray_d[base + mid].x) == 0xffffffffu) {
-            hi = mid;
-        }
-        else {
-            lo = mid + 1;
-        }
-    }
-    const uint32_t part = wave / n_logs;
-    uint32_t pos = (uint32_t)((unsigned long long)lo * part / parts);
-    const uint32_t end = (uint32_t)((unsigned long long)lo * (part + 1) / parts);
-
-    bool active = false;
-    Walk w;
-    w.o = v3(0, 0, 0);
-    w.d = v3(0, 0, 1);
-    w.inv = v3(0, 0, 0);
-    w.pack();
-    w.thr = 0.0f;
-    w.dest = 0;
-    w.best_t = 0.0f;
-    w.best_ref = PT_REF_NONE;
-    w.set_t_max(FLT_MAX);
-    w.cur = PT_REF_NONE;
-    w.sp = 0;
-    w.occluded = false;
-    typename Tracer<STACK_LDS, false>::Rec rec;
-    rec.r0 = rec.r1 = rec.r2 = rec.r3 = (f4v){0.0f, 0.0f, 0.0f, 0.0f};
-    uint32_t n_nodes = 0, n_leaves = 0, n_rays = 0, checksum = 0, w_steps = 0;
-    for(;;) {
-        if(active && w.cur == PT_REF_NONE) {
-            checksum += (w.dest & PT_DEST_SHADOW) ? (w.occluded ? 1u : 2u) : (w.best_ref ^ __float_as_uint(w.best_t));
-            active = false;
-        }
-        const unsigned long long idle_mask = __ballot(!active);
-        const uint32_t n_idle = (uint32_t)__popcll(idle_mask);
-        if(n_idle >= (uint32_t)refill_idle && pos < end) {
-            const uint32_t left = end - pos;
-            const uint32_t take = left < n_idle ? left : n_idle;
-            if(!active) {
-                const uint32_t rank = (uint32_t)__popcll(idle_mask & ((1ULL << lane) - 1ULL));
-                if(rank < take) {
-                    const float4 ro = Q.ray_o[base + pos + rank];
-                    const float4 rd = Q.ray_d[base + pos + rank];
-                    if(__float_as_uint(rd.w) != PT_DEST_NULL) {
-                        tr.start(w, rec, root, ro, rd);
-                        active = true;
-                        n_rays++;
-                    }
-                }
-            }
-            pos += take;
-        }
-        if(__ballot(active) == 0ULL) {
-            if(pos >= end) {
-                break;
-            }
-            continue;
-        }
-#pragma unroll 1
-        for(int burst = 0; burst < burst_steps; burst++) {
-            w_steps++;
-            if(!tr.step(w, rec, leaf_min, n_nodes, n_leaves)) {
-                w_steps--;
-                break;
-            }
-        }
-    }
-    for(int off = 32; off > 0; off >>= 1) {
-        n_rays += __shfl_down(n_rays, off); // (n_nodes and n_leaves are counted for the whole wavefront: Tracer::step)
-        checksum += __shfl_down(checksum, off);
-    }
-    if(lane == 0) {
-        atomicAdd(&out[0], (unsigned long long)n_rays);
-        atomicAdd(&out[1], (unsigned long long)n_nodes);
-        atomicAdd(&out[2], (unsigned long long)n_leaves);
-        atomicAdd(&out[3], (unsigned long long)w_steps);
-        atomicAdd(&out[4], (unsigned long long)checksum);
-    }
-}
-
-template<int STACK_LDS, int WAVES>
-int launch_replay(hipStream_t stream, const PtDevScene &scene, const PtLocalQueue &Q, uint32_t n_logs, uint32_t parts, const PtPathConfig &cfg, uint2 *spill,
-                  unsigned long long *out) {
-    const size_t lds = (size_t)STACK_LDS * 256 * sizeof(uint2);
-    int blocks = 0;
-    if(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, pt_replay_kernel<STACK_LDS, WAVES>, 256, lds) != hipSuccess) {
-        blocks = -1;
-    }
-    const uint32_t waves = n_logs * parts;
-    hipLaunchKernelGGL((pt_replay_kernel<STACK_LDS, WAVES>), dim3((waves + 3) / 4), dim3(256), lds, stream, scene, Q, n_logs, parts, cfg.refill_idle,
-                       cfg.burst_steps, cfg.leaf_min, spill, cfg.spill_depth, out);
-    return blocks;
-}
-
 template<bool WIDE, bool IN_LDS, int STACK_LDS>
 void launch_path(hipStream_t stream, const PtPathConfig &cfg, const PtPathArgs *d_args) {
     hipLaunchKernelGGL((pt_path_kernel<WIDE, IN_LDS, STACK_LDS>), dim3(cfg.grid), dim3(256), cfg.lds_bytes, stream, d_args);
@@ -1995,44 +1207,6 @@ void occupancy(size_t lds_bytes, int *out) {
     int blocks = 0;
     const hipError_t err = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, pt_path_kernel<WIDE, IN_LDS, STACK_LDS>, 256, lds_bytes);
     *out = (err != hipSuccess || blocks < 1) ? 1 : blocks;
-}
-
-template<int STACK_LDS, bool IN_LDS>
-void launch_closest(hipStream_t stream, const PtDevScene &scene, const float *rays6, uint32_t n, uint2 *out, const PtPathConfig &cfg) {
-    const size_t lds = (size_t)STACK_LDS * 256 * sizeof(uint2) + (IN_LDS ? ((size_t)scene.n_lds_pairs + scene.pair_base) * 64 : 0);
-    hipLaunchKernelGGL((pt_closest_kernel<STACK_LDS, IN_LDS>), dim3((n + 255) / 256), dim3(256), lds, stream, scene, rays6, n, out, cfg.spill, cfg.spill_depth);
-}
-
-// views == nullptr: the frame of `cam`; else the stacked frames of views[0 .. height / view_height)
-template<int STACK_LDS, bool IN_LDS>
-void launch_features(hipStream_t stream, const PtDevScene &scene, const PtDevCamera &cam, int32_t width, int32_t height, float4 *out, const PtPathConfig &cfg,
-                     const PtViewCamera *views = nullptr, int32_t view_height = 0) {
-    const size_t lds = (size_t)STACK_LDS * 256 * sizeof(uint2) + (IN_LDS ? ((size_t)scene.n_lds_pairs + scene.pair_base) * 64 : 0);
-    const size_t n = (size_t)width * (size_t)height;
-    if(views != nullptr) {
-        hipLaunchKernelGGL((pt_feature_kernel<STACK_LDS, IN_LDS, true>), dim3((unsigned)((n + 255) / 256)), dim3(256), lds, stream, scene, cam, width, height, out,
-                           cfg.spill, cfg.spill_depth, views, view_height);
-    }
-    else {
-        hipLaunchKernelGGL((pt_feature_kernel<STACK_LDS, IN_LDS, false>), dim3((unsigned)((n + 255) / 256)), dim3(256), lds, stream, scene, cam, width, height, out,
-                           cfg.spill, cfg.spill_depth, nullptr, 0);
-    }
-}
-
-// the followed form of launch_features (pt_follow_kernel): the same grid, LDS and spill area
-template<int STACK_LDS, bool IN_LDS>
-void launch_follow(hipStream_t stream, const PtDevScene &scene, const PtDevCamera &cam, int32_t width, int32_t height, float4 *out, const PtPathConfig &cfg,
-                   int32_t max_bounces, float epsilon, const PtViewCamera *views = nullptr, int32_t view_height = 0) {
-    const size_t lds = (size_t)STACK_LDS * 256 * sizeof(uint2) + (IN_LDS ? ((size_t)scene.n_lds_pairs + scene.pair_base) * 64 : 0);
-    const size_t n = (size_t)width * (size_t)height;
-    if(views != nullptr) {
-        hipLaunchKernelGGL((pt_follow_kernel<STACK_LDS, IN_LDS, true>), dim3((unsigned)((n + 255) / 256)), dim3(256), lds, stream, scene, cam, width, height, out,
-                           cfg.spill, cfg.spill_depth, views, view_height, max_bounces, epsilon);
-    }
-    else {
-        hipLaunchKernelGGL((pt_follow_kernel<STACK_LDS, IN_LDS, false>), dim3((unsigned)((n + 255) / 256)), dim3(256), lds, stream, scene, cam, width, height, out,
-                           cfg.spill, cfg.spill_depth, nullptr, 0, max_bounces, epsilon);
-    }
 }
 
 } // namespace
@@ -2095,109 +1269,6 @@ void pt_launch_path(hipStream_t stream, const PtDevScene &scene, const PtDevCame
     a.wave_counters = cfg.wave_counters;
     (void)hipMemcpyAsync(d_args, host_args, sizeof(PtPathArgs), hipMemcpyHostToDevice, stream);
     PT_DISPATCH_PATH(launch_path, cfg, stream, cfg, d_args);
-}
-
-void pt_launch_steptime(hipStream_t stream, const PtDevScene &scene, const float *rays6, uint32_t n, uint32_t lanes_per_wave, uint4 *out, uint2 *spill, uint32_t spill_depth, int flags) {
-    const uint32_t waves = (n + lanes_per_wave - 1) / lanes_per_wave;
-    if(flags & 2) { // bit 1: stamp the waits (each stamp is a scalar memory round trip of its own: the totals of such a run are inflated)
-        hipLaunchKernelGGL((pt_steptime_kernel<8, true>), dim3((waves + 3) / 4), dim3(256), (size_t)8 * 256 * sizeof(uint2), stream, scene, rays6, n, lanes_per_wave, out, spill, spill_depth);
-    }
-    else {
-        hipLaunchKernelGGL((pt_steptime_kernel<8, false>), dim3((waves + 3) / 4), dim3(256), (size_t)8 * 256 * sizeof(uint2), stream, scene, rays6, n, lanes_per_wave, out, spill, spill_depth);
-    }
-}
-
-void pt_launch_closest(hipStream_t stream, const PtDevScene &scene, const float *rays6, uint32_t n, uint2 *out, const PtPathConfig &cfg) {
-    if(n == 0) {
-        return;
-    }
-    if(cfg.in_lds && cfg.stack_lds == PT_PATH_STACK_LDS_SMALL) {
-        launch_closest<PT_PATH_STACK_LDS_SMALL, true>(stream, scene, rays6, n, out, cfg);
-    }
-    else if(cfg.in_lds) {
-        launch_closest<PT_PATH_STACK_LDS, true>(stream, scene, rays6, n, out, cfg);
-    }
-    else {
-        launch_closest<PT_PATH_STACK_LDS, false>(stream, scene, rays6, n, out, cfg);
-    }
-}
-
-void pt_launch_features(hipStream_t stream, const PtDevScene &scene, const PtDevCamera &camera, int32_t width, int32_t height, float4 *out, const PtPathConfig &cfg) {
-    if(width <= 0 || height <= 0) {
-        return;
-    }
-    if(cfg.in_lds && cfg.stack_lds == PT_PATH_STACK_LDS_SMALL) {
-        launch_features<PT_PATH_STACK_LDS_SMALL, true>(stream, scene, camera, width, height, out, cfg);
-    }
-    else if(cfg.in_lds) {
-        launch_features<PT_PATH_STACK_LDS, true>(stream, scene, camera, width, height, out, cfg);
-    }
-    else {
-        launch_features<PT_PATH_STACK_LDS, false>(stream, scene, camera, width, height, out, cfg);
-    }
-}
-
-void pt_launch_features_views(hipStream_t stream, const PtDevScene &scene, const PtViewCamera *views, int32_t n_views, int32_t width, int32_t height, float4 *out,
-                              const PtPathConfig &cfg) {
-    if(width <= 0 || height <= 0 || n_views <= 0) {
-        return;
-    }
-    const PtDevCamera none{}; // (never read: every pixel has its view's camera)
-    const int32_t rows = n_views * height;
-    if(cfg.in_lds && cfg.stack_lds == PT_PATH_STACK_LDS_SMALL) {
-        launch_features<PT_PATH_STACK_LDS_SMALL, true>(stream, scene, none, width, rows, out, cfg, views, height);
-    }
-    else if(cfg.in_lds) {
-        launch_features<PT_PATH_STACK_LDS, true>(stream, scene, none, width, rows, out, cfg, views, height);
-    }
-    else {
-        launch_features<PT_PATH_STACK_LDS, false>(stream, scene, none, width, rows, out, cfg, views, height);
-    }
-}
-
-void pt_launch_features_followed(hipStream_t stream, const PtDevScene &scene, const PtDevCamera &camera, int32_t width, int32_t height, float4 *out, const PtPathConfig &cfg,
-                                 int32_t max_bounces, float epsilon) {
-    if(width <= 0 || height <= 0) {
-        return;
-    }
-    if(cfg.in_lds && cfg.stack_lds == PT_PATH_STACK_LDS_SMALL) {
-        launch_follow<PT_PATH_STACK_LDS_SMALL, true>(stream, scene, camera, width, height, out, cfg, max_bounces, epsilon);
-    }
-    else if(cfg.in_lds) {
-        launch_follow<PT_PATH_STACK_LDS, true>(stream, scene, camera, width, height, out, cfg, max_bounces, epsilon);
-    }
-    else {
-        launch_follow<PT_PATH_STACK_LDS, false>(stream, scene, camera, width, height, out, cfg, max_bounces, epsilon);
-    }
-}
-
-void pt_launch_features_followed_views(hipStream_t stream, const PtDevScene &scene, const PtViewCamera *views, int32_t n_views, int32_t width, int32_t height, float4 *out,
-                                       const PtPathConfig &cfg, int32_t max_bounces, float epsilon) {
-    if(width <= 0 || height <= 0 || n_views <= 0) {
-        return;
-    }
-    const PtDevCamera none{}; // (never read: every pixel has its view's camera)
-    const int32_t rows = n_views * height;
-    if(cfg.in_lds && cfg.stack_lds == PT_PATH_STACK_LDS_SMALL) {
-        launch_follow<PT_PATH_STACK_LDS_SMALL, true>(stream, scene, none, width, rows, out, cfg, max_bounces, epsilon, views, height);
-    }
-    else if(cfg.in_lds) {
-        launch_follow<PT_PATH_STACK_LDS, true>(stream, scene, none, width, rows, out, cfg, max_bounces, epsilon, views, height);
-    }
-    else {
-        launch_follow<PT_PATH_STACK_LDS, false>(stream, scene, none, width, rows, out, cfg, max_bounces, epsilon, views, height);
-    }
-}
-
-int pt_launch_replay(hipStream_t stream, const PtDevScene &scene, const PtLocalQueue &Q, uint32_t n_logs, uint32_t parts, int waves_per_simd, const PtPathConfig &cfg,
-                     uint2 *spill, unsigned long long *out) {
-    switch(waves_per_simd) {
-    case 4: return launch_replay<8, 4>(stream, scene, Q, n_logs, parts, cfg, spill, out);
-    case 5: return launch_replay<8, 5>(stream, scene, Q, n_logs, parts, cfg, spill, out);
-    case 6: return launch_replay<8, 6>(stream, scene, Q, n_logs, parts, cfg, spill, out);
-    case 7: return launch_replay<8, 7>(stream, scene, Q, n_logs, parts, cfg, spill, out);
-    default: return launch_replay<8, 8>(stream, scene, Q, n_logs, parts, cfg, spill, out);
-    }
 }
 
 size_t pt_path_lds_bytes(int wide, int rows, int stack_lds, uint32_t n_lds_pairs, uint32_t n_lds_leaf_records) {

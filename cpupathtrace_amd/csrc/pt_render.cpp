@@ -12,7 +12,7 @@ int setup_path(pt_scene *s) {
     }
     cfg.in_lds = (s->dev.n_lds_pairs == s->dev.n_pairs && s->dev.n_lds_tris == s->dev.n_tris && s->dev.n_lds_pairs + s->dev.n_lds_tris > 0) ? 1 : 0;
     // 8 stack entries per lane in LDS (16 KB per workgroup) let four workgroups share a CU; deeper walks use the HBM spill area.  A scene
-    // staged in LDS that leaves no room for four workgroups that way gets a window of 4 entries (pt_path.hip, PT_PATH_STACK_LDS_SMALL)
+    // staged in LDS that leaves no room for four workgroups that way gets a window of 4 entries (pt_trace.h, PT_PATH_STACK_LDS_SMALL)
     cfg.wide = s->dev.n_lights + s->dev.n_object_samples > 8U ? 1 : 0;
     cfg.rows = std::min(std::max(env_int("PT_ROWS", 4), 1), PT_MAX_ROWS);
     cfg.stack_lds = pt_path_stack_lds(cfg.in_lds, pt_path_lds_bytes(cfg.wide, cfg.rows, 8, cfg.in_lds ? s->dev.n_lds_pairs : 0U, cfg.in_lds ? s->dev.pair_base : 0U));

@@ -1,6 +1,6 @@
 // pt_shading.h -- device functions of the shading side of the hot path: the per-pixel adaptive estimator of processItem
 // (src/worker.cpp:149-326), one light sample of Scene::sampleLights (src/scene/scene.cpp:238-286), the per-pixel engine seed.
-// Shared by the kernels of pt_path.hip; everything keeps the reference's evaluation order (see pt_device.h).
+// Shared by the kernels of pt_path.hip and pt_walks.hip; everything keeps the reference's evaluation order (see pt_device.h).
 #ifndef PT_SHADING_H
 #define PT_SHADING_H
 

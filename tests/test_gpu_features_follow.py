@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from cpupathtrace_amd import binding, scenes
+from tests import denoise_ref
 from tests import features_follow_ref as ffr
 from tests import unit_cases as uc
 from tests.util import assert_bits_equal, env
@@ -56,19 +57,34 @@ def test_records_in_lds_and_in_hbm(world):
     assert world("hall")[0].info()["n_nodes"] < 64 and world("mesh")[0].info()["n_nodes"] >= 2 * 1024 - 1
 
 
+def walk_calls(gpu, cam, opt, rays):
+    """The calls that go through the walk kernels' dispatch beside the followed pass: first-hit features, single and views, and a ray batch."""
+    return gpu.render_features(cam, opt), gpu.render_features_views(ffr.view_cameras(cam)[:2], opt), gpu.get_intersection(rays)
+
+
 @pytest.mark.parametrize("knobs", [{"PT_LDS_SMALL": 0}, {"PT_STACK_WINDOW": 4}], ids=["records_in_hbm", "window_of_4"])
-def test_other_instantiations_on_a_small_scene(oracle_lib, knobs):
-    """A small scene with its records left in HBM, and staged in LDS with the 4-entry stack window: the same bits."""
+def test_other_instantiations_on_a_small_scene(oracle_lib, world, knobs):
+    """A small scene with its records left in HBM, and staged in LDS with the 4-entry stack window: the same bits, from the followed pass
+    and from the first-hit pass and intersect_batch (the frame's primary rays), which take the same route."""
     sc, cam, epsilon = ffr.scene("glass")
+    opt = scenes.options(W, H, 1, 1, epsilon=epsilon)
+    rays = denoise_ref.feature_rays(oracle_lib, cam, W, H).reshape(-1, 6)
     with env(**knobs):
         gpu = binding.Scene(sc, device=0)
         try:
-            got = gpu.render_features(cam, scenes.options(W, H, 1, 1, epsilon=epsilon), followed={"max_bounces": 8})
-            views = gpu.render_features_views(ffr.view_cameras(cam)[:2], scenes.options(W, H, 1, 1, epsilon=epsilon), followed={"max_bounces": 8})
+            got = gpu.render_features(cam, opt, followed={"max_bounces": 8})
+            views = gpu.render_features_views(ffr.view_cameras(cam)[:2], opt, followed={"max_bounces": 8})
+            first, first_views, (t, obj) = walk_calls(gpu, cam, opt, rays)
         finally:
             gpu.close()
     assert_bits_equal(got, ffr.reference(oracle_lib, "glass", 8)[0], str(knobs))
     assert_bits_equal(views[0], got, "%s, view 0" % knobs)
+    want_first, want_views, (want_t, want_obj) = walk_calls(world("glass")[0], cam, opt, rays)
+    assert len(rays) == 4 * W * H and (want_obj >= 0).any()
+    assert_bits_equal(first, want_first, "%s, first-hit features" % knobs)
+    assert_bits_equal(first_views, want_views, "%s, first-hit features of two views" % knobs)
+    assert_bits_equal(t, want_t, "%s, intersect_batch t" % knobs)
+    assert_bits_equal(obj, want_obj, "%s, intersect_batch object" % knobs)
 
 
 @pytest.mark.parametrize("name", list(ffr.SCENE_SET))
