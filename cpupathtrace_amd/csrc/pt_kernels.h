@@ -28,7 +28,7 @@
 // sampling records (64 B) and shading records (96 B: the vertex normals of an emissive triangle), and the materials (64 B).
 #define PT_LDS_TABLE_MAX 16
 #define PT_LDS_TABLE_BYTES (PT_LDS_TABLE_MAX * (4 + 64 + 96 + 64))
-#define PT_WALK_SAVE_WORDS 17
+#define PT_WALK_SAVE_WORDS 13
 #define PT_MAX_ROWS 8      /* rows of 64 slots per wavefront */
 #define PT_F_STREAM 128u   /* the slot holds a stream (flag bit, next to PT_F_*) */
 

@@ -201,8 +201,8 @@ PT_D V *slot_plane(const PtSlots &S, uint32_t k, uint32_t p) {
 template<bool WIDE>
 PT_D void shade_row(const PtDevScene &sc, const PtDevCamera &cam, const PtDevOptions &opt, const PtSlots &S, const PtStreams &T, const PtLocalQueue &Q,
                     WaveCtx &ctx, uint32_t row, uint32_t ls_in, uint32_t lane, uint32_t slot_base, size_t queue_base, typename SlotWord<WIDE>::lds_ptr word_l, lds_u2_ptr hit_l,
-                    float4 *__restrict__ image, PtDevCounters *counters, const ShadeTables &tb, bool stop, uint32_t &n_samples, uint32_t &n_vertices) {
-    // (n_samples, n_vertices: the wavefront's counts, the same in every lane; stop: the host has asked the launch to stop (PtStreams::cancel),
+                    float4 *__restrict__ image, PtDevCounters *counters, const ShadeTables &tb, bool stop, uint32_t &n_samples, uint32_t &n_vertices, uint32_t &n_shadow) {
+    // (n_samples, n_vertices, n_shadow: the wavefront's counts, the same in every lane; stop: the host has asked the launch to stop (PtStreams::cancel),
     // a scalar read once per pass -- no stream is taken any more, and a stream that would start another sample is dropped instead)
     // the lane's slot of the wave: lane `lane` of row `row`, or -- in a compacted pass (see the kernel) -- the slot the list names; PT_NO_SLOT = none
     const bool have_slot = ls_in != PT_NO_SLOT;
@@ -592,6 +592,7 @@ PT_D void shade_row(const PtDevScene &sc, const PtDevCamera &cam, const PtDevOpt
     const uint32_t ext_pos = tail + (uint32_t)__popcll(ext_mask & lt);
     tail += (uint32_t)__popcll(ext_mask);
     ctx.q_count += (uint32_t)__popcll(ext_mask);
+    n_shadow -= (uint32_t)__popcll(ext_mask); // (the kernel adds what the pass queued: what is left are the shadow rays)
     auto ring = [&](uint32_t i) -> size_t { return queue_base + (i >= Q.cap ? i - Q.cap : i); };
 
     // ---- vertex, part 2: light sampling, shadow rays (worker.cpp:73-103) -------------------------------------------------------------------
@@ -789,6 +790,9 @@ __global__ __launch_bounds__(256, PT_PATH_WAVES) void pt_path_kernel(const PtPat
     // diagnostic (PT_DEBUG_LANES): only the first `debug_lanes` lanes of a wavefront take rays -- throughput against walks per step with everything else equal
     const unsigned long long lane_cap = A->debug_lanes >= 64 ? ~0ULL : ((1ULL << A->debug_lanes) - 1ULL);
     PtLocalQueue Q = A->Q;
+    // (the ring as the traversal loop reads it: typed global, so the window's reloads are global_load, not flat_load -- which would also count
+    // in lgkmcnt, where the next step's stack read waits)
+    const glb_f4_cptr ring_o = (glb_f4_cptr)reinterpret_cast<const f4v *>(Q.ray_o), ring_d = (glb_f4_cptr)reinterpret_cast<const f4v *>(Q.ray_d);
     RootBox root;
     root.ref = A->sc.root_ref;
     for(int k = 0; k < 3; k++) {
@@ -924,7 +928,7 @@ __global__ __launch_bounds__(256, PT_PATH_WAVES) void pt_path_kernel(const PtPat
     uint32_t n_nodes = 0, n_leaves = 0, n_rays = 0, n_shadow = 0, n_samples = 0, n_vertices = 0;
     uint32_t w_steps = 0, w_passes = 0; // wave-level diagnostics (same value in every lane)
 #ifdef PT_PATH_TIMING
-    unsigned long long t_shade = 0, t_burst = 0;
+    unsigned long long t_shade = 0, t_burst = 0, t_inner = 0;
     const unsigned long long t_begin = __builtin_amdgcn_s_memtime();
 #endif
 
@@ -948,8 +952,8 @@ __global__ __launch_bounds__(256, PT_PATH_WAVES) void pt_path_kernel(const PtPat
             const size_t save_stride = P->save_stride;
             const uint32_t lane_s = lane_afresh(); // (the lane number of the pass)
 
-            // Nothing of the traversal lives in registers across a shading pass (which needs them all): the walks in progress and the
-            // lane's counters are parked in this lane's column of the save area and read back afterwards.
+            // No vector register of the traversal lives across a shading pass (which needs them all): the walks in progress are parked in
+            // this lane's column of the save area and read back afterwards.  (The work counters are wavefront totals: scalars, which stay.)
             {
                 uint32_t *sv = walk_save + (size_t)wave * 64 + lane_s;
                 const size_t st = save_stride;
@@ -966,10 +970,6 @@ __global__ __launch_bounds__(256, PT_PATH_WAVES) void pt_path_kernel(const PtPat
                 sv[10 * st] = __float_as_uint(w.t_max);
                 sv[11 * st] = w.cur;
                 sv[12 * st] = w.sp | (w.occluded ? 0x80000000u : 0u);
-                sv[13 * st] = n_nodes;
-                sv[14 * st] = n_leaves;
-                sv[15 * st] = n_rays;
-                sv[16 * st] = n_shadow;
             }
             // A pass costs a chain of memory round trips per ROW it visits, however few of the row's slots take part.  Once streams end
             // for good (adaptive sampling stops pixels early; the last streams of any job) the ready slots thin out in every row alike, so
@@ -1001,6 +1001,9 @@ __global__ __launch_bounds__(256, PT_PATH_WAVES) void pt_path_kernel(const PtPat
                 stop_word = __hip_atomic_load(P->T.cancel, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
             }
             const bool stop = __builtin_amdgcn_readfirstlane(stop_word) != 0u;
+            // shadow rays are counted where they are queued (every queued ray is walked before the wavefront ends): all the pass queues but
+            // the extension rays, which shade_row takes off
+            n_shadow -= ctx.q_count;
 #pragma unroll 1
             for(uint32_t k = 0; k < n_chunks; k++) {
                 // (in a compacted pass `row` is not used: the first round is over)
@@ -1008,8 +1011,9 @@ __global__ __launch_bounds__(256, PT_PATH_WAVES) void pt_path_kernel(const PtPat
                 if(compact) {
                     ls = ls < n_listed ? (uint32_t)list_l[ls] : PT_NO_SLOT;
                 }
-                shade_row<WIDE>(P->sc, P->cam, P->opt, P->S, P->T, P->Q, ctx, k, ls, lane_s, (uint32_t)slot_base, queue_base, word_l, hit_l, P->image, P->counters, tb, stop, n_samples, n_vertices);
+                shade_row<WIDE>(P->sc, P->cam, P->opt, P->S, P->T, P->Q, ctx, k, ls, lane_s, (uint32_t)slot_base, queue_base, word_l, hit_l, P->image, P->counters, tb, stop, n_samples, n_vertices, n_shadow);
             }
+            n_shadow += ctx.q_count;
             // the rays just written are read back by other lanes of this wavefront
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
             __builtin_amdgcn_s_waitcnt(0);
@@ -1033,10 +1037,6 @@ __global__ __launch_bounds__(256, PT_PATH_WAVES) void pt_path_kernel(const PtPat
                 const uint32_t packed = sv[12 * st];
                 w.sp = packed & 0x7fffffffu;
                 w.occluded = (packed >> 31) != 0;
-                n_nodes = sv[13 * st];
-                n_leaves = sv[14 * st];
-                n_rays = sv[15 * st];
-                n_shadow = sv[16 * st];
             }
 #ifdef PT_PATH_TIMING
             t_shade += __builtin_amdgcn_s_memtime() - t_pass;
@@ -1048,8 +1048,8 @@ __global__ __launch_bounds__(256, PT_PATH_WAVES) void pt_path_kernel(const PtPat
             if(lane_w < ctx.q_count) {
                 uint32_t i = ctx.q_head + lane_w;
                 i = i >= Q.cap ? i - Q.cap : i;
-                win_o = Q.ray_o[queue_base + i];
-                win_d = Q.ray_d[queue_base + i];
+                win_o = to_f4(ring_o[queue_base + i]);
+                win_d = to_f4(ring_d[queue_base + i]);
             }
             // the record registers do not live across a shading pass: walks in progress fetch theirs again
             rec.r0 = rec.r1 = rec.r2 = rec.r3 = (f4v){0.0f, 0.0f, 0.0f, 0.0f};
@@ -1063,8 +1063,15 @@ __global__ __launch_bounds__(256, PT_PATH_WAVES) void pt_path_kernel(const PtPat
             asm volatile("" : "+s"(bind_offset));
             bind_lane((const PtPathArgs *)(args_c4)((const char __attribute__((address_space(4))) *)A4 + bind_offset), lane_afresh());
         }
+        // (One way round the loop and one way out of it -- `leave` -- instead of a break for the pass, one for the end and a continue for a
+        // wavefront without walks: with several exits the compiler gave the walk and the record registers a home per exit and moved all of them
+        // from one to the next on every trip.)
         bool finished = false;
-        for(;;) {
+        bool leave = false;
+#ifdef PT_PATH_TIMING
+        const unsigned long long t_i0 = __builtin_amdgcn_s_memtime();
+#endif
+        do {
             // ---- 1. retire finished walks: the result goes to the slot's words in LDS -----------------------------------------------------
             if(active && w.cur == PT_REF_NONE) {
                 const uint32_t ls = w.dest & PT_DEST_SLOT_MASK;
@@ -1106,10 +1113,10 @@ __global__ __launch_bounds__(256, PT_PATH_WAVES) void pt_path_kernel(const PtPat
                     // is only worth its fixed price when `early_ready` slots take part)
                     if(ctx.q_count == 0 ? (n_ready >= need || n_idle == (uint32_t)__popcll(lane_cap)) : n_ready >= (uint32_t)early_ready) {
                         want_pass = true;
-                        break;
+                        leave = true;
                     }
                 }
-                if(ctx.q_count > 0) {
+                if(!leave && ctx.q_count > 0) {
                     // The ring's next 64 rays are already in registers, one per lane (requested when the ring's head last moved:
                     // reading them here would stall the whole wavefront, walks in progress included, for a memory round trip); an
                     // idle lane takes the ray of the lane whose number is its rank among the idle ones.
@@ -1121,14 +1128,23 @@ __global__ __launch_bounds__(256, PT_PATH_WAVES) void pt_path_kernel(const PtPat
                     auto from = [src](float v) { return __int_as_float(__builtin_amdgcn_ds_bpermute(src << 2, __float_as_int(v))); };
                     const float4 ro = make_float4(from(win_o.x), from(win_o.y), from(win_o.z), from(win_o.w));
                     const float4 rd = make_float4(from(win_d.x), from(win_d.y), from(win_d.z), from(win_d.w));
-                    if(!active && rank < take && __float_as_uint(rd.w) != PT_DEST_NULL) {
-                        tr.start(w, rec, root, ro, rd);
+                    // The lanes that take a ray, as ONE condition and ONE branch, and the request of the root's record in a branch of its own
+                    // behind it.  Nested, each level of branches kept the walk and the record registers of the lanes it skips in a copy: every
+                    // refill moved all of them to other registers and back (which also made it wait for the records in flight).
+                    const bool take_it = !active & (rank < take) & (__float_as_uint(rd.w) != PT_DEST_NULL);
+                    n_rays += (uint32_t)__popcll(__ballot(take_it)); // (rays walked, for the whole wavefront: the branch's own mask)
+                    uint32_t first = PT_REF_NONE;
+                    if(take_it) {
+                        tr.begin(w, root, ro, rd);
                         if(cost_on) {
                             *born_l = w_steps;
                         }
                         active = true;
-                        n_rays++;
-                        n_shadow += (w.dest & PT_DEST_SHADOW) ? 1u : 0u;
+                        first = w.cur;
+                    }
+                    asm volatile("" : "+v"(first)); // (opaque: the compiler must not fold the second branch back into the first)
+                    if(first != PT_REF_NONE) {
+                        tr.fetch(first, rec);
                     }
                     ctx.q_head += take;
                     ctx.q_head = ctx.q_head >= Q.cap ? ctx.q_head - Q.cap : ctx.q_head;
@@ -1136,17 +1152,15 @@ __global__ __launch_bounds__(256, PT_PATH_WAVES) void pt_path_kernel(const PtPat
                     if(lane < ctx.q_count) {
                         uint32_t i = ctx.q_head + lane;
                         i = i >= Q.cap ? i - Q.cap : i;
-                        win_o = Q.ray_o[queue_base + i];
-                        win_d = Q.ray_d[queue_base + i];
+                        win_o = to_f4(ring_o[queue_base + i]);
+                        win_d = to_f4(ring_d[queue_base + i]);
                     }
                 }
             }
-            if(__ballot(active) == 0ULL) {
-                if(ctx.q_count == 0 && ctx.n_dead >= n_slots) {
-                    finished = true; // every slot is dead, nothing queued, nothing walking
-                    break;
-                }
-                continue;
+            const bool walking = __ballot(active) != 0ULL;
+            if(!leave && !walking && ctx.q_count == 0 && ctx.n_dead >= n_slots) {
+                finished = true; // every slot is dead, nothing queued, nothing walking
+                leave = true;
             }
 
             // ---- 3. a burst of traversal steps ---------------------------------------------------------------------------------------------
@@ -1155,29 +1169,44 @@ __global__ __launch_bounds__(256, PT_PATH_WAVES) void pt_path_kernel(const PtPat
 #ifdef PT_PATH_TIMING
             const unsigned long long t_b0 = __builtin_amdgcn_s_memtime();
 #endif
+            // (a lane without a walk in progress has cur == PT_REF_NONE: retire leaves it there, and nothing else changes it)
+            // A burst that runs out of walks ends through the loop's own test -- one way out of the loop, a step shorter by its second exit's
+            // flag.  The kernels with the wide slot word keep the break: in the other form their shading pass spills two registers more
+            // (tests/test_kernel_resources.py; the census of tools/loop_census.py holds both forms at or below what they were).
+            if(WIDE) {
 #pragma unroll 1
-            for(int burst = 0; burst < burst_steps; burst++) {
-                // (a lane without a walk in progress has cur == PT_REF_NONE: retire leaves it there, and nothing else changes it)
-                w_steps++;
-                if(!tr.step(w, rec, leaf_min, n_nodes, n_leaves)) {
-                    w_steps--;
-                    break;
+                for(int burst = (!leave && walking) ? 0 : burst_steps; burst < burst_steps; burst++) {
+                    w_steps++;
+                    if(!tr.step(w, rec, leaf_min, n_nodes, n_leaves)) {
+                        w_steps--;
+                        break;
+                    }
+                }
+            }
+            else {
+#pragma unroll 1
+                for(int burst = (!leave && walking) ? 0 : burst_steps; burst < burst_steps; burst++) {
+                    w_steps++;
+                    if(!tr.step(w, rec, leaf_min, n_nodes, n_leaves)) {
+                        w_steps--;
+                        burst = burst_steps;
+                    }
                 }
             }
 #ifdef PT_PATH_TIMING
             t_burst += __builtin_amdgcn_s_memtime() - t_b0;
 #endif
-        }
+        } while(!leave);
+#ifdef PT_PATH_TIMING
+        t_inner += __builtin_amdgcn_s_memtime() - t_i0;
+#endif
         if(finished) {
             break;
         }
     }
 
     // Work counters: every wave owns one 64-byte slot (plain stores; atomics on a shared line from every wave serialise at the memory side)
-    for(int off = 32; off > 0; off >>= 1) {
-        n_rays += __shfl_down(n_rays, off); // (n_nodes, n_leaves, n_samples and n_vertices are counted for the whole wavefront)
-        n_shadow += __shfl_down(n_shadow, off);
-    }
+    // (all of them are counted for the whole wavefront)
     if(lane == 0) {
         unsigned long long *slot = A->wave_counters + 8 * (size_t)wave;
         slot[0] += n_nodes;
@@ -1189,7 +1218,9 @@ __global__ __launch_bounds__(256, PT_PATH_WAVES) void pt_path_kernel(const PtPat
         slot[6] += n_samples;
         slot[7] += n_vertices;
 #ifdef PT_PATH_TIMING
-        // diagnostic build: shader-clock cycles of this wavefront in shading passes, in traversal bursts, and in all
+        // diagnostic build: shader-clock cycles of this wavefront in shading passes, in traversal bursts, in all, and in the inner loop (bursts
+        // included: what it spends outside them is retire, pass trigger, hand-out and window reload)
+        slot[6] = (unsigned long long)n_samples | ((t_inner >> 10) << 32);
         slot[5] = (unsigned long long)w_passes | ((t_shade >> 10) << 32);
         slot[4] = (unsigned long long)w_steps | ((t_burst >> 10) << 32);
         slot[3] = (unsigned long long)n_shadow | (((__builtin_amdgcn_s_memtime() - t_begin) >> 10) << 32);

@@ -438,18 +438,20 @@ int path_stats(pt_scene *s, const PtStreams &T, const PtPathConfig &cfg, bool co
     PT_HIP(hipEventElapsedTime(&ms, ev_begin.e, ev_end.e));
     std::vector<unsigned long long> slots(static_cast<size_t>(s->path_waves) * 8U);
     PT_HIP(hipMemcpy(slots.data(), s->path_wave_counters.ptr, slots.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    unsigned long long sum[8] = {0, 0, 0, 0, 0, 0, 0, 0}, kcycles[3] = {0, 0, 0};
+    unsigned long long sum[8] = {0, 0, 0, 0, 0, 0, 0, 0}, kcycles[4] = {0, 0, 0, 0};
     for(size_t i = 0; i < slots.size(); i++) {
-        // (a PT_PATH_TIMING build packs kilo-cycle totals into the high words of three slots; they are zero otherwise)
+        // (a PT_PATH_TIMING build packs kilo-cycle totals into the high words of four slots; they are zero otherwise: a wavefront's counts fit 32 bits)
         const size_t k = i & 7U;
-        sum[k] += (k >= 3 && k <= 5) ? (slots[i] & 0xffffffffULL) : slots[i];
-        if(k >= 3 && k <= 5) {
+        sum[k] += (k >= 3 && k <= 6) ? (slots[i] & 0xffffffffULL) : slots[i];
+        if(k >= 3 && k <= 6) {
             kcycles[k - 3] += slots[i] >> 32;
         }
     }
     if(kcycles[0] != 0 && env_int("PT_DEBUG", 0) != 0) {
-        std::fprintf(stderr, "[pt] wave time: %.1f %% in shading passes, %.1f %% in traversal bursts (of the waves' lifetimes; %llu kilo-cycles in all)\n",
-                     100.0 * static_cast<double>(kcycles[2]) / static_cast<double>(kcycles[0]), 100.0 * static_cast<double>(kcycles[1]) / static_cast<double>(kcycles[0]), kcycles[0]);
+        const double all = static_cast<double>(kcycles[0]);
+        std::fprintf(stderr, "[pt] wave time: %.1f %% in shading passes, %.1f %% in traversal bursts, %.1f %% in the inner loop outside the bursts (of the waves' lifetimes; %llu kilo-cycles in all)\n",
+                     100.0 * static_cast<double>(kcycles[2]) / all, 100.0 * static_cast<double>(kcycles[1]) / all,
+                     100.0 * (static_cast<double>(kcycles[3]) - static_cast<double>(kcycles[1])) / all, kcycles[0]);
     }
     PtDevCounters done{};
     PT_HIP(hipMemcpy(&done, s->counters.ptr, sizeof(done), hipMemcpyDeviceToHost));

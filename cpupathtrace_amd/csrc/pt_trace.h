@@ -139,8 +139,10 @@ struct Tracer {
     static PT_D unsigned long long node_lanes(uint32_t cur) { return __builtin_amdgcn_uicmp(cur, 0x40000000u, 36); }       // cur < 2^30
     static PT_D unsigned long long slow_lanes(uint32_t cur) { return __builtin_amdgcn_uicmp(cur + 1u, 0x40000000u, 34); }  // 2^30 <= cur < NONE
 
-    // Start a walk: Scene::getIntersection tests the root box first (scene.cpp:211-219).
-    PT_D void start(Walk &w, Rec &R, const RootBox &root, float4 ro, float4 rd) const {
+    // Start a walk: Scene::getIntersection tests the root box first (scene.cpp:211-219).  begin() is the walk's side of it -- afterwards
+    // w.cur is the root, or PT_REF_NONE where the ray misses the root box -- and start() also requests the root's record.  (The path kernel
+    // calls the two apart: see its hand-out.)
+    PT_D void begin(Walk &w, const RootBox &root, float4 ro, float4 rd) const {
         w.o = v3(ro.x, ro.y, ro.z);
         w.d = v3(rd.x, rd.y, rd.z);
         w.thr = ro.w;
@@ -164,13 +166,14 @@ struct Tracer {
         stack_l[0] = sentinel;
         w.sp = 1;
         w.occluded = false;
-        w.cur = PT_REF_NONE;
-        if(root.ref != PT_REF_NONE) {
-            const float t_root = slab_walk(ld3(root.lo), ld3(root.hi), w.o, w.inv);
-            if(t_root >= 0.0f) {
-                w.cur = root.ref;
-                fetch(w.cur, R);
-            }
+        // (one select, no branch: an empty scene's root box is never entered whatever the test says)
+        const float t_root = slab_walk(ld3(root.lo), ld3(root.hi), w.o, w.inv);
+        w.cur = ((root.ref != PT_REF_NONE) & (t_root >= 0.0f)) ? root.ref : PT_REF_NONE;
+    }
+    PT_D void start(Walk &w, Rec &R, const RootBox &root, float4 ro, float4 rd) const {
+        begin(w, root, ro, rd);
+        if(w.cur != PT_REF_NONE) {
+            fetch(w.cur, R);
         }
     }
 
