@@ -1,6 +1,6 @@
 // pt_api.cpp -- host side of libpathtrace_hip.so: the C ABI of include/pt_hip.h.  This unit holds the calling thread's error message, the
-// helpers every unit starts a call with, and scenes; render calls are in pt_render.cpp, resumable frames in pt_frames.cpp, post-processing,
-// features and denoising in pt_image.cpp (pt_host.h is what they share).
+// helpers every unit starts a call with, and scenes; render calls are in pt_render.cpp, resumable frames in pt_frames.cpp and
+// pt_frame_maps.cpp, post-processing, features and denoising in pt_image.cpp (pt_host.h is what they share).
 //
 // Scene creation flattens the caller's object list into the HBM layout of pt_types.h (building the reference's BVH
 // topology on the way, pt_bvh.cpp / pt_build.hip); a render call is ONE launch of the persistent path kernel (pt_path.hip), whose

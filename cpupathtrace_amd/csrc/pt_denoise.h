@@ -1,4 +1,5 @@
-// pt_denoise.h -- the feature-guided a-trous denoiser (pt_denoise.hip): launch interface for the host side (pt_image.cpp, pt_frames.cpp).
+// pt_denoise.h -- the feature-guided a-trous denoiser (pt_denoise.hip): launch interface for the host side (pt_image.cpp,
+// pt_frame_maps.cpp).
 #ifndef PT_DENOISE_H
 #define PT_DENOISE_H
 

@@ -36,37 +36,37 @@ constexpr uint32_t kPerBlock = kThreads * kPerThread;
 // a record of the launch's INPUT buffer that the carry kernel has yet to move: bit 31 of a work-list entry's y (a record index has 28 bits)
 constexpr uint32_t kCarry = 0x80000000u;
 
-// what became of entry i: 0 = finished, 1 = parked in this launch, 2 = still to do from its seed.  In a progressive frame (target > 0):
-// 0 = finished, 1 = its pixel has fewer than `target` samples, 2 = it has them; `samples` is that count and `where` says where the stream's
-// record is: 0 = it has none, 1 = in the launch's output records (index `rec`), 2 = in its input records (index `rec`: never claimed).
-// With a noise target, 3 = held: the stream has a record and its pixel's error is at or below the target (an unrated pixel's is +inf).
+// what became of entry i (PtEntryClass): finished, FIRST = parked in this launch, SECOND = still to do from its seed.  In a progressive
+// frame (target > 0): finished, FIRST = its pixel has fewer than `target` samples, SECOND = it has them; `samples` is that count and `where`
+// (PtEntryRecord) says where the stream's record, index `rec`, is: it has none, the launch wrote it, or it was never claimed.  With a noise
+// target, HELD: the stream has a record and its pixel's error is at or below the target (an unrated pixel's is +inf).
 __device__ uint32_t entry_class(const uint2 *todo, const uint32_t *status, uint32_t i, int32_t target, const PtParkRecord *parked, const PtParkRecord *park_in,
                                 const PtNoiseRule &noise, uint32_t &where, uint32_t &rec, int32_t &samples) {
     const uint2 e = todo[i];
     const uint32_t st = status[e.x];
-    where = 0;
+    where = PT_RECORD_NONE;
     rec = PT_NO_PARK;
     samples = 0;
     if(target <= 0) {
-        return st == PT_STREAM_FINISHED ? 0u : (st >= PT_STREAM_PARKED ? 1u : 2u);
+        return st == PT_STREAM_FINISHED ? PT_ENTRY_FINISHED : (st >= PT_STREAM_PARKED ? PT_ENTRY_FIRST : PT_ENTRY_SECOND);
     }
     if(st == PT_STREAM_FINISHED) {
-        return 0u;
+        return PT_ENTRY_FINISHED;
     }
     if(st >= PT_STREAM_PARKED) {
-        where = 1;
+        where = PT_RECORD_WRITTEN;
         rec = st - PT_STREAM_PARKED;
         samples = parked[rec].est.pixel_sample;
     }
     else if(e.y != PT_NO_PARK) {
-        where = 2;
+        where = PT_RECORD_UNCLAIMED;
         rec = e.y;
         samples = park_in[rec].est.pixel_sample;
     }
-    if(noise.target > 0.0f && where != 0u && pixel_error((where == 1u ? parked : park_in)[rec].est, noise.opt, noise.floor) <= noise.target) {
-        return 3u;
+    if(noise.target > 0.0f && where != PT_RECORD_NONE && pixel_error((where == PT_RECORD_WRITTEN ? parked : park_in)[rec].est, noise.opt, noise.floor) <= noise.target) {
+        return PT_ENTRY_HELD;
     }
-    return samples < target ? 1u : 2u;
+    return samples < target ? PT_ENTRY_FIRST : PT_ENTRY_SECOND;
 }
 
 __global__ __launch_bounds__(kThreads) void pt_frame_count_kernel(const uint2 *__restrict__ todo, uint32_t n, const uint32_t *__restrict__ status,
@@ -84,9 +84,9 @@ __global__ __launch_bounds__(kThreads) void pt_frame_count_kernel(const uint2 *_
             uint32_t where, rec;
             int32_t samples;
             const uint32_t c = entry_class(todo, status, i, target, parked, park_in, noise, where, rec, samples);
-            first += c == 1u ? 1u : 0u;
-            second += c == 2u ? 1u : 0u;
-            third += c == 3u ? 1u : 0u;
+            first += c == PT_ENTRY_FIRST ? 1u : 0u;
+            second += c == PT_ENTRY_SECOND ? 1u : 0u;
+            third += c == PT_ENTRY_HELD ? 1u : 0u;
         }
     }
     atomicAdd(&sum[0], first);
@@ -135,11 +135,11 @@ __global__ __launch_bounds__(kThreads) void pt_frame_place_kernel(const uint2 *_
     unsigned long long mine = 0;
     for(uint32_t k = 0; k < kPerThread; k++) {
         const uint32_t i = blockIdx.x * kPerBlock + threadIdx.x * kPerThread + k;
-        where[k] = 0;
+        where[k] = PT_RECORD_NONE;
         rec[k] = PT_NO_PARK;
         samples[k] = 0;
-        cls[k] = i < n ? entry_class(todo, status, i, target, parked, park_in, noise, where[k], rec[k], samples[k]) : 0u;
-        mine += cls[k] == 1u ? 1ull : (cls[k] == 2u ? 1ull << 21 : (cls[k] == 3u ? 1ull << 42 : 0ull));
+        cls[k] = i < n ? entry_class(todo, status, i, target, parked, park_in, noise, where[k], rec[k], samples[k]) : PT_ENTRY_FINISHED;
+        mine += cls[k] == PT_ENTRY_FIRST ? 1ull : (cls[k] == PT_ENTRY_SECOND ? 1ull << 21 : (cls[k] == PT_ENTRY_HELD ? 1ull << 42 : 0ull));
     }
     scan[threadIdx.x] = mine;
     __syncthreads();
@@ -156,7 +156,7 @@ __global__ __launch_bounds__(kThreads) void pt_frame_place_kernel(const uint2 *_
     uint32_t lost = 0, carried = 0, with_candidates = 0, with_record = 0, written = 0, least = 0xffffffffu, most = 0;
     for(uint32_t k = 0; k < kPerThread; k++) {
         const uint32_t i = blockIdx.x * kPerBlock + threadIdx.x * kPerThread + k;
-        if(i >= n || cls[k] == 0u) {
+        if(i >= n || cls[k] == PT_ENTRY_FINISHED) {
             continue;
         }
         const uint2 e = todo[i];
@@ -164,24 +164,24 @@ __global__ __launch_bounds__(kThreads) void pt_frame_place_kernel(const uint2 *_
         if(target > 0) {
             // a progressive frame: the record stays with the stream wherever it is (an unclaimed one is moved by the carry kernel,
             // unless the list is only split again: then the input records stay the frame's records)
-            const uint32_t y = where[k] == 1u ? rec[k] : (where[k] == 2u ? (resort != 0 ? rec[k] : (rec[k] | kCarry)) : PT_NO_PARK);
-            if(cls[k] == 1u) {
+            const uint32_t y = where[k] == PT_RECORD_WRITTEN ? rec[k] : (where[k] == PT_RECORD_UNCLAIMED ? (resort != 0 ? rec[k] : (rec[k] | kCarry)) : PT_NO_PARK);
+            if(cls[k] == PT_ENTRY_FIRST) {
                 todo_out[at_first++] = make_uint2(e.x, y);
             }
-            else if(cls[k] == 2u) {
+            else if(cls[k] == PT_ENTRY_SECOND) {
                 todo_out[at_second++] = make_uint2(e.x, y);
             }
             else {
                 todo_out[at_held++] = make_uint2(e.x, y);
             }
             s = (uint32_t)samples[k];
-            if(where[k] != 0u) {
+            if(where[k] != PT_RECORD_NONE) {
                 with_record++;
-                written += where[k] == 1u ? 1u : 0u;
-                with_candidates += (where[k] == 1u ? parked[rec[k]] : park_in[rec[k]]).est.n_candidates > 0 ? 1u : 0u;
+                written += where[k] == PT_RECORD_WRITTEN ? 1u : 0u;
+                with_candidates += (where[k] == PT_RECORD_WRITTEN ? parked[rec[k]] : park_in[rec[k]]).est.n_candidates > 0 ? 1u : 0u;
             }
         }
-        else if(cls[k] == 1u) {
+        else if(cls[k] == PT_ENTRY_FIRST) {
             const uint32_t r = status[e.x] - PT_STREAM_PARKED;
             todo_out[at_first++] = make_uint2(e.x, r);
             s = (uint32_t)parked[r].est.pixel_sample;
@@ -200,41 +200,41 @@ __global__ __launch_bounds__(kThreads) void pt_frame_place_kernel(const uint2 *_
         status[e.x] = PT_STREAM_UNTOUCHED; // (the status describes one launch)
     }
     if(lost != 0) {
-        atomicAdd(&result[2], (unsigned long long)lost);
+        atomicAdd(&result[PT_COMPACT_LOST], (unsigned long long)lost);
     }
     if(carried != 0) {
-        atomicAdd(&result[3], (unsigned long long)carried);
+        atomicAdd(&result[PT_COMPACT_CARRIED], (unsigned long long)carried);
     }
     if(with_candidates != 0) {
-        atomicAdd(&result[4], (unsigned long long)with_candidates);
+        atomicAdd(&result[PT_COMPACT_WITH_CANDIDATES], (unsigned long long)with_candidates);
     }
     if(least != 0xffffffffu) {
-        atomicMax(&result[5], (unsigned long long)(0xffffffffu - least)); // (a minimum over a word that starts at zero)
-        atomicMax(&result[6], (unsigned long long)most);
+        atomicMax(&result[PT_COMPACT_MIN_INVERTED], (unsigned long long)(0xffffffffu - least)); // (a minimum over a word that starts at zero)
+        atomicMax(&result[PT_COMPACT_MAX], (unsigned long long)most);
     }
     if(with_record != 0) {
-        atomicAdd(&result[7], (unsigned long long)with_record);
+        atomicAdd(&result[PT_COMPACT_WITH_RECORD], (unsigned long long)with_record);
     }
     if(written != 0) {
-        atomicAdd(&result[8], (unsigned long long)written);
+        atomicAdd(&result[PT_COMPACT_WRITTEN], (unsigned long long)written);
     }
     if(blockIdx.x == n_blocks - 1 && threadIdx.x == kThreads - 1) {
-        result[0] = before[2];
-        result[1] = before[4];
-        result[10] = before[3] + (uint32_t)(scan[threadIdx.x] >> 42);
+        result[PT_COMPACT_FIRST] = before[2];
+        result[PT_COMPACT_SECOND] = before[4];
+        result[PT_COMPACT_HELD] = before[3] + (uint32_t)(scan[threadIdx.x] >> 42);
     }
 }
 
 // A progressive frame: the records of the entries the launch never claimed, from its input records to its output records.  A wavefront
 // takes kCarryPerWave entries of the new work list one after the other; a record is 33 x 16 bytes, copied by 33 neighbouring lanes.  The
-// record's new place is the next free one behind those the launch wrote (park_count goes on counting).  result[9] counts the samples of
-// records that found no room (none: the host sizes the output for every entry of the list).
+// record's new place is the next free one behind those the launch wrote (park_count goes on counting).  result[PT_COMPACT_NO_ROOM]
+// counts the samples of records that found no room (none: the host sizes the output for every entry of the list).
 constexpr uint32_t kCarryPerWave = 16;
 static_assert(sizeof(PtParkRecord) == 33 * sizeof(uint4), "a park record is 33 x 16 bytes");
 
 __global__ __launch_bounds__(kThreads) void pt_frame_carry_kernel(uint2 *__restrict__ todo_out, const PtParkRecord *__restrict__ park_in, PtParkRecord *__restrict__ park_out,
                                                                   uint32_t *__restrict__ park_count, uint32_t park_cap, unsigned long long *__restrict__ result) {
-    const uint32_t n = (uint32_t)(result[0] + result[1] + result[10]); // (the new list's length, left by the place kernel)
+    const uint32_t n = (uint32_t)(result[PT_COMPACT_FIRST] + result[PT_COMPACT_SECOND] + result[PT_COMPACT_HELD]); // (the new list's length, left by the place kernel)
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = (blockIdx.x * kThreads + threadIdx.x) / 64u;
     for(uint32_t k = 0; k < kCarryPerWave; k++) {
@@ -262,12 +262,12 @@ __global__ __launch_bounds__(kThreads) void pt_frame_carry_kernel(uint2 *__restr
         }
         else if(lane == 0) {
             todo_out[i].y = PT_NO_PARK;
-            atomicAdd(&result[9], (unsigned long long)park_in[src].est.pixel_sample);
+            atomicAdd(&result[PT_COMPACT_NO_ROOM], (unsigned long long)park_in[src].est.pixel_sample);
         }
     }
 }
 
-// ---- the preview of a frame (pt_frame_preview, pt_frames.cpp) ---------------------------------------------------------------------------
+// ---- the preview of a frame (pt_frame_preview, pt_frame_maps.cpp) -----------------------------------------------------------------------
 // Each replica gathers its work list into compact entries (gather); replica 0's device lays the frame out from the caller's image (base)
 // and writes every replica's entries over it (scatter).
 
@@ -346,12 +346,11 @@ __global__ __launch_bounds__(kThreads) void pt_frame_scatter_kernel(const float4
     samples[a.x] = a.y;
 }
 
-// ---- the rating of a frame (pt_frame_get_noise, pt_frames.cpp) --------------------------------------------------------------------------
+// ---- the rating of a frame (pt_frame_get_noise, pt_frame_maps.cpp) ----------------------------------------------------------------------
 // One thread per entry of a replica's work list, as the gather kernel: out[i] = (pixel, bits of its error), +inf for an entry without a
 // record or with fewer than two batch means (unrated).  Reads the estimator's fields pixel_error needs, not the record.  The summary is
-// reduced with integer atomics only, per block in LDS and then once per block: summary[0..2] = rated, unrated and held entries (held:
-// rated, and error <= noise.target > 0), [3] = the bits of the largest error of a rated entry (errors are never negative, so their bits
-// order as they do), [4 .. 67] = rated entries by pixel_error_bin.
+// reduced with integer atomics only, per block in LDS and then once per block (PtNoiseWord; errors are never negative, so their bits order as
+// they do).
 __global__ __launch_bounds__(kThreads) void pt_frame_rate_kernel(const uint2 *__restrict__ todo, uint32_t n, const PtParkRecord *__restrict__ park,
                                                                  const int4 *__restrict__ tiles, const uint32_t *__restrict__ tile_offset, uint32_t n_tiles,
                                                                  int32_t width, PtNoiseRule noise, uint2 *__restrict__ out, uint32_t *__restrict__ summary) {
@@ -372,21 +371,21 @@ __global__ __launch_bounds__(kThreads) void pt_frame_rate_kernel(const uint2 *__
         }
         out[i] = make_uint2((uint32_t)stream_pixel(e.x, tiles, tile_offset, n_tiles, width), __float_as_uint(error));
         if(rated) {
-            atomicAdd(&part[0], 1u);
+            atomicAdd(&part[PT_NOISE_RATED], 1u);
             if(noise.target > 0.0f && error <= noise.target) {
-                atomicAdd(&part[2], 1u);
+                atomicAdd(&part[PT_NOISE_HELD], 1u);
             }
-            atomicMax(&part[3], __float_as_uint(error));
-            atomicAdd(&part[4 + pixel_error_bin(error)], 1u);
+            atomicMax(&part[PT_NOISE_MAX_BITS], __float_as_uint(error));
+            atomicAdd(&part[PT_NOISE_FIRST_BIN + pixel_error_bin(error)], 1u);
         }
         else {
-            atomicAdd(&part[1], 1u);
+            atomicAdd(&part[PT_NOISE_UNRATED], 1u);
         }
     }
     __syncthreads();
     if(threadIdx.x < PT_NOISE_SUMMARY_WORDS && part[threadIdx.x] != 0) {
-        if(threadIdx.x == 3) {
-            atomicMax(&summary[3], part[3]);
+        if(threadIdx.x == PT_NOISE_MAX_BITS) {
+            atomicMax(&summary[PT_NOISE_MAX_BITS], part[PT_NOISE_MAX_BITS]);
         }
         else {
             atomicAdd(&summary[threadIdx.x], part[threadIdx.x]);
@@ -411,7 +410,7 @@ __global__ __launch_bounds__(kThreads) void pt_frame_noise_scatter_kernel(const 
     }
 }
 
-// ---- the variance map of a frame (pt_frame_get_variance, pt_frames.cpp) -----------------------------------------------------------------
+// ---- the variance map of a frame (pt_frame_get_variance, pt_frame_maps.cpp) -------------------------------------------------------------
 // One thread per entry of a replica's work list, as the rating kernel: out_var[i] = pixel_variance of the entry's record, (0, 0, 0, 0)
 // for an entry without one, and out_at[i] its pixel.  Reads the estimator's M2 and sample count, not the record.
 __global__ __launch_bounds__(kThreads) void pt_frame_variance_kernel(const uint2 *__restrict__ todo, uint32_t n, const PtParkRecord *__restrict__ park,
@@ -439,6 +438,16 @@ __global__ __launch_bounds__(kThreads) void pt_frame_variance_scatter_kernel(con
     }
 }
 
+// One thread per item: the launch of every kernel above that takes its items one by one.  0, or 1 when the launch failed.
+template<typename Kernel, typename... Args>
+int launch_per_item(Kernel kernel, uint32_t n, hipStream_t stream, Args... args) {
+    if(n == 0) {
+        return 0;
+    }
+    kernel<<<(n + kThreads - 1) / kThreads, kThreads, 0, stream>>>(args...);
+    return hipGetLastError() == hipSuccess ? 0 : 1;
+}
+
 } // namespace
 
 int pt_launch_frame_rate(hipStream_t stream, const uint2 *todo, uint32_t n, const PtParkRecord *park, const int4 *tiles, const uint32_t *tile_offset, uint32_t n_tiles,
@@ -446,33 +455,21 @@ int pt_launch_frame_rate(hipStream_t stream, const uint2 *todo, uint32_t n, cons
     if(hipMemsetAsync(summary, 0, PT_NOISE_SUMMARY_WORDS * sizeof(uint32_t), stream) != hipSuccess) {
         return 1;
     }
-    if(n == 0) {
-        return 0;
-    }
-    pt_frame_rate_kernel<<<(n + kThreads - 1) / kThreads, kThreads, 0, stream>>>(todo, n, park, tiles, tile_offset, n_tiles, width, noise, out, summary);
-    return hipGetLastError() == hipSuccess ? 0 : 1;
+    return launch_per_item(pt_frame_rate_kernel, n, stream, todo, n, park, tiles, tile_offset, n_tiles, width, noise, out, summary);
 }
 
 int pt_launch_frame_noise_base(hipStream_t stream, float *map, const uint8_t *cover, uint32_t n_pixels) {
-    if(n_pixels == 0) {
-        return 0;
-    }
-    pt_frame_noise_base_kernel<<<(n_pixels + kThreads - 1) / kThreads, kThreads, 0, stream>>>(map, cover, n_pixels);
-    return hipGetLastError() == hipSuccess ? 0 : 1;
+    return launch_per_item(pt_frame_noise_base_kernel, n_pixels, stream, map, cover, n_pixels);
 }
 
 int pt_launch_frame_noise_scatter(hipStream_t stream, const uint2 *rated, uint32_t n, float *map) {
-    if(n == 0) {
-        return 0;
-    }
-    pt_frame_noise_scatter_kernel<<<(n + kThreads - 1) / kThreads, kThreads, 0, stream>>>(rated, n, map);
-    return hipGetLastError() == hipSuccess ? 0 : 1;
+    return launch_per_item(pt_frame_noise_scatter_kernel, n, stream, rated, n, map);
 }
 
 int pt_launch_frame_compact(hipStream_t stream, const uint2 *todo, uint32_t n, uint32_t *status, const PtParkRecord *parked, uint2 *todo_out, uint32_t *block_counts,
                             unsigned long long *result, int32_t target, const PtParkRecord *park_in, PtParkRecord *park_out, uint32_t *park_count, uint32_t park_cap,
                             const PtNoiseRule &noise, int resort) {
-    if(hipMemsetAsync(result, 0, 16 * sizeof(unsigned long long), stream) != hipSuccess) {
+    if(hipMemsetAsync(result, 0, PT_COMPACT_WORDS * sizeof(unsigned long long), stream) != hipSuccess) {
         return 1;
     }
     if(n == 0) {
@@ -490,42 +487,22 @@ int pt_launch_frame_compact(hipStream_t stream, const uint2 *todo, uint32_t n, u
 
 int pt_launch_frame_gather(hipStream_t stream, const uint2 *todo, uint32_t n, uint32_t n_parked, const PtParkRecord *park, const int4 *tiles,
                            const uint32_t *tile_offset, uint32_t n_tiles, int32_t width, float4 *out_rgba, int2 *out_at) {
-    if(n == 0) {
-        return 0;
-    }
-    pt_frame_gather_kernel<<<(n + kThreads - 1) / kThreads, kThreads, 0, stream>>>(todo, n, n_parked, park, tiles, tile_offset, n_tiles, width, out_rgba, out_at);
-    return hipGetLastError() == hipSuccess ? 0 : 1;
+    return launch_per_item(pt_frame_gather_kernel, n, stream, todo, n, n_parked, park, tiles, tile_offset, n_tiles, width, out_rgba, out_at);
 }
 
 int pt_launch_frame_preview_base(hipStream_t stream, float4 *view, int32_t *samples, const uint8_t *cover, uint32_t n_pixels) {
-    if(n_pixels == 0) {
-        return 0;
-    }
-    pt_frame_preview_base_kernel<<<(n_pixels + kThreads - 1) / kThreads, kThreads, 0, stream>>>(view, samples, cover, n_pixels);
-    return hipGetLastError() == hipSuccess ? 0 : 1;
+    return launch_per_item(pt_frame_preview_base_kernel, n_pixels, stream, view, samples, cover, n_pixels);
 }
 
 int pt_launch_frame_scatter(hipStream_t stream, const float4 *rgba, const int2 *at, uint32_t n, float4 *view, int32_t *samples) {
-    if(n == 0) {
-        return 0;
-    }
-    pt_frame_scatter_kernel<<<(n + kThreads - 1) / kThreads, kThreads, 0, stream>>>(rgba, at, n, view, samples);
-    return hipGetLastError() == hipSuccess ? 0 : 1;
+    return launch_per_item(pt_frame_scatter_kernel, n, stream, rgba, at, n, view, samples);
 }
 
 int pt_launch_frame_variance(hipStream_t stream, const uint2 *todo, uint32_t n, const PtParkRecord *park, const int4 *tiles, const uint32_t *tile_offset,
                              uint32_t n_tiles, int32_t width, const PtDevOptions &opt, float4 *out_var, int32_t *out_at) {
-    if(n == 0) {
-        return 0;
-    }
-    pt_frame_variance_kernel<<<(n + kThreads - 1) / kThreads, kThreads, 0, stream>>>(todo, n, park, tiles, tile_offset, n_tiles, width, opt, out_var, out_at);
-    return hipGetLastError() == hipSuccess ? 0 : 1;
+    return launch_per_item(pt_frame_variance_kernel, n, stream, todo, n, park, tiles, tile_offset, n_tiles, width, opt, out_var, out_at);
 }
 
 int pt_launch_frame_variance_scatter(hipStream_t stream, const float4 *var, const int32_t *at, uint32_t n, float4 *map) {
-    if(n == 0) {
-        return 0;
-    }
-    pt_frame_variance_scatter_kernel<<<(n + kThreads - 1) / kThreads, kThreads, 0, stream>>>(var, at, n, map);
-    return hipGetLastError() == hipSuccess ? 0 : 1;
+    return launch_per_item(pt_frame_variance_scatter_kernel, n, stream, var, at, n, map);
 }

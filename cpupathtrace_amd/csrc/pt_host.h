@@ -1,6 +1,7 @@
-// pt_host.h -- what the host units of libpathtrace_hip.so share: pt_api.cpp (scenes), pt_render.cpp (render calls), pt_frames.cpp
-// (resumable frames) and pt_image.cpp (post-processing, features, denoising).  Internal: not installed, not part of the C ABI.
-// Everything but the ABI's own handle types lives in namespace pth, so that no helper can collide with a pt_* name of include/pt_hip.h.
+// pt_host.h -- what the host units of libpathtrace_hip.so share: pt_api.cpp (scenes), pt_render.cpp (render calls), pt_frames.cpp and
+// pt_frame_maps.cpp (resumable frames and their maps; pt_frames.h) and pt_image.cpp (post-processing, features, denoising).  Internal:
+// not installed, not part of the C ABI.  Everything but the ABI's own handle types lives in namespace pth, so that no helper can collide
+// with a pt_* name of include/pt_hip.h.
 #ifndef PT_HOST_H
 #define PT_HOST_H
 
@@ -49,6 +50,15 @@ const std::string &last_error();
         const int rc_ = (call);                                                                                    \
         if(rc_ != PT_OK) {                                                                                         \
             return rc_;                                                                                            \
+        }                                                                                                          \
+    } while(0)
+
+// ... and for a launch wrapper of a kernel file that returns 0, or 1 when a launch failed
+#define PT_LAUNCH(call, what)                                                                                      \
+    do {                                                                                                           \
+        if((call) != 0) {                                                                                          \
+            PT_HIP(hipGetLastError());                                                                             \
+            return fail(PT_ERR_HIP, what);                                                                         \
         }                                                                                                          \
     } while(0)
 
@@ -147,6 +157,20 @@ struct Event {
             (void)hipEventDestroy(e);
         }
     }
+};
+
+// The device time of what a stream does between begin() and end(): ms(), once the stream has been synchronised
+struct EventPair {
+    Event first, last;
+    hipError_t begin(hipStream_t stream) {
+        hipError_t err = first.create();
+        if(err == hipSuccess) {
+            err = last.create();
+        }
+        return err == hipSuccess ? hipEventRecord(first.e, stream) : err;
+    }
+    hipError_t end(hipStream_t stream) { return hipEventRecord(last.e, stream); }
+    hipError_t ms(float *out) { return hipEventElapsedTime(out, first.e, last.e); }
 };
 
 } // namespace pth

@@ -1,4 +1,5 @@
-// pt_kernels.h -- launch interface between the host side of libpathtrace_hip.so (pt_render.cpp, pt_frames.cpp, pt_image.cpp) and the kernels of pt_path.hip and pt_walks.hip.
+// pt_kernels.h -- launch interface between the host side of libpathtrace_hip.so (pt_render.cpp, pt_frames.cpp, pt_frame_maps.cpp,
+// pt_image.cpp) and the kernels of pt_path.hip, pt_walks.hip and pt_frame.hip.
 #ifndef PT_KERNELS_H
 #define PT_KERNELS_H
 
@@ -151,19 +152,33 @@ struct PtPathArgs {
 // fills *host_args (which must stay valid until the launch has been issued), copies it to d_args on `stream` and launches
 void pt_launch_path(hipStream_t stream, const PtDevScene &scene, const PtDevCamera &camera, const PtDevOptions &options, PtSlots slots, PtStreams streams,
                     PtLocalQueue queue, const PtPathConfig &cfg, float4 *image, PtDevCounters *counters, PtPathArgs *host_args, PtPathArgs *d_args);
-// the work list of a resumable frame's next launch (pt_frame.hip): the streams of `todo` that `status` does not call finished, parked ones
-// first, each part in the order of `todo`.  result[0..4] = parked streams, untouched ones, untouched ones
-// whose earlier record went unused (such a stream starts afresh), samples the streams of the list carry, streams with closed candidates;
-// result[5] = 0xffffffff - the least sample count of an unfinished pixel, [6] = the greatest, [7] = streams that have a record, [8] = records
-// the launch wrote (result: 16 words).
-// target > 0, a progressive frame's pass: the list is split into streams below `target` samples (result[0]) and streams at or above it
-// (result[1]) instead, every stream keeps its record, and those the launch never claimed are copied from park_in (the launch's input
-// records) into park_out behind the park_count records the launch wrote (park_cap: room for every entry); result[2] stays 0 and result[9]
-// counts samples of records that found no room (0 with that room).  target <= 0: park_in, park_out, park_count are not used.
-// noise.target > 0 (a progressive frame with a noise target, pt_frame_set_noise_target): a third part behind those two, the HELD streams
-// (result[10]): those with a record whose pixel_error (pt_noise.h) is at or below noise.target.  resort != 0: nothing was launched (every
-// status is untouched) and the list is only split again -- no record moves, park_in stays the frame's records, park_out is not used.
-// block_counts: [3 * ceil(n / 1024)].  Returns 0, or 1 when a launch failed.
+// the work list of a resumable frame's next launch (pt_frame.hip): the streams of `todo` that `status` does not call finished, in two
+// parts, each in the order of `todo`, and what the list holds in result[PT_COMPACT_*].  block_counts: [3 * ceil(n / 1024)].  Returns 0, or
+// 1 when a launch failed.
+// target <= 0, a plain frame: parked streams first, then untouched ones; park_in, park_out and park_count are not used.
+// target > 0, a progressive frame's pass: streams below `target` samples first, then those at or above it; every stream keeps its record,
+// and those the launch never claimed are copied from park_in (the launch's input records) into park_out behind the park_count records the
+// launch wrote (park_cap: room for every entry, so that PT_COMPACT_NO_ROOM stays 0).
+// noise.target > 0 (a progressive frame with a noise target, pt_frame_set_noise_target): a third part behind those two, the HELD streams:
+// those with a record whose pixel_error (pt_noise.h) is at or below noise.target.  resort != 0: nothing was launched (every status is
+// untouched) and the list is only split again -- no record moves, park_in stays the frame's records, park_out is not used.
+enum PtCompactWord {
+    PT_COMPACT_FIRST = 0,        // streams of the first part
+    PT_COMPACT_SECOND,           // ... and of the second
+    PT_COMPACT_LOST,             // plain frame: untouched streams whose earlier record went unused (such a stream starts afresh)
+    PT_COMPACT_CARRIED,          // samples the streams of the list carry
+    PT_COMPACT_WITH_CANDIDATES,  // streams with closed candidates
+    PT_COMPACT_MIN_INVERTED,     // 0xffffffff - the least sample count of an unfinished pixel (a minimum over a word that starts at zero)
+    PT_COMPACT_MAX,              // the greatest
+    PT_COMPACT_WITH_RECORD,      // streams that have a record
+    PT_COMPACT_WRITTEN,          // records the launch wrote
+    PT_COMPACT_NO_ROOM,          // samples of records that found no room in park_out
+    PT_COMPACT_HELD,             // streams of the third part
+    PT_COMPACT_WORDS = 16
+};
+// what the compaction makes of one entry: the part of the list it goes to, and where the stream's record is
+enum PtEntryClass : uint32_t { PT_ENTRY_FINISHED = 0, PT_ENTRY_FIRST = 1, PT_ENTRY_SECOND = 2, PT_ENTRY_HELD = 3 };
+enum PtEntryRecord : uint32_t { PT_RECORD_NONE = 0, PT_RECORD_WRITTEN = 1 /* park_out, by the launch */, PT_RECORD_UNCLAIMED = 2 /* park_in */ };
 struct PtNoiseRule {
     PtDevOptions opt; // (its stats_sample_count: the samples of a batch mean)
     float target;     // 0 = none: nothing is held
@@ -173,9 +188,15 @@ int pt_launch_frame_compact(hipStream_t stream, const uint2 *todo, uint32_t n, u
                             unsigned long long *result, int32_t target, const PtParkRecord *park_in, PtParkRecord *park_out, uint32_t *park_count, uint32_t park_cap,
                             const PtNoiseRule &noise, int resort);
 // The rating of a frame (pt_frame.hip; pt_frame_get_noise).  rate: out[i] = (pixel, bits of pixel_error) per entry of a replica's work list
-// and the summary of PT_NOISE_SUMMARY_WORDS words (zeroed first): rated, unrated, held entries, bits of the largest error, 64 bins by
-// exponent.  base: the map of replica 0's device, -1 where cover[p] != 0, else +inf.  scatter: n entries into the map.
-#define PT_NOISE_SUMMARY_WORDS 68
+// and the summary (zeroed first).  base: the map of replica 0's device, -1 where cover[p] != 0, else +inf.  scatter: n entries into the map.
+enum PtNoiseWord {
+    PT_NOISE_RATED = 0,
+    PT_NOISE_UNRATED,
+    PT_NOISE_HELD,      // rated, and error <= noise.target > 0
+    PT_NOISE_MAX_BITS,  // the bits of the largest error of a rated entry
+    PT_NOISE_FIRST_BIN, // rated entries by pixel_error_bin: 64 bins
+    PT_NOISE_SUMMARY_WORDS = PT_NOISE_FIRST_BIN + 64
+};
 int pt_launch_frame_rate(hipStream_t stream, const uint2 *todo, uint32_t n, const PtParkRecord *park, const int4 *tiles, const uint32_t *tile_offset, uint32_t n_tiles,
                          int32_t width, const PtNoiseRule &noise, uint2 *out, uint32_t *summary);
 int pt_launch_frame_noise_base(hipStream_t stream, float *map, const uint8_t *cover, uint32_t n_pixels);

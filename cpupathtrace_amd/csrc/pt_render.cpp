@@ -587,16 +587,14 @@ extern "C" int pt_debug_replay_rays(pt_scene *s, int waves_per_simd, int parts, 
     Q.ray_o = reinterpret_cast<float4 *>(s->lq_ray_o.ptr);
     Q.ray_d = reinterpret_cast<float4 *>(s->lq_ray_d.ptr);
     Q.cap = s->path_cap;
-    Event e0, e1;
-    PT_HIP(e0.create());
-    PT_HIP(e1.create());
-    PT_HIP(hipEventRecord(e0.e, s->stream));
+    EventPair timer;
+    PT_HIP(timer.begin(s->stream));
     *out_blocks = pt_launch_replay(s->stream, s->dev, Q, s->path_waves, static_cast<uint32_t>(parts), waves_per_simd, cfg, s->path_spill.ptr, s->path_wave_counters.ptr);
     PT_HIP(hipGetLastError());
-    PT_HIP(hipEventRecord(e1.e, s->stream));
+    PT_HIP(timer.end(s->stream));
     PT_HIP(hipMemcpyAsync(out, s->path_wave_counters.ptr, 5 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s->stream));
     PT_HIP(hipStreamSynchronize(s->stream));
-    PT_HIP(hipEventElapsedTime(out_ms, e0.e, e1.e));
+    PT_HIP(timer.ms(out_ms));
     return PT_OK;
 }
 

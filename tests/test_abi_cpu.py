@@ -116,6 +116,7 @@ UNIT_FAULTS = [
     ("pt_api.cpp", "pt_scene_info", (None, None, None, None), b"null scene"),
     ("pt_render.cpp", "pt_render_cancel", (None,), b"null control"),
     ("pt_frames.cpp", "pt_frame_destroy", (None,), b"null frame"),
+    ("pt_frame_maps.cpp", "pt_frame_get_variance", (None, None), b"null argument"),
     ("pt_image.cpp", "pt_denoise", (0, _ZERO, _ZERO, 0, 0, None, _ZERO), b"image size must be positive"),
     ("pt_image.cpp", "pt_temporal_params_default", (None,), b"null argument"),
 ]
