@@ -55,6 +55,8 @@ VARIANCE_EXPORTS = ["pt_denoise_measured_params_default", "pt_frame_get_variance
 # (... and these in include/pt_features.h)
 FEATURES_EXPORTS = ["pt_feature_params_default", "pt_render_features_followed", "pt_render_features_followed_device", "pt_render_features_followed_views",
                     "pt_render_features_followed_views_device", "pt_frame_set_feature_params"]
+# (... and these in include/pt_mesh.h)
+MESH_EXPORTS = ["pt_scene_create_meshes", "pt_mesh_assemble", "pt_scene_instance_ranges", "pt_scene_get_triangles"]
 
 
 
@@ -338,6 +340,46 @@ class SceneDesc(C.Structure):
                 ("n_point_lights", C.c_uint32), ("light_pos", C.c_void_p), ("light_spectrum", C.c_void_p)]
 
 
+class MeshData(C.Structure):
+    _fields_ = [("n_vertices", C.c_uint32), ("vertices", C.c_void_p), ("n_faces", C.c_uint32), ("faces", C.c_void_p)]
+
+
+class MeshInstance(C.Structure):
+    _fields_ = [("mesh", C.c_uint32), ("transform", C.c_float * 16), ("smooth", C.c_int32), ("cull_backface", C.c_int32), ("material", C.c_uint32)]
+
+
+def _mesh_data(vertices, faces):
+    """pt_mesh_data over (n, 3) float32 vertices and (m, 3) int32 faces; returns it with the arrays it points into."""
+    v = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3)
+    f = np.ascontiguousarray(faces, dtype=np.int32).reshape(-1, 3)
+    return MeshData(len(v), v.ctypes.data, len(f), f.ctypes.data), (v, f)
+
+
+def _mesh_instance(mesh=0, transform=None, smooth=True, cull=True, material=0xFFFFFFFF):
+    inst = MeshInstance()
+    inst.mesh = mesh
+    m = np.eye(4, dtype=np.float32) if transform is None else np.asarray(transform, dtype=np.float32).reshape(16)
+    inst.transform[:] = [float(x) for x in m.reshape(16)]
+    inst.smooth, inst.cull_backface, inst.material = int(bool(smooth)), int(bool(cull)), int(material)
+    return inst
+
+
+def mesh_assemble(vertices, faces, transform=None, smooth=True, capacity=None, device=0, out_pos=None, out_nrm=None):
+    """pt_mesh_assemble: one instance of an indexed mesh expanded on the device, as io::loadMesh returns it.  Returns (count, positions,
+    normals), each (min(count, capacity), 9); capacity defaults to the number of faces.  out_pos / out_nrm: arrays to write into
+    (at least capacity rows); the returned arrays are views of them."""
+    md, keep = _mesh_data(vertices, faces)
+    capacity = md.n_faces if capacity is None else int(capacity)
+    pos = np.zeros((capacity, 9), np.float32) if out_pos is None else out_pos
+    nrm = np.zeros((capacity, 9), np.float32) if out_nrm is None else out_nrm
+    inst = _mesh_instance(0, transform, smooth)
+    n = C.c_uint64()
+    _check(load().pt_mesh_assemble(C.c_int(device), C.byref(md), C.byref(inst), C.c_uint64(capacity), _ptr(pos), _ptr(nrm), C.byref(n)))
+    del keep
+    k = min(n.value, capacity)
+    return n.value, pos[:k], nrm[:k]
+
+
 class CameraParams(C.Structure):
     _fields_ = [("origin", C.c_float * 3), ("look_at", C.c_float * 3), ("up", C.c_float * 3), ("focal_length", C.c_float),
                 ("height", C.c_float), ("aspect_ratio", C.c_float), ("aperture_width", C.c_float), ("aperture_height", C.c_float),
@@ -522,8 +564,36 @@ class Scene:
         d.n_point_lights, d.light_pos, d.light_spectrum = len(keep["light_pos"]), _ptr(keep["light_pos"]), _ptr(keep["light_spectrum"])
         self.n_objects = d.n_objects
         self._h = C.c_void_p()
-        _check(lib.pt_scene_create(C.c_int(device), C.byref(d), C.byref(self._h)))
+        instances = scene.get("instances") or []
+        self.n_instances = len(instances)
+        if instances:
+            # meshes and instances recorded by SceneBuilder.mesh: assembled on the device behind the objects above
+            mesh_keep = [_mesh_data(v, f) for v, f in scene["meshes"]]
+            meshes = (MeshData * len(mesh_keep))(*[m for m, _ in mesh_keep])
+            insts = (MeshInstance * len(instances))(*[_mesh_instance(i["mesh"], i["transform"], i["smooth"], i["cull"], i["material"]) for i in instances])
+            _check(lib.pt_scene_create_meshes(C.c_int(device), C.byref(d), meshes, C.c_uint32(len(mesh_keep)), insts, C.c_uint32(len(instances)), C.byref(self._h)))
+            first, count = self._instance_ranges()
+            self.n_objects = d.n_objects + int(count.sum())
+        else:
+            _check(lib.pt_scene_create(C.c_int(device), C.byref(d), C.byref(self._h)))
         self.device = device
+
+    def _instance_ranges(self):
+        first, count = np.zeros(self.n_instances, np.uint32), np.zeros(self.n_instances, np.uint32)
+        _check(load().pt_scene_instance_ranges(self._h, _ptr(first), _ptr(count)))
+        return first, count
+
+    def instance_ranges(self):
+        """(first object, number of objects) of every mesh instance: its surviving triangles, in instance order."""
+        return self._instance_ranges()
+
+    def triangles(self, first, count):
+        """pt_scene_get_triangles: the triangle objects first .. first + count - 1 of a scene with mesh instances, as the builder took
+        them: positions (count, 9), normals (count, 9), cull flags, materials."""
+        pos, nrm = np.zeros((count, 9), np.float32), np.zeros((count, 9), np.float32)
+        cull, mat = np.zeros(count, np.uint8), np.zeros(count, np.uint32)
+        _check(load().pt_scene_get_triangles(self._h, C.c_uint32(first), C.c_uint32(count), _ptr(pos), _ptr(nrm), _ptr(cull), _ptr(mat)))
+        return pos, nrm, cull, mat
 
     def close(self):
         if getattr(self, "_h", None):

@@ -106,6 +106,21 @@ int check_render_args(pt_scene *scene, const pt_camera_params *camera, const pt_
     return PT_OK;
 }
 
+bool builds_on_device(uint32_t n_objects) {
+    // PT_BUILD=device | host forces one; by default scenes of 1024 objects or more are built on the device (pt_build.hip) and smaller
+    // ones by the host recursion (pt_bvh.cpp).  Both produce the same arrays, bit for bit.
+    bool use_device = n_objects >= static_cast<uint32_t>(std::max(env_int("PT_BUILD_DEVICE_MIN", 1024), 2));
+    if(const char *mode = std::getenv("PT_BUILD")) {
+        if(std::strcmp(mode, "host") == 0) {
+            use_device = false;
+        }
+        else if(std::strcmp(mode, "device") == 0) {
+            use_device = n_objects >= 2;
+        }
+    }
+    return use_device;
+}
+
 } // namespace pth
 
 using namespace pth;
@@ -156,6 +171,12 @@ size_t pt_job_tiles(int32_t image_width, int32_t image_height, pt_tile *out, siz
 }
 
 int pt_scene_create(int device, const pt_scene_desc *d, pt_scene **out) {
+    return create_scene(device, d, nullptr, out);
+}
+
+} // extern "C"
+
+int pth::create_scene(int device, const pt_scene_desc *d, const DeviceTriangles *assembled, pt_scene **out) {
     if(d == nullptr || out == nullptr) {
         return fail(PT_ERR_INVALID, "null argument");
     }
@@ -175,6 +196,13 @@ int pt_scene_create(int device, const pt_scene_desc *d, pt_scene **out) {
     if(d->n_triangles > PT_REF_INDEX || d->n_spheres > PT_REF_INDEX) {
         return fail(PT_ERR_UNSUPPORTED, "too many objects");
     }
+    // all triangles and objects: the description's, and behind them those of the mesh instances (object d->n_objects + k is triangle
+    // d->n_triangles + k)
+    const uint32_t n_tris = assembled != nullptr ? assembled->n_triangles : d->n_triangles;
+    const uint32_t n_objs = d->n_objects + (n_tris - d->n_triangles);
+    if(n_tris < d->n_triangles || n_tris > PT_REF_INDEX) {
+        return fail(PT_ERR_UNSUPPORTED, "too many objects");
+    }
 
     std::unique_ptr<pt_scene> s(new pt_scene());
     s->device = device;
@@ -183,7 +211,9 @@ int pt_scene_create(int device, const pt_scene_desc *d, pt_scene **out) {
     PT_HIP(hipGetDeviceProperties(&prop, device));
     s->cu_count = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     PT_HIP(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
-    s->n_objects = d->n_objects;
+    s->n_objects = n_objs;
+    s->n_desc_objects = d->n_objects;
+    s->n_desc_tris = d->n_triangles;
 
     using clock = std::chrono::steady_clock;
     const auto t_begin = clock::now();
@@ -223,18 +253,12 @@ int pt_scene_create(int device, const pt_scene_desc *d, pt_scene **out) {
             }
         }
     }
-    s->n_nodes = d->n_objects > 0 ? 2ULL * d->n_objects - 1ULL : 0ULL;
+    s->n_nodes = n_objs > 0 ? 2ULL * n_objs - 1ULL : 0ULL;
 
-    // Where the tree is built.  PT_BUILD=device | host forces one; by default scenes of 1024 objects or more are built on the
-    // device (pt_build.hip) and smaller ones by the host recursion (pt_bvh.cpp).  Both produce the same arrays, bit for bit.
-    bool use_device = d->n_objects >= static_cast<uint32_t>(std::max(env_int("PT_BUILD_DEVICE_MIN", 1024), 2));
-    if(const char *mode = std::getenv("PT_BUILD")) {
-        if(std::strcmp(mode, "host") == 0) {
-            use_device = false;
-        }
-        else if(std::strcmp(mode, "device") == 0) {
-            use_device = d->n_objects >= 2;
-        }
+    // Where the tree is built (builds_on_device)
+    const bool use_device = builds_on_device(n_objs);
+    if(assembled != nullptr && !use_device) {
+        return fail(PT_ERR_INVALID, "internal: triangles in device memory need the device builder");
     }
     s->device_built = use_device;
     const bool align_siblings = env_int("PT_ALIGN_SIBLINGS", 1) != 0;
@@ -256,9 +280,17 @@ int pt_scene_create(int device, const pt_scene_desc *d, pt_scene **out) {
             }
             return hipMemcpy(buf.ptr, src, count * sizeof(*src), hipMemcpyHostToDevice);
         };
-        PT_HIP(up(raw_pos, d->tri_pos, 9 * static_cast<size_t>(d->n_triangles)));
-        if(d->tri_nrm != nullptr) {
-            PT_HIP(up(raw_nrm, d->tri_nrm, 9 * static_cast<size_t>(d->n_triangles)));
+        if(assembled == nullptr) {
+            PT_HIP(up(raw_pos, d->tri_pos, 9 * static_cast<size_t>(d->n_triangles)));
+            if(d->tri_nrm != nullptr) {
+                PT_HIP(up(raw_nrm, d->tri_nrm, 9 * static_cast<size_t>(d->n_triangles)));
+            }
+        }
+        else {
+            // positions and normals are in HBM already; the three small arrays get room for the instances' triangles behind the description's
+            PT_HIP(raw_cull.ensure(n_tris));
+            PT_HIP(raw_tri_mat.ensure(n_tris));
+            PT_HIP(raw_tri_obj.ensure(n_tris));
         }
         PT_HIP(up(raw_cull, d->tri_cull, d->n_triangles));
         PT_HIP(up(raw_tri_mat, d->tri_material, d->n_triangles));
@@ -266,19 +298,25 @@ int pt_scene_create(int device, const pt_scene_desc *d, pt_scene **out) {
         PT_HIP(up(raw_sph, d->sph, 4 * static_cast<size_t>(d->n_spheres)));
         PT_HIP(up(raw_sph_mat, d->sph_material, d->n_spheres));
         PT_HIP(up(raw_sph_obj, s->sph_obj.data(), d->n_spheres));
-        PT_HIP(s->tris.ensure(PT_TRI_QUADS * (static_cast<size_t>(d->n_triangles) + 1 + d->n_spheres))); // triangles, a spare record, spheres (pt_types.h)
-        PT_HIP(hipMemsetAsync(s->tris.ptr + PT_TRI_QUADS * static_cast<size_t>(d->n_triangles), 0, PT_TRI_QUADS * sizeof(F4), s->stream));
-        PT_HIP(s->tri_shade.ensure(8 * static_cast<size_t>(d->n_triangles)));
+        if(assembled != nullptr) {
+            for(const MeshRange &r : assembled->ranges) {
+                PT_HIP(pt_mesh_fill_range(s->stream, r.first_tri, r.count, r.cull, r.material, d->n_objects + (r.first_tri - d->n_triangles), raw_cull.ptr, raw_tri_mat.ptr,
+                                          raw_tri_obj.ptr));
+            }
+        }
+        PT_HIP(s->tris.ensure(PT_TRI_QUADS * (static_cast<size_t>(n_tris) + 1 + d->n_spheres))); // triangles, a spare record, spheres (pt_types.h)
+        PT_HIP(hipMemsetAsync(s->tris.ptr + PT_TRI_QUADS * static_cast<size_t>(n_tris), 0, PT_TRI_QUADS * sizeof(F4), s->stream));
+        PT_HIP(s->tri_shade.ensure(8 * static_cast<size_t>(n_tris)));
         PT_HIP(s->spheres.ensure(d->n_spheres));
         PT_HIP(s->sph_meta.ensure(d->n_spheres));
         s->build_ms[1] = ms_since(t_upload);
 
         PtBuildInput in;
-        in.n_objects = d->n_objects;
-        in.n_triangles = d->n_triangles;
+        in.n_objects = n_objs;
+        in.n_triangles = n_tris;
         in.n_spheres = d->n_spheres;
-        in.tri_pos = raw_pos.ptr;
-        in.tri_nrm = d->tri_nrm != nullptr ? raw_nrm.ptr : nullptr;
+        in.tri_pos = assembled != nullptr ? assembled->pos : raw_pos.ptr;
+        in.tri_nrm = assembled != nullptr ? assembled->nrm : (d->tri_nrm != nullptr ? raw_nrm.ptr : nullptr);
         in.tri_cull = raw_cull.ptr;
         in.tri_material = raw_tri_mat.ptr;
         in.tri_obj = raw_tri_obj.ptr;
@@ -300,7 +338,7 @@ int pt_scene_create(int device, const pt_scene_desc *d, pt_scene **out) {
         s->pairs.count = 4 * static_cast<size_t>(built.n_pairs);
         DevBuf<uint32_t> dfs_dev;
         dfs_dev.ptr = built.dfs;
-        dfs_dev.count = d->n_objects;
+        dfs_dev.count = n_objs;
         s->build_ms[2] = built.build_ms;
         s->depth = built.depth;
         if(s->depth > PT_MAX_DEPTH) {
@@ -322,7 +360,7 @@ int pt_scene_create(int device, const pt_scene_desc *d, pt_scene **out) {
             any_lit = any_lit || lit[m] != 0;
         }
         if(any_lit) {
-            std::vector<uint32_t> mask((static_cast<size_t>(d->n_objects) + 31) / 32, 0U);
+            std::vector<uint32_t> mask((static_cast<size_t>(n_objs) + 31) / 32, 0U);
             uint32_t n_selected = 0;
             for(uint32_t t = 0; t < d->n_triangles; t++) {
                 const uint32_t m = d->tri_material[t];
@@ -340,8 +378,20 @@ int pt_scene_create(int device, const pt_scene_desc *d, pt_scene **out) {
                     n_selected++;
                 }
             }
+            if(assembled != nullptr) {
+                // an instance has one material: a lit one selects its whole range of objects
+                for(const MeshRange &r : assembled->ranges) {
+                    if(r.material != PT_NO_MATERIAL && lit[r.material] != 0) {
+                        const uint32_t first = d->n_objects + (r.first_tri - d->n_triangles);
+                        for(uint32_t o = first; o < first + r.count; o++) {
+                            mask[o >> 5] |= 1U << (o & 31U);
+                        }
+                        n_selected += r.count;
+                    }
+                }
+            }
             std::vector<uint32_t> ordered;
-            PT_HIP(pt_build_order_subset(s->stream, dfs_dev.ptr, d->n_objects, mask, n_selected, ordered));
+            PT_HIP(pt_build_order_subset(s->stream, dfs_dev.ptr, n_objs, mask, n_selected, ordered));
             dfs.assign(ordered.begin(), ordered.end());
         }
     }
@@ -452,11 +502,42 @@ int pt_scene_create(int device, const pt_scene_desc *d, pt_scene **out) {
     std::vector<F4> emis;
     std::vector<float> cdf;
     const float pi = static_cast<float>(M_PI);
+    // the positions of the candidates among the instances' triangles (all of them have a lit material) are gathered on the device: E records, not n
+    std::vector<float> gathered;
+    if(assembled != nullptr) {
+        std::vector<uint32_t> wanted;
+        for(int32_t obj : dfs) {
+            if(static_cast<uint32_t>(obj) >= d->n_objects) {
+                wanted.push_back(d->n_triangles + (static_cast<uint32_t>(obj) - d->n_objects));
+            }
+        }
+        if(!wanted.empty()) {
+            DevBuf<uint32_t> wanted_dev;
+            DevBuf<float> gathered_dev;
+            PT_HIP(wanted_dev.upload(wanted));
+            PT_HIP(gathered_dev.ensure(9 * wanted.size()));
+            PT_HIP(pt_mesh_gather_pos(s->stream, assembled->pos, wanted_dev.ptr, static_cast<uint32_t>(wanted.size()), gathered_dev.ptr));
+            gathered.resize(9 * wanted.size());
+            PT_HIP(hipMemcpyAsync(gathered.data(), gathered_dev.ptr, gathered.size() * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+            PT_HIP(hipStreamSynchronize(s->stream));
+        }
+    }
+    size_t next_gathered = 0;
     for(int32_t obj : dfs) {
-        const uint32_t ref = leaf_ref[obj];
+        const bool of_instance = static_cast<uint32_t>(obj) >= d->n_objects;
+        const uint32_t ref = of_instance ? (PT_REF_LEAF | (d->n_triangles + (static_cast<uint32_t>(obj) - d->n_objects))) : leaf_ref[obj];
         const uint32_t idx = ref & PT_REF_INDEX;
         const bool is_sphere = (ref & PT_REF_SPHERE) != 0;
-        const uint32_t mat = is_sphere ? d->sph_material[idx] : d->tri_material[idx];
+        const MeshRange *range = nullptr;
+        const float *tri_p = nullptr; // the triangle's nine coordinates
+        if(of_instance) {
+            range = &*(std::upper_bound(assembled->ranges.begin(), assembled->ranges.end(), idx, [](uint32_t t, const MeshRange &r) { return t < r.first_tri; }) - 1);
+            tri_p = gathered.data() + 9 * next_gathered++;
+        }
+        else if(!is_sphere) {
+            tri_p = d->tri_pos + 9 * static_cast<size_t>(idx);
+        }
+        const uint32_t mat = of_instance ? range->material : (is_sphere ? d->sph_material[idx] : d->tri_material[idx]);
         if(mat == PT_NO_MATERIAL) {
             continue; // default material has no emission
         }
@@ -471,7 +552,7 @@ int pt_scene_create(int device, const pt_scene_desc *d, pt_scene **out) {
             area = 4.0F * pi * (r * r); // object.cpp:95-99
         }
         else {
-            const float *p = d->tri_pos + 9 * static_cast<size_t>(idx);
+            const float *p = tri_p;
             const Vec3 c = cross(sub(ld(p + 3), ld(p)), sub(ld(p + 6), ld(p)));
             area = std::sqrt(dot(c, c)) / 2.0F; // object.cpp:188-190
         }
@@ -486,10 +567,11 @@ int pt_scene_create(int device, const pt_scene_desc *d, pt_scene **out) {
             emis.push_back({0.0F, from_bits(ref), 0.0F, from_bits(mat)});
         }
         else {
-            const float *p = d->tri_pos + 9 * static_cast<size_t>(idx);
+            const float *p = tri_p;
+            const bool cull = of_instance ? range->cull != 0 : d->tri_cull[idx] != 0;
             emis.push_back({p[0], p[1], p[2], p[3]});
             emis.push_back({p[4], p[5], p[6], p[7]});
-            emis.push_back({p[8], from_bits(ref), from_bits(d->tri_cull[idx] != 0 ? 1U : 0U), from_bits(mat)});
+            emis.push_back({p[8], from_bits(ref), from_bits(cull ? 1U : 0U), from_bits(mat)});
         }
         emis.push_back({e[0], e[1], e[2], e[3]});
         cdf.push_back(object_probability);
@@ -523,7 +605,7 @@ int pt_scene_create(int device, const pt_scene_desc *d, pt_scene **out) {
 
     // ---- link: leaf records and pair records become ONE array, and the tree's references indices into it (pt_types.h) --------------
     // (the pair records start on an even record: two sibling nodes on slots 2k, 2k + 1 share one aligned 128-byte line only then)
-    const uint32_t sphere_base = d->n_triangles + 1U, leaf_count = sphere_base + d->n_spheres, pair_base = (leaf_count + 1U) & ~1U;
+    const uint32_t sphere_base = n_tris + 1U, leaf_count = sphere_base + d->n_spheres, pair_base = (leaf_count + 1U) & ~1U;
     if(static_cast<uint64_t>(pair_base) + n_pairs > PT_REF_INDEX) {
         return fail(PT_ERR_UNSUPPORTED, "too many records for 30-bit references");
     }
@@ -561,7 +643,7 @@ int pt_scene_create(int device, const pt_scene_desc *d, pt_scene **out) {
     }
     dev.root_ref = root_ref;
     dev.n_pairs = n_pairs;
-    dev.n_tris = d->n_triangles;
+    dev.n_tris = n_tris;
     dev.n_spheres = d->n_spheres;
     dev.n_lights = d->n_point_lights;
     dev.n_emis = s->n_emissive;
@@ -578,7 +660,7 @@ int pt_scene_create(int device, const pt_scene_desc *d, pt_scene **out) {
     const size_t room = other_lds < 40960 ? 40960 - other_lds : 0;
     if(small_bytes <= static_cast<size_t>(std::max(env_int("PT_LDS_SMALL_BYTES", static_cast<int>(room)), 0)) && env_int("PT_LDS_SMALL", 1) != 0) {
         dev.n_lds_pairs = n_pairs;
-        dev.n_lds_tris = d->n_triangles;
+        dev.n_lds_tris = n_tris;
     }
     else {
         dev.n_lds_pairs = 0;
@@ -592,11 +674,13 @@ int pt_scene_create(int device, const pt_scene_desc *d, pt_scene **out) {
     s->build_ms[3] = ms_since(t_rest);
     if(env_int("PT_DEBUG", 0) != 0) {
         std::fprintf(stderr, "[pt] scene build (%s): %u objects, %u pair records, depth %u; host preparation %.1f ms, upload %.1f ms, device tree %.1f ms, rest %.1f ms\n",
-                     s->device_built ? "device" : "host", d->n_objects, n_pairs, s->depth, s->build_ms[0], s->build_ms[1], s->build_ms[2], s->build_ms[3]);
+                     s->device_built ? "device" : "host", n_objs, n_pairs, s->depth, s->build_ms[0], s->build_ms[1], s->build_ms[2], s->build_ms[3]);
     }
     *out = s.release();
     return PT_OK;
 }
+
+extern "C" {
 
 void pt_scene_destroy(pt_scene *scene) {
     if(scene == nullptr) {
@@ -679,7 +763,7 @@ int pt_scene_bvh_dump(const pt_scene *scene, int32_t *out_obj, float *out_box, u
             box.push_back(it.box);
             if((it.ref & PT_REF_LEAF) != 0) {
                 const uint32_t idx = it.ref & PT_REF_INDEX; // (record indices: pt_types.h)
-                obj.push_back(static_cast<int32_t>((it.ref & PT_REF_SPHERE) != 0 ? scene->sph_obj[idx - sphere_base] : scene->tri_obj[idx]));
+                obj.push_back(static_cast<int32_t>((it.ref & PT_REF_SPHERE) != 0 ? scene->sph_obj[idx - sphere_base] : scene->tri_object(idx)));
             }
             else {
                 obj.push_back(-1);
@@ -739,7 +823,7 @@ int pt_intersect_batch(pt_scene *s, const float *rays, size_t n, float *out_t, i
             const float t = from_bits(hits[i].x);
             const uint32_t ref = hits[i].y;
             out_t[i] = t;
-            out_obj[i] = (t < 0.0F || ref == PT_REF_NONE) ? -1 : static_cast<int32_t>((ref & PT_REF_SPHERE) ? s->sph_obj[(ref & PT_REF_INDEX) - (s->dev.n_tris + 1U)] : s->tri_obj[ref & PT_REF_INDEX]);
+            out_obj[i] = (t < 0.0F || ref == PT_REF_NONE) ? -1 : static_cast<int32_t>((ref & PT_REF_SPHERE) ? s->sph_obj[(ref & PT_REF_INDEX) - (s->dev.n_tris + 1U)] : s->tri_object(ref & PT_REF_INDEX));
         }
         return PT_OK;
     }

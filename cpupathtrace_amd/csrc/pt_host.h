@@ -1,5 +1,6 @@
-// pt_host.h -- what the host units of libpathtrace_hip.so share: pt_api.cpp (scenes), pt_render.cpp (render calls), pt_frames.cpp and
-// pt_frame_maps.cpp (resumable frames and their maps; pt_frames.h) and pt_image.cpp (post-processing, features, denoising).  Internal:
+// pt_host.h -- what the host units of libpathtrace_hip.so share: pt_api.cpp (scenes), pt_meshes.cpp (scenes from meshes and instances),
+// pt_render.cpp (render calls), pt_frames.cpp and pt_frame_maps.cpp (resumable frames and their maps; pt_frames.h) and pt_image.cpp
+// (post-processing, features, denoising).  Internal:
 // not installed, not part of the C ABI.  Everything but the ABI's own handle types lives in namespace pth, so that no helper can collide
 // with a pt_* name of include/pt_hip.h.
 #ifndef PT_HOST_H
@@ -24,6 +25,7 @@
 #include <vector>
 
 #include "pt_build.h"
+#include "pt_mesh.h"
 #include "pt_bvh.h"
 #include "pt_kernels.h"
 #include "pt_denoise.h"
@@ -186,9 +188,15 @@ struct pt_scene {
     uint32_t depth = 0;      // levels of the tree (a single leaf has depth 1)
     bool device_built = false;
     float build_ms[4] = {0, 0, 0, 0}; // host preparation, upload, device tree construction, emissive registration + rest
-    std::vector<uint32_t> tri_obj;
+    std::vector<uint32_t> tri_obj; // object of every triangle of the description; the triangles of mesh instances follow them and need no table:
     std::vector<uint32_t> sph_obj;
     uint32_t n_objects = 0;
+    uint32_t n_desc_objects = 0, n_desc_tris = 0; // ... triangle n_desc_tris + k is object n_desc_objects + k (pt_scene_create_meshes)
+    uint32_t tri_object(uint32_t t) const { return t < tri_obj.size() ? tri_obj[t] : n_desc_objects + (t - n_desc_tris); }
+    // scenes of pt_scene_create_meshes with instances: their object ranges, the triangle or sphere of every object of the description
+    // (PT_REF_SPHERE | index), and the triangles' positions as the builder took them (pt_scene_get_triangles)
+    std::vector<uint32_t> inst_first, inst_count, desc_ref;
+    pth::DevBuf<float> tri_pos_kept;
     uint32_t n_emissive = 0;
     std::vector<int32_t> emissive_obj;
     std::vector<float> emissive_cdf;
@@ -271,6 +279,25 @@ int check_device(int device); // PT_ERR_NO_DEVICE without a HIP device, or for a
 PtDevCamera derive_camera(const pt_camera_params *c);
 int derive_options(const pt_options *o, PtDevOptions *out);
 int check_render_args(pt_scene *scene, const pt_camera_params *camera, const pt_options *options);
+
+// Triangles that are in device memory already (pt_meshes.cpp): those of the description first, then the ranges of the mesh instances, each
+// with one cull flag and one material.
+struct MeshRange {
+    uint32_t first_tri, count;
+    uint8_t cull;
+    uint32_t material;
+};
+struct DeviceTriangles {
+    const float *pos = nullptr; // [n_triangles][9]
+    const float *nrm = nullptr; // [n_triangles][9] or null: face normals
+    uint32_t n_triangles = 0;   // the description's and the ranges'
+    std::vector<MeshRange> ranges;
+};
+// Whether a scene of n_objects is built on the device (PT_BUILD_DEVICE_MIN, PT_BUILD)
+bool builds_on_device(uint32_t n_objects);
+// pt_scene_create; with `assembled` (device builder only) the triangles are taken from device memory: d's own per-triangle arrays tri_pos
+// and tri_nrm are not read, and nothing per triangle of the ranges crosses to the host but the positions of the emissive ones.
+int create_scene(int device, const pt_scene_desc *d, const DeviceTriangles *assembled, pt_scene **out);
 
 // ---- pt_render.cpp: the persistent path kernel (pt_path.hip), one launch per render call ----------------------------------------------
 

@@ -130,6 +130,8 @@ class SceneBuilder:
         self.sph, self.sph_mat = [], []
         self.materials = []
         self.light_pos, self.light_spec = [], []
+        self.meshes, self.instances = [], []
+        self._mesh_sources = []
 
     def material(self, diffuse=(1, 1, 1, 1), ior=1.0, emission=(0, 0, 0, 0), bsdf=BSDF_LAMBERTIAN, one_way=False, specular=(1, 1, 1, 1)):
         """ConstantMaterial(diffuse, ior, emission) + BSDF -> ConstantMaterialHandler (material.h:53-68, object.h:26-40)."""
@@ -156,6 +158,21 @@ class SceneBuilder:
         self.sph.append(np.array([origin[0], origin[1], origin[2], radius], dtype=F))
         self.sph_mat.append(np.uint32(material))
 
+    def mesh(self, vertices, faces, transform=None, material=NO_MATERIAL, cull=True, smooth=True):
+        """An instance of an indexed mesh (vertices (n, 3) float32 untransformed, faces (m, 3) int32 0-based) under `transform`, as
+        io::loadMesh(file, transform, cull, smooth) + moveObjects would add it: its surviving triangles follow every object recorded by
+        triangles() and sphere(), instance after instance, and are made on the device.  Instances of the same arrays share one mesh."""
+        for k, (v, f) in enumerate(self._mesh_sources):
+            if v is vertices and f is faces:
+                break
+        else:
+            k = len(self.meshes)
+            self._mesh_sources.append((vertices, faces))
+            self.meshes.append((np.ascontiguousarray(vertices, dtype=F).reshape(-1, 3), np.ascontiguousarray(faces, dtype=np.int32).reshape(-1, 3)))
+        m = np.eye(4, dtype=F) if transform is None else np.ascontiguousarray(transform, dtype=F).reshape(4, 4)
+        self.instances.append({"mesh": k, "transform": m, "smooth": bool(smooth), "cull": bool(cull), "material": int(material)})
+        return len(self.instances) - 1
+
     def point_light(self, pos, spectrum):
         self.light_pos.append(np.asarray(pos, dtype=F))
         self.light_spec.append(np.asarray(spectrum, dtype=F))
@@ -164,7 +181,7 @@ class SceneBuilder:
         def cat(parts, shape, dtype):
             return np.concatenate(parts, axis=0).astype(dtype, copy=False) if parts else np.zeros(shape, dtype=dtype)
 
-        return {
+        out = {
             "obj_kind": cat(self.kind, (0,), np.uint8),
             "tri_pos": cat(self.tri_pos, (0, 9), F),
             "tri_nrm": cat(self.tri_nrm, (0, 9), F),
@@ -176,6 +193,9 @@ class SceneBuilder:
             "light_pos": np.array(self.light_pos, dtype=F).reshape(-1, 3),
             "light_spectrum": np.array(self.light_spec, dtype=F).reshape(-1, 4),
         }
+        if self.instances:
+            out["meshes"], out["instances"] = list(self.meshes), list(self.instances)
+        return out
 
 
 def camera(origin, look_at, up, focal_length, height, aspect_ratio, aperture_width=0.0, aperture_height=0.0, aperture_kind=APERTURE_NONE,

@@ -17,6 +17,7 @@
 #include <PathTrace/detail/core.h>
 
 #include <array>
+#include <cstdint>
 #include <memory>
 #include <tuple>
 #include <utility>
@@ -255,12 +256,30 @@ class AABB {
 
 struct pt_scene;
 
+namespace io {
+    struct MeshData; // PathTrace/scene/mesh.h
+}
+
+// One placement of an indexed mesh in a Scene: what io::loadMesh(file, transformation, cull_backface, smooth) + setMaterialHandler(handler)
+// + moveObjects would add, without a host Triangle per face -- the triangles are made on the device (include/pt_mesh.h).  Instances may
+// share one MeshData.  A null handler is the default one (white Lambertian), as for an Object.
+struct MeshInstance {
+    std::shared_ptr<const io::MeshData> mesh;
+    mat4<float> transformation = mat4_identity<float>;
+    bool cull_backface = true;
+    bool smooth = true;
+    std::shared_ptr<MaterialHandler> handler;
+};
+
 class Scene {
   public:
     // takes ownership; builds the hierarchy and the device-resident copy (device = $PATHTRACE_DEVICE, default 0).  With
     // $PATHTRACE_DEVICES = N (or "all") the scene is replicated on N devices starting at that one and processJob deals its tiles
     // out to them (src/worker.cpp:364-387's worker threads become one persistent launch per device).
     Scene(std::vector<std::unique_ptr<Object>> &&objects, std::vector<std::unique_ptr<LightSource>> &&light_sources);
+    // ... followed by the surviving triangles of every mesh instance, in instance order.  No Triangle is created per mesh triangle:
+    // getIntersection and sampleLights materialise the ones they return or sample on first use (emitters at construction).
+    Scene(std::vector<std::unique_ptr<Object>> &&objects, std::vector<std::unique_ptr<LightSource>> &&light_sources, std::vector<MeshInstance> &&mesh_instances);
     ~Scene();
     Scene(const Scene &) = delete;
     Scene &operator=(const Scene &) = delete;
@@ -282,6 +301,10 @@ class Scene {
     std::vector<float> emissive_cdf;           // normalised inclusive prefix sums
     pt_scene *device_scene = nullptr;     // = replicas[0]
     std::vector<pt_scene *> replicas;     // one per device
+    // The data members above are the class's whole layout and stay what they were: a program compiled against an earlier version of this
+    // header keeps working with the library.  What a Scene with mesh instances keeps beyond them -- the instances, their object ranges and
+    // the Triangles handed out so far, guarded by a mutex -- lives in the library, looked up by the Scene's address (src/host/scene.cpp).
+    const Object *meshObject(uint32_t index) const;
 };
 
 #endif

@@ -5,6 +5,8 @@
 
 #include <PathTrace/scene/object.h>
 
+#include <array>
+#include <cstdint>
 #include <filesystem>
 #include <istream>
 #include <memory>
@@ -19,6 +21,17 @@ namespace io {
                                    bool smooth = true);
     std::vector<Triangle> loadMesh(const std::filesystem::path &path, mat4<float> transformation = mat4_identity<float>, bool cull_backface = true,
                                    bool smooth = true);
+
+    // An indexed mesh as its file states it: the `v` records untransformed, and the `f` records (0-based, first three vertices) that name
+    // vertices read so far.  Nothing geometric is decided here: a MeshInstance of it in a Scene is transformed, filtered, smoothed and
+    // expanded into triangles on the device (include/pt_mesh.h), to exactly the triangles loadMesh returns for the same text and matrix.
+    struct MeshData {
+        std::vector<vec3<float>> vertices;
+        std::vector<std::array<int32_t, 3>> faces;
+    };
+    // The parallel reader of loadMesh, stopping before the transform.
+    MeshData loadMeshData(std::basic_istream<char> &stream);
+    MeshData loadMeshData(const std::filesystem::path &path);
 
 } // namespace io
 

@@ -56,6 +56,27 @@ uint64_t pth_load_mesh(const char *obj_text, uint64_t len, const float *mat16, i
     return store(io::loadMesh(stream, matrixFrom(mat16), false, smooth != 0), capacity, pos, nrm);
 }
 
+// io::loadMeshData: the numbers of the text.  Returns the number of faces; *n_vertices receives the number of vertices; at most the given
+// capacities are written ([capacity][3] each).
+uint64_t pth_load_mesh_data(const char *obj_text, uint64_t len, uint64_t vertex_capacity, float *vertices, uint64_t face_capacity, int32_t *faces, uint64_t *n_vertices) {
+    std::istringstream stream(std::string(obj_text, len));
+    const io::MeshData mesh = io::loadMeshData(stream);
+    for(uint64_t i = 0; i < mesh.vertices.size() && i < vertex_capacity; i++) {
+        for(int k = 0; k < 3; k++) {
+            vertices[3 * i + k] = mesh.vertices[i][k];
+        }
+    }
+    for(uint64_t i = 0; i < mesh.faces.size() && i < face_capacity; i++) {
+        for(int k = 0; k < 3; k++) {
+            faces[3 * i + k] = mesh.faces[i][static_cast<size_t>(k)];
+        }
+    }
+    if(n_vertices != nullptr) {
+        *n_vertices = mesh.vertices.size();
+    }
+    return mesh.faces.size();
+}
+
 // Writes an indexed triangle mesh as a Wavefront OBJ file ("v x y z" with 9 significant digits -- exact for float32 -- and 1-based
 // "f a b c" lines): the committed stand-in for assets/xyzrgb_dragon.obj goes to disk this way for the reference's benchmark program.
 int pth_write_obj(const char *path, const float *vertices, uint64_t n_vertices, const int32_t *faces, uint64_t n_faces) {

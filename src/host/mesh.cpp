@@ -5,6 +5,7 @@
 #include <PathTrace/scene/mesh.h>
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <chrono>
 #include <cstdio>
@@ -178,7 +179,8 @@ namespace {
 
     // Reads the lines that START in [begin, end).  The reader may run past `end` (a number that continues on the next line): the
     // position it stops at tells the caller whether the next piece really started at a line start.
-    void readPiece(const char *text, size_t size, size_t begin, size_t end, const mat4<float> &transformation, Piece &result) {
+    // `transformation` may be null: the vertices stay as they are written (io::loadMeshData).
+    void readPiece(const char *text, size_t size, size_t begin, size_t end, const mat4<float> *transformation, Piece &result) {
         Piece piece; // filled locally: neighbouring entries of the callers' array share cache lines
         // one slot per line for either list: growing the lists while reading makes the threads queue up in the allocator
         size_t lines = 1;
@@ -198,7 +200,7 @@ namespace {
                 const float x = reader.real();
                 const float y = reader.real();
                 const float z = reader.real();
-                piece.vertices.push_back(vec3<float>(transformation * vec3<float>{x, y, z}));
+                piece.vertices.push_back(transformation != nullptr ? vec3<float>(*transformation * vec3<float>{x, y, z}) : vec3<float>{x, y, z});
             }
             else if(tag == 'f' && reader.takeIf(' ')) {
                 FaceLine face;
@@ -235,10 +237,63 @@ namespace {
         }
     }
 
-    std::vector<Triangle> meshFromText(const char *text, size_t size, const mat4<float> &transformation, bool cull_backface, bool smooth) {
+    unsigned loaderThreads() {
         const char *threads_env = std::getenv("PATHTRACE_LOADER_THREADS");
-        unsigned threads = threads_env != nullptr ? static_cast<unsigned>(std::max(1, std::atoi(threads_env))) : std::max(1U, std::thread::hardware_concurrency());
-        threads = std::min(threads, 64U);
+        const unsigned threads = threads_env != nullptr ? static_cast<unsigned>(std::max(1, std::atoi(threads_env))) : std::max(1U, std::thread::hardware_concurrency());
+        return std::min(threads, 64U);
+    }
+
+    // ---- read: the text is cut at line starts and the pieces are read concurrently.  A piece is only right if the piece
+    // before it stopped exactly where it starts (a line whose numbers spill over a line end breaks that); otherwise the
+    // whole text is read again as one piece, which is what a sequential reader does.
+    std::vector<Piece> readPieces(const char *text, size_t size, const mat4<float> *transformation, unsigned threads, bool debug) {
+        std::vector<Piece> pieces;
+        // PATHTRACE_LOADER_PIECE_BYTES: smallest piece (default 256 KiB; the tests use a few bytes to exercise the cutting)
+        const char *piece_env = std::getenv("PATHTRACE_LOADER_PIECE_BYTES");
+        const size_t piece_bytes = piece_env != nullptr ? static_cast<size_t>(std::max(1, std::atoi(piece_env))) : (size_t{1} << 18);
+        const size_t wanted = size < 4 * piece_bytes ? 1 : std::min<size_t>(threads * 4, size / piece_bytes);
+        std::vector<size_t> cuts{0};
+        for(size_t k = 1; k < wanted; k++) {
+            size_t at = size * k / wanted;
+            while(at < size && text[at - 1] != '\n') {
+                at++;
+            }
+            if(at > cuts.back() && at < size) {
+                cuts.push_back(at);
+            }
+        }
+        cuts.push_back(size);
+        pieces.resize(cuts.size() - 1);
+        std::atomic<size_t> next{0};
+        auto worker = [&]() {
+            for(size_t k = next.fetch_add(1); k < pieces.size(); k = next.fetch_add(1)) {
+                readPiece(text, size, cuts[k], cuts[k + 1], transformation, pieces[k]);
+            }
+        };
+        std::vector<std::thread> pool;
+        for(unsigned t = 1; t < std::min<size_t>(threads, pieces.size()); t++) {
+            pool.emplace_back(worker);
+        }
+        worker();
+        for(auto &th : pool) {
+            th.join();
+        }
+        bool consistent = true;
+        for(size_t k = 0; k + 1 < pieces.size(); k++) {
+            consistent = consistent && pieces[k].end == cuts[k + 1];
+        }
+        if(debug) {
+            std::fprintf(stderr, "[loadMesh] %zu pieces on %u threads, %s\n", pieces.size(), threads, consistent ? "consistent" : "NOT consistent: reading again as one piece");
+        }
+        if(!consistent) {
+            pieces.assign(1, Piece{});
+            readPiece(text, size, 0, size, transformation, pieces[0]);
+        }
+        return pieces;
+    }
+
+    std::vector<Triangle> meshFromText(const char *text, size_t size, const mat4<float> &transformation, bool cull_backface, bool smooth) {
+        const unsigned threads = loaderThreads();
         const bool debug = std::getenv("PATHTRACE_LOADER_DEBUG") != nullptr;
         auto t_last = std::chrono::steady_clock::now();
         auto lap = [&](const char *what) {
@@ -249,53 +304,7 @@ namespace {
             }
         };
 
-        // ---- read: the text is cut at line starts and the pieces are read concurrently.  A piece is only right if the piece
-        // before it stopped exactly where it starts (a line whose numbers spill over a line end breaks that); otherwise the
-        // whole text is read again as one piece, which is what a sequential reader does.
-        std::vector<Piece> pieces;
-        {
-            // PATHTRACE_LOADER_PIECE_BYTES: smallest piece (default 256 KiB; the tests use a few bytes to exercise the cutting)
-            const char *piece_env = std::getenv("PATHTRACE_LOADER_PIECE_BYTES");
-            const size_t piece_bytes = piece_env != nullptr ? static_cast<size_t>(std::max(1, std::atoi(piece_env))) : (size_t{1} << 18);
-            const size_t wanted = size < 4 * piece_bytes ? 1 : std::min<size_t>(threads * 4, size / piece_bytes);
-            std::vector<size_t> cuts{0};
-            for(size_t k = 1; k < wanted; k++) {
-                size_t at = size * k / wanted;
-                while(at < size && text[at - 1] != '\n') {
-                    at++;
-                }
-                if(at > cuts.back() && at < size) {
-                    cuts.push_back(at);
-                }
-            }
-            cuts.push_back(size);
-            pieces.resize(cuts.size() - 1);
-            std::atomic<size_t> next{0};
-            auto worker = [&]() {
-                for(size_t k = next.fetch_add(1); k < pieces.size(); k = next.fetch_add(1)) {
-                    readPiece(text, size, cuts[k], cuts[k + 1], transformation, pieces[k]);
-                }
-            };
-            std::vector<std::thread> pool;
-            for(unsigned t = 1; t < std::min<size_t>(threads, pieces.size()); t++) {
-                pool.emplace_back(worker);
-            }
-            worker();
-            for(auto &th : pool) {
-                th.join();
-            }
-            bool consistent = true;
-            for(size_t k = 0; k + 1 < pieces.size(); k++) {
-                consistent = consistent && pieces[k].end == cuts[k + 1];
-            }
-            if(debug) {
-                std::fprintf(stderr, "[loadMesh] %zu pieces on %u threads, %s\n", pieces.size(), threads, consistent ? "consistent" : "NOT consistent: reading again as one piece");
-            }
-            if(!consistent) {
-                pieces.assign(1, Piece{});
-                readPiece(text, size, 0, size, transformation, pieces[0]);
-            }
-        }
+        std::vector<Piece> pieces = readPieces(text, size, &transformation, threads, debug);
 
         lap("read");
         // ---- vertices of the whole file, and for every face line the number of vertices that precede it
@@ -427,9 +436,72 @@ namespace {
         return faces;
     }
 
+    // The numbers of the text and nothing else: vertices as written, and the faces whose three indices name vertices read SO FAR (the
+    // one rejection that depends on the text's order; every geometric one is the device's, include/pt_mesh.h).
+    io::MeshData meshDataFromText(const char *text, size_t size) {
+        const unsigned threads = loaderThreads();
+        const std::vector<Piece> pieces = readPieces(text, size, nullptr, threads, std::getenv("PATHTRACE_LOADER_DEBUG") != nullptr);
+        std::vector<size_t> vertex_base(pieces.size() + 1, 0), face_base(pieces.size() + 1, 0);
+        for(size_t k = 0; k < pieces.size(); k++) {
+            vertex_base[k + 1] = vertex_base[k] + pieces[k].vertices.size();
+            face_base[k + 1] = face_base[k] + pieces[k].faces.size();
+        }
+        io::MeshData mesh;
+        mesh.vertices.resize(vertex_base.back());
+        std::vector<std::vector<std::array<int32_t, 3>>> kept(pieces.size());
+        inParallel(pieces.size(), threads, [&](size_t first, size_t last) {
+            for(size_t k = first; k < last; k++) {
+                std::copy(pieces[k].vertices.begin(), pieces[k].vertices.end(), mesh.vertices.begin() + static_cast<std::ptrdiff_t>(vertex_base[k]));
+                kept[k].reserve(pieces[k].faces.size());
+                for(const FaceLine &f : pieces[k].faces) {
+                    const long count = static_cast<long>(vertex_base[k] + f.vertices_before);
+                    if(f.index[0] >= 0 && f.index[0] < count && f.index[1] >= 0 && f.index[1] < count && f.index[2] >= 0 && f.index[2] < count) {
+                        kept[k].push_back({f.index[0], f.index[1], f.index[2]});
+                    }
+                }
+            }
+        });
+        size_t total = 0;
+        for(const auto &part : kept) {
+            total += part.size();
+        }
+        mesh.faces.reserve(total);
+        for(const auto &part : kept) {
+            mesh.faces.insert(mesh.faces.end(), part.begin(), part.end());
+        }
+        return mesh;
+    }
+
 } // namespace
 
 namespace io {
+
+    MeshData loadMeshData(std::basic_istream<char> &stream) {
+        const std::string text{std::istreambuf_iterator<char>(stream), std::istreambuf_iterator<char>()};
+        return meshDataFromText(text.data(), text.size());
+    }
+
+    MeshData loadMeshData(const std::filesystem::path &path) {
+        const int fd = ::open(path.c_str(), O_RDONLY);
+        if(fd < 0) {
+            return {};
+        }
+        struct stat info {};
+        if(::fstat(fd, &info) != 0 || info.st_size <= 0) {
+            ::close(fd);
+            return {};
+        }
+        const size_t size = static_cast<size_t>(info.st_size);
+        void *mapped = ::mmap(nullptr, size, PROT_READ, MAP_PRIVATE | MAP_POPULATE, fd, 0);
+        ::close(fd);
+        if(mapped == MAP_FAILED) {
+            std::ifstream stream(path, std::ios_base::in | std::ios_base::binary);
+            return loadMeshData(stream);
+        }
+        MeshData mesh = meshDataFromText(static_cast<const char *>(mapped), size);
+        ::munmap(mapped, size);
+        return mesh;
+    }
 
     std::vector<Triangle> loadMesh(std::basic_istream<char> &stream, mat4<float> transformation, bool cull_backface, bool smooth) {
         const std::string text{std::istreambuf_iterator<char>(stream), std::istreambuf_iterator<char>()};

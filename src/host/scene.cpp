@@ -1,5 +1,6 @@
 // src/host/scene.cpp -- Scene: flattens the caller's object graph into the arrays of include/pt_hip.h and owns the device scene.
 #include <PathTrace/detail/world.h>
+#include <PathTrace/scene/mesh.h>
 
 #include "../../include/pt_hip.h"
 
@@ -8,11 +9,13 @@
 #include <cmath>
 #include <cstdlib>
 #include <map>
+#include <mutex>
 #include <random>
 #include <stdexcept>
 #include <string>
 #include <thread>
 #include <typeinfo>
+#include <unordered_map>
 
 namespace {
 
@@ -62,10 +65,64 @@ namespace {
         return index;
     }
 
+    // What a Scene with mesh instances keeps beyond its data members (whose layout is fixed, detail/world.h): the instances, their object
+    // ranges, and the Triangles handed out so far.
+    struct MeshState {
+        std::vector<MeshInstance> instances;
+        std::vector<uint32_t> first, count; // object range of every instance
+        std::mutex mutex;                   // guards `made`
+        std::unordered_map<uint32_t, std::unique_ptr<Object>> made; // object index -> Triangle
+
+        // The Triangle behind object `index`, made on first use from the arrays the device builder took
+        const Object *object(pt_scene *device_scene, uint32_t index) {
+            std::lock_guard<std::mutex> lock(mutex);
+            auto found = made.find(index);
+            if(found != made.end()) {
+                return found->second.get();
+            }
+            float pos[9], nrm[9];
+            uint8_t cull = 0;
+            if(pt_scene_get_triangles(device_scene, index, 1, pos, nrm, &cull, nullptr) != PT_OK) {
+                return nullptr;
+            }
+            auto triangle = std::make_unique<Triangle>(vec3<float>{pos[0], pos[1], pos[2]}, vec3<float>{pos[3], pos[4], pos[5]}, vec3<float>{pos[6], pos[7], pos[8]}, cull != 0);
+            triangle->normal_a = vec3<float>{nrm[0], nrm[1], nrm[2]};
+            triangle->normal_b = vec3<float>{nrm[3], nrm[4], nrm[5]};
+            triangle->normal_c = vec3<float>{nrm[6], nrm[7], nrm[8]};
+            const size_t instance = static_cast<size_t>(std::upper_bound(first.begin(), first.end(), index) - first.begin()) - 1;
+            if(instances[instance].handler != nullptr) {
+                triangle->setMaterialHandler(instances[instance].handler);
+            }
+            return made.emplace(index, std::move(triangle)).first->second.get();
+        }
+    };
+
+    // The states of the Scenes that have one, by the Scene's address (a Scene is neither copied nor moved).  Never destroyed: a Scene
+    // with static storage may outlive any static of this file.
+    struct MeshStates {
+        std::mutex mutex;
+        std::unordered_map<const Scene *, std::unique_ptr<MeshState>> of;
+    };
+    MeshStates &meshStates() {
+        static MeshStates *states = new MeshStates();
+        return *states;
+    }
+
 } // namespace
 
 Scene::Scene(std::vector<std::unique_ptr<Object>> &&objs, std::vector<std::unique_ptr<LightSource>> &&lights) :
+  Scene(std::move(objs), std::move(lights), std::vector<MeshInstance>{}) {}
+
+Scene::Scene(std::vector<std::unique_ptr<Object>> &&objs, std::vector<std::unique_ptr<LightSource>> &&lights, std::vector<MeshInstance> &&mesh_instances) :
   objects(std::move(objs)), light_sources(std::move(lights)) {
+    // (registered under this Scene's address at the end, when nothing can throw any more)
+    std::unique_ptr<MeshState> state;
+    if(!mesh_instances.empty()) {
+        state = std::make_unique<MeshState>();
+        state->instances = std::move(mesh_instances);
+    }
+    const std::vector<MeshInstance> no_instances;
+    const std::vector<MeshInstance> &instances = state != nullptr ? state->instances : no_instances;
     std::vector<uint8_t> kinds(objects.size());
     std::vector<float> tri_pos, tri_nrm, spheres, light_pos, light_spectrum;
     std::vector<uint8_t> tri_cull;
@@ -194,6 +251,42 @@ Scene::Scene(std::vector<std::unique_ptr<Object>> &&objs, std::vector<std::uniqu
     desc.light_pos = light_pos.data();
     desc.light_spectrum = light_spectrum.data();
 
+    // the mesh instances: every MeshData once, and per instance its matrix, flags and material
+    static_assert(sizeof(vec3<float>) == 3 * sizeof(float) && sizeof(std::array<int32_t, 3>) == 3 * sizeof(int32_t), "MeshData is handed over as flat arrays");
+    std::vector<pt_mesh_data> mesh_data;
+    std::vector<pt_mesh_instance> mesh_instances_flat(instances.size());
+    {
+        std::map<const io::MeshData *, uint32_t> mesh_of;
+        for(size_t i = 0; i < instances.size(); i++) {
+            const MeshInstance &instance = instances[i];
+            if(instance.mesh == nullptr) {
+                throw std::invalid_argument("PathTrace: a MeshInstance without a mesh");
+            }
+            auto found = mesh_of.find(instance.mesh.get());
+            if(found == mesh_of.end()) {
+                pt_mesh_data data{};
+                data.n_vertices = static_cast<uint32_t>(instance.mesh->vertices.size());
+                data.vertices = reinterpret_cast<const float *>(instance.mesh->vertices.data());
+                data.n_faces = static_cast<uint32_t>(instance.mesh->faces.size());
+                data.faces = reinterpret_cast<const int32_t *>(instance.mesh->faces.data());
+                found = mesh_of.emplace(instance.mesh.get(), static_cast<uint32_t>(mesh_data.size())).first;
+                mesh_data.push_back(data);
+            }
+            pt_mesh_instance &flat = mesh_instances_flat[i];
+            flat.mesh = found->second;
+            for(int r = 0; r < 4; r++) {
+                for(int c = 0; c < 4; c++) {
+                    flat.transform[4 * r + c] = instance.transformation.rows[r][c];
+                }
+            }
+            flat.smooth = instance.smooth ? 1 : 0;
+            flat.cull_backface = instance.cull_backface ? 1 : 0;
+            flat.material = instance.handler != nullptr ? materialIndex(instance.handler.get(), known, materials) : PT_NO_MATERIAL;
+        }
+        desc.n_materials = static_cast<uint32_t>(materials.size());
+        desc.materials = materials.data();
+    }
+
     const char *device_env = std::getenv("PATHTRACE_DEVICE");
     const int device = device_env != nullptr ? std::atoi(device_env) : 0;
     int n_replicas = 1;
@@ -209,7 +302,8 @@ Scene::Scene(std::vector<std::unique_ptr<Object>> &&objs, std::vector<std::uniqu
     }
     for(int r = 0; r < n_replicas; r++) {
         pt_scene *replica = nullptr;
-        if(pt_scene_create(share > 0 ? device : device + r, &desc, &replica) != PT_OK) {
+        if(pt_scene_create_meshes(share > 0 ? device : device + r, &desc, mesh_data.data(), static_cast<uint32_t>(mesh_data.size()), mesh_instances_flat.data(),
+                                  static_cast<uint32_t>(mesh_instances_flat.size()), &replica) != PT_OK) {
             const std::string message = pt_last_error();
             for(pt_scene *made : replicas) {
                 pt_scene_destroy(made);
@@ -220,6 +314,11 @@ Scene::Scene(std::vector<std::unique_ptr<Object>> &&objs, std::vector<std::uniqu
         replicas.push_back(replica);
     }
     device_scene = replicas[0];
+    if(state != nullptr) {
+        state->first.resize(instances.size());
+        state->count.resize(instances.size());
+        pt_scene_instance_ranges(device_scene, state->first.data(), state->count.data());
+    }
 
     // emissive objects and their cumulative selection probabilities, in the order the hierarchy registers them
     uint64_t n_emissive = 0;
@@ -228,11 +327,35 @@ Scene::Scene(std::vector<std::unique_ptr<Object>> &&objs, std::vector<std::uniqu
     emissive_cdf.resize(n_emissive);
     pt_scene_emissive(device_scene, indices.data(), emissive_cdf.data(), n_emissive, nullptr);
     for(int32_t i : indices) {
-        emissive.push_back(objects[static_cast<size_t>(i)].get());
+        emissive.push_back(static_cast<size_t>(i) < objects.size() ? objects[static_cast<size_t>(i)].get() : state->object(device_scene, static_cast<uint32_t>(i)));
+    }
+    if(state != nullptr) {
+        MeshStates &states = meshStates();
+        std::lock_guard<std::mutex> lock(states.mutex);
+        states.of[this] = std::move(state);
     }
 }
 
+// The Triangle behind object `index` of a mesh instance (MeshState::object)
+const Object *Scene::meshObject(uint32_t index) const {
+    MeshState *state = nullptr;
+    {
+        MeshStates &states = meshStates();
+        std::lock_guard<std::mutex> lock(states.mutex);
+        auto found = states.of.find(this);
+        if(found != states.of.end()) {
+            state = found->second.get();
+        }
+    }
+    return state != nullptr ? state->object(device_scene, index) : nullptr;
+}
+
 Scene::~Scene() {
+    {
+        MeshStates &states = meshStates();
+        std::lock_guard<std::mutex> lock(states.mutex);
+        states.of.erase(this);
+    }
     for(pt_scene *replica : replicas) {
         pt_scene_destroy(replica);
     }
@@ -244,6 +367,10 @@ std::tuple<float, const Object *> Scene::getIntersection(const Ray &ray) const n
     int32_t index = -1;
     if(pt_intersect_batch(device_scene, packed, 1, &t, &index) != PT_OK || index < 0) {
         return {t < 0.0F ? t : -1.0F, nullptr};
+    }
+    if(static_cast<size_t>(index) >= objects.size()) {
+        const Object *object = meshObject(static_cast<uint32_t>(index));
+        return {object != nullptr ? t : -1.0F, object};
     }
     return {t, objects[static_cast<size_t>(index)].get()};
 }
