@@ -57,6 +57,8 @@ FEATURES_EXPORTS = ["pt_feature_params_default", "pt_render_features_followed", 
                     "pt_render_features_followed_views_device", "pt_frame_set_feature_params"]
 # (... and these in include/pt_mesh.h)
 MESH_EXPORTS = ["pt_scene_create_meshes", "pt_mesh_assemble", "pt_scene_instance_ranges", "pt_scene_get_triangles"]
+# ... and these in include/pt_pose.h
+POSE_EXPORTS = ["pt_scene_pose", "pt_scene_get_pose", "pt_mesh_assemble_batch"]
 
 
 
@@ -380,6 +382,36 @@ def mesh_assemble(vertices, faces, transform=None, smooth=True, capacity=None, d
     return n.value, pos[:k], nrm[:k]
 
 
+class PoseInfo(C.Structure):  # pt_pose_info
+    _fields_ = [("n_instances", C.c_uint32), ("n_triangles", C.c_uint32), ("assembly_syncs", C.c_uint32), ("assembly_chunks", C.c_uint32),
+                ("upload_ms", C.c_float), ("assembly_ms", C.c_float), ("tree_ms", C.c_float), ("rest_ms", C.c_float), ("total_ms", C.c_float)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+def mesh_assemble_batch(meshes, instances, capacity=None, device=0, out_pos=None, out_nrm=None):
+    """pt_mesh_assemble_batch: every instance of `instances` expanded on the device by one chain of launches, the survivors of instance
+    0, 1, ... end to end.  meshes: [(vertices, faces), ...]; instances: [(mesh index, transform, smooth), ...].  Returns (total count,
+    per-instance counts, positions, normals), the arrays (min(total, capacity), 9); capacity defaults to the faces of all instances.
+    out_pos / out_nrm: arrays to write into (at least capacity rows); the returned arrays are views of them."""
+    mesh_keep = [_mesh_data(v, f) for v, f in meshes]
+    md = (MeshData * max(len(mesh_keep), 1))(*[m for m, _ in mesh_keep])
+    insts = (MeshInstance * max(len(instances), 1))(*[_mesh_instance(m, t, s) for m, t, s in instances])
+    if capacity is None:
+        capacity = sum(mesh_keep[m][0].n_faces for m, _, _ in instances)
+    capacity = int(capacity)
+    pos = np.zeros((capacity, 9), np.float32) if out_pos is None else out_pos
+    nrm = np.zeros((capacity, 9), np.float32) if out_nrm is None else out_nrm
+    counts = np.zeros(len(instances), np.uint32)
+    n = C.c_uint64()
+    _check(load().pt_mesh_assemble_batch(C.c_int(device), md, C.c_uint32(len(mesh_keep)), insts, C.c_uint32(len(instances)), C.c_uint64(capacity), _ptr(pos), _ptr(nrm),
+                                         _ptr(counts), C.byref(n)))
+    del mesh_keep
+    k = min(n.value, capacity)
+    return n.value, counts, pos[:k], nrm[:k]
+
+
 class CameraParams(C.Structure):
     _fields_ = [("origin", C.c_float * 3), ("look_at", C.c_float * 3), ("up", C.c_float * 3), ("focal_length", C.c_float),
                 ("height", C.c_float), ("aspect_ratio", C.c_float), ("aperture_width", C.c_float), ("aperture_height", C.c_float),
@@ -562,7 +594,7 @@ class Scene:
         d.n_spheres, d.sph, d.sph_material = len(keep["sph"]), _ptr(keep["sph"]), _ptr(keep["sph_material"])
         d.n_materials, d.materials = len(keep["materials"]), _ptr(keep["materials"])
         d.n_point_lights, d.light_pos, d.light_spectrum = len(keep["light_pos"]), _ptr(keep["light_pos"]), _ptr(keep["light_spectrum"])
-        self.n_objects = d.n_objects
+        self.n_objects = self._n_desc_objects = d.n_objects
         self._h = C.c_void_p()
         instances = scene.get("instances") or []
         self.n_instances = len(instances)
@@ -586,6 +618,25 @@ class Scene:
     def instance_ranges(self):
         """(first object, number of objects) of every mesh instance: its surviving triangles, in instance order."""
         return self._instance_ranges()
+
+    def pose(self, transforms, instances=None):
+        """pt_scene_pose: new matrices ((n, 4, 4) or (n, 16), rows) for the instances named by `instances` (all of them, in order, by
+        default).  The scene is then what a new Scene of the same description with these matrices would be, bit for bit; it keeps its
+        handle, stream and workspace.  Returns the pt_pose_info as a dict and updates n_objects."""
+        m = np.ascontiguousarray(transforms, dtype=np.float32).reshape(-1, 16)
+        idx = None if instances is None else np.ascontiguousarray(instances, dtype=np.uint32).reshape(-1)
+        if idx is not None and len(idx) != len(m):
+            raise ValueError("pose: %d instance indices for %d matrices" % (len(idx), len(m)))
+        info = PoseInfo()
+        _check(load().pt_scene_pose(self._h, _ptr(idx), C.c_uint32(len(m)), _ptr(m), C.byref(info)))
+        self.n_objects = self._n_desc_objects + int(info.n_triangles)
+        return info.as_dict()
+
+    def pose_transforms(self):
+        """pt_scene_get_pose: the current matrices of all instances, (n_instances, 4, 4)."""
+        out = np.zeros((self.n_instances, 4, 4), np.float32)
+        _check(load().pt_scene_get_pose(self._h, _ptr(out)))
+        return out
 
     def triangles(self, first, count):
         """pt_scene_get_triangles: the triangle objects first .. first + count - 1 of a scene with mesh instances, as the builder took

@@ -211,6 +211,9 @@ int pth::create_scene(int device, const pt_scene_desc *d, const DeviceTriangles 
     PT_HIP(hipGetDeviceProperties(&prop, device));
     s->cu_count = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     PT_HIP(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
+    if(assembled != nullptr && assembled->ready != nullptr) {
+        PT_HIP(hipStreamWaitEvent(s->stream, assembled->ready, 0)); // (a pose: the arrays are being finished on the posed scene's stream)
+    }
     s->n_objects = n_objs;
     s->n_desc_objects = d->n_objects;
     s->n_desc_tris = d->n_triangles;
@@ -298,7 +301,16 @@ int pth::create_scene(int device, const pt_scene_desc *d, const DeviceTriangles 
         PT_HIP(up(raw_sph, d->sph, 4 * static_cast<size_t>(d->n_spheres)));
         PT_HIP(up(raw_sph_mat, d->sph_material, d->n_spheres));
         PT_HIP(up(raw_sph_obj, s->sph_obj.data(), d->n_spheres));
-        if(assembled != nullptr) {
+        if(assembled != nullptr && assembled->batch_scratch != nullptr) {
+            // one launch for all ranges (pt_mesh_batch.h): the same three arrays
+            std::vector<PtBatchRange> table;
+            for(const MeshRange &r : assembled->ranges) {
+                table.push_back(PtBatchRange{r.first_tri, r.count, r.material, r.cull});
+            }
+            PT_HIP(pt_mesh_batch_fill_ranges(s->stream, *assembled->batch_scratch, table.data(), static_cast<uint32_t>(table.size()), d->n_triangles, n_tris - d->n_triangles,
+                                             d->n_objects, raw_cull.ptr, raw_tri_mat.ptr, raw_tri_obj.ptr));
+        }
+        else if(assembled != nullptr) {
             for(const MeshRange &r : assembled->ranges) {
                 PT_HIP(pt_mesh_fill_range(s->stream, r.first_tri, r.count, r.cull, r.material, d->n_objects + (r.first_tri - d->n_triangles), raw_cull.ptr, raw_tri_mat.ptr,
                                           raw_tri_obj.ptr));

@@ -298,6 +298,7 @@ static int frame_create_impl(pt_scene *const *scenes, int n_scenes, const pt_cam
     }
     for(auto &r : f->reps) {
         r->n_todo = r->n_streams;
+        r->s->live_frames.fetch_add(1); // (pt_scene_pose refuses a scene that has a frame; pt_frame_destroy counts down)
     }
     *out = f.release();
     return PT_OK;
@@ -562,6 +563,7 @@ int pt_frame_destroy(pt_frame *f) {
                 (void)hipSetDevice(r->s->device);
                 (void)hipStreamSynchronize(r->s->stream);
             }
+            r->s->live_frames.fetch_sub(1);
             r.reset();
         }
     }

@@ -1,4 +1,5 @@
 // pt_host.h -- what the host units of libpathtrace_hip.so share: pt_api.cpp (scenes), pt_meshes.cpp (scenes from meshes and instances),
+// pt_pose.cpp (their instances under new matrices, in place),
 // pt_render.cpp (render calls), pt_frames.cpp and pt_frame_maps.cpp (resumable frames and their maps; pt_frames.h) and pt_image.cpp
 // (post-processing, features, denoising).  Internal:
 // not installed, not part of the C ABI.  Everything but the ABI's own handle types lives in namespace pth, so that no helper can collide
@@ -26,6 +27,7 @@
 
 #include "pt_build.h"
 #include "pt_mesh.h"
+#include "pt_mesh_batch.h"
 #include "pt_bvh.h"
 #include "pt_kernels.h"
 #include "pt_denoise.h"
@@ -175,6 +177,46 @@ struct EventPair {
     hipError_t ms(float *out) { return hipEventElapsedTime(out, first.e, last.e); }
 };
 
+// ---- what a scene with mesh instances keeps for pt_scene_pose (pt_pose.cpp; include/pt_pose.h has the memory cost) --------------------------
+
+// One mesh in device memory
+struct KeptMesh {
+    DevBuf<float> vertices;
+    DevBuf<int32_t> faces;
+    uint32_t n_vertices = 0, n_faces = 0;
+    int upload(const pt_mesh_data &m);
+    PtMeshDevice view() const {
+        PtMeshDevice v;
+        v.n_vertices = n_vertices;
+        v.vertices = vertices.ptr;
+        v.n_faces = n_faces;
+        v.faces = faces.ptr;
+        return v;
+    }
+};
+
+// A deep copy of a scene description: create_scene reads the description's host arrays (emitters, materials, the host builder's boxes)
+struct DescCopy {
+    pt_scene_desc d{};
+    std::vector<uint8_t> obj_kind, tri_cull;
+    std::vector<float> tri_pos, tri_nrm, sph, light_pos, light_spectrum;
+    std::vector<uint32_t> tri_material, sph_material;
+    std::vector<pt_material> materials;
+    void assign(const pt_scene_desc &src);
+};
+
+struct PoseKeep {
+    std::vector<std::unique_ptr<KeptMesh>> meshes; // by mesh index of the creating call; null for a mesh no instance uses
+    std::vector<pt_mesh_instance> instances;
+    DescCopy desc;
+    bool any_smooth = false;
+    uint64_t capacity = 0;               // the description's triangles + the faces of all instances, before any is rejected
+    PtBatchScratch scratch;              // the batched assembler's, grown by the first pose
+    DevBuf<float> spare_pos, spare_nrm;  // the arrays the next pose assembles into (the scene keeps the positions it was built from)
+    std::vector<PtBatchInstance> table;  // host side of the instance table, and of the counts that come back
+    std::vector<uint32_t> counts;
+};
+
 } // namespace pth
 
 struct pt_scene {
@@ -197,6 +239,8 @@ struct pt_scene {
     // (PT_REF_SPHERE | index), and the triangles' positions as the builder took them (pt_scene_get_triangles)
     std::vector<uint32_t> inst_first, inst_count, desc_ref;
     pth::DevBuf<float> tri_pos_kept;
+    std::unique_ptr<pth::PoseKeep> pose;      // ... and their meshes, instance table and description, for pt_scene_pose
+    std::atomic<uint32_t> live_frames{0};     // pt_frame handles (replicas counted) on this scene: pt_scene_pose refuses while there is one
     uint32_t n_emissive = 0;
     std::vector<int32_t> emissive_obj;
     std::vector<float> emissive_cdf;
@@ -292,12 +336,25 @@ struct DeviceTriangles {
     const float *nrm = nullptr; // [n_triangles][9] or null: face normals
     uint32_t n_triangles = 0;   // the description's and the ranges'
     std::vector<MeshRange> ranges;
+    // a pose (pt_pose.cpp): the arrays are complete once this event of another stream is, and the ranges' constants are filled in one
+    // launch with this scratch instead of one launch per range
+    hipEvent_t ready = nullptr;
+    PtBatchScratch *batch_scratch = nullptr;
 };
 // Whether a scene of n_objects is built on the device (PT_BUILD_DEVICE_MIN, PT_BUILD)
 bool builds_on_device(uint32_t n_objects);
 // pt_scene_create; with `assembled` (device builder only) the triangles are taken from device memory: d's own per-triangle arrays tri_pos
 // and tri_nrm are not read, and nothing per triangle of the ranges crosses to the host but the positions of the emissive ones.
 int create_scene(int device, const pt_scene_desc *d, const DeviceTriangles *assembled, pt_scene **out);
+
+// ---- pt_meshes.cpp ---------------------------------------------------------------------------------------------------------------------
+
+int check_mesh(const pt_mesh_data *m);
+// From the assembled arrays to the finished scene, with either builder: `assembled` names the triangles in `pos` / `nrm` (device memory:
+// the description's first, then the instances' ranges).  The scene takes `pos` over (pt_scene_get_triangles); on failure it stays
+// with the caller.  Used by pt_scene_create_meshes and pt_scene_pose.
+int finish_mesh_scene(int device, const pt_scene_desc *d, DeviceTriangles &assembled, DevBuf<float> &pos, DevBuf<float> &nrm, bool with_normals,
+                      const std::vector<uint32_t> &inst_first, const std::vector<uint32_t> &inst_count, pt_scene **out);
 
 // ---- pt_render.cpp: the persistent path kernel (pt_path.hip), one launch per render call ----------------------------------------------
 

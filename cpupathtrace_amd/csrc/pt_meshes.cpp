@@ -16,6 +16,10 @@ struct StreamGuard {
     }
 };
 
+} // namespace
+
+namespace pth {
+
 int check_mesh(const pt_mesh_data *m) {
     if((m->n_vertices > 0 && m->vertices == nullptr) || (m->n_faces > 0 && m->faces == nullptr)) {
         return fail(PT_ERR_INVALID, "missing array in mesh");
@@ -26,34 +30,106 @@ int check_mesh(const pt_mesh_data *m) {
     return PT_OK;
 }
 
-// One mesh in device memory
-struct UploadedMesh {
-    DevBuf<float> vertices;
-    DevBuf<int32_t> faces;
-    bool present = false;
-    int upload(const pt_mesh_data &m) {
-        PT_HIP(vertices.ensure(3 * static_cast<size_t>(m.n_vertices)));
-        PT_HIP(faces.ensure(3 * static_cast<size_t>(m.n_faces)));
-        if(m.n_vertices > 0) {
-            PT_HIP(hipMemcpy(vertices.ptr, m.vertices, 3 * static_cast<size_t>(m.n_vertices) * sizeof(float), hipMemcpyHostToDevice));
-        }
-        if(m.n_faces > 0) {
-            PT_HIP(hipMemcpy(faces.ptr, m.faces, 3 * static_cast<size_t>(m.n_faces) * sizeof(int32_t), hipMemcpyHostToDevice));
-        }
-        present = true;
-        return PT_OK;
+int KeptMesh::upload(const pt_mesh_data &m) {
+    PT_HIP(vertices.ensure(3 * static_cast<size_t>(m.n_vertices)));
+    PT_HIP(faces.ensure(3 * static_cast<size_t>(m.n_faces)));
+    if(m.n_vertices > 0) {
+        PT_HIP(hipMemcpy(vertices.ptr, m.vertices, 3 * static_cast<size_t>(m.n_vertices) * sizeof(float), hipMemcpyHostToDevice));
     }
-    PtMeshDevice view(const pt_mesh_data &m) const {
-        PtMeshDevice v;
-        v.n_vertices = m.n_vertices;
-        v.vertices = vertices.ptr;
-        v.n_faces = m.n_faces;
-        v.faces = faces.ptr;
-        return v;
+    if(m.n_faces > 0) {
+        PT_HIP(hipMemcpy(faces.ptr, m.faces, 3 * static_cast<size_t>(m.n_faces) * sizeof(int32_t), hipMemcpyHostToDevice));
     }
-};
+    n_vertices = m.n_vertices;
+    n_faces = m.n_faces;
+    return PT_OK;
+}
 
-} // namespace
+void DescCopy::assign(const pt_scene_desc &src) {
+    auto take = [](auto &to, const auto *from, size_t count) {
+        to.clear();
+        if(from != nullptr && count > 0) {
+            to.assign(from, from + count);
+        }
+        return to.empty() ? nullptr : to.data();
+    };
+    d = src;
+    d.obj_kind = take(obj_kind, src.obj_kind, src.n_objects);
+    d.tri_pos = take(tri_pos, src.tri_pos, 9 * static_cast<size_t>(src.n_triangles));
+    d.tri_nrm = take(tri_nrm, src.tri_nrm, 9 * static_cast<size_t>(src.n_triangles));
+    d.tri_cull = take(tri_cull, src.tri_cull, src.n_triangles);
+    d.tri_material = take(tri_material, src.tri_material, src.n_triangles);
+    d.sph = take(sph, src.sph, 4 * static_cast<size_t>(src.n_spheres));
+    d.sph_material = take(sph_material, src.sph_material, src.n_spheres);
+    d.materials = take(materials, src.materials, src.n_materials);
+    d.light_pos = take(light_pos, src.light_pos, 3 * static_cast<size_t>(src.n_point_lights));
+    d.light_spectrum = take(light_spectrum, src.light_spectrum, 4 * static_cast<size_t>(src.n_point_lights));
+}
+
+int finish_mesh_scene(int device, const pt_scene_desc *d, DeviceTriangles &assembled, DevBuf<float> &pos, DevBuf<float> &nrm, bool with_normals,
+                      const std::vector<uint32_t> &inst_first, const std::vector<uint32_t> &inst_count, pt_scene **out) {
+    *out = nullptr;
+    assembled.pos = pos.ptr;
+    assembled.nrm = with_normals ? nrm.ptr : nullptr;
+    const uint32_t n_mesh_tris = assembled.n_triangles - d->n_triangles, n_objs = d->n_objects + n_mesh_tris;
+
+    pt_scene *scene = nullptr;
+    if(builds_on_device(n_objs)) {
+        PT_TRY(create_scene(device, d, &assembled, &scene));
+    }
+    else {
+        // ---- the host builder: the assembled arrays come back and the scene is pt_scene_create's of the merged description --------------
+        if(assembled.ready != nullptr) {
+            PT_HIP(hipEventSynchronize(assembled.ready));
+        }
+        const size_t n_tris = assembled.n_triangles;
+        std::vector<float> h_pos(9 * n_tris), h_nrm(with_normals ? 9 * n_tris : 0);
+        std::vector<uint8_t> kind(n_objs, static_cast<uint8_t>(PT_OBJ_TRIANGLE)), cull(n_tris);
+        std::vector<uint32_t> material(n_tris);
+        if(n_tris > 0) {
+            PT_HIP(hipMemcpy(h_pos.data(), pos.ptr, h_pos.size() * sizeof(float), hipMemcpyDeviceToHost));
+            if(with_normals) {
+                PT_HIP(hipMemcpy(h_nrm.data(), nrm.ptr, h_nrm.size() * sizeof(float), hipMemcpyDeviceToHost));
+            }
+        }
+        std::copy(d->obj_kind, d->obj_kind + d->n_objects, kind.begin());
+        std::copy(d->tri_cull, d->tri_cull + d->n_triangles, cull.begin());
+        std::copy(d->tri_material, d->tri_material + d->n_triangles, material.begin());
+        for(const MeshRange &r : assembled.ranges) {
+            std::fill(cull.begin() + r.first_tri, cull.begin() + r.first_tri + r.count, r.cull);
+            std::fill(material.begin() + r.first_tri, material.begin() + r.first_tri + r.count, r.material);
+        }
+        pt_scene_desc merged = *d;
+        merged.n_objects = n_objs;
+        merged.obj_kind = kind.data();
+        merged.n_triangles = static_cast<uint32_t>(n_tris);
+        merged.tri_pos = h_pos.data();
+        merged.tri_nrm = with_normals ? h_nrm.data() : nullptr;
+        merged.tri_cull = cull.data();
+        merged.tri_material = material.data();
+        PT_TRY(create_scene(device, &merged, nullptr, &scene));
+    }
+    // ---- what pt_scene_instance_ranges and pt_scene_get_triangles answer from ----------------------------------------------------------------
+    scene->n_desc_objects = d->n_objects;
+    scene->n_desc_tris = d->n_triangles;
+    scene->inst_first = inst_first;
+    scene->inst_count = inst_count;
+    scene->desc_ref.resize(d->n_objects);
+    {
+        uint32_t ti = 0, si = 0;
+        for(uint32_t i = 0; i < d->n_objects; i++) {
+            scene->desc_ref[i] = d->obj_kind[i] == PT_OBJ_TRIANGLE ? ti++ : (PT_REF_SPHERE | si++);
+        }
+    }
+    scene->tri_pos_kept.release();
+    scene->tri_pos_kept.ptr = pos.ptr;
+    scene->tri_pos_kept.count = pos.count;
+    pos.ptr = nullptr;
+    pos.count = 0;
+    *out = scene;
+    return PT_OK;
+}
+
+} // namespace pth
 
 extern "C" {
 
@@ -67,14 +143,14 @@ int pt_mesh_assemble(int device, const pt_mesh_data *mesh, const pt_mesh_instanc
     PT_HIP(hipSetDevice(device));
     StreamGuard sg;
     PT_HIP(hipStreamCreateWithFlags(&sg.stream, hipStreamNonBlocking));
-    UploadedMesh up;
+    KeptMesh up;
     PT_TRY(up.upload(*mesh));
     DevBuf<float> pos, nrm;
     PT_HIP(pos.ensure(9 * static_cast<size_t>(mesh->n_faces)));
     PT_HIP(nrm.ensure(9 * static_cast<size_t>(mesh->n_faces)));
     uint32_t kept = 0;
     const char *what = "";
-    const hipError_t e = pt_mesh_assemble_device(sg.stream, up.view(*mesh), instance->transform, instance->smooth != 0, pos.ptr, nrm.ptr, &kept, nullptr, &what);
+    const hipError_t e = pt_mesh_assemble_device(sg.stream, up.view(), instance->transform, instance->smooth != 0, pos.ptr, nrm.ptr, &kept, nullptr, &what);
     if(e != hipSuccess) {
         return fail(PT_ERR_HIP, std::string("mesh assembly (") + what + "): " + hipGetErrorString(e));
     }
@@ -132,11 +208,14 @@ int pt_scene_create_meshes(int device, const pt_scene_desc *d, const pt_mesh_dat
     StreamGuard sg;
     PT_HIP(hipStreamCreateWithFlags(&sg.stream, hipStreamNonBlocking));
     // ---- upload: every mesh that is used, once; the description's own triangles in front of the arrays the instances are expanded into ----
-    std::vector<UploadedMesh> uploaded(n_meshes);
+    // (the scene keeps them, with the instance table and a copy of the description, for pt_scene_pose)
+    std::unique_ptr<PoseKeep> keep(new PoseKeep());
+    keep->meshes.resize(n_meshes);
     uint64_t upload_bytes = 0;
     for(uint32_t m = 0; m < n_meshes; m++) {
         if(used[m] != 0) {
-            PT_TRY(uploaded[m].upload(meshes[m]));
+            keep->meshes[m].reset(new KeptMesh());
+            PT_TRY(keep->meshes[m]->upload(meshes[m]));
             upload_bytes += 12ULL * meshes[m].n_vertices + 12ULL * meshes[m].n_faces;
         }
     }
@@ -169,7 +248,7 @@ int pt_scene_create_meshes(int device, const pt_scene_desc *d, const pt_mesh_dat
         uint32_t kept = 0;
         float ms = 0.0F;
         const char *what = "";
-        const hipError_t e = pt_mesh_assemble_device(sg.stream, uploaded[in.mesh].view(meshes[in.mesh]), in.transform, in.smooth != 0, pos.ptr + at,
+        const hipError_t e = pt_mesh_assemble_device(sg.stream, keep->meshes[in.mesh]->view(), in.transform, in.smooth != 0, pos.ptr + at,
                                                      with_normals ? nrm.ptr + at : nullptr, &kept, &ms, &what);
         if(e != hipSuccess) {
             return fail(PT_ERR_HIP, std::string("mesh assembly (") + what + "): " + hipGetErrorString(e));
@@ -181,60 +260,13 @@ int pt_scene_create_meshes(int device, const pt_scene_desc *d, const pt_mesh_dat
         assembled.n_triangles += kept;
     }
     PT_HIP(hipStreamSynchronize(sg.stream));
-    uploaded.clear();
-    assembled.pos = pos.ptr;
-    assembled.nrm = with_normals ? nrm.ptr : nullptr;
-    const uint32_t n_mesh_tris = assembled.n_triangles - d->n_triangles, n_objs = d->n_objects + n_mesh_tris;
-
     pt_scene *scene = nullptr;
-    if(builds_on_device(n_objs)) {
-        PT_TRY(create_scene(device, d, &assembled, &scene));
-    }
-    else {
-        // ---- the host builder: the assembled arrays come back and the scene is pt_scene_create's of the merged description --------------
-        const size_t n_tris = assembled.n_triangles;
-        std::vector<float> h_pos(9 * n_tris), h_nrm(with_normals ? 9 * n_tris : 0);
-        std::vector<uint8_t> kind(n_objs, static_cast<uint8_t>(PT_OBJ_TRIANGLE)), cull(n_tris);
-        std::vector<uint32_t> material(n_tris);
-        if(n_tris > 0) {
-            PT_HIP(hipMemcpy(h_pos.data(), pos.ptr, h_pos.size() * sizeof(float), hipMemcpyDeviceToHost));
-            if(with_normals) {
-                PT_HIP(hipMemcpy(h_nrm.data(), nrm.ptr, h_nrm.size() * sizeof(float), hipMemcpyDeviceToHost));
-            }
-        }
-        std::copy(d->obj_kind, d->obj_kind + d->n_objects, kind.begin());
-        std::copy(d->tri_cull, d->tri_cull + d->n_triangles, cull.begin());
-        std::copy(d->tri_material, d->tri_material + d->n_triangles, material.begin());
-        for(const MeshRange &r : assembled.ranges) {
-            std::fill(cull.begin() + r.first_tri, cull.begin() + r.first_tri + r.count, r.cull);
-            std::fill(material.begin() + r.first_tri, material.begin() + r.first_tri + r.count, r.material);
-        }
-        pt_scene_desc merged = *d;
-        merged.n_objects = n_objs;
-        merged.obj_kind = kind.data();
-        merged.n_triangles = static_cast<uint32_t>(n_tris);
-        merged.tri_pos = h_pos.data();
-        merged.tri_nrm = with_normals ? h_nrm.data() : nullptr;
-        merged.tri_cull = cull.data();
-        merged.tri_material = material.data();
-        PT_TRY(create_scene(device, &merged, nullptr, &scene));
-    }
-    // ---- what pt_scene_instance_ranges and pt_scene_get_triangles answer from ----------------------------------------------------------------
-    scene->n_desc_objects = d->n_objects;
-    scene->n_desc_tris = d->n_triangles;
-    scene->inst_first = inst_first;
-    scene->inst_count = inst_count;
-    scene->desc_ref.resize(d->n_objects);
-    {
-        uint32_t ti = 0, si = 0;
-        for(uint32_t i = 0; i < d->n_objects; i++) {
-            scene->desc_ref[i] = d->obj_kind[i] == PT_OBJ_TRIANGLE ? ti++ : (PT_REF_SPHERE | si++);
-        }
-    }
-    scene->tri_pos_kept.ptr = pos.ptr;
-    scene->tri_pos_kept.count = pos.count;
-    pos.ptr = nullptr;
-    pos.count = 0;
+    PT_TRY(finish_mesh_scene(device, d, assembled, pos, nrm, with_normals, inst_first, inst_count, &scene));
+    keep->instances.assign(instances, instances + n_instances);
+    keep->desc.assign(*d);
+    keep->any_smooth = any_smooth;
+    keep->capacity = capacity;
+    scene->pose = std::move(keep);
     if(env_int("PT_DEBUG", 0) != 0) {
         std::fprintf(stderr, "[pt] mesh scene: %u instances, %u of %llu triangles kept; mesh upload %.1f ms (%llu bytes), assembly %.1f ms on the device\n", n_instances,
                      assembled.n_triangles, static_cast<unsigned long long>(capacity), upload_ms, static_cast<unsigned long long>(upload_bytes), assembly_ms);

@@ -290,6 +290,17 @@ class Scene {
     // light samples for a surface point: every LightSource, then min(2 + log10(E + 1), E) points on emissive objects
     std::vector<std::tuple<vec3<float>, Spectrum, float>> sampleLights(vec3<float> pos, vec3<float> n, RandomEngine &re) const noexcept;
 
+    // New matrices for the mesh instances, in place (pt_scene_pose, include/pt_pose.h): all of them in order, or those named by
+    // `instances` (a repeated index gets the last of its matrices).  Afterwards the Scene renders, intersects and samples lights exactly
+    // as a Scene constructed with these matrices would; every replica is posed.  Object pointers returned earlier for MESH triangles
+    // (getIntersection, the emitters behind sampleLights) are INVALID after a pose: the Triangles are made anew on first use.  Pointers to
+    // the objects handed to the constructor stay valid.  Not to be called while another thread renders, intersects or samples this Scene.
+    // Throws what the constructor throws: std::invalid_argument for a wrong count or index or a Scene without mesh instances,
+    // std::runtime_error when the device refuses (a live FrameRender on the scene, no memory); a refused pose leaves the Scene as it was
+    // unless a later replica of several failed.  Non-virtual: the class's layout is what it was.
+    void pose(const std::vector<mat4<float>> &transformations);
+    void pose(const std::vector<uint32_t> &instances, const std::vector<mat4<float>> &transformations);
+
     // the device scene behind the C ABI (include/pt_hip.h); used by processJob / processItem
     pt_scene *deviceScene() const noexcept { return device_scene; }
     const std::vector<pt_scene *> &deviceScenes() const noexcept { return replicas; }
@@ -305,6 +316,7 @@ class Scene {
     // header keeps working with the library.  What a Scene with mesh instances keeps beyond them -- the instances, their object ranges and
     // the Triangles handed out so far, guarded by a mutex -- lives in the library, looked up by the Scene's address (src/host/scene.cpp).
     const Object *meshObject(uint32_t index) const;
+    void registerEmitters(); // emissive / emissive_cdf from the device scene, as the constructors and pose() fill them
 };
 
 #endif

@@ -423,6 +423,9 @@ int pt_frame_preview(pt_frame *frame, const float *image, const pt_denoise_param
 /* Scenes from indexed meshes instantiated under transforms, assembled on the device (pt_scene_create_meshes, pt_mesh_assemble,
  * pt_scene_instance_ranges, pt_scene_get_triangles): the structs and entry points are declared, with their contracts, in: */
 #include "pt_mesh.h"
+/* Re-posing the instances of such a scene in place, and the batched assembler behind it (pt_scene_pose, pt_scene_get_pose,
+ * pt_mesh_assemble_batch): the struct and entry points are declared, with their contracts, in: */
+#include "pt_pose.h"
 
 /* Temporal denoising of a sequence of frames of one static scene (a camera path, a turntable): the temporal half of SVGF (Schied et al. 2017)
  * in front of pt_denoise's spatial filter.  A pt_temporal handle keeps the history of the frames pushed so far, on its own

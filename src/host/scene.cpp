@@ -320,20 +320,90 @@ Scene::Scene(std::vector<std::unique_ptr<Object>> &&objs, std::vector<std::uniqu
         pt_scene_instance_ranges(device_scene, state->first.data(), state->count.data());
     }
 
-    // emissive objects and their cumulative selection probabilities, in the order the hierarchy registers them
-    uint64_t n_emissive = 0;
-    pt_scene_emissive(device_scene, nullptr, nullptr, 0, &n_emissive);
-    std::vector<int32_t> indices(n_emissive);
-    emissive_cdf.resize(n_emissive);
-    pt_scene_emissive(device_scene, indices.data(), emissive_cdf.data(), n_emissive, nullptr);
-    for(int32_t i : indices) {
-        emissive.push_back(static_cast<size_t>(i) < objects.size() ? objects[static_cast<size_t>(i)].get() : state->object(device_scene, static_cast<uint32_t>(i)));
-    }
+    // (the emitters among the mesh triangles are materialised through the state, which is registered first; nothing below throws)
     if(state != nullptr) {
         MeshStates &states = meshStates();
         std::lock_guard<std::mutex> lock(states.mutex);
         states.of[this] = std::move(state);
     }
+    registerEmitters();
+}
+
+// emissive objects and their cumulative selection probabilities, in the order the hierarchy registers them
+void Scene::registerEmitters() {
+    uint64_t n_emissive = 0;
+    pt_scene_emissive(device_scene, nullptr, nullptr, 0, &n_emissive);
+    std::vector<int32_t> indices(n_emissive);
+    emissive.clear();
+    emissive_cdf.assign(n_emissive, 0.0F);
+    pt_scene_emissive(device_scene, indices.data(), emissive_cdf.data(), n_emissive, nullptr);
+    for(int32_t i : indices) {
+        emissive.push_back(static_cast<size_t>(i) < objects.size() ? objects[static_cast<size_t>(i)].get() : meshObject(static_cast<uint32_t>(i)));
+    }
+}
+
+void Scene::pose(const std::vector<mat4<float>> &transformations) {
+    std::vector<uint32_t> all(transformations.size());
+    for(size_t i = 0; i < all.size(); i++) {
+        all[i] = static_cast<uint32_t>(i);
+    }
+    MeshState *state = nullptr;
+    {
+        MeshStates &states = meshStates();
+        std::lock_guard<std::mutex> lock(states.mutex);
+        auto found = states.of.find(this);
+        state = found != states.of.end() ? found->second.get() : nullptr;
+    }
+    if(state != nullptr && transformations.size() != state->instances.size()) {
+        throw std::invalid_argument("PathTrace: Scene::pose needs one transformation per mesh instance");
+    }
+    pose(all, transformations);
+}
+
+void Scene::pose(const std::vector<uint32_t> &instances, const std::vector<mat4<float>> &transformations) {
+    MeshState *state = nullptr;
+    {
+        MeshStates &states = meshStates();
+        std::lock_guard<std::mutex> lock(states.mutex);
+        auto found = states.of.find(this);
+        state = found != states.of.end() ? found->second.get() : nullptr;
+    }
+    if(state == nullptr) {
+        throw std::invalid_argument("PathTrace: Scene::pose on a Scene without mesh instances");
+    }
+    if(instances.size() != transformations.size()) {
+        throw std::invalid_argument("PathTrace: Scene::pose needs one transformation per named instance");
+    }
+    for(uint32_t i : instances) {
+        if(i >= state->instances.size()) {
+            throw std::invalid_argument("PathTrace: Scene::pose names an instance that is not there");
+        }
+    }
+    if(instances.empty()) {
+        return;
+    }
+    std::vector<float> flat(16 * transformations.size());
+    for(size_t k = 0; k < transformations.size(); k++) {
+        for(int r = 0; r < 4; r++) {
+            for(int c = 0; c < 4; c++) {
+                flat[16 * k + 4 * static_cast<size_t>(r) + static_cast<size_t>(c)] = transformations[k].rows[r][c];
+            }
+        }
+    }
+    for(size_t r = 0; r < replicas.size(); r++) {
+        if(pt_scene_pose(replicas[r], instances.data(), static_cast<uint32_t>(instances.size()), flat.data(), nullptr) != PT_OK) {
+            throw std::runtime_error("PathTrace: cannot pose the device scene (replica " + std::to_string(r) + "): " + pt_last_error());
+        }
+    }
+    {
+        std::lock_guard<std::mutex> lock(state->mutex);
+        for(size_t k = 0; k < instances.size(); k++) {
+            state->instances[instances[k]].transformation = transformations[k];
+        }
+        pt_scene_instance_ranges(device_scene, state->first.data(), state->count.data());
+        state->made.clear(); // (the Triangles handed out so far: their objects are other triangles now, or none)
+    }
+    registerEmitters();
 }
 
 // The Triangle behind object `index` of a mesh instance (MeshState::object)
