@@ -59,6 +59,9 @@ FEATURES_EXPORTS = ["pt_feature_params_default", "pt_render_features_followed", 
 MESH_EXPORTS = ["pt_scene_create_meshes", "pt_mesh_assemble", "pt_scene_instance_ranges", "pt_scene_get_triangles"]
 # ... and these in include/pt_pose.h
 POSE_EXPORTS = ["pt_scene_pose", "pt_scene_get_pose", "pt_mesh_assemble_batch"]
+# ... and these in include/pt_motion.h
+MOTION_EXPORTS = ["pt_motion_table", "pt_render_features_motion", "pt_render_features_motion_device", "pt_temporal_denoise_motion", "pt_temporal_denoise_motion_device"]
+MOTION_STATIC, MOTION_MOVED, MOTION_NONE = 0, 1, 2
 
 
 
@@ -280,8 +283,9 @@ def _temporal_params(params):
 
 
 class TemporalDenoiser:
-    """A pt_temporal handle: denoises the frames of one sequence (one static scene, one image size) one push at a time, each with the
-    reprojected history of the ones before.  params: None = defaults, or a dict of TemporalParams fields."""
+    """A pt_temporal handle: denoises the frames of one sequence (one scene, one image size) one push at a time, each with the
+    reprojected history of the ones before; a scene posed between the frames is followed through the `motion` of
+    Scene.render_features_motion.  params: None = defaults, or a dict of TemporalParams fields."""
 
     def __init__(self, width, height, params=None, device=0):
         self.width, self.height, self.device = int(width), int(height), device
@@ -291,9 +295,11 @@ class TemporalDenoiser:
                                          C.byref(h)))
         self._h = h
 
-    def denoise(self, image, features, camera):
+    def denoise(self, image, features, camera, motion=None):
         """One push: the (h, w, 4) frame, its (h, w, 3, 4) features and its camera (dict).  Returns (out, history): the denoised frame and
-        the (h, w) int32 history length of every pixel (0 where no ray hit, 1 where the pixel has no history)."""
+        the (h, w) int32 history length of every pixel (0 where no ray hit, 1 where the pixel has no history).  motion: the frame's
+        (h, w, 2, 4) motion (Scene.render_features_motion) reprojects where every pixel's surface was at the previous pose
+        (pt_temporal_denoise_motion); None = the scene did not move."""
         img = np.ascontiguousarray(image, dtype=np.float32)
         feat = np.ascontiguousarray(features, dtype=np.float32)
         if img.shape != (self.height, self.width, 4) or feat.shape != (self.height, self.width, 3, 4):
@@ -301,13 +307,24 @@ class TemporalDenoiser:
         out = np.empty_like(img)
         hist = np.empty((self.height, self.width), np.int32)
         cp = _camera(camera)
+        if motion is not None:
+            mot = np.ascontiguousarray(motion, dtype=np.float32)
+            if mot.shape != (self.height, self.width, 2, 4):
+                raise ValueError("motion must be (%d, %d, 2, 4)" % (self.height, self.width))
+            _check(load().pt_temporal_denoise_motion(self._h, _ptr(img), _ptr(feat), _ptr(mot), C.byref(cp), _ptr(out), _ptr(hist)))
+            return out, hist
         _check(load().pt_temporal_denoise(self._h, _ptr(img), _ptr(feat), C.byref(cp), _ptr(out), _ptr(hist)))
         return out, hist
 
-    def denoise_device(self, d_rgba_ptr, d_features_ptr, camera, d_out_ptr, d_history_ptr=0, stream_ptr=0):
+    def denoise_device(self, d_rgba_ptr, d_features_ptr, camera, d_out_ptr, d_history_ptr=0, stream_ptr=0, motion=None):
         """One push on device memory (e.g. torch tensors' data_ptr()): rgba and out h*w*4 floats (out may equal rgba), features h*w*12 floats,
-        history h*w int32 (0 = not written); ordered on stream_ptr (0 = the default stream), which is synchronised before the call returns."""
+        history h*w int32 (0 = not written); ordered on stream_ptr (0 = the default stream), which is synchronised before the call returns.
+        motion: the device address of the frame's h*w*8 floats of motion (None = the scene did not move)."""
         cp = _camera(camera)
+        if motion is not None:
+            _check(load().pt_temporal_denoise_motion_device(self._h, C.c_void_p(d_rgba_ptr), C.c_void_p(d_features_ptr), C.c_void_p(motion), C.byref(cp),
+                                                            C.c_void_p(d_out_ptr), C.c_void_p(d_history_ptr or None), C.c_void_p(stream_ptr)))
+            return
         _check(load().pt_temporal_denoise_device(self._h, C.c_void_p(d_rgba_ptr), C.c_void_p(d_features_ptr), C.byref(cp), C.c_void_p(d_out_ptr),
                                                  C.c_void_p(d_history_ptr or None), C.c_void_p(stream_ptr)))
 
@@ -331,6 +348,20 @@ class TemporalDenoiser:
 
     def __exit__(self, *exc):
         self.close()
+
+
+def motion_table(current, previous):
+    """pt_motion_table: for n instances with the matrices current and previous ((n, 4, 4) or (n, 16), rows) the way from the current pose
+    back to the previous one: (kind (n,) uint8 -- MOTION_STATIC | MOTION_MOVED | MOTION_NONE, back (n, 3, 4), normal (n, 3, 3)).  Host
+    arithmetic: needs no device."""
+    cur = np.ascontiguousarray(current, dtype=np.float32).reshape(-1, 16)
+    prev = np.ascontiguousarray(previous, dtype=np.float32).reshape(-1, 16)
+    if cur.shape != prev.shape:
+        raise ValueError("motion_table: %d current and %d previous matrices" % (len(cur), len(prev)))
+    n = len(cur)
+    kind, back, normal = np.zeros(n, np.uint8), np.zeros((n, 3, 4), np.float32), np.zeros((n, 3, 3), np.float32)
+    _check(load().pt_motion_table(_ptr(cur), _ptr(prev), C.c_uint32(n), _ptr(kind), _ptr(back), _ptr(normal)))
+    return kind, back, normal
 
 
 class SceneDesc(C.Structure):
@@ -725,16 +756,51 @@ class Scene:
         _check(load().pt_render_features(self._h, C.byref(cp), C.byref(op), _ptr(out)))
         return out
 
-    def denoise_sequence(self, frames, cameras, options, params=None):
+    def _previous(self, previous):
+        if previous is None:
+            return None
+        prev = np.ascontiguousarray(previous, dtype=np.float32).reshape(-1, 16)
+        if self.n_instances and len(prev) != self.n_instances:
+            raise ValueError("previous: %d matrices for %d instances" % (len(prev), self.n_instances))
+        return prev
+
+    def render_features_motion(self, camera, options, previous=None):
+        """render_features and, from the same walks, the frame's motion (pt_render_features_motion): (features, motion), motion an
+        (H, W, 2, 4) float32 array, the mean over the 4 rays of [previous position xyz, fraction moved], [previous normal xyz, fraction
+        without a previous position].  previous: the matrices (n_instances, 4, 4) the instances had at the previous frame (a NaN matrix:
+        the instance was not there); None = nothing moved.  The current matrices are the scene's (pose_transforms)."""
+        h, w = options["image_height"], options["image_width"]
+        feat, mot = np.empty((h, w, 3, 4), np.float32), np.empty((h, w, 2, 4), np.float32)
+        cp, op, prev = _camera(camera), _options(options), self._previous(previous)
+        _check(load().pt_render_features_motion(self._h, C.byref(cp), C.byref(op), _ptr(prev), _ptr(feat), _ptr(mot)))
+        return feat, mot
+
+    def render_features_motion_device(self, camera, options, d_features_ptr, d_motion_ptr, stream_ptr=0, previous=None):
+        """render_features_motion into device memory (H*W*12 and H*W*8 floats), ordered on stream_ptr."""
+        cp, op, prev = _camera(camera), _options(options), self._previous(previous)
+        _check(load().pt_render_features_motion_device(self._h, C.byref(cp), C.byref(op), _ptr(prev), C.c_void_p(d_features_ptr), C.c_void_p(d_motion_ptr),
+                                                       C.c_void_p(stream_ptr)))
+
+    def denoise_sequence(self, frames, cameras, options, params=None, poses=None):
         """Temporal denoising of a sequence of frames of this scene, frames[v] seen through cameras[v] (e.g. process_views' output): a fresh
-        TemporalDenoiser pushes every frame with its render_features; returns a (V, H, W, 4) float32 array."""
+        TemporalDenoiser pushes every frame with its render_features; returns a (V, H, W, 4) float32 array.  poses: poses[v] are the
+        matrices of all instances at frame v, (V, n_instances, 4, 4): the scene is posed to poses[v], the frame's features and motion are
+        rendered with poses[v - 1] as the previous pose (none for the first frame) and pushed with that motion; the scene is left at the
+        last pose."""
         frames = np.asarray(frames, dtype=np.float32)
         if len(frames) != len(cameras):
             raise ValueError("one camera per frame")
+        if poses is not None and len(poses) != len(frames):
+            raise ValueError("one pose per frame")
         out = np.empty_like(frames)
         with TemporalDenoiser(options["image_width"], options["image_height"], params=params, device=self.device) as t:
             for v, cam in enumerate(cameras):
-                out[v], _ = t.denoise(frames[v], self.render_features(cam, options), cam)
+                if poses is None:
+                    out[v], _ = t.denoise(frames[v], self.render_features(cam, options), cam)
+                    continue
+                self.pose(poses[v])
+                feat, mot = self.render_features_motion(cam, options, previous=poses[v - 1] if v > 0 else None)
+                out[v], _ = t.denoise(frames[v], feat, cam, motion=mot)
         return out
 
     def render_features_views(self, cameras, options, followed=None):

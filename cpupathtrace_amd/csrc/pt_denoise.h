@@ -82,4 +82,11 @@ struct PtTemporalState {
 hipError_t pt_temporal_run(hipStream_t stream, const float4 *rgba, const float4 *features, int32_t width, int32_t height, const PtTemporalParams &params,
                            const PtReprojection &reprojection, const PtDenoiseScratch &scratch, const PtTemporalState &state, float4 *out);
 
+// pt_temporal_run with the frame's motion (width * height * 2 float4, pt_render_features_motion; include/pt_motion.h): the accumulate step
+// reprojects where every pixel's surface was at the previous pose.  `reprojection` carries the previous camera's origin and rows in mode
+// PT_REPROJECT_IDENTICAL too: a pixel on a moved surface is projected even under the same camera.
+hipError_t pt_temporal_run_motion(hipStream_t stream, const float4 *rgba, const float4 *features, const float4 *motion, int32_t width, int32_t height,
+                                  const PtTemporalParams &params, const PtReprojection &reprojection, const PtDenoiseScratch &scratch, const PtTemporalState &state,
+                                  float4 *out);
+
 #endif

@@ -445,11 +445,18 @@ __device__ __forceinline__ float dot3(float ax, float ay, float az, float bx, fl
 // Temporal step of pt_temporal_run: reprojects every covered pixel's first-hit position into the previous push's camera, gathers the
 // previous push's history at the 2x2 bilinear taps that see the same surface, and blends.  Only + - * /, one square root and comparisons,
 // all correctly rounded (the build has -ffp-contract=off), so the history lengths equal tests/temporal_ref.py's exactly.
-__global__ __launch_bounds__(256) void pt_temporal_accumulate_kernel(const float4 *__restrict__ feat, const float4 *__restrict__ col_in,
-                                                                     const uint32_t *__restrict__ cls, int32_t width, int32_t height, PtReprojection rp,
-                                                                     PtTemporalPrev prev, PtTemporalBlend bl, float4 *__restrict__ col_out,
-                                                                     float2 *__restrict__ mom_out, int32_t *__restrict__ len_out, float4 *__restrict__ pos_out,
-                                                                     float4 *__restrict__ nrm_out) {
+//
+// kMotion (pt_temporal_run_motion; include/pt_motion.h): `motion` says where the pixel's surface was at the previous pose.
+// A pixel with rays that had no previous position (motion[1].w > 0) has no history.  Otherwise Xr = motion[0].xyz / coverage and nr =
+// motion[1].xyz at unit length are what is reprojected and what the taps' normal and position tests compare; the pixel is its own tap
+// only under the same camera AND with no ray on a moved surface (motion[0].w == 0), every other pixel projects Xr into the previous
+// camera (rp's origin and rows are filled whenever there is a previous push).  The tolerance's t and what is stored for the next push
+// stay the current frame's.  The plain kernel is the kMotion = false instantiation: `motion` is not read.
+template<bool kMotion>
+__device__ __forceinline__ void temporal_accumulate(const float4 *__restrict__ feat, const float4 *__restrict__ col_in, const uint32_t *__restrict__ cls, int32_t width,
+                                                    int32_t height, const PtReprojection &rp, const PtTemporalPrev &prev, const PtTemporalBlend &bl,
+                                                    float4 *__restrict__ col_out, float2 *__restrict__ mom_out, int32_t *__restrict__ len_out,
+                                                    float4 *__restrict__ pos_out, float4 *__restrict__ nrm_out, const float4 *__restrict__ motion) {
     const int x = blockIdx.x * 16 + threadIdx.x, y = blockIdx.y * 16 + threadIdx.y;
     if(x >= width || y >= height) {
         return;
@@ -476,16 +483,33 @@ __global__ __launch_bounds__(256) void pt_temporal_accumulate_kernel(const float
     pos_out[p] = make_float4(X, Y, Z, 0.0f);
     nrm_out[p] = make_float4(nx, ny, nz, 0.0f);
 
+    // what is reprojected and compared with the taps: the pixel's own position and normal, or (kMotion) those it had at the previous pose
+    float Xr = X, Yr = Y, Zr = Z, nrx = nx, nry = ny, nrz = nz;
+    bool own_tap = rp.mode == PT_REPROJECT_IDENTICAL, project = rp.mode == PT_REPROJECT_CAMERA;
+    if constexpr(kMotion) {
+        const float4 m0 = motion[2 * p], m1 = motion[2 * p + 1];
+        Xr = m0.x / cov;
+        Yr = m0.y / cov;
+        Zr = m0.z / cov;
+        const float mlen2 = dot3(m1.x, m1.y, m1.z, m1.x, m1.y, m1.z);
+        const float minv = 1.0f / sqrtf(mlen2);
+        nrx = mlen2 > 0.0f ? m1.x * minv : 0.0f;
+        nry = mlen2 > 0.0f ? m1.y * minv : 0.0f;
+        nrz = mlen2 > 0.0f ? m1.z * minv : 0.0f;
+        const bool had_position = !(m1.w > 0.0f);
+        project = had_position && (project || (own_tap && !(m0.w == 0.0f)));
+        own_tap = had_position && own_tap && m0.w == 0.0f;
+    }
     float px = 0.0f, py = 0.0f;
     bool found = false;
-    if(rp.mode == PT_REPROJECT_IDENTICAL) {
+    if(own_tap) {
         px = (float)x;
         py = (float)y;
         found = true;
     }
-    else if(rp.mode == PT_REPROJECT_CAMERA) {
+    else if(project) {
         // X - origin = a forward + b up + c right; the rows are the inverse of [forward up right] times |det|
-        const float dx = X - rp.origin[0], dy = Y - rp.origin[1], dz = Z - rp.origin[2];
+        const float dx = Xr - rp.origin[0], dy = Yr - rp.origin[1], dz = Zr - rp.origin[2];
         const float a = dot3(dx, dy, dz, rp.row[0][0], rp.row[0][1], rp.row[0][2]);
         const float b = dot3(dx, dy, dz, rp.row[1][0], rp.row[1][1], rp.row[1][2]);
         const float cc = dot3(dx, dy, dz, rp.row[2][0], rp.row[2][1], rp.row[2][2]);
@@ -517,11 +541,11 @@ __global__ __launch_bounds__(256) void pt_temporal_accumulate_kernel(const float
                 continue;
             }
             const float4 nq = prev.nrm[q];
-            if(!(dot3(nx, ny, nz, nq.x, nq.y, nq.z) >= bl.normal_min)) {
+            if(!(dot3(nrx, nry, nrz, nq.x, nq.y, nq.z) >= bl.normal_min)) {
                 continue;
             }
             const float4 xq = prev.pos[q];
-            const float ex = X - xq.x, ey = Y - xq.y, ez = Z - xq.z;
+            const float ex = Xr - xq.x, ey = Yr - xq.y, ez = Zr - xq.z;
             if(!(dot3(ex, ey, ez, ex, ey, ez) <= r2)) {
                 continue;
             }
@@ -552,6 +576,23 @@ __global__ __launch_bounds__(256) void pt_temporal_accumulate_kernel(const float
     const float b = (1.0f - ac) * (sb / sw) + ac * c.z;
     col_out[p] = make_float4(r, g, b, lum_of(r, g, b));
     mom_out[p] = make_float2((1.0f - am) * (s1 / sw) + am * l, (1.0f - am) * (s2 / sw) + am * (l * l));
+}
+
+__global__ __launch_bounds__(256) void pt_temporal_accumulate_kernel(const float4 *__restrict__ feat, const float4 *__restrict__ col_in,
+                                                                     const uint32_t *__restrict__ cls, int32_t width, int32_t height, PtReprojection rp,
+                                                                     PtTemporalPrev prev, PtTemporalBlend bl, float4 *__restrict__ col_out,
+                                                                     float2 *__restrict__ mom_out, int32_t *__restrict__ len_out, float4 *__restrict__ pos_out,
+                                                                     float4 *__restrict__ nrm_out) {
+    temporal_accumulate<false>(feat, col_in, cls, width, height, rp, prev, bl, col_out, mom_out, len_out, pos_out, nrm_out, nullptr);
+}
+
+__global__ __launch_bounds__(256) void pt_temporal_accumulate_motion_kernel(const float4 *__restrict__ feat, const float4 *__restrict__ col_in,
+                                                                            const uint32_t *__restrict__ cls, int32_t width, int32_t height, PtReprojection rp,
+                                                                            PtTemporalPrev prev, PtTemporalBlend bl, float4 *__restrict__ col_out,
+                                                                            float2 *__restrict__ mom_out, int32_t *__restrict__ len_out,
+                                                                            float4 *__restrict__ pos_out, float4 *__restrict__ nrm_out,
+                                                                            const float4 *__restrict__ motion) {
+    temporal_accumulate<true>(feat, col_in, cls, width, height, rp, prev, bl, col_out, mom_out, len_out, pos_out, nrm_out, motion);
 }
 
 // (rgba and out may be the same array: no __restrict__ on them)
@@ -716,8 +757,11 @@ hipError_t pt_denoise_views_run(hipStream_t stream, const float4 *rgba, const fl
     return hipSuccess;
 }
 
-hipError_t pt_temporal_run(hipStream_t stream, const float4 *rgba, const float4 *features, int32_t width, int32_t height, const PtTemporalParams &params,
-                           const PtReprojection &reprojection, const PtDenoiseScratch &scratch, const PtTemporalState &state, float4 *out) {
+namespace {
+
+// pt_temporal_run (motion == nullptr) and pt_temporal_run_motion
+hipError_t temporal_run(hipStream_t stream, const float4 *rgba, const float4 *features, const float4 *motion, int32_t width, int32_t height, const PtTemporalParams &params,
+                        const PtReprojection &reprojection, const PtDenoiseScratch &scratch, const PtTemporalState &state, float4 *out) {
     const dim3 block(16, 16), grid((width + 15) / 16, (height + 15) / 16);
     const int cur = state.cur, prv = state.cur ^ 1;
     PtDenoiseScratch s = scratch;
@@ -726,8 +770,14 @@ hipError_t pt_temporal_run(hipStream_t stream, const float4 *rgba, const float4 
     hipLaunchKernelGGL(pt_denoise_prepare_kernel<false>, grid, block, 0, stream, rgba, features, width, height, nullptr, s.col[1], s.guide, s.cls);
     const PtTemporalPrev prev{state.col_hist, state.moments[prv], state.len[prv], state.pos[prv], state.nrm[prv], state.cls[prv]};
     const PtTemporalBlend bl{params.alpha_color, params.alpha_moments, params.max_history, params.normal_min, params.position_tolerance};
-    hipLaunchKernelGGL(pt_temporal_accumulate_kernel, grid, block, 0, stream, features, s.col[1], s.cls, width, height, reprojection, prev, bl, s.col[0],
-                       state.moments[cur], state.len[cur], state.pos[cur], state.nrm[cur]);
+    if(motion != nullptr) {
+        hipLaunchKernelGGL(pt_temporal_accumulate_motion_kernel, grid, block, 0, stream, features, s.col[1], s.cls, width, height, reprojection, prev, bl, s.col[0],
+                           state.moments[cur], state.len[cur], state.pos[cur], state.nrm[cur], motion);
+    }
+    else {
+        hipLaunchKernelGGL(pt_temporal_accumulate_kernel, grid, block, 0, stream, features, s.col[1], s.cls, width, height, reprojection, prev, bl, s.col[0],
+                           state.moments[cur], state.len[cur], state.pos[cur], state.nrm[cur]);
+    }
     const PtTemporalPixel tp{state.len[cur], state.moments[cur], params.moments_min_history, params.sigma_luminance_temporal};
     const PtDenoiseParams &sp = params.spatial;
     hipLaunchKernelGGL((pt_denoise_variance_kernel<true, false>), grid, block, 0, stream, s.col[0], s.guide, s.cls, width, height, sp.sigma_normal, sp.sigma_depth,
@@ -749,4 +799,17 @@ hipError_t pt_temporal_run(hipStream_t stream, const float4 *rgba, const float4 
     }
     hipLaunchKernelGGL(pt_denoise_finish_kernel<false>, grid, block, 0, stream, col, rgba, features, width, height, nullptr, nullptr, out);
     return hipGetLastError();
+}
+
+} // namespace
+
+hipError_t pt_temporal_run(hipStream_t stream, const float4 *rgba, const float4 *features, int32_t width, int32_t height, const PtTemporalParams &params,
+                           const PtReprojection &reprojection, const PtDenoiseScratch &scratch, const PtTemporalState &state, float4 *out) {
+    return temporal_run(stream, rgba, features, nullptr, width, height, params, reprojection, scratch, state, out);
+}
+
+hipError_t pt_temporal_run_motion(hipStream_t stream, const float4 *rgba, const float4 *features, const float4 *motion, int32_t width, int32_t height,
+                                  const PtTemporalParams &params, const PtReprojection &reprojection, const PtDenoiseScratch &scratch, const PtTemporalState &state,
+                                  float4 *out) {
+    return temporal_run(stream, rgba, features, motion, width, height, params, reprojection, scratch, state, out);
 }

@@ -294,6 +294,9 @@ struct pt_scene {
     pth::DevBuf<pth::F4> features;
     pth::DevBuf<uint2> feature_spill;
     pth::DevBuf<PtViewCamera> feature_cams; // pt_render_features_views: the views' cameras, aperture none
+    // pt_render_features_motion (pt_motion.cpp): the host form's motion plane and the instance table of the call
+    pth::DevBuf<pth::F4> motion;
+    pth::DevBuf<PtMotionInstance> motion_instances;
     bool debug_collect_costs = false;                // pt_debug_collect_costs: every launch records them
     std::vector<uint32_t> debug_place;               // pt_debug_set_place: the next launch starts from this table ...
     uint32_t debug_place_waves = 0, debug_place_slots = 0; // ... with this many wavefronts and slots in each

@@ -438,7 +438,7 @@ struct pt_temporal {
     int32_t width = 0, height = 0;
     PtTemporalParams params{};
     std::mutex mutex;
-    DevBuf<float4> col[2], guide, col_hist, pos[2], nrm[2], in_rgba, in_features;
+    DevBuf<float4> col[2], guide, col_hist, pos[2], nrm[2], in_rgba, in_features, in_motion; // (in_motion: pt_temporal_denoise_motion's host form)
     DevBuf<float> var[2];
     DevBuf<float2> grad, moments[2];
     DevBuf<int32_t> len[2];
@@ -523,7 +523,8 @@ int temporal_check_push(const pt_temporal *t, const void *rgba, const void *feat
 // Enqueues one push on `st` (handle mutex held by the caller).  The launch rewrites the colour history, so the handle has no usable history
 // until the caller, once every copy of the push's outputs has succeeded, commits the push with temporal_commit; a failure in between leaves
 // it with none (its next push starts afresh) rather than pairing this push's camera with the last push's buffers.
-int temporal_push(pt_temporal *t, hipStream_t st, const float4 *rgba, const float4 *features, const pt_camera_params *camera, float4 *out) {
+// `motion` (may be null: the plain push): the frame's motion in device memory (include/pt_motion.h).
+int temporal_push(pt_temporal *t, hipStream_t st, const float4 *rgba, const float4 *features, const float4 *motion, const pt_camera_params *camera, float4 *out) {
     PtReprojection rp{};
     PtDevCamera cam{};
     float rows[3][3];
@@ -534,6 +535,10 @@ int temporal_push(pt_temporal *t, hipStream_t st, const float4 *rgba, const floa
     else if(std::memcmp(cam.origin, t->prev.origin, sizeof cam.origin) == 0 && std::memcmp(cam.forward, t->prev.forward, sizeof cam.forward) == 0 &&
             std::memcmp(cam.up, t->prev.up, sizeof cam.up) == 0 && std::memcmp(cam.right, t->prev.right, sizeof cam.right) == 0) {
         rp.mode = PT_REPROJECT_IDENTICAL;
+        if(motion != nullptr) { // a pixel on a moved surface is projected under the same camera too
+            std::memcpy(rp.origin, t->prev.origin, sizeof rp.origin);
+            std::memcpy(rp.row, t->prev_rows, sizeof rp.row);
+        }
     }
     else { // into the previous camera
         rp.mode = PT_REPROJECT_CAMERA;
@@ -560,7 +565,12 @@ int temporal_push(pt_temporal *t, hipStream_t st, const float4 *rgba, const floa
     t->has_prev = false;
     t->pending = cam;
     std::memcpy(t->pending_rows, rows, sizeof rows);
-    PT_HIP(pt_temporal_run(st, rgba, features, t->width, t->height, t->params, rp, s, state, out));
+    if(motion != nullptr) {
+        PT_HIP(pt_temporal_run_motion(st, rgba, features, motion, t->width, t->height, t->params, rp, s, state, out));
+    }
+    else {
+        PT_HIP(pt_temporal_run(st, rgba, features, t->width, t->height, t->params, rp, s, state, out));
+    }
     return PT_OK;
 }
 
@@ -635,6 +645,11 @@ int pt_temporal_create(int device, int32_t width, int32_t height, const pt_tempo
 }
 
 int pt_temporal_denoise(pt_temporal *t, const float *rgba, const float *features, const pt_camera_params *camera, float *out_rgba, int32_t *out_history) {
+    return pt_temporal_denoise_motion(t, rgba, features, nullptr, camera, out_rgba, out_history);
+}
+
+int pt_temporal_denoise_motion(pt_temporal *t, const float *rgba, const float *features, const float *motion, const pt_camera_params *camera, float *out_rgba,
+                               int32_t *out_history) {
     PT_TRY(temporal_check_push(t, rgba, features, camera, out_rgba));
     std::lock_guard<std::mutex> lock(t->mutex);
     const size_t n = static_cast<size_t>(t->width) * static_cast<size_t>(t->height);
@@ -643,8 +658,12 @@ int pt_temporal_denoise(pt_temporal *t, const float *rgba, const float *features
     PT_HIP(t->in_features.ensure(3 * n));
     PT_HIP(hipMemcpy(t->in_rgba.ptr, rgba, n * sizeof(float4), hipMemcpyHostToDevice));
     PT_HIP(hipMemcpy(t->in_features.ptr, features, 3 * n * sizeof(float4), hipMemcpyHostToDevice));
+    if(motion != nullptr) {
+        PT_HIP(t->in_motion.ensure(2 * n));
+        PT_HIP(hipMemcpy(t->in_motion.ptr, motion, 2 * n * sizeof(float4), hipMemcpyHostToDevice));
+    }
     // in place, as pt_denoise
-    PT_TRY(temporal_push(t, nullptr, t->in_rgba.ptr, t->in_features.ptr, camera, t->in_rgba.ptr));
+    PT_TRY(temporal_push(t, nullptr, t->in_rgba.ptr, t->in_features.ptr, motion != nullptr ? t->in_motion.ptr : nullptr, camera, t->in_rgba.ptr));
     PT_HIP(hipMemcpy(out_rgba, t->in_rgba.ptr, n * sizeof(float4), hipMemcpyDeviceToHost));
     if(out_history != nullptr) {
         PT_HIP(hipMemcpy(out_history, t->len[t->cur].ptr, n * sizeof(int32_t), hipMemcpyDeviceToHost));
@@ -655,12 +674,18 @@ int pt_temporal_denoise(pt_temporal *t, const float *rgba, const float *features
 
 int pt_temporal_denoise_device(pt_temporal *t, const float *d_rgba, const float *d_features, const pt_camera_params *camera, float *d_out_rgba,
                                int32_t *d_out_history, void *stream) {
+    return pt_temporal_denoise_motion_device(t, d_rgba, d_features, nullptr, camera, d_out_rgba, d_out_history, stream);
+}
+
+int pt_temporal_denoise_motion_device(pt_temporal *t, const float *d_rgba, const float *d_features, const float *d_motion, const pt_camera_params *camera,
+                                      float *d_out_rgba, int32_t *d_out_history, void *stream) {
     PT_TRY(temporal_check_push(t, d_rgba, d_features, camera, d_out_rgba));
     std::lock_guard<std::mutex> lock(t->mutex);
     const size_t n = static_cast<size_t>(t->width) * static_cast<size_t>(t->height);
     PT_HIP(hipSetDevice(t->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    PT_TRY(temporal_push(t, st, reinterpret_cast<const float4 *>(d_rgba), reinterpret_cast<const float4 *>(d_features), camera, reinterpret_cast<float4 *>(d_out_rgba)));
+    PT_TRY(temporal_push(t, st, reinterpret_cast<const float4 *>(d_rgba), reinterpret_cast<const float4 *>(d_features), reinterpret_cast<const float4 *>(d_motion), camera,
+                         reinterpret_cast<float4 *>(d_out_rgba)));
     if(d_out_history != nullptr) {
         PT_HIP(hipMemcpyAsync(d_out_history, t->len[t->cur].ptr, n * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
     }

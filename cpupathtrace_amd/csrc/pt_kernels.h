@@ -237,6 +237,19 @@ struct PtFollow {
 };
 void pt_launch_features(hipStream_t stream, const PtDevScene &scene, const PtDevCamera &camera, const PtViewCamera *views, int32_t n_views, int32_t width, int32_t height,
                         float4 *out, const PtPathConfig &cfg, const PtFollow *follow);
+// The first-hit features of ONE frame and its motion in one launch (pt_motion_kernel; include/pt_motion.h): `out` as
+// pt_launch_features gives it without views and without follow, bit for bit, and motion[2 * pixel + k], k = previous position + fraction
+// moved, previous normal + fraction without a previous position.  `instances` (device memory) holds the n_instances mesh instances that
+// have objects, by ascending first object; their ranges are disjoint.  n_instances == 0: nothing moved, and `instances` is not read.
+struct alignas(16) PtMotionInstance {
+    uint32_t first, count; // the instance's objects: first .. first + count - 1, count > 0
+    uint32_t kind;         // PT_MOTION_STATIC | PT_MOTION_MOVED | PT_MOTION_NONE
+    uint32_t pad;
+    float back[12];        // previous position = back * (position, 1): 3 rows of 4
+    float normal[12];      // previous normal direction = normal * normal: 3 rows of 3, each padded to 4
+};
+void pt_launch_features_motion(hipStream_t stream, const PtDevScene &scene, const PtDevCamera &camera, int32_t width, int32_t height, float4 *out, float4 *motion,
+                               const PtMotionInstance *instances, uint32_t n_instances, const PtPathConfig &cfg);
 // diagnostic (tools/step_timing.py): stamped walks, `lanes_per_wave` rays per wavefront; out[ray] = (steps, cycles waiting for records, cycles in all, price of a stamp pair)
 void pt_launch_steptime(hipStream_t stream, const PtDevScene &scene, const float *rays6, uint32_t n, uint32_t lanes_per_wave, uint4 *out, uint2 *spill, uint32_t spill_depth, int flags);
 

@@ -1,5 +1,5 @@
 // pt_walks.hip -- the kernels that trace ONE walk per lane to its end with the path kernel's traversal machinery (pt_trace.h): closest hits
-// of a ray batch (pt_closest_kernel), the denoiser's first-hit and followed features (pt_feature_kernel, pt_follow_kernel) and two
+// of a ray batch (pt_closest_kernel), the denoiser's first-hit and followed features (pt_feature_kernel, pt_follow_kernel), the first-hit features with motion (pt_motion_kernel) and two
 // diagnostics (pt_steptime_kernel, pt_replay_kernel).  They live apart from pt_path.hip so that an edit here neither recompiles nor
 // re-schedules the path kernel.  Written once: the dispatch over the three (stack window, records) routes, the LDS size, and the prologue
 // that binds a lane's Tracer (bind_lane) where it leaves a kernel's instructions as they were: the closest-hit and the step-timing kernel.
@@ -300,6 +300,133 @@ __global__ __launch_bounds__(256) void pt_follow_kernel(PtDevScene sc, PtDevCame
     o[2] = make_float4(acc2.x * q, acc2.y * q, acc2.z * q, (0.2126f * er + 0.7152f * eg) + 0.0722f * eb);
 }
 
+// pt_denoise.hip's dot3: (a x + b y) + c z
+PT_D float motion_dot3(float a, float b, float c, V3 v) {
+    return (a * v.x + b * v.y) + c * v.z;
+}
+
+// First-hit features AND motion of a single frame (include/pt_motion.h): the rays, the walk, the accumulators and the
+// stores of pt_feature_kernel<.., false>, operation for operation, so `out` has its bits; each hit also adds where its surface point was
+// at the previous pose and the normal it had there.  The object of a triangle hit is in its record (the word object_normal's load
+// brings anyway); `inst` holds the instances that have objects by ascending first object, so the instance of an object is the last one
+// whose first is not above it -- if its range holds the object; objects of the description lie below inst[0].first, spheres are never
+// looked up.  n_inst == 0: nothing moved, and motion is the features' position and normal with w = 0.
+template<int STACK_LDS, bool IN_LDS>
+__global__ __launch_bounds__(256) void pt_motion_kernel(PtDevScene sc, PtDevCamera cam, int32_t width, int32_t height, float4 *__restrict__ out, uint2 *__restrict__ spill,
+                                                        uint32_t spill_depth, float4 *__restrict__ motion, const PtMotionInstance *__restrict__ inst, uint32_t n_inst) {
+    extern __shared__ __align__(16) unsigned char lds_raw[];
+    const int tid = threadIdx.x;
+    lds_u2_ptr stack_l = (lds_u2_ptr)reinterpret_cast<uint2 *>(lds_raw) + tid;
+    float4 *lds_recs = reinterpret_cast<float4 *>(lds_raw + (size_t)STACK_LDS * 256 * sizeof(uint2));
+    if(IN_LDS) {
+        for(uint32_t i = tid; i < 4u * (sc.pair_base + sc.n_pairs); i += 256) {
+            lds_recs[i] = sc.recs[i];
+        }
+        __syncthreads();
+    }
+    Tracer<STACK_LDS, IN_LDS> tr;
+    if(IN_LDS) {
+        tr.recs = (typename RecPtr<IN_LDS>::type)(lds_f4_cptr)lds_recs;
+    }
+    else {
+        tr.recs = (typename RecPtr<IN_LDS>::type)(glb_f4_cptr)sc.recs;
+    }
+    tr.stack_l = stack_l;
+    const size_t gid = (size_t)blockIdx.x * 256 + tid;
+    tr.my_spill = (glb_u2_ptr)(spill + gid * spill_depth);
+    if(gid >= (size_t)width * (size_t)height) {
+        return;
+    }
+    const int32_t px = (int32_t)(gid % (size_t)width);
+    const int32_t py = (int32_t)(gid / (size_t)width);
+    RootBox root;
+    root.ref = sc.root_ref;
+    for(int k = 0; k < 3; k++) {
+        root.lo[k] = sc.root_lo[k];
+        root.hi[k] = sc.root_hi[k];
+    }
+    float4 acc0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), acc1 = acc0, acc2 = acc0, emis = acc0, mot0 = acc0, mot1 = acc0;
+    for(int k = 0; k < 4; k++) {
+        const float dx = (k & 1) ? 0.25f : -0.25f, dy = (k & 2) ? 0.25f : -0.25f;
+        const float one_half = 1.0f / 2.0f;
+        const float x_camera = 2 * (((float)px + one_half + dx) / (float)width - one_half);
+        float y_camera = 2 * (((float)py + one_half + dy) / (float)height - one_half);
+        y_camera = -y_camera;
+        uint64_t rng = 0; // (drawn from, never used: both offsets are +0 and there is no aperture)
+        const Ray ray = camera_shoot(cam, x_camera, y_camera, 0.0f, 0.0f, rng);
+        Walk w;
+        typename Tracer<STACK_LDS, IN_LDS>::Rec rec;
+        rec.r0 = rec.r1 = rec.r2 = rec.r3 = (f4v){0.0f, 0.0f, 0.0f, 0.0f};
+        tr.start(w, rec, root, make_float4(ray.o.x, ray.o.y, ray.o.z, 0.0f), make_float4(ray.d.x, ray.d.y, ray.d.z, __uint_as_float(0u)));
+        uint32_t n_nodes = 0, n_leaves = 0;
+        while(tr.step(w, rec, 1, n_nodes, n_leaves)) {
+        }
+        float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), n4 = a, p4 = a, e4 = a, m0 = a, m1 = a;
+        if(w.best_ref != PT_REF_NONE) {
+            const float t = w.best_t;
+            const V3 pos = ray.o + ray.d * t;
+            uint32_t material_index;
+            const V3 n = object_normal(sc, w.best_ref, pos, material_index);
+            const Material mat = material_load(sc.materials, material_index);
+            const bool lambertian = mat.bsdf == 0; // PT_BSDF_LAMBERTIAN
+            a = make_float4(lambertian ? mat.diffuse.r : mat.specular.r, lambertian ? mat.diffuse.g : mat.specular.g, lambertian ? mat.diffuse.b : mat.specular.b, 1.0f);
+            n4 = make_float4(n.x, n.y, n.z, t);
+            p4 = make_float4(pos.x, pos.y, pos.z, 0.0f);
+            e4 = make_float4(mat.emission.r, mat.emission.g, mat.emission.b, 0.0f);
+            m0 = p4;
+            m1 = make_float4(n.x, n.y, n.z, 0.0f);
+            if(n_inst != 0 && !(w.best_ref & PT_REF_SPHERE)) {
+                const uint32_t obj = __float_as_uint(sc.tri_shade[8 * (size_t)(w.best_ref & PT_REF_INDEX) + 2].z) & 0x7fffffffu;
+                uint32_t lo = 0, hi = n_inst; // the last instance whose first object is <= obj lies in [lo, hi)
+                while(hi - lo > 1) {
+                    const uint32_t mid = lo + (hi - lo) / 2;
+                    if(inst[mid].first <= obj) {
+                        lo = mid;
+                    }
+                    else {
+                        hi = mid;
+                    }
+                }
+                const PtMotionInstance *mi = inst + lo;
+                const uint32_t first = mi->first;
+                if(obj >= first && obj - first < mi->count) {
+                    const uint32_t kind = mi->kind;
+                    if(kind == 2u) { // PT_MOTION_NONE
+                        m0 = make_float4(0.0f, 0.0f, 0.0f, 1.0f);
+                        m1 = make_float4(0.0f, 0.0f, 0.0f, 1.0f);
+                    }
+                    else if(kind == 1u) { // PT_MOTION_MOVED
+                        const float4 b0 = *reinterpret_cast<const float4 *>(mi->back), b1 = *reinterpret_cast<const float4 *>(mi->back + 4),
+                                     b2 = *reinterpret_cast<const float4 *>(mi->back + 8);
+                        const float4 r0 = *reinterpret_cast<const float4 *>(mi->normal), r1 = *reinterpret_cast<const float4 *>(mi->normal + 4),
+                                     r2 = *reinterpret_cast<const float4 *>(mi->normal + 8);
+                        m0 = make_float4(motion_dot3(b0.x, b0.y, b0.z, pos) + b0.w, motion_dot3(b1.x, b1.y, b1.z, pos) + b1.w, motion_dot3(b2.x, b2.y, b2.z, pos) + b2.w, 1.0f);
+                        const V3 v = v3(motion_dot3(r0.x, r0.y, r0.z, n), motion_dot3(r1.x, r1.y, r1.z, n), motion_dot3(r2.x, r2.y, r2.z, n));
+                        const float len2 = motion_dot3(v.x, v.y, v.z, v);
+                        const float inv = 1.0f / sqrtf(len2);
+                        m1 = make_float4(len2 > 0.0f ? v.x * inv : 0.0f, len2 > 0.0f ? v.y * inv : 0.0f, len2 > 0.0f ? v.z * inv : 0.0f, 0.0f);
+                    }
+                }
+            }
+        }
+        acc0 = make_float4(acc0.x + a.x, acc0.y + a.y, acc0.z + a.z, acc0.w + a.w);
+        acc1 = make_float4(acc1.x + n4.x, acc1.y + n4.y, acc1.z + n4.z, acc1.w + n4.w);
+        acc2 = make_float4(acc2.x + p4.x, acc2.y + p4.y, acc2.z + p4.z, 0.0f);
+        emis = make_float4(emis.x + e4.x, emis.y + e4.y, emis.z + e4.z, 0.0f);
+        mot0 = make_float4(mot0.x + m0.x, mot0.y + m0.y, mot0.z + m0.z, mot0.w + m0.w);
+        mot1 = make_float4(mot1.x + m1.x, mot1.y + m1.y, mot1.z + m1.z, mot1.w + m1.w);
+    }
+    const float q = 0.25f;
+    const float er = emis.x * q, eg = emis.y * q, eb = emis.z * q;
+    float4 *o = out + 3 * gid;
+    o[0] = make_float4(acc0.x * q, acc0.y * q, acc0.z * q, acc0.w * q);
+    o[1] = make_float4(acc1.x * q, acc1.y * q, acc1.z * q, acc1.w * q);
+    o[2] = make_float4(acc2.x * q, acc2.y * q, acc2.z * q, (0.2126f * er + 0.7152f * eg) + 0.0722f * eb);
+    float4 *m = motion + 2 * gid;
+    m[0] = make_float4(mot0.x * q, mot0.y * q, mot0.z * q, mot0.w * q);
+    m[1] = make_float4(mot1.x * q, mot1.y * q, mot1.z * q, mot1.w * q);
+}
+
 // ---- diagnostic: where the cycles of a traversal step go -------------------------------------------------------------------------------
 // One walk per lane as in pt_closest_kernel, but only the first `lanes_per_wave` lanes of every wavefront get a ray, and every step is
 // stamped (s_memtime): cycles spent waiting for the record that was requested at the end of the previous step, and everything else.
@@ -536,6 +663,18 @@ void pt_launch_features(hipStream_t stream, const PtDevScene &scene, const PtDev
         else {
             launch(pt_feature_kernel<kWindow, kInLds, false>, pt_follow_kernel<kWindow, kInLds, false>);
         }
+    });
+}
+
+void pt_launch_features_motion(hipStream_t stream, const PtDevScene &scene, const PtDevCamera &camera, int32_t width, int32_t height, float4 *out, float4 *motion,
+                               const PtMotionInstance *instances, uint32_t n_instances, const PtPathConfig &cfg) {
+    if(width <= 0 || height <= 0) {
+        return;
+    }
+    const dim3 grid((unsigned)(((size_t)width * (size_t)height + 255) / 256));
+    dispatch_route(cfg, scene, [&](auto window, auto in_lds, size_t lds) {
+        hipLaunchKernelGGL((pt_motion_kernel<decltype(window)::value, decltype(in_lds)::value>), grid, dim3(256), lds, stream, scene, camera, width, height, out, cfg.spill,
+                           cfg.spill_depth, motion, instances, n_instances);
     });
 }
 

@@ -21,10 +21,15 @@ struct TemporalDenoiseParams {
     float sigma_luminance_temporal = 4.0F;  // luminance sigma where it is
     float normal_min = 0.9F;                // least dot product of the normals of a reprojected tap
     float position_tolerance = 2.0F;        // largest distance of a reprojected tap, in pixel footprints
+    // reproject through the poses of the scene's mesh instances (Scene::pose between the pushes; include/pt_motion.h)
+    bool follow_motion = false;
 };
 
 // The temporal half of SVGF in front of denoise()'s spatial filter: every push reprojects the history of the frames pushed before it
-// (through the pixels' first-hit positions: a Scene does not move) and blends it into the new frame before filtering.  The first push,
+// (through the pixels' first-hit positions) and blends it into the new frame before filtering.  By default the history is reprojected as
+// for a Scene that does not move.  With params.follow_motion every push reads the pose of the scene's mesh instances and reprojects
+// where each pixel's surface was at the pose of the push before (pt_render_features_motion, pt_temporal_denoise_motion): the first push,
+// and the first after reset(), have no previous pose, and a Scene whose number of instances changed resets the history.  The first push,
 // and the first after reset(), equals denoise() with params.spatial bit for bit.  One device history per object, on the scene's first
 // replica; the scene must outlive the object.  Throws std::invalid_argument for parameters outside their range or a frame of another
 // size than options.image_width x image_height, std::runtime_error if the device fails.
@@ -44,6 +49,9 @@ class TemporalDenoiser {
     const Scene &scene;
     RenderOptions options;
     struct pt_temporal *handle = nullptr;
+    bool follow_motion = false;
+    bool has_pose = false;         // follow_motion: last_pose is the pose of the push before
+    std::vector<float> last_pose;  // [instances][16]
 };
 
 // frames[v] seen through cameras[v], pushed in order through one TemporalDenoiser.

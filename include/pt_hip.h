@@ -426,9 +426,14 @@ int pt_frame_preview(pt_frame *frame, const float *image, const pt_denoise_param
 /* Re-posing the instances of such a scene in place, and the batched assembler behind it (pt_scene_pose, pt_scene_get_pose,
  * pt_mesh_assemble_batch): the struct and entry points are declared, with their contracts, in: */
 #include "pt_pose.h"
+/* Where the surface a pixel sees was at the previous pose, and the temporal push that reprojects that point (pt_motion_table,
+ * pt_render_features_motion, pt_temporal_denoise_motion): the entry points are declared, with their contracts, in: */
+#include "pt_motion.h"
 
-/* Temporal denoising of a sequence of frames of one static scene (a camera path, a turntable): the temporal half of SVGF (Schied et al. 2017)
- * in front of pt_denoise's spatial filter.  A pt_temporal handle keeps the history of the frames pushed so far, on its own
+/* Temporal denoising of a sequence of frames of one scene (a camera path, a turntable): the temporal half of SVGF (Schied et al. 2017)
+ * in front of pt_denoise's spatial filter.  The entry points below reproject as for a scene that does not move; for a
+ * scene posed between the frames (pt_scene_pose) the motion forms of include/pt_motion.h reproject through the poses.
+ * A pt_temporal handle keeps the history of the frames pushed so far, on its own
  * device buffers (two handles may be interleaved).  Each push of a frame, its pt_render_features and its camera:
  *   - reprojects every covered pixel's mean hit position into the previous push's camera (a pinhole: the feature rays ignore the aperture)
  *     and takes the 2x2 bilinear taps there.  A tap is kept if it lies in the image, has the pixel's class (covered, emissive), a normal with

@@ -107,6 +107,9 @@ namespace pathtrace_host {
         return worker_count > 0 ? std::min(worker_count, static_cast<int>(replicas.size())) : static_cast<int>(replicas.size());
     }
 
+    // the number of mesh instances of `scene` (src/host/scene.cpp; 0 for a Scene without any)
+    size_t sceneInstanceCount(const Scene &scene);
+
 } // namespace pathtrace_host
 
 #endif

@@ -3,6 +3,7 @@
 #include <PathTrace/scene/mesh.h>
 
 #include "../../include/pt_hip.h"
+#include "job_params.h"
 
 #include <algorithm>
 #include <atomic>
@@ -407,6 +408,13 @@ void Scene::pose(const std::vector<uint32_t> &instances, const std::vector<mat4<
 }
 
 // The Triangle behind object `index` of a mesh instance (MeshState::object)
+size_t pathtrace_host::sceneInstanceCount(const Scene &scene) {
+    MeshStates &states = meshStates();
+    std::lock_guard<std::mutex> lock(states.mutex);
+    auto found = states.of.find(&scene);
+    return found != states.of.end() ? found->second->instances.size() : 0;
+}
+
 const Object *Scene::meshObject(uint32_t index) const {
     MeshState *state = nullptr;
     {

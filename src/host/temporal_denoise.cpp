@@ -43,7 +43,8 @@ namespace {
 
 } // namespace
 
-TemporalDenoiser::TemporalDenoiser(const Scene &scene_, const RenderOptions &options_, const TemporalDenoiseParams &params) : scene(scene_), options(options_) {
+TemporalDenoiser::TemporalDenoiser(const Scene &scene_, const RenderOptions &options_, const TemporalDenoiseParams &params) :
+  scene(scene_), options(options_), follow_motion(params.follow_motion) {
     const pt_temporal_params p = temporalParams(params);
     if(options.image_width <= 0 || options.image_height <= 0) {
         throw std::invalid_argument("PathTrace: TemporalDenoiser needs a positive image size");
@@ -64,10 +65,29 @@ Image<> TemporalDenoiser::push(const Image<> &frame, const Camera &camera) {
     const pt_camera_params cam = cameraParams(camera);
     const pt_options opt = renderOptions(options);
     pt_scene *replica = scene.deviceScenes().front();
-    std::vector<float> features(static_cast<size_t>(frame.getWidth()) * static_cast<size_t>(frame.getHeight()) * 12);
-    check(pt_render_features(replica, &cam, &opt, features.data()), "TemporalDenoiser::push (features)");
+    const size_t pixels = static_cast<size_t>(frame.getWidth()) * static_cast<size_t>(frame.getHeight());
+    std::vector<float> features(pixels * 12);
     static_assert(sizeof(Color<float>) == 4 * sizeof(float), "Image<Color<float>> is a packed RGBA float array");
     Image<> out(frame.getWidth(), frame.getHeight());
+    const size_t n_instances = follow_motion ? sceneInstanceCount(scene) : 0;
+    if(n_instances > 0) {
+        // the pose now, and the one this object saw at its last push
+        std::vector<float> pose(16 * n_instances);
+        check(pt_scene_get_pose(replica, pose.data()), "TemporalDenoiser::push (pose)");
+        if(has_pose && last_pose.size() != pose.size()) {
+            reset();
+        }
+        std::vector<float> motion(pixels * 8);
+        check(pt_render_features_motion(replica, &cam, &opt, has_pose ? last_pose.data() : nullptr, features.data(), motion.data()),
+              "TemporalDenoiser::push (features and motion)");
+        check(pt_temporal_denoise_motion(handle, reinterpret_cast<const float *>(frame.data()), features.data(), motion.data(), &cam,
+                                         reinterpret_cast<float *>(out.data()), nullptr),
+              "TemporalDenoiser::push");
+        last_pose = std::move(pose);
+        has_pose = true;
+        return out;
+    }
+    check(pt_render_features(replica, &cam, &opt, features.data()), "TemporalDenoiser::push (features)");
     check(pt_temporal_denoise(handle, reinterpret_cast<const float *>(frame.data()), features.data(), &cam, reinterpret_cast<float *>(out.data()), nullptr),
           "TemporalDenoiser::push");
     return out;
@@ -75,6 +95,7 @@ Image<> TemporalDenoiser::push(const Image<> &frame, const Camera &camera) {
 
 void TemporalDenoiser::reset() {
     check(pt_temporal_reset(handle), "TemporalDenoiser::reset");
+    has_pose = false;
 }
 
 std::vector<Image<>> denoiseSequence(const std::vector<Image<>> &frames, const Scene &scene, const std::vector<const Camera *> &cameras, const RenderOptions &options,
