@@ -212,7 +212,7 @@ int pth::create_scene(int device, const pt_scene_desc *d, const DeviceTriangles 
     s->cu_count = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     PT_HIP(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
     if(assembled != nullptr && assembled->ready != nullptr) {
-        PT_HIP(hipStreamWaitEvent(s->stream, assembled->ready, 0)); // (a pose: the arrays are being finished on the posed scene's stream)
+        PT_HIP(hipStreamWaitEvent(s->stream, assembled->ready, 0)); // (the arrays are being finished on the assembly's stream)
     }
     s->n_objects = n_objs;
     s->n_desc_objects = d->n_objects;
@@ -301,20 +301,10 @@ int pth::create_scene(int device, const pt_scene_desc *d, const DeviceTriangles 
         PT_HIP(up(raw_sph, d->sph, 4 * static_cast<size_t>(d->n_spheres)));
         PT_HIP(up(raw_sph_mat, d->sph_material, d->n_spheres));
         PT_HIP(up(raw_sph_obj, s->sph_obj.data(), d->n_spheres));
-        if(assembled != nullptr && assembled->batch_scratch != nullptr) {
-            // one launch for all ranges (pt_mesh_batch.h): the same three arrays
-            std::vector<PtBatchRange> table;
-            for(const MeshRange &r : assembled->ranges) {
-                table.push_back(PtBatchRange{r.first_tri, r.count, r.material, r.cull});
-            }
-            PT_HIP(pt_mesh_batch_fill_ranges(s->stream, *assembled->batch_scratch, table.data(), static_cast<uint32_t>(table.size()), d->n_triangles, n_tris - d->n_triangles,
-                                             d->n_objects, raw_cull.ptr, raw_tri_mat.ptr, raw_tri_obj.ptr));
-        }
-        else if(assembled != nullptr) {
-            for(const MeshRange &r : assembled->ranges) {
-                PT_HIP(pt_mesh_fill_range(s->stream, r.first_tri, r.count, r.cull, r.material, d->n_objects + (r.first_tri - d->n_triangles), raw_cull.ptr, raw_tri_mat.ptr,
-                                          raw_tri_obj.ptr));
-            }
+        if(assembled != nullptr) {
+            // the instances' triangles: one launch for all ranges (pt_mesh_batch.h)
+            PT_HIP(pt_mesh_batch_fill_ranges(s->stream, *assembled->scratch, assembled->ranges.data(), static_cast<uint32_t>(assembled->ranges.size()), d->n_triangles,
+                                             n_tris - d->n_triangles, d->n_objects, raw_cull.ptr, raw_tri_mat.ptr, raw_tri_obj.ptr));
         }
         PT_HIP(s->tris.ensure(PT_TRI_QUADS * (static_cast<size_t>(n_tris) + 1 + d->n_spheres))); // triangles, a spare record, spheres (pt_types.h)
         PT_HIP(hipMemsetAsync(s->tris.ptr + PT_TRI_QUADS * static_cast<size_t>(n_tris), 0, PT_TRI_QUADS * sizeof(F4), s->stream));
@@ -392,7 +382,7 @@ int pth::create_scene(int device, const pt_scene_desc *d, const DeviceTriangles 
             }
             if(assembled != nullptr) {
                 // an instance has one material: a lit one selects its whole range of objects
-                for(const MeshRange &r : assembled->ranges) {
+                for(const PtBatchRange &r : assembled->ranges) {
                     if(r.material != PT_NO_MATERIAL && lit[r.material] != 0) {
                         const uint32_t first = d->n_objects + (r.first_tri - d->n_triangles);
                         for(uint32_t o = first; o < first + r.count; o++) {
@@ -540,10 +530,10 @@ int pth::create_scene(int device, const pt_scene_desc *d, const DeviceTriangles 
         const uint32_t ref = of_instance ? (PT_REF_LEAF | (d->n_triangles + (static_cast<uint32_t>(obj) - d->n_objects))) : leaf_ref[obj];
         const uint32_t idx = ref & PT_REF_INDEX;
         const bool is_sphere = (ref & PT_REF_SPHERE) != 0;
-        const MeshRange *range = nullptr;
+        const PtBatchRange *range = nullptr;
         const float *tri_p = nullptr; // the triangle's nine coordinates
         if(of_instance) {
-            range = &*(std::upper_bound(assembled->ranges.begin(), assembled->ranges.end(), idx, [](uint32_t t, const MeshRange &r) { return t < r.first_tri; }) - 1);
+            range = &*(std::upper_bound(assembled->ranges.begin(), assembled->ranges.end(), idx, [](uint32_t t, const PtBatchRange &r) { return t < r.first_tri; }) - 1);
             tri_p = gathered.data() + 9 * next_gathered++;
         }
         else if(!is_sphere) {

@@ -149,8 +149,28 @@ struct DevBuf {
     }
 };
 
+// to takes from's memory over (what it had is freed)
+template<typename T>
+void take(DevBuf<T> &to, DevBuf<T> &from) {
+    to.release();
+    to.ptr = from.ptr;
+    to.count = from.count;
+    from.ptr = nullptr;
+    from.count = 0;
+}
+
 struct F4 {
     float x, y, z, w;
+};
+
+// A stream of a call's own, destroyed with the call
+struct StreamGuard {
+    hipStream_t stream = nullptr;
+    ~StreamGuard() {
+        if(stream != nullptr) {
+            (void)hipStreamDestroy(stream);
+        }
+    }
 };
 
 struct Event {
@@ -185,14 +205,6 @@ struct KeptMesh {
     DevBuf<int32_t> faces;
     uint32_t n_vertices = 0, n_faces = 0;
     int upload(const pt_mesh_data &m);
-    PtMeshDevice view() const {
-        PtMeshDevice v;
-        v.n_vertices = n_vertices;
-        v.vertices = vertices.ptr;
-        v.n_faces = n_faces;
-        v.faces = faces.ptr;
-        return v;
-    }
 };
 
 // A deep copy of a scene description: create_scene reads the description's host arrays (emitters, materials, the host builder's boxes)
@@ -211,10 +223,8 @@ struct PoseKeep {
     DescCopy desc;
     bool any_smooth = false;
     uint64_t capacity = 0;               // the description's triangles + the faces of all instances, before any is rejected
-    PtBatchScratch scratch;              // the batched assembler's, grown by the first pose
+    PtBatchScratch scratch;              // the assembler's, grown by the first pose (creation has one of its own, freed when it returns)
     DevBuf<float> spare_pos, spare_nrm;  // the arrays the next pose assembles into (the scene keeps the positions it was built from)
-    std::vector<PtBatchInstance> table;  // host side of the instance table, and of the counts that come back
-    std::vector<uint32_t> counts;
 };
 
 } // namespace pth
@@ -327,22 +337,17 @@ PtDevCamera derive_camera(const pt_camera_params *c);
 int derive_options(const pt_options *o, PtDevOptions *out);
 int check_render_args(pt_scene *scene, const pt_camera_params *camera, const pt_options *options);
 
-// Triangles that are in device memory already (pt_meshes.cpp): those of the description first, then the ranges of the mesh instances, each
-// with one cull flag and one material.
-struct MeshRange {
-    uint32_t first_tri, count;
-    uint8_t cull;
-    uint32_t material;
-};
+// Triangles that are in device memory already (assemble_mesh_scene, pt_meshes.cpp): those of the description first, then the ranges of the
+// mesh instances, each with one cull flag and one material.
 struct DeviceTriangles {
     const float *pos = nullptr; // [n_triangles][9]
     const float *nrm = nullptr; // [n_triangles][9] or null: face normals
     uint32_t n_triangles = 0;   // the description's and the ranges'
-    std::vector<MeshRange> ranges;
-    // a pose (pt_pose.cpp): the arrays are complete once this event of another stream is, and the ranges' constants are filled in one
-    // launch with this scratch instead of one launch per range
-    hipEvent_t ready = nullptr;
-    PtBatchScratch *batch_scratch = nullptr;
+    std::vector<PtBatchRange> ranges; // one per instance, in order (sorted by first_tri, empty ones included)
+    hipEvent_t ready = nullptr;       // the arrays are complete once this event of the assembly's stream is
+    // The ranges' constants are filled in one launch on the new scene's stream, which reads the range table from this scratch: it stays
+    // alive, and is not used again, until that stream has been waited for
+    PtBatchScratch *scratch = nullptr;
 };
 // Whether a scene of n_objects is built on the device (PT_BUILD_DEVICE_MIN, PT_BUILD)
 bool builds_on_device(uint32_t n_objects);
@@ -353,11 +358,24 @@ int create_scene(int device, const pt_scene_desc *d, const DeviceTriangles *asse
 // ---- pt_meshes.cpp ---------------------------------------------------------------------------------------------------------------------
 
 int check_mesh(const pt_mesh_data *m);
+// The front half of pt_scene_create_meshes and pt_scene_pose: the description's triangles at the front of pos / nrm (device memory, room
+// for `capacity` triangles; nrm null: no normal array, the builder makes face normals), with face normals for them where the description
+// has none, and behind them all instances through the batched assembler (pt_mesh_batch.h), chunk after chunk.  Everything is enqueued on
+// `stream`, which is waited for once per chunk; the last chunk's corner sort and smoothing are still in flight when this returns:
+// triangles.ready is their end.  `scratch` must outlive what finish_mesh_scene enqueues on the new scene's stream.
+struct MeshAssembly {
+    DeviceTriangles triangles;                    // what create_scene takes
+    std::vector<uint32_t> inst_first, inst_count; // the instances' object ranges (pt_scene_instance_ranges)
+    uint32_t chunks = 0;                          // one wait each
+    EventPair chain;                              // the device time of the assembly, once `stream` has been waited for
+    std::chrono::steady_clock::time_point front_done; // when the description's triangles had been handed over
+};
+int assemble_mesh_scene(hipStream_t stream, const pt_scene_desc *d, const std::vector<std::unique_ptr<KeptMesh>> &meshes, const std::vector<pt_mesh_instance> &instances,
+                        PtBatchScratch &scratch, uint64_t capacity, float *pos, float *nrm, MeshAssembly *out);
 // From the assembled arrays to the finished scene, with either builder: `assembled` names the triangles in `pos` / `nrm` (device memory:
 // the description's first, then the instances' ranges).  The scene takes `pos` over (pt_scene_get_triangles); on failure it stays
 // with the caller.  Used by pt_scene_create_meshes and pt_scene_pose.
-int finish_mesh_scene(int device, const pt_scene_desc *d, DeviceTriangles &assembled, DevBuf<float> &pos, DevBuf<float> &nrm, bool with_normals,
-                      const std::vector<uint32_t> &inst_first, const std::vector<uint32_t> &inst_count, pt_scene **out);
+int finish_mesh_scene(int device, const pt_scene_desc *d, const MeshAssembly &assembly, DevBuf<float> &pos, pt_scene **out);
 
 // ---- pt_render.cpp: the persistent path kernel (pt_path.hip), one launch per render call ----------------------------------------------
 

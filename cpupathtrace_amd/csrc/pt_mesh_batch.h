@@ -1,6 +1,8 @@
-// pt_mesh_batch.h -- all instances of a pose through ONE chain of launches (pt_mesh_batch.hip, kernels in pt_mesh_batch_kernels.h;
-// DESIGN.md 4.3.2): what pt_mesh_assemble_device (pt_mesh.h) does for one instance, over the concatenated vertices and faces of many,
-// driven by an instance table in device memory.  The results are bit for bit those of one pt_mesh_assemble_device call per instance.
+// pt_mesh_batch.h -- the mesh assembler: indexed meshes under transforms, expanded into triangle arrays in device memory, all instances
+// of a call through ONE chain of launches (pt_mesh_batch.hip, kernels in pt_mesh_batch_kernels.h, where the steps are described;
+// DESIGN.md 4.3.1 and 4.3.2).  The chain works over the concatenated vertices and faces of a chunk of instances, driven by an instance
+// table in device memory.  An instance's triangles do not depend on what else is in its chunk: they are, bit for bit, what io::loadMesh
+// makes of that mesh under that matrix.
 #ifndef PT_MESH_BATCH_H
 #define PT_MESH_BATCH_H
 
@@ -31,7 +33,8 @@ struct PtBatchLimits {
     uint64_t max_vertices = 0xffffffffull, max_faces = 0xffffffffull, max_corners = 0x7fffffffull;
 };
 
-// Device scratch of the chain, grown on demand and never shrunk: a pose of a scene that has been posed before allocates nothing
+// Device scratch of the chain, grown on demand and never shrunk: a pose of a scene that has been posed before allocates nothing.  It
+// may be released only when the streams that were given it have been waited for
 struct PtBatchScratch {
     struct Buf {
         void *ptr = nullptr;

@@ -1,16 +1,26 @@
-// pt_mesh_batch_kernels.h -- the kernels and the launch chain of the batched mesh assembler (pt_mesh_batch.h).  Included
-// once, by pt_mesh_batch.hip; tests/hip/pose_probe.hip includes it as well and, compiled for the host, runs this very source on the CPU.
+// pt_mesh_batch_kernels.h -- the kernels and the launch chain of the mesh assembler (pt_mesh_batch.h): indexed
+// meshes under transforms, expanded into triangle arrays in HBM.  It is everything io::loadMesh does after it has read the numbers
+// (src/scene/mesh.cpp of the reference; src/host/mesh.cpp has the host restatement), so that a mesh is handed over once as vertices +
+// faces and every instance of it is made where the builder (pt_build.hip) reads it.  Included once, by pt_mesh_batch.hip;
+// tests/hip/pose_probe.hip includes it as well and, compiled for the host, runs this very source on the CPU.
 //
 // The index spaces of a chunk's instances are concatenated: global vertex g = vertex_base[i] + v, global face f = face_base[i] + k.
-//   1. kb_transform  one thread per global vertex: k_transform's arithmetic (pt_mesh.hip) with the matrix of the vertex's instance
-//   2. kb_face_keep  one thread per global face and one trailing zero flag: k_face_keep's test, indices against the instance's n_vertices
+//   1. kb_transform  one thread per global vertex: v' = M * (x, y, z, 1) row by row with dot() from zero, then * (1 / w'), with the
+//                    matrix of the vertex's instance   (matrix.h, mat4::operator*)
+//   2. kb_face_keep  one thread per global face and one trailing zero flag: an index outside [0, n_vertices) of the face's instance, two
+//                    coincident corners (written so that NaN rejects) or a cross product of squared length <= 0 drop the face -- all on
+//                    the TRANSFORMED vertices
 //   3. ONE exclusive sum over all flags.  Instances are concatenated in order and survivors keep face order, so the rank of a face IS its
 //      triangle index in the output; kb_counts takes the per-instance counts as differences of the ranks at the face bases
-//   4. kb_expand     k_expand's arithmetic; the corner key of a smooth instance is the GLOBAL vertex, that of a flat one the chunk's
-//                    vertex count, which no vertex has: such corners sort behind all others and no vertex's run holds them
-//   5. one stable radix sort of (key, corner id) over the bits of the vertex count, then kb_smooth, one thread per global vertex of a
-//      smooth instance: k_smooth's serial sum.  Within a vertex's run the corner ids ascend, and ascending global corner id is ascending
-//      face order inside the instance: the additions happen in the reference's order.  No atomics, no tree sums.
+//   4. kb_expand     one thread per global face: the survivor's nine coordinates, its unit normal (Triangle::Triangle) three times, and
+//                    its corners' (key, corner id = survivor * 3 + slot) pairs.  The key of a smooth instance's corner is its GLOBAL
+//                    vertex, that of a flat one's the chunk's vertex count, which no vertex has: such corners sort behind all others
+//                    and no vertex's run holds them
+//   5. smooth only:  one STABLE radix sort of the pairs over the bits of the vertex count, so the corners of a vertex are contiguous and
+//                    their ids ascend, and ascending global corner id is ascending face order inside the instance; kb_smooth, one
+//                    thread per global vertex of a smooth instance, adds the unit face normals serially in that order (float addition
+//                    is not associative: neither atomics nor a tree would give the reference's bits), skips the vertex when the sum's
+//                    squared length is <= 0, and otherwise writes the normalised sum to every corner.
 // Every thread finds its instance by a binary search of the bases in the instance table.  Indices are 64-bit where 9 * index can pass 2^32.
 #ifndef PT_MESH_BATCH_KERNELS_H
 #define PT_MESH_BATCH_KERNELS_H
@@ -182,6 +192,7 @@ __global__ void kb_expand(uint32_t n_total, const PtBatchInstance *__restrict__ 
     }
 }
 
+// The corners of vertex v are sorted_vertex's run of v: [lower bound of v, lower bound of v + 1)
 __device__ __forceinline__ uint32_t lower_bound(const uint32_t *__restrict__ a, uint32_t n, uint32_t key) {
     uint32_t lo = 0, hi = n;
     while(lo < hi) {
@@ -297,7 +308,7 @@ hipError_t pt_mesh_batch_chunk(hipStream_t stream, PtBatchScratch &sc, PtBatchIn
         any_smooth = any_smooth || table[i].smooth != 0u;
         counts[i] = 0;
     }
-    // (one instance alone may not pass the limits either: the callers refuse a mesh of more than PT_MESH_MAX_FACES faces)
+    // (one instance alone may not pass the limits either: the callers refuse a mesh of more than PT_MESH_MAX_FACES faces, pt_mesh.h)
     if(nv64 > 0xffffffffull || 3 * nf64 > 0x7fffffffull || (any_smooth && nrm == nullptr)) {
         if(what != nullptr) {
             *what = "mesh batch arguments";

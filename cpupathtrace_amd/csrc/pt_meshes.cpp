@@ -1,20 +1,54 @@
-// pt_meshes.cpp -- the entry points of include/pt_mesh.h: scenes from indexed meshes and instances.  The meshes are uploaded once, every
-// instance is transformed, filtered, smoothed and expanded in HBM (pt_mesh.hip) behind the description's own triangles, and the arrays go
-// to the device builder where they are (create_scene, pt_api.cpp); the host builder gets them downloaded and takes pt_scene_create's path.
+// pt_meshes.cpp -- the entry points of include/pt_mesh.h, and pt_mesh_assemble_batch of include/pt_pose.h: scenes from indexed meshes and
+// instances.  The meshes are uploaded once, all instances are transformed, filtered, expanded and smoothed in HBM by the batched assembler
+// (pt_mesh_batch.h) behind the description's own triangles, and the arrays go to the device builder where they are (create_scene,
+// pt_api.cpp); the host builder gets them downloaded and takes pt_scene_create's path.  pt_scene_pose (pt_pose.cpp) shares both halves.
 #include "pt_host.h"
 
 using namespace pth;
 
 namespace {
 
-struct StreamGuard {
-    hipStream_t stream = nullptr;
-    ~StreamGuard() {
-        if(stream != nullptr) {
-            (void)hipStreamDestroy(stream);
-        }
+// All instances through the batched assembler, chunk after chunk, each behind the survivors of the one before: positions and normals at
+// pos / nrm (room for `room` triangles), the per-instance counts to counts[n_instances], their sum to *kept.  One wait per chunk; the
+// last chunk's sort and smoothing are only enqueued when this returns.
+int assemble_batch(hipStream_t stream, PtBatchScratch &scratch, const std::vector<std::unique_ptr<KeptMesh>> &meshes, const pt_mesh_instance *instances, uint32_t n_instances,
+                   uint64_t room, float *pos, float *nrm, uint32_t *counts, uint64_t *kept, uint32_t *chunks) {
+    std::vector<PtBatchInstance> table(n_instances);
+    std::vector<uint32_t> nv(n_instances), nf(n_instances);
+    for(uint32_t i = 0; i < n_instances; i++) {
+        const KeptMesh &m = *meshes[instances[i].mesh];
+        PtBatchInstance &t = table[i];
+        t.vertices = m.vertices.ptr;
+        t.faces = m.faces.ptr;
+        t.n_vertices = nv[i] = m.n_vertices;
+        t.n_faces = nf[i] = m.n_faces;
+        t.vertex_base = t.face_base = 0;
+        t.smooth = instances[i].smooth != 0 ? 1u : 0u;
+        t.pad = 0;
+        std::copy(instances[i].transform, instances[i].transform + 16, t.m);
     }
-};
+    *kept = 0;
+    *chunks = 0;
+    const PtBatchLimits limits;
+    for(uint32_t first = 0; first < n_instances;) {
+        const uint32_t end = pt_mesh_batch_chunk_end(nv.data(), nf.data(), n_instances, first, limits);
+        const size_t at = 9 * static_cast<size_t>(*kept);
+        uint64_t kept_here = 0;
+        const char *what = "";
+        const hipError_t e = pt_mesh_batch_chunk(stream, scratch, table.data() + first, end - first, room - *kept, pos + at, nrm != nullptr ? nrm + at : nullptr, counts + first,
+                                                 &kept_here, &what);
+        if(e != hipSuccess) {
+            return fail(PT_ERR_HIP, std::string("batched mesh assembly (") + what + "): " + hipGetErrorString(e));
+        }
+        *kept += kept_here;
+        (*chunks)++;
+        first = end;
+    }
+    if(*kept > room) {
+        return fail(PT_ERR_HIP, "internal: batched mesh assembly kept more triangles than there are faces");
+    }
+    return PT_OK;
+}
 
 } // namespace
 
@@ -65,11 +99,49 @@ void DescCopy::assign(const pt_scene_desc &src) {
     d.light_spectrum = take(light_spectrum, src.light_spectrum, 4 * static_cast<size_t>(src.n_point_lights));
 }
 
-int finish_mesh_scene(int device, const pt_scene_desc *d, DeviceTriangles &assembled, DevBuf<float> &pos, DevBuf<float> &nrm, bool with_normals,
-                      const std::vector<uint32_t> &inst_first, const std::vector<uint32_t> &inst_count, pt_scene **out) {
+int assemble_mesh_scene(hipStream_t stream, const pt_scene_desc *d, const std::vector<std::unique_ptr<KeptMesh>> &meshes, const std::vector<pt_mesh_instance> &instances,
+                        PtBatchScratch &scratch, uint64_t capacity, float *pos, float *nrm, MeshAssembly *out) {
+    const uint32_t n_instances = static_cast<uint32_t>(instances.size());
+    const size_t front = 9 * static_cast<size_t>(d->n_triangles);
+    if(d->n_triangles > 0) {
+        PT_HIP(hipMemcpyAsync(pos, d->tri_pos, front * sizeof(float), hipMemcpyHostToDevice, stream));
+        if(d->tri_nrm != nullptr) {
+            PT_HIP(hipMemcpyAsync(nrm, d->tri_nrm, front * sizeof(float), hipMemcpyHostToDevice, stream));
+        }
+        else if(nrm != nullptr) {
+            PT_HIP(pt_mesh_face_normals(stream, d->n_triangles, pos, nrm));
+        }
+    }
+    out->front_done = std::chrono::steady_clock::now();
+
+    // ---- assembly: one chain of launches for all instances, one wait per chunk for their counts -------------------------------------------
+    PT_HIP(out->chain.begin(stream));
+    out->inst_first.assign(n_instances, 0);
+    out->inst_count.assign(n_instances, 0);
+    uint64_t kept = 0;
+    PT_TRY(assemble_batch(stream, scratch, meshes, instances.data(), n_instances, capacity - d->n_triangles, pos + front, nrm != nullptr ? nrm + front : nullptr,
+                          out->inst_count.data(), &kept, &out->chunks));
+    PT_HIP(out->chain.end(stream));
+
+    DeviceTriangles &t = out->triangles;
+    t.pos = pos;
+    t.nrm = nrm;
+    t.n_triangles = d->n_triangles;
+    t.ranges.clear();
+    for(uint32_t i = 0; i < n_instances; i++) {
+        t.ranges.push_back(PtBatchRange{t.n_triangles, out->inst_count[i], instances[i].material, instances[i].cull_backface != 0 ? 1u : 0u});
+        out->inst_first[i] = d->n_objects + (t.n_triangles - d->n_triangles);
+        t.n_triangles += out->inst_count[i];
+    }
+    t.ready = out->chain.last.e;
+    t.scratch = &scratch;
+    return PT_OK;
+}
+
+int finish_mesh_scene(int device, const pt_scene_desc *d, const MeshAssembly &assembly, DevBuf<float> &pos, pt_scene **out) {
     *out = nullptr;
-    assembled.pos = pos.ptr;
-    assembled.nrm = with_normals ? nrm.ptr : nullptr;
+    const DeviceTriangles &assembled = assembly.triangles;
+    const bool with_normals = assembled.nrm != nullptr;
     const uint32_t n_mesh_tris = assembled.n_triangles - d->n_triangles, n_objs = d->n_objects + n_mesh_tris;
 
     pt_scene *scene = nullptr;
@@ -86,16 +158,16 @@ int finish_mesh_scene(int device, const pt_scene_desc *d, DeviceTriangles &assem
         std::vector<uint8_t> kind(n_objs, static_cast<uint8_t>(PT_OBJ_TRIANGLE)), cull(n_tris);
         std::vector<uint32_t> material(n_tris);
         if(n_tris > 0) {
-            PT_HIP(hipMemcpy(h_pos.data(), pos.ptr, h_pos.size() * sizeof(float), hipMemcpyDeviceToHost));
+            PT_HIP(hipMemcpy(h_pos.data(), assembled.pos, h_pos.size() * sizeof(float), hipMemcpyDeviceToHost));
             if(with_normals) {
-                PT_HIP(hipMemcpy(h_nrm.data(), nrm.ptr, h_nrm.size() * sizeof(float), hipMemcpyDeviceToHost));
+                PT_HIP(hipMemcpy(h_nrm.data(), assembled.nrm, h_nrm.size() * sizeof(float), hipMemcpyDeviceToHost));
             }
         }
         std::copy(d->obj_kind, d->obj_kind + d->n_objects, kind.begin());
         std::copy(d->tri_cull, d->tri_cull + d->n_triangles, cull.begin());
         std::copy(d->tri_material, d->tri_material + d->n_triangles, material.begin());
-        for(const MeshRange &r : assembled.ranges) {
-            std::fill(cull.begin() + r.first_tri, cull.begin() + r.first_tri + r.count, r.cull);
+        for(const PtBatchRange &r : assembled.ranges) {
+            std::fill(cull.begin() + r.first_tri, cull.begin() + r.first_tri + r.count, static_cast<uint8_t>(r.cull));
             std::fill(material.begin() + r.first_tri, material.begin() + r.first_tri + r.count, r.material);
         }
         pt_scene_desc merged = *d;
@@ -111,8 +183,8 @@ int finish_mesh_scene(int device, const pt_scene_desc *d, DeviceTriangles &assem
     // ---- what pt_scene_instance_ranges and pt_scene_get_triangles answer from ----------------------------------------------------------------
     scene->n_desc_objects = d->n_objects;
     scene->n_desc_tris = d->n_triangles;
-    scene->inst_first = inst_first;
-    scene->inst_count = inst_count;
+    scene->inst_first = assembly.inst_first;
+    scene->inst_count = assembly.inst_count;
     scene->desc_ref.resize(d->n_objects);
     {
         uint32_t ti = 0, si = 0;
@@ -120,11 +192,7 @@ int finish_mesh_scene(int device, const pt_scene_desc *d, DeviceTriangles &assem
             scene->desc_ref[i] = d->obj_kind[i] == PT_OBJ_TRIANGLE ? ti++ : (PT_REF_SPHERE | si++);
         }
     }
-    scene->tri_pos_kept.release();
-    scene->tri_pos_kept.ptr = pos.ptr;
-    scene->tri_pos_kept.count = pos.count;
-    pos.ptr = nullptr;
-    pos.count = 0;
+    take(scene->tri_pos_kept, pos);
     *out = scene;
     return PT_OK;
 }
@@ -133,34 +201,79 @@ int finish_mesh_scene(int device, const pt_scene_desc *d, DeviceTriangles &assem
 
 extern "C" {
 
+int pt_mesh_assemble_batch(int device, const pt_mesh_data *meshes, uint32_t n_meshes, const pt_mesh_instance *instances, uint32_t n_instances, uint64_t capacity,
+                           float *out_pos, float *out_nrm, uint32_t *out_counts, uint64_t *n_triangles) {
+    if(n_triangles == nullptr || (n_meshes > 0 && meshes == nullptr) || (n_instances > 0 && instances == nullptr) ||
+       (capacity > 0 && (out_pos == nullptr || out_nrm == nullptr))) {
+        return fail(PT_ERR_INVALID, "null argument");
+    }
+    *n_triangles = 0;
+    std::vector<uint8_t> used(n_meshes, 0);
+    uint64_t faces = 0;
+    for(uint32_t i = 0; i < n_instances; i++) {
+        if(instances[i].mesh >= n_meshes) {
+            return fail(PT_ERR_INVALID, "instance names a mesh that is not there");
+        }
+        used[instances[i].mesh] = 1;
+        faces += meshes[instances[i].mesh].n_faces;
+    }
+    for(uint32_t m = 0; m < n_meshes; m++) {
+        if(used[m] != 0) {
+            PT_TRY(check_mesh(&meshes[m]));
+        }
+    }
+    if(faces > PT_REF_INDEX) {
+        return fail(PT_ERR_UNSUPPORTED, "too many faces");
+    }
+    PT_TRY(check_device(device));
+    PT_HIP(hipSetDevice(device));
+    if(n_instances == 0) {
+        return PT_OK;
+    }
+    StreamGuard sg;
+    PT_HIP(hipStreamCreateWithFlags(&sg.stream, hipStreamNonBlocking));
+    std::vector<std::unique_ptr<KeptMesh>> uploaded(n_meshes);
+    for(uint32_t m = 0; m < n_meshes; m++) {
+        if(used[m] != 0) {
+            uploaded[m].reset(new KeptMesh());
+            PT_TRY(uploaded[m]->upload(meshes[m]));
+        }
+    }
+    DevBuf<float> pos, nrm;
+    PT_HIP(pos.ensure(9 * static_cast<size_t>(faces)));
+    PT_HIP(nrm.ensure(9 * static_cast<size_t>(faces)));
+    PtBatchScratch scratch;
+    std::vector<uint32_t> counts(n_instances, 0);
+    uint64_t kept = 0;
+    uint32_t chunks = 0;
+    const int rc = assemble_batch(sg.stream, scratch, uploaded, instances, n_instances, faces, pos.ptr, nrm.ptr, counts.data(), &kept, &chunks);
+    const size_t n_out = rc == PT_OK ? static_cast<size_t>(std::min<uint64_t>(kept, capacity)) : 0;
+    hipError_t e = hipSuccess;
+    if(n_out > 0) {
+        e = hipMemcpyAsync(out_pos, pos.ptr, 9 * n_out * sizeof(float), hipMemcpyDeviceToHost, sg.stream);
+        if(e == hipSuccess) {
+            e = hipMemcpyAsync(out_nrm, nrm.ptr, 9 * n_out * sizeof(float), hipMemcpyDeviceToHost, sg.stream);
+        }
+    }
+    const hipError_t drained = hipStreamSynchronize(sg.stream); // (whatever happened: before the scratch and the arrays go)
+    PT_TRY(rc);
+    PT_HIP(e);
+    PT_HIP(drained);
+    if(out_counts != nullptr) {
+        std::copy(counts.begin(), counts.end(), out_counts);
+    }
+    *n_triangles = kept;
+    return PT_OK;
+}
+
+// A batch of one
 int pt_mesh_assemble(int device, const pt_mesh_data *mesh, const pt_mesh_instance *instance, uint64_t capacity, float *out_pos, float *out_nrm, uint64_t *n_triangles) {
     if(mesh == nullptr || instance == nullptr || n_triangles == nullptr || (capacity > 0 && (out_pos == nullptr || out_nrm == nullptr))) {
         return fail(PT_ERR_INVALID, "null argument");
     }
-    *n_triangles = 0;
-    PT_TRY(check_mesh(mesh));
-    PT_TRY(check_device(device));
-    PT_HIP(hipSetDevice(device));
-    StreamGuard sg;
-    PT_HIP(hipStreamCreateWithFlags(&sg.stream, hipStreamNonBlocking));
-    KeptMesh up;
-    PT_TRY(up.upload(*mesh));
-    DevBuf<float> pos, nrm;
-    PT_HIP(pos.ensure(9 * static_cast<size_t>(mesh->n_faces)));
-    PT_HIP(nrm.ensure(9 * static_cast<size_t>(mesh->n_faces)));
-    uint32_t kept = 0;
-    const char *what = "";
-    const hipError_t e = pt_mesh_assemble_device(sg.stream, up.view(), instance->transform, instance->smooth != 0, pos.ptr, nrm.ptr, &kept, nullptr, &what);
-    if(e != hipSuccess) {
-        return fail(PT_ERR_HIP, std::string("mesh assembly (") + what + "): " + hipGetErrorString(e));
-    }
-    const size_t n_out = static_cast<size_t>(std::min<uint64_t>(kept, capacity));
-    if(n_out > 0) {
-        PT_HIP(hipMemcpy(out_pos, pos.ptr, 9 * n_out * sizeof(float), hipMemcpyDeviceToHost));
-        PT_HIP(hipMemcpy(out_nrm, nrm.ptr, 9 * n_out * sizeof(float), hipMemcpyDeviceToHost));
-    }
-    *n_triangles = kept;
-    return PT_OK;
+    pt_mesh_instance one = *instance;
+    one.mesh = 0; // (the instance's own mesh index is not read: `mesh` is the mesh)
+    return pt_mesh_assemble_batch(device, mesh, 1, &one, 1, capacity, out_pos, out_nrm, nullptr, n_triangles);
 }
 
 int pt_scene_create_meshes(int device, const pt_scene_desc *d, const pt_mesh_data *meshes, uint32_t n_meshes, const pt_mesh_instance *instances, uint32_t n_instances,
@@ -203,12 +316,11 @@ int pt_scene_create_meshes(int device, const pt_scene_desc *d, const pt_mesh_dat
     PT_HIP(hipSetDevice(device));
 
     using clock = std::chrono::steady_clock;
-    auto ms_since = [](clock::time_point t0) { return std::chrono::duration<float, std::milli>(clock::now() - t0).count(); };
     const auto t_upload = clock::now();
     StreamGuard sg;
     PT_HIP(hipStreamCreateWithFlags(&sg.stream, hipStreamNonBlocking));
-    // ---- upload: every mesh that is used, once; the description's own triangles in front of the arrays the instances are expanded into ----
-    // (the scene keeps them, with the instance table and a copy of the description, for pt_scene_pose)
+    // ---- upload: every mesh that is used, once (the scene keeps them, with the instance table and a copy of the description, for
+    // pt_scene_pose) ----
     std::unique_ptr<PoseKeep> keep(new PoseKeep());
     keep->meshes.resize(n_meshes);
     uint64_t upload_bytes = 0;
@@ -219,6 +331,9 @@ int pt_scene_create_meshes(int device, const pt_scene_desc *d, const pt_mesh_dat
             upload_bytes += 12ULL * meshes[m].n_vertices + 12ULL * meshes[m].n_faces;
         }
     }
+    keep->instances.assign(instances, instances + n_instances);
+    keep->any_smooth = any_smooth;
+    keep->capacity = capacity;
     // without normals from the caller and without a smooth instance there is no normal array: the builder makes face normals itself
     const bool with_normals = any_smooth || (d->n_triangles > 0 && d->tri_nrm != nullptr);
     DevBuf<float> pos, nrm;
@@ -226,52 +341,39 @@ int pt_scene_create_meshes(int device, const pt_scene_desc *d, const pt_mesh_dat
     if(with_normals) {
         PT_HIP(nrm.ensure(9 * static_cast<size_t>(capacity)));
     }
-    if(d->n_triangles > 0) {
-        PT_HIP(hipMemcpy(pos.ptr, d->tri_pos, 9 * static_cast<size_t>(d->n_triangles) * sizeof(float), hipMemcpyHostToDevice));
-        if(d->tri_nrm != nullptr) {
-            PT_HIP(hipMemcpy(nrm.ptr, d->tri_nrm, 9 * static_cast<size_t>(d->n_triangles) * sizeof(float), hipMemcpyHostToDevice));
-        }
-        else if(with_normals) {
-            PT_HIP(pt_mesh_face_normals(sg.stream, d->n_triangles, pos.ptr, nrm.ptr));
-        }
-    }
-    const float upload_ms = ms_since(t_upload);
 
-    // ---- assembly: instance after instance, each behind the survivors of the one before (its count is read back) --------------------------
-    DeviceTriangles assembled;
-    assembled.n_triangles = d->n_triangles;
-    std::vector<uint32_t> inst_first(n_instances), inst_count(n_instances);
-    float assembly_ms = 0.0F;
-    for(uint32_t i = 0; i < n_instances; i++) {
-        const pt_mesh_instance &in = instances[i];
-        const size_t at = 9 * static_cast<size_t>(assembled.n_triangles);
-        uint32_t kept = 0;
-        float ms = 0.0F;
-        const char *what = "";
-        const hipError_t e = pt_mesh_assemble_device(sg.stream, keep->meshes[in.mesh]->view(), in.transform, in.smooth != 0, pos.ptr + at,
-                                                     with_normals ? nrm.ptr + at : nullptr, &kept, &ms, &what);
-        if(e != hipSuccess) {
-            return fail(PT_ERR_HIP, std::string("mesh assembly (") + what + "): " + hipGetErrorString(e));
+    // ---- assembly, with a scratch of this call's own: a scene that is never posed keeps none.  However the call ends, the scratch and
+    // the arrays go only when nothing reads them any more: the chain on the assembly stream, and the range fill on the new scene's
+    // stream, which reads the scratch's range table (a scene that failed has taken its stream along: then the device is waited for) ----
+    PtBatchScratch scratch;
+    std::unique_ptr<pt_scene> scene;
+    struct Drain {
+        hipStream_t assembly, scene;
+        PtBatchScratch &scratch;
+        ~Drain() {
+            (void)hipStreamSynchronize(assembly);
+            (void)(scene != nullptr ? hipStreamSynchronize(scene) : hipDeviceSynchronize());
+            scratch.release();
         }
-        assembly_ms += ms;
-        assembled.ranges.push_back(MeshRange{assembled.n_triangles, kept, static_cast<uint8_t>(in.cull_backface != 0 ? 1 : 0), in.material});
-        inst_first[i] = d->n_objects + (assembled.n_triangles - d->n_triangles);
-        inst_count[i] = kept;
-        assembled.n_triangles += kept;
-    }
+    } drain{sg.stream, nullptr, scratch};
+    MeshAssembly assembly;
+    PT_TRY(assemble_mesh_scene(sg.stream, d, keep->meshes, keep->instances, scratch, capacity, pos.ptr, with_normals ? nrm.ptr : nullptr, &assembly));
+    const float upload_ms = std::chrono::duration<float, std::milli>(assembly.front_done - t_upload).count();
+    pt_scene *built = nullptr;
+    PT_TRY(finish_mesh_scene(device, d, assembly, pos, &built));
+    scene.reset(built);
+    drain.scene = scene->stream;
     PT_HIP(hipStreamSynchronize(sg.stream));
-    pt_scene *scene = nullptr;
-    PT_TRY(finish_mesh_scene(device, d, assembled, pos, nrm, with_normals, inst_first, inst_count, &scene));
-    keep->instances.assign(instances, instances + n_instances);
+    PT_HIP(hipStreamSynchronize(scene->stream)); // (an error of either stream is this call's; ~Drain waits again whatever happens)
+    float assembly_ms = 0.0F;
+    PT_HIP(assembly.chain.ms(&assembly_ms));
     keep->desc.assign(*d);
-    keep->any_smooth = any_smooth;
-    keep->capacity = capacity;
     scene->pose = std::move(keep);
     if(env_int("PT_DEBUG", 0) != 0) {
         std::fprintf(stderr, "[pt] mesh scene: %u instances, %u of %llu triangles kept; mesh upload %.1f ms (%llu bytes), assembly %.1f ms on the device\n", n_instances,
-                     assembled.n_triangles, static_cast<unsigned long long>(capacity), upload_ms, static_cast<unsigned long long>(upload_bytes), assembly_ms);
+                     assembly.triangles.n_triangles, static_cast<unsigned long long>(capacity), upload_ms, static_cast<unsigned long long>(upload_bytes), assembly_ms);
     }
-    *out = scene;
+    *out = scene.release();
     return PT_OK;
 }
 

@@ -1,4 +1,4 @@
-"""Scenes from indexed meshes and instances, assembled on the device (include/pt_mesh.h, pt_mesh.hip), bit for bit against io::loadMesh:
+"""Scenes from indexed meshes and instances, assembled on the device (include/pt_mesh.h, pt_mesh_batch.hip), bit for bit against io::loadMesh:
 the golden answers of the compiled reference (tests/golden/mesh_assembly.npz) and the host library's loader (pth_load_mesh, which
 test_oracle_vs_reference.py holds equal to the reference) for pt_mesh_assemble, and a flat pt_scene_create scene of the loader's triangles
 for pt_scene_create_meshes: tree, emitters, hits, triangles and pixels.  No tolerance anywhere; NaN compares by NaN-ness."""
@@ -236,3 +236,80 @@ def test_degenerate_mesh_as_a_scene(host, mode, smooth):
     mesh_cases.share_conditions(counts[0])
     assert counts[0] < len(f) and counts[1] < len(f)
     _assert_same_scene(sa, sb_, counts, mode, spp=(4, 4))
+
+
+# ---- one creation call, one chain: what several instances of different kinds share ---------------------------------------------------------
+# Every scene here is compared as created, never posed.
+
+COLLAPSE = np.diag(np.array([0, 0, 0, 1], F))  # every vertex to the origin: every face is rejected (as tests/test_gpu_pose.py)
+
+
+@pytest.mark.parametrize("mode", ["host", "device"])
+def test_smooth_and_flat_instances_around_an_empty_one(host, mode):
+    """A smooth instance, one whose every face is rejected, and a flat one in one call: the flat instance's corners take the key no vertex
+    has, and the empty range lies between the two survivors."""
+    from cpupathtrace_amd import binding
+    v, f = scenes.bumpy_sphere_vertices(24, 16)
+    v2, f2 = mesh_cases.MESHES["faces64"]
+    instances = [(v, f, IN_BOX, "glass", False, True), (v2, f2, COLLAPSE, None, True, True), (v2, f2, SMALL_IN_BOX, None, False, False)]
+    sa, sb_, counts = _pair(host, instances, GLASS)
+    assert counts[0] > 0 and counts[1] == 0 and counts[2] > 0
+    _assert_same_scene(sa, sb_, counts, mode, spp=(4, 4))
+    with env(PT_BUILD=mode):
+        g = binding.Scene(sa)
+        try:
+            first, count = g.instance_ranges()
+            assert count.tolist() == counts and first[1] == first[2] == first[0] + counts[0]
+        finally:
+            g.close()
+
+
+@pytest.mark.parametrize("mode", ["host", "device"])
+def test_flat_instances_without_any_normals(host, mode):
+    """No smooth instance and no normals in the description: there is no normal array at all, the builder makes every face normal."""
+    v, f = scenes.bumpy_sphere_vertices(24, 16)
+    v2, f2 = mesh_cases.MESHES["faces64"]
+    instances = [(v, f, IN_BOX, "glass", False, False), (v2, f2, SMALL_IN_BOX, None, True, False), (v, f, _shift(IN_BOX, 0.2, 0.1, -0.2), None, False, False)]
+    sa, sb_, counts = _pair(host, instances, GLASS, desc_normals=False)
+    assert min(counts) > 0
+    _assert_same_scene(sa, sb_, counts, mode, spp=(4, 4))
+
+
+@pytest.mark.parametrize("mode", ["host", "device"])
+def test_description_without_normals_and_a_smooth_instance(host, mode):
+    """The description's triangles come without normals and one of two instances is smooth: the front of the normal array is filled with
+    face normals on the device, the rest by the assembly."""
+    v, f = scenes.bumpy_sphere_vertices(24, 16)
+    v2, f2 = mesh_cases.MESHES["faces64"]
+    instances = [(v2, f2, SMALL_IN_BOX, None, True, False), (v, f, IN_BOX, "glass", False, True)]
+    sa, sb_, counts = _pair(host, instances, GLASS, desc_normals=False)
+    assert min(counts) > 0
+    _assert_same_scene(sa, sb_, counts, mode, spp=(4, 4))
+
+
+@pytest.mark.parametrize("mode", ["host", "device"])
+def test_eighteen_instances_in_one_creation(host, mode):
+    """The nine meshes of the assembler's tests, flat and smooth, created in one call (the instances tests/test_gpu_pose.py poses): the
+    triangles read back per instance range are the loader's."""
+    from cpupathtrace_amd import binding
+    from tests import pose_cases
+    instances = [(v, f, _shift(SMALL_IN_BOX, 0.01 * i, 0, 0), None, False, bool(s)) for i, (v, f, s) in
+                 enumerate((v, f, s) for v, f in pose_cases.MESH_LIST for s in (0, 1))]
+    sa, sb_, counts = _pair(host, instances, GLASS)
+    assert len(sa["instances"]) == 18 and len(sa["meshes"]) == 9
+    _assert_same_scene(sa, sb_, counts, mode, frame=False)
+    with env(PT_BUILD=mode):
+        g = binding.Scene(sa)
+        try:
+            first, count = g.instance_ranges()
+            assert count.tolist() == counts
+            at = len(sa["tri_pos"])  # (the flat scene has the loader's triangles behind the description's, in instance order)
+            for i, n in enumerate(counts):
+                if n > 0:
+                    pos, nrm, _, _ = g.triangles(int(first[i]), n)
+                    assert_bits_equal(pos, sb_["tri_pos"][at:at + n], "instance %d: positions" % i)
+                    assert_bits_equal(nrm, sb_["tri_nrm"][at:at + n], "instance %d: normals" % i)
+                at += n
+            assert at == len(sb_["tri_pos"])
+        finally:
+            g.close()

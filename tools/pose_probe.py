@@ -4,8 +4,8 @@ a warm-up pose; every figure is the median of --repeat (5 at least) runs.
     python tools/pose_probe.py many     [--instances 256] [--mesh-n 120]   all instances posed: pt_scene_pose against destroy + pt_scene_create_meshes
     python tools/pose_probe.py big      [--instances 16] [--mesh-n 1900]   the same with 16 x 7.2 M faces
     python tools/pose_probe.py one      [--instances 256] [--mesh-n 120]   one moved instance among many (the subset form), against the same
-    python tools/pose_probe.py assembly [--mesh-n 120]                      the batched assembly alone (pose_info.assembly_ms and the wall time around it)
-                                                                            against creation's per-instance loop, at 16 and 256 instances
+    python tools/pose_probe.py assembly [--mesh-n 120]                      the assembly alone (pose_info.assembly_ms and the wall time around it)
+                                                                            against the same chain inside a creation, at 16 and 256 instances
     python tools/pose_probe.py render   [--instances 256] [--mesh-n 120]   the first render (1024 x 1024, 4 spp) after a pose / of a fresh scene
 
 The library's phases come from pt_pose_info and from its PT_DEBUG lines (tools/ingest_probe.py).  Every part prints one JSON line."""
@@ -139,17 +139,17 @@ def main():
             poses = [matrices(scenes, g, k) for k in range(repeat + 2)]
             live, _ = create(binding, description(scenes, verts, faces, g, poses[0]))
             pose(live, poses[1])
-            batched, looped = [], []
+            posed, created = [], []
             for k in range(1, repeat + 1):
                 info = pose(live, poses[k])
-                batched.append({"assembly_ms": info["assembly_ms"], "syncs": float(info["assembly_syncs"]), "pose_wall_ms": info["wall_ms"]})
+                posed.append({"assembly_ms": info["assembly_ms"], "syncs": float(info["assembly_syncs"]), "pose_wall_ms": info["wall_ms"]})
                 other, made = create(binding, description(scenes, verts, faces, g, poses[k]))
                 other.close()
-                # the loop's own wall time is what creation spends beside its other phases
+                # the assembly's own wall time is what creation spends beside its other phases
                 rest = sum(made.get(x, 0.0) for x in ("host_preparation_ms", "upload_ms", "device_tree_ms", "rest_ms", "mesh_upload_ms"))
-                looped.append({"assembly_ms": made.get("assembly_ms", float("nan")), "syncs": 2.0 * c, "loop_wall_ms": made["wall_ms"] - rest})
+                created.append({"assembly_ms": made.get("assembly_ms", float("nan")), "assembly_wall_ms": made["wall_ms"] - rest})
             live.close()
-            result["%d_instances" % c] = {"batched": medians(batched), "per_instance_loop": medians(looped)}
+            result["%d_instances" % c] = {"pose": medians(posed), "creation": medians(created)}
     else:
         poses = [matrices(scenes, grid, k) for k in range(repeat + 2)]
         camera = scenes.camera((0, 0, -3.0 * grid), (0, 0, 0), (0, 1, 0), 1.0, 1.0, -1.0)
