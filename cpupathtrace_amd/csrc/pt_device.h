@@ -187,32 +187,41 @@ PT_D float slab_walk(V3 lo, V3 hi, V3 o, V3 inv) {
 
 // ---- a-6: Triangle::getIntersection, src/scene/object.cpp:146-182 -------------------------------------------------------
 
+// STRAIGHT-LINE code: the walk runs it for the few lanes that stand on a leaf while the rest of the wavefront waits (pt_trace.h:
+// slow_step), where each early return was a divergent region of its own.  Every product, sum and the one division is the reference's, in
+// its order; the early returns are selects of -1 on exactly the reference's predicates, so a NaN u or v -- which fails none of them
+// there -- fails none here, and a lane the reference turns away early (det = 0, +-inf or NaN included) divides and multiplies on and
+// drops what it computed.
+// `opaque` keeps the compiler from pairing two scalar products into one packed multiply where the pair's operands are not neighbours
+// in registers: it paid for each such pair with the moves that bring them together (20 moves in this function as plain code).  ALL_APART:
+// the twelve products of the two cross products and the first barycentric's dot product each on their own -- 5 moves and 11 instructions
+// less than plain, and what the one-walk-per-lane kernels of pt_walks.hip need to stay within 128 registers (122; 130 as plain code).  The
+// path kernel takes the other form, four products of the second cross product apart (12 moves, 5 instructions less than plain): with
+// any other of 126 subsets tried its instantiations with the wide slot word spill 30 registers in their shading pass,
+// over the cap of tests/test_kernel_resources.py.  The arithmetic is the same in both: `opaque` is the identity.
+PT_D float opaque(float x) {
+    asm("" : "+v"(x));
+    return x;
+}
+PT_D V3 cross_apart(V3 a, V3 b) {
+    return v3(opaque(a.y * b.z) - opaque(a.z * b.y), opaque(a.z * b.x) - opaque(a.x * b.z), opaque(a.x * b.y) - opaque(a.y * b.x));
+}
+template<bool ALL_APART = true>
 PT_D float tri_intersect(V3 a, V3 ab, V3 ac, bool cull, V3 o, V3 d) {
     const float epsilon = 1E-6f;
-    V3 pvec = cross(d, ac);
+    V3 pvec = ALL_APART ? cross_apart(d, ac) : cross(d, ac);
     float det = dot(ab, pvec);
-    if(cull) {
-        if(det <= epsilon) {
-            return -1.0f;
-        }
-    }
-    else {
-        if(__builtin_fabsf(det) <= epsilon) {
-            return -1.0f;
-        }
-    }
+    bool miss = (cull ? det : __builtin_fabsf(det)) <= epsilon;
     float inv_det = 1.0f / det;
     V3 tvec = o - a;
-    float u = dot(tvec, pvec) * inv_det;
-    if(u < 0 || u > 1) {
-        return -1.0f;
-    }
-    V3 qvec = cross(tvec, ab);
+    float u = (ALL_APART ? opaque(dot(tvec, pvec)) : dot(tvec, pvec)) * inv_det;
+    miss |= (u < 0) | (u > 1);
+    V3 qvec = ALL_APART ? cross_apart(tvec, ab)
+                        : v3(opaque(tvec.y * ab.z) - opaque(tvec.z * ab.y), opaque(tvec.z * ab.x) - opaque(tvec.x * ab.z), tvec.x * ab.y - tvec.y * ab.x);
     float v = dot(d, qvec) * inv_det;
-    if(v < 0 || u + v > 1) {
-        return -1.0f;
-    }
-    return dot(ac, qvec) * inv_det;
+    miss |= (v < 0) | (u + v > 1);
+    const float t = dot(ac, qvec) * inv_det;
+    return miss ? -1.0f : t;
 }
 
 // a-7: Triangle::getSurfaceNormal, object.cpp:126-144

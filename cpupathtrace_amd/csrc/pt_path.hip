@@ -880,7 +880,7 @@ __global__ __launch_bounds__(256, PT_PATH_WAVES) void pt_path_kernel(const PtPat
     }
     __syncthreads(); // the only barrier: from here on the four wavefronts of the workgroup never wait for each other
 
-    Tracer<STACK_LDS, IN_LDS> tr;
+    Tracer<STACK_LDS, IN_LDS, true> tr;
     if(IN_LDS) {
         tr.recs = (typename RecPtr<IN_LDS>::type)(lds_f4_cptr)lds_recs;
     }
@@ -922,7 +922,7 @@ __global__ __launch_bounds__(256, PT_PATH_WAVES) void pt_path_kernel(const PtPat
     w.cur = PT_REF_NONE;
     w.sp = 0;
     w.occluded = false;
-    typename Tracer<STACK_LDS, IN_LDS>::Rec rec;
+    typename Tracer<STACK_LDS, IN_LDS, true>::Rec rec;
     rec.r0 = rec.r1 = rec.r2 = rec.r3 = (f4v){0.0f, 0.0f, 0.0f, 0.0f};
     float4 win_o = make_float4(0, 0, 0, 0), win_d = make_float4(0, 0, 0, __uint_as_float(PT_DEST_NULL)); // the lane's ray of the ring's window
     uint32_t n_nodes = 0, n_leaves = 0, n_rays = 0, n_shadow = 0, n_samples = 0, n_vertices = 0;
@@ -1224,6 +1224,11 @@ __global__ __launch_bounds__(256, PT_PATH_WAVES) void pt_path_kernel(const PtPat
         slot[5] = (unsigned long long)w_passes | ((t_shade >> 10) << 32);
         slot[4] = (unsigned long long)w_steps | ((t_burst >> 10) << 32);
         slot[3] = (unsigned long long)n_shadow | (((__builtin_amdgcn_s_memtime() - t_begin) >> 10) << 32);
+        // ... and, of the bursts, in Tracer::slow_step (kilo-cycles), with its invocations, the lanes it served and the trips of its pop loop
+        slot[0] = (unsigned long long)n_nodes | ((tr.slow_cycles >> 10) << 32);
+        slot[1] = (unsigned long long)n_leaves | ((unsigned long long)tr.slow_calls << 32);
+        slot[2] = (unsigned long long)n_rays | ((unsigned long long)tr.slow_served << 32);
+        slot[7] = (unsigned long long)n_vertices | ((unsigned long long)tr.slow_trips << 32);
 #endif
     }
 }

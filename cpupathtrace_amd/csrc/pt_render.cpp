@@ -148,6 +148,9 @@ int ensure_path_workspace(pt_scene *s, uint32_t n, PtPathConfig *out_cfg, const 
     // Cornell / Box with full rows (profiles/r03_lds_scene_knobs.txt); wavefronts with less than a row of slots keep 8
     // trees in HBM of up to 24 levels (720 K triangles) with full rows: 12 instead of 8 brings 1-4 % (3 K triangles 599 -> 610, 20 K 552 -> 564, 180 K 523 -> 530,
     // 720 K 483 -> 488); the benchmark's 30 levels keep 8 (430 against 425)
+    // Swept again with the rare step as straight-line code, a third cheaper (profiles/slow_step_leaf_min_sweep.txt; 2 / 4 / 6 / 8 / 12 / 16): benchmark frame
+    // 445 / 475 / 489 / 490 / 492 / 480, Box 1403 / 1413 / 1428 / 1444 / 1458 / 1473, Cornell 772 / 795 / 813 / 827 / 851 / 865 Msamples/s.  The optimum did
+    // not move: 8 against 12 on the benchmark frame is less than one run differs from the next (spreads of 1.5 - 3.9), the scenes in LDS still want 16.
     int leaf_default = cfg.in_lds ? (slots_per_wave >= 64U ? 16 : 8) : static_cast<int>(std::min<uint32_t>(std::max<uint32_t>(slots_per_wave / 8U, 2U), 8U));
     if(!cfg.in_lds && slots_per_wave >= 64U && s->depth <= 24U) {
         leaf_default = 12;
@@ -438,13 +441,18 @@ int path_stats(pt_scene *s, const PtStreams &T, const PtPathConfig &cfg, bool co
     PT_HIP(hipEventElapsedTime(&ms, ev_begin.e, ev_end.e));
     std::vector<unsigned long long> slots(static_cast<size_t>(s->path_waves) * 8U);
     PT_HIP(hipMemcpy(slots.data(), s->path_wave_counters.ptr, slots.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    unsigned long long sum[8] = {0, 0, 0, 0, 0, 0, 0, 0}, kcycles[4] = {0, 0, 0, 0};
+    unsigned long long sum[8] = {0, 0, 0, 0, 0, 0, 0, 0}, high[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     for(size_t i = 0; i < slots.size(); i++) {
-        // (a PT_PATH_TIMING build packs kilo-cycle totals into the high words of four slots; they are zero otherwise: a wavefront's counts fit 32 bits)
+        // (a PT_PATH_TIMING build packs kilo-cycle totals and slow_step's counts into the high words; they are zero otherwise: a wavefront's counts fit 32 bits)
         const size_t k = i & 7U;
-        sum[k] += (k >= 3 && k <= 6) ? (slots[i] & 0xffffffffULL) : slots[i];
-        if(k >= 3 && k <= 6) {
-            kcycles[k - 3] += slots[i] >> 32;
+        sum[k] += slots[i] & 0xffffffffULL;
+        high[k] += slots[i] >> 32;
+    }
+    const unsigned long long *kcycles = high + 3; // the waves' lifetimes, traversal bursts, shading passes, the inner loop
+    if(kcycles[0] == 0) {
+        // (not a timing build: the other four counters are whole 64-bit words)
+        for(const size_t k : {size_t{0}, size_t{1}, size_t{2}, size_t{7}}) {
+            sum[k] += high[k] << 32;
         }
     }
     if(kcycles[0] != 0 && env_int("PT_DEBUG", 0) != 0) {
@@ -452,6 +460,12 @@ int path_stats(pt_scene *s, const PtStreams &T, const PtPathConfig &cfg, bool co
         std::fprintf(stderr, "[pt] wave time: %.1f %% in shading passes, %.1f %% in traversal bursts, %.1f %% in the inner loop outside the bursts (of the waves' lifetimes; %llu kilo-cycles in all)\n",
                      100.0 * static_cast<double>(kcycles[2]) / all, 100.0 * static_cast<double>(kcycles[1]) / all,
                      100.0 * (static_cast<double>(kcycles[3]) - static_cast<double>(kcycles[1])) / all, kcycles[0]);
+        // the rare step's part of the bursts: high words of slots 0, 1, 2 and 7 (kilo-cycles, invocations, lanes served, trips of the pop loop)
+        const double calls = static_cast<double>(std::max<unsigned long long>(high[1], 1));
+        std::fprintf(stderr, "[pt] slow_step: %.1f %% of the waves' lifetimes (%.1f %% of the bursts); %.4f invocations per wave step, %.2f lanes and %.2f pop trips per invocation (%llu invocations)\n",
+                     100.0 * static_cast<double>(high[0]) / all, 100.0 * static_cast<double>(high[0]) / static_cast<double>(std::max<unsigned long long>(kcycles[1], 1)),
+                     static_cast<double>(high[1]) / static_cast<double>(std::max<unsigned long long>(sum[4], 1)), static_cast<double>(high[2]) / calls,
+                     static_cast<double>(high[7]) / calls, high[1]);
     }
     PtDevCounters done{};
     PT_HIP(hipMemcpy(&done, s->counters.ptr, sizeof(done), hipMemcpyDeviceToHost));

@@ -105,11 +105,18 @@ struct Walk {
 #define PT_STAMP(k) do { } while(0)
 #endif
 
-template<int STACK_LDS, bool IN_LDS>
+// (PATH_KERNEL: which form of the triangle test slow_step takes -- pt_device.h: tri_intersect)
+template<int STACK_LDS, bool IN_LDS, bool PATH_KERNEL = false>
 struct Tracer {
     static_assert((STACK_LDS & (STACK_LDS - 1)) == 0, "the stack window is indexed with a mask");
 #ifdef PT_STEP_STAMPS
     mutable unsigned long long stamp_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, stamp_last = 0;
+#endif
+#ifdef PT_PATH_TIMING
+    // diagnostic build: what slow_step costs a wavefront (the same values in every lane) -- shader-clock cycles inside it, its invocations, the
+    // lanes it served (leaves + walks that came to pop) and the trips of its pop loop
+    mutable unsigned long long slow_cycles = 0;
+    mutable uint32_t slow_calls = 0, slow_served = 0, slow_trips = 0;
 #endif
     typedef typename RecPtr<IN_LDS>::type rec_ptr;
     rec_ptr recs;         // the 64-byte records the tree's references index: leaves, then pairs (pt_types.h)
@@ -256,67 +263,73 @@ struct Tracer {
 
     // Everything that is not the common step: the leaves in `leaf_mask` (Object::getIntersection) and the walks that must (go on) pop(ping).
     // n_leaves counts visits for the whole wavefront (the same value in every lane).
+    // It runs for the lanes that wait for it while the others stand still, and on the flagship it is a fifth of a wavefront's life
+    // (profiles/slow_step_share.txt), so it is shaped like node_step: ONE divergent region around the leaf test, whose
+    // result is applied with selects on lane predicates, and a pop loop that carries nothing but `sp` and `cur` -- "has to pop" IS
+    // cur == PT_REF_POPPING, a leaf lane that goes on popping takes that code -- with one test at its bottom and one way out.  (With a
+    // flag beside cur and the test on top, every trip copied cur and sp to other registers and back and carried four lane masks
+    // through the scalar unit; the early returns of the triangle test and the nested tests behind it were sixteen divergent regions.)
     PT_D void slow_step(Walk &w, Rec &R, unsigned long long leaf_mask, uint32_t &n_leaves) const {
         uint32_t cur = w.cur;
-        bool need_pop = cur == PT_REF_POPPING;
-        bool moved = false;
+#ifdef PT_PATH_TIMING
+        const unsigned long long t_slow = __builtin_amdgcn_s_memtime();
+        slow_calls++;
+        slow_served += (uint32_t)__popcll(leaf_mask) + (uint32_t)__popcll(__ballot(cur == PT_REF_POPPING));
+#endif
         if(leaf_mask != 0ULL) {
             n_leaves += (uint32_t)__popcll(leaf_mask);
             if(__builtin_amdgcn_inverse_ballot_w64(leaf_mask)) {
                 // a leaf reports Object::getIntersection unconditionally (scene.cpp:105-109); among the non-negative hits the smallest wins and a
                 // later-visited leaf wins ties (scene.cpp:141-146); a shadow walk ends at its first hit below the threshold (worker.cpp:86)
                 const float4 q0 = to_f4(R.r0), q1 = to_f4(R.r1), q2 = to_f4(R.r2);
-                float t_leaf;
+                // (the triangle test is straight-line code and runs on a sphere's record too, where its result is replaced: a wavefront
+                // without a lane on a sphere skips the sphere's code as a whole, and no scene pays for a branch around the triangle's)
+                const TriRec tr = tri_unpack(q0, q1, q2);
+                float t_leaf = tri_intersect<!PATH_KERNEL>(tr.a, tr.ab, tr.ac, (tr.obj_cull >> 31) != 0, w.o, w.d);
                 if(cur & PT_REF_SPHERE) {
                     t_leaf = sphere_intersect(v3(q0.x, q0.y, q0.z), q0.w, w.o, w.d);
                 }
-                else {
-                    const TriRec tr = tri_unpack(q0, q1, q2);
-                    t_leaf = tri_intersect(tr.a, tr.ab, tr.ac, (tr.obj_cull >> 31) != 0, w.o, w.d);
-                }
-                need_pop = true;
-                if(t_leaf >= 0.0f) {
-                    if((w.dest & PT_DEST_SHADOW) && t_leaf < w.thr) {
-                        w.occluded = true;
-                        need_pop = false;
-                    }
-                    else {
-                        if(w.best_ref == PT_REF_NONE || !(w.best_t < t_leaf)) {
-                            w.best_t = t_leaf;
-                            w.best_ref = cur;
-                        }
-                        w.set_t_max(fmin_std(w.t_max, t_leaf));
-                    }
-                }
-                cur = PT_REF_NONE;
+                const bool hit = t_leaf >= 0.0f;
+                const bool ends = hit & ((w.dest & PT_DEST_SHADOW) != 0u) & (t_leaf < w.thr); // the shadow walk is over: occluded
+                const bool counts = hit & !ends;
+                const bool best = counts & ((w.best_ref == PT_REF_NONE) | !(w.best_t < t_leaf));
+                w.best_t = best ? t_leaf : w.best_t;
+                w.best_ref = best ? cur : w.best_ref;
+                w.set_t_max((counts & (t_leaf < w.t_max)) ? t_leaf : w.t_max); // std::min(t_max, t_leaf); t_lim of an unchanged t_max is the value it had
+                w.occluded = w.occluded | ends;
+                cur = ends ? PT_REF_NONE : PT_REF_POPPING;
             }
         }
         // pop: the first parked node whose entry distance is still below t_max (scene.cpp:137: re-tested against the then-current distance);
-        // the sentinel at the bottom passes the test and ends the walk
-        if(__ballot(need_pop) != 0ULL) {
+        // the sentinel at the bottom passes the test and ends the walk.  Every lane reads the entry below ITS top (a slot of its own column
+        // whatever sp is: the index is masked) and only the popping ones take it; the one divergent region of a trip is the window moving down.
+        const bool popper = cur == PT_REF_POPPING;
+        if(__ballot(popper) != 0ULL) {
             uint32_t sp = w.sp;
             const float t_max = w.t_max;
-            while(__ballot(need_pop) != 0ULL) {
-                if(need_pop) {
-                    sp--;
-                    const uint32_t slot = (sp & (uint32_t)(STACK_LDS - 1)) * 256u;
-                    const u2v e = stack_l[slot];
-                    if(sp >= (uint32_t)STACK_LDS) {
-                        stack_l[slot] = my_spill[sp - STACK_LDS]; // the window moves down: the entry that left it last comes back
-                    }
-                    if(__uint_as_float(e.y) < t_max) {
-                        cur = e.x;
-                        need_pop = false;
-                        moved = true;
-                    }
+            do {
+#ifdef PT_PATH_TIMING
+                slow_trips++;
+#endif
+                const bool popping = cur == PT_REF_POPPING;
+                const uint32_t below = sp - 1u;
+                const uint32_t slot = (below & (uint32_t)(STACK_LDS - 1)) * 256u;
+                const u2v e = stack_l[slot];
+                if(popping & (below >= (uint32_t)STACK_LDS)) {
+                    stack_l[slot] = my_spill[below - STACK_LDS]; // the window moves down: the entry that left it last comes back
                 }
-            }
+                sp = popping ? below : sp;
+                cur = (popping & (__uint_as_float(e.y) < t_max)) ? e.x : cur;
+            } while(__ballot(cur == PT_REF_POPPING) != 0ULL);
             w.sp = sp;
         }
         w.cur = cur;
-        if(moved & (cur != PT_REF_NONE)) {
+        if(popper & (cur != PT_REF_NONE)) {
             fetch(cur, R);
         }
+#ifdef PT_PATH_TIMING
+        slow_cycles += __builtin_amdgcn_s_memtime() - t_slow;
+#endif
     }
 
     // One step of the wavefront: the common step for the lanes on inner nodes; then, if no lane is left on one or `leaf_min` lanes wait for

@@ -4,18 +4,19 @@
     python tools/loop_census.py [--csrc DIR] [--asm FILE] [--keep FILE]
 
 Compiles csrc/pt_path.hip to gfx950 assembly with the flags of cpupathtrace_amd/build.py (device side only) and reports, for every
-instantiation of pt_path_kernel, three regions:
+instantiation of pt_path_kernel, four regions:
 
     ahead    the inner for(;;) of the kernel in front of the burst loop (text order)
     behind   the rest of that loop behind the burst loop
     burst    the burst loop itself (with the loop of slow_step's pops inside it)
+    pop      the loop of slow_step's pops alone: the one loop nested in the burst loop (counted in `burst` as well)
 
 and per region: instructions, VGPR-to-VGPR moves (v_mov_b32 / v_mov_b64 from a vector register), lane reads and writes (v_readlane /
 v_writelane: the reloads and saves of spilled scalars), flat loads, scratch accesses and branches.
 
 The regions are found by the loop annotations the compiler writes next to every basic block ("in Loop: Header=BB0_123 Depth=2"), not by
 markers in the source, which would change the code they are meant to measure: the inner loop is the innermost loop whose own blocks hold
-the hand-out's ds_bpermute_b32, the burst loop the one loop nested in it that holds the packed slab arithmetic (v_pk_mul_f32).
+the hand-out's ds_bpermute_b32, the burst loop the one loop nested in it that holds the packed slab arithmetic (v_pk_mul_f32), the pop loop the one loop nested in that.
 --csrc DIR takes the sources of another checkout (the parent's, for a side-by-side table); --asm FILE reads an assembly file made earlier.
 tests/test_path_loop_census.py holds ceilings on these numbers."""
 import argparse
@@ -28,7 +29,7 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-REGIONS = ("ahead", "behind", "burst")
+REGIONS = ("ahead", "behind", "burst", "pop")
 COLUMNS = ("instructions", "moves", "lane_reads", "lane_writes", "flat_loads", "scratch", "branches")
 
 _KERNEL = re.compile(r"^(_Z\w*pt_path_kernelILb([01])ELb([01])ELi(\d+)E\w*):")
@@ -127,16 +128,22 @@ def census_function(lines):
     if len(burst) != 1:
         raise RuntimeError("expected one burst loop inside %s, found %r" % (inner, burst))
     burst = burst[0]
+    pop = [h for h, p in parent.items() if p == burst]
+    if len(pop) != 1:
+        raise RuntimeError("expected one pop loop inside %s, found %r" % (burst, pop))
+    pop = pop[0]
     order = [k for k, b in enumerate(blocks) if within(b[1], burst)]
     first, last = order[0], order[-1]
     region = {r: [] for r in REGIONS}
     for k, b in enumerate(blocks):
         if within(b[1], burst):
             region["burst"] += b[2]
+            if within(b[1], pop):
+                region["pop"] += b[2]
         elif within(b[1], inner):
             region["ahead" if k < first else "behind" if k > last else "ahead"] += b[2]
     out = {r: _count(region[r]) for r in REGIONS}
-    out["loops"] = {"inner": inner, "burst": burst, "inner_depth": depth(inner)}
+    out["loops"] = {"inner": inner, "burst": burst, "pop": pop, "inner_depth": depth(inner)}
     return out
 
 
