@@ -61,6 +61,8 @@ MESH_EXPORTS = ["pt_scene_create_meshes", "pt_mesh_assemble", "pt_scene_instance
 POSE_EXPORTS = ["pt_scene_pose", "pt_scene_get_pose", "pt_mesh_assemble_batch"]
 # ... and these in include/pt_motion.h
 MOTION_EXPORTS = ["pt_motion_table", "pt_render_features_motion", "pt_render_features_motion_device", "pt_temporal_denoise_motion", "pt_temporal_denoise_motion_device"]
+# ... and these in include/pt_relight.h
+RELIGHT_EXPORTS = ["pt_scene_relight", "pt_scene_get_materials", "pt_scene_get_point_lights"]
 MOTION_STATIC, MOTION_MOVED, MOTION_NONE = 0, 1, 2
 
 
@@ -421,6 +423,19 @@ class PoseInfo(C.Structure):  # pt_pose_info
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class Relight(C.Structure):  # pt_relight
+    _fields_ = [("materials", C.c_void_p), ("n_materials", C.c_uint32), ("set_point_lights", C.c_int32), ("light_pos", C.c_void_p), ("light_spectrum", C.c_void_p),
+                ("n_point_lights", C.c_uint32), ("instances", C.c_void_p), ("instance_material", C.c_void_p), ("n_instance_materials", C.c_uint32)]
+
+
+class RelightInfo(C.Structure):  # pt_relight_info
+    _fields_ = [("n_emissive", C.c_uint32), ("n_object_samples", C.c_uint32), ("n_candidates", C.c_uint32), ("registry_rebuilt", C.c_uint32),
+                ("triangles_rewritten", C.c_uint32), ("registry_ms", C.c_float), ("total_ms", C.c_float)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 def mesh_assemble_batch(meshes, instances, capacity=None, device=0, out_pos=None, out_nrm=None):
     """pt_mesh_assemble_batch: every instance of `instances` expanded on the device by one chain of launches, the survivors of instance
     0, 1, ... end to end.  meshes: [(vertices, faces), ...]; instances: [(mesh index, transform, smooth), ...].  Returns (total count,
@@ -668,6 +683,51 @@ class Scene:
         out = np.zeros((self.n_instances, 4, 4), np.float32)
         _check(load().pt_scene_get_pose(self._h, _ptr(out)))
         return out
+
+    def relight(self, materials=None, point_lights=None, instance_materials=None):
+        """pt_scene_relight: a new look in place.  materials: the whole new table (MATERIAL_DTYPE), None = it stays; point_lights:
+        (positions (n, 3), spectra (n, 4)), None = they stay; instance_materials: {instance: material index or 0xFFFFFFFF} or a list of
+        such pairs (a repeated instance gets the last).  The tree is not touched; the scene is then what a new Scene of the same geometry
+        with this look would be, bit for bit.  Returns the RelightInfo."""
+        look, keep = Relight(), []
+        if materials is not None:
+            m = np.ascontiguousarray(materials, dtype=MATERIAL_DTYPE).reshape(-1)
+            backing = m if len(m) > 0 else np.zeros(1, MATERIAL_DTYPE)  # (a NULL pointer would say "the table stays": an empty table has an address too)
+            keep += [m, backing]
+            look.materials, look.n_materials = backing.ctypes.data, len(m)
+        if point_lights is not None:
+            pos = np.ascontiguousarray(point_lights[0], dtype=np.float32).reshape(-1, 3)
+            spectrum = np.ascontiguousarray(point_lights[1], dtype=np.float32).reshape(-1, 4)
+            if len(pos) != len(spectrum):
+                raise ValueError("relight: %d light positions for %d spectra" % (len(pos), len(spectrum)))
+            keep += [pos, spectrum]
+            look.set_point_lights, look.light_pos, look.light_spectrum, look.n_point_lights = 1, pos.ctypes.data, spectrum.ctypes.data, len(pos)
+        if instance_materials is not None:
+            pairs = list(instance_materials.items()) if isinstance(instance_materials, dict) else list(instance_materials)
+            idx = np.array([p[0] for p in pairs], dtype=np.uint32)
+            mat = np.array([p[1] for p in pairs], dtype=np.uint32)
+            keep += [idx, mat]
+            look.instances, look.instance_material, look.n_instance_materials = idx.ctypes.data, mat.ctypes.data, len(idx)
+        info = RelightInfo()
+        _check(load().pt_scene_relight(self._h, C.byref(look), C.byref(info)))
+        del keep
+        return info
+
+    def materials(self):
+        """pt_scene_get_materials: the current material table (MATERIAL_DTYPE)."""
+        n = C.c_uint32()
+        _check(load().pt_scene_get_materials(self._h, None, C.c_uint32(0), C.byref(n)))
+        out = np.zeros(n.value, MATERIAL_DTYPE)
+        _check(load().pt_scene_get_materials(self._h, _ptr(out), C.c_uint32(n.value), None))
+        return out
+
+    def point_lights(self):
+        """pt_scene_get_point_lights: (positions (n, 3), spectra (n, 4))."""
+        n = C.c_uint32()
+        _check(load().pt_scene_get_point_lights(self._h, None, None, C.c_uint32(0), C.byref(n)))
+        pos, spectrum = np.zeros((n.value, 3), np.float32), np.zeros((n.value, 4), np.float32)
+        _check(load().pt_scene_get_point_lights(self._h, _ptr(pos), _ptr(spectrum), C.c_uint32(n.value), None))
+        return pos, spectrum
 
     def triangles(self, first, count):
         """pt_scene_get_triangles: the triangle objects first .. first + count - 1 of a scene with mesh instances, as the builder took

@@ -176,6 +176,58 @@ int pt_scene_create(int device, const pt_scene_desc *d, pt_scene **out) {
 
 } // extern "C"
 
+namespace pth {
+
+std::vector<F4> material_table(const pt_material *materials, uint32_t n) {
+    std::vector<F4> table(4 * static_cast<size_t>(n));
+    for(uint32_t i = 0; i < n; i++) {
+        const pt_material &m = materials[i];
+        table[4 * static_cast<size_t>(i) + 0] = {m.diffuse[0], m.diffuse[1], m.diffuse[2], m.diffuse[3]};
+        table[4 * static_cast<size_t>(i) + 1] = {m.specular[0], m.specular[1], m.specular[2], m.specular[3]};
+        table[4 * static_cast<size_t>(i) + 2] = {m.emission[0], m.emission[1], m.emission[2], m.emission[3]};
+        table[4 * static_cast<size_t>(i) + 3] = {m.ior, from_bits(static_cast<uint32_t>(m.bsdf)), from_bits(static_cast<uint32_t>(m.one_way != 0)), 0.0F};
+    }
+    return table;
+}
+
+std::vector<F4> light_table(const float *pos, const float *spectrum, uint32_t n) {
+    std::vector<F4> table(2 * static_cast<size_t>(n));
+    for(uint32_t i = 0; i < n; i++) {
+        const float *p = pos + 3 * static_cast<size_t>(i);
+        const float *c = spectrum + 4 * static_cast<size_t>(i);
+        table[2 * static_cast<size_t>(i) + 0] = {p[0], p[1], p[2], 0.0F};
+        table[2 * static_cast<size_t>(i) + 1] = {c[0], c[1], c[2], c[3]};
+    }
+    return table;
+}
+
+int object_samples(uint32_t n_emissive) {
+    const int emissive_object_count = static_cast<int>(n_emissive);
+    return std::min(2 + static_cast<int>(std::log10(emissive_object_count + 1)), emissive_object_count); // scene.cpp:226
+}
+
+void stage_small_scene(PtDevScene &dev) {
+    // LDS staging: a scene whose whole tree and leaf records fit in LDS NEXT TO everything else a workgroup keeps there, four workgroups
+    // to the CU, lives in LDS entirely (the path kernel's IN_LDS variant): up to 15.8 KB of records with the small stack window, i.e. about
+    // 120 triangles.  Larger ones are read through the caches like any tree: staged at three workgroups per CU they are slower than that
+    // (176 triangles: 754 against 785 Msamples/s; at two, 256 triangles: 581 against 715 -- profiles/r03_lds_threshold.txt; round 2 staged up to
+    // 24 KB).  An LDS copy of only the top of a larger tree was measured in round 1 and does not pay.  PT_LDS_SMALL_BYTES overrides the limit.
+    const size_t small_bytes = (static_cast<size_t>(dev.n_pairs) + dev.pair_base) * 64;
+    const int wide_word = dev.n_lights + dev.n_object_samples > 8U ? 1 : 0;
+    const size_t other_lds = pt_path_lds_bytes(wide_word, std::min(std::max(env_int("PT_ROWS", 4), 1), PT_MAX_ROWS), 4, 0U, 0U);
+    const size_t room = other_lds < 40960 ? 40960 - other_lds : 0;
+    if(small_bytes <= static_cast<size_t>(std::max(env_int("PT_LDS_SMALL_BYTES", static_cast<int>(room)), 0)) && env_int("PT_LDS_SMALL", 1) != 0) {
+        dev.n_lds_pairs = dev.n_pairs;
+        dev.n_lds_tris = dev.n_tris;
+    }
+    else {
+        dev.n_lds_pairs = 0;
+        dev.n_lds_tris = 0;
+    }
+}
+
+} // namespace pth
+
 int pth::create_scene(int device, const pt_scene_desc *d, const DeviceTriangles *assembled, pt_scene **out) {
     if(d == nullptr || out == nullptr) {
         return fail(PT_ERR_INVALID, "null argument");
@@ -396,6 +448,9 @@ int pth::create_scene(int device, const pt_scene_desc *d, const DeviceTriangles 
             PT_HIP(pt_build_order_subset(s->stream, dfs_dev.ptr, n_objs, mask, n_selected, ordered));
             dfs.assign(ordered.begin(), ordered.end());
         }
+        if(assembled != nullptr) {
+            take(s->leaf_order, dfs_dev); // (a scene with mesh instances keeps the order: pt_scene_relight's registry pass walks it)
+        }
     }
     else {
         // ---- host: leaf boxes, the recursion of pt_bvh.cpp, breadth-first flattening, records -----------------------------------
@@ -481,24 +536,13 @@ int pth::create_scene(int device, const pt_scene_desc *d, const DeviceTriangles 
     }
     const auto t_rest = clock::now();
 
-    std::vector<F4> materials(4 * static_cast<size_t>(d->n_materials));
     for(uint32_t i = 0; i < d->n_materials; i++) {
-        const pt_material &m = d->materials[i];
-        materials[4 * static_cast<size_t>(i) + 0] = {m.diffuse[0], m.diffuse[1], m.diffuse[2], m.diffuse[3]};
-        materials[4 * static_cast<size_t>(i) + 1] = {m.specular[0], m.specular[1], m.specular[2], m.specular[3]};
-        materials[4 * static_cast<size_t>(i) + 2] = {m.emission[0], m.emission[1], m.emission[2], m.emission[3]};
-        materials[4 * static_cast<size_t>(i) + 3] = {m.ior, from_bits(static_cast<uint32_t>(m.bsdf)), from_bits(static_cast<uint32_t>(m.one_way != 0)), 0.0F};
-        if(m.bsdf < PT_BSDF_LAMBERTIAN || m.bsdf > PT_BSDF_MIRROR) {
+        if(d->materials[i].bsdf < PT_BSDF_LAMBERTIAN || d->materials[i].bsdf > PT_BSDF_MIRROR) {
             return fail(PT_ERR_INVALID, "unknown BSDF kind");
         }
     }
-    std::vector<F4> lights(2 * static_cast<size_t>(d->n_point_lights));
-    for(uint32_t i = 0; i < d->n_point_lights; i++) {
-        const float *p = d->light_pos + 3 * static_cast<size_t>(i);
-        const float *c = d->light_spectrum + 4 * static_cast<size_t>(i);
-        lights[2 * static_cast<size_t>(i) + 0] = {p[0], p[1], p[2], 0.0F};
-        lights[2 * static_cast<size_t>(i) + 1] = {c[0], c[1], c[2], c[3]};
-    }
+    const std::vector<F4> materials = material_table(d->materials, d->n_materials);
+    const std::vector<F4> lights = light_table(d->light_pos, d->light_spectrum, d->n_point_lights);
 
     // ---- emissive objects: Scene::registerEmissiveObjects + CDF (scene.cpp:183-208, 167-180) -----------------------------------
     std::vector<F4> emis;
@@ -592,8 +636,7 @@ int pth::create_scene(int device, const pt_scene_desc *d, const DeviceTriangles 
     }
     s->n_emissive = static_cast<uint32_t>(cdf.size());
     s->emissive_cdf = cdf;
-    const int emissive_object_count = static_cast<int>(cdf.size());
-    const int object_sample_count = std::min(2 + static_cast<int>(std::log10(emissive_object_count + 1)), emissive_object_count); // scene.cpp:226
+    const int object_sample_count = object_samples(s->n_emissive);
     if(d->n_point_lights + static_cast<uint32_t>(object_sample_count) > PT_MAX_NEE) {
         return fail(PT_ERR_UNSUPPORTED, "more than 32 light samples per path vertex (" + std::to_string(d->n_point_lights) + " point lights + " + std::to_string(object_sample_count) +
                                         " emitter samples): the visibility mask of a path vertex has 32 bits");
@@ -651,23 +694,7 @@ int pth::create_scene(int device, const pt_scene_desc *d, const DeviceTriangles 
     dev.n_emis = s->n_emissive;
     dev.n_materials = d->n_materials;
     dev.n_object_samples = static_cast<uint32_t>(object_sample_count);
-    // LDS staging: a scene whose whole tree and leaf records fit in LDS NEXT TO everything else a workgroup keeps there, four workgroups
-    // to the CU, lives in LDS entirely (the path kernel's IN_LDS variant): up to 15.8 KB of records with the small stack window, i.e. about
-    // 120 triangles.  Larger ones are read through the caches like any tree: staged at three workgroups per CU they are slower than that
-    // (176 triangles: 754 against 785 Msamples/s; at two, 256 triangles: 581 against 715 -- profiles/r03_lds_threshold.txt; round 2 staged up to
-    // 24 KB).  An LDS copy of only the top of a larger tree was measured in round 1 and does not pay.  PT_LDS_SMALL_BYTES overrides the limit.
-    const size_t small_bytes = (static_cast<size_t>(n_pairs) + pair_base) * 64;
-    const int wide_word = d->n_point_lights + static_cast<uint32_t>(object_sample_count) > 8U ? 1 : 0;
-    const size_t other_lds = pt_path_lds_bytes(wide_word, std::min(std::max(env_int("PT_ROWS", 4), 1), PT_MAX_ROWS), 4, 0U, 0U);
-    const size_t room = other_lds < 40960 ? 40960 - other_lds : 0;
-    if(small_bytes <= static_cast<size_t>(std::max(env_int("PT_LDS_SMALL_BYTES", static_cast<int>(room)), 0)) && env_int("PT_LDS_SMALL", 1) != 0) {
-        dev.n_lds_pairs = n_pairs;
-        dev.n_lds_tris = n_tris;
-    }
-    else {
-        dev.n_lds_pairs = 0;
-        dev.n_lds_tris = 0;
-    }
+    stage_small_scene(dev);
 
     int rc = setup_path(s.get());
     if(rc != PT_OK) {

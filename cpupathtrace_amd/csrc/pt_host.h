@@ -1,5 +1,6 @@
 // pt_host.h -- what the host units of libpathtrace_hip.so share: pt_api.cpp (scenes), pt_meshes.cpp (scenes from meshes and instances),
 // pt_pose.cpp (their instances under new matrices, in place),
+// pt_relight.cpp (their materials and lights replaced in place),
 // pt_render.cpp (render calls), pt_frames.cpp and pt_frame_maps.cpp (resumable frames and their maps; pt_frames.h) and pt_image.cpp
 // (post-processing, features, denoising).  Internal:
 // not installed, not part of the C ABI.  Everything but the ABI's own handle types lives in namespace pth, so that no helper can collide
@@ -249,6 +250,9 @@ struct pt_scene {
     // (PT_REF_SPHERE | index), and the triangles' positions as the builder took them (pt_scene_get_triangles)
     std::vector<uint32_t> inst_first, inst_count, desc_ref;
     pth::DevBuf<float> tri_pos_kept;
+    // ... and for pt_scene_relight (pt_relight.cpp) the depth-first order of the leaves in device memory -- the device builder's array,
+    // or the host tree's order uploaded by the first relight -- and, from the first relight on, desc_ref
+    pth::DevBuf<uint32_t> leaf_order, desc_ref_dev;
     std::unique_ptr<pth::PoseKeep> pose;      // ... and their meshes, instance table and description, for pt_scene_pose
     std::atomic<uint32_t> live_frames{0};     // pt_frame handles (replicas counted) on this scene: pt_scene_pose refuses while there is one
     uint32_t n_emissive = 0;
@@ -354,6 +358,13 @@ bool builds_on_device(uint32_t n_objects);
 // pt_scene_create; with `assembled` (device builder only) the triangles are taken from device memory: d's own per-triangle arrays tri_pos
 // and tri_nrm are not read, and nothing per triangle of the ranges crosses to the host but the positions of the emissive ones.
 int create_scene(int device, const pt_scene_desc *d, const DeviceTriangles *assembled, pt_scene **out);
+// What create_scene derives from a look, for pt_scene_relight to derive again: the material and the light table as the device reads them
+// (4 and 2 float4 each), the emitter samples per path vertex of a registry of n_emissive objects (scene.cpp:226), and whether the scene
+// is staged in LDS (dev.n_lds_pairs / n_lds_tris, from the record counts, n_lights and n_object_samples of dev)
+std::vector<F4> material_table(const pt_material *materials, uint32_t n);
+std::vector<F4> light_table(const float *pos, const float *spectrum, uint32_t n);
+int object_samples(uint32_t n_emissive);
+void stage_small_scene(PtDevScene &dev);
 
 // ---- pt_meshes.cpp ---------------------------------------------------------------------------------------------------------------------
 

@@ -114,6 +114,7 @@ int pt_scene_pose(pt_scene *s, const uint32_t *instances, uint32_t n, const floa
     s->desc_ref = std::move(t->desc_ref);
     take(keep.spare_pos, s->tri_pos_kept); // (the positions of the pose before: the next pose assembles into them)
     take(s->tri_pos_kept, t->tri_pos_kept);
+    take(s->leaf_order, t->leaf_order); // (empty behind the host builder: the next relight uploads the new tree's order)
     s->n_emissive = t->n_emissive;
     s->emissive_obj = std::move(t->emissive_obj);
     s->emissive_cdf = std::move(t->emissive_cdf);

@@ -301,6 +301,18 @@ class Scene {
     void pose(const std::vector<mat4<float>> &transformations);
     void pose(const std::vector<uint32_t> &instances, const std::vector<mat4<float>> &transformations);
 
+    // A new look in place (pt_scene_relight, include/pt_relight.h): the hierarchy is not touched.  Materials are immutable objects, so the
+    // edit is by handler: every pair (from, to) replaces the handler `from` by `to` everywhere it is used, on the Scene's objects and on
+    // its mesh instances; `to` takes the material slot of `from`.  The second form replaces the light sources.  Afterwards the Scene
+    // renders and samples lights exactly as a Scene constructed with the new handlers or lights would; every replica is relit, one after
+    // the other.  Object pointers returned earlier for MESH triangles are INVALID afterwards, as after a pose.  Not to be called while
+    // another thread renders, intersects or samples this Scene.  Throws as pose does: std::invalid_argument for a Scene without mesh
+    // instances, a handler the Scene does not use or one the device cannot evaluate; std::runtime_error when the device refuses (a live
+    // FrameRender on the scene, more than 32 light samples per path vertex); a refused relight leaves the Scene as it was unless a later
+    // replica of several failed.  Non-virtual: the class's layout is what it was.
+    void relight(const std::vector<std::pair<std::shared_ptr<MaterialHandler>, std::shared_ptr<MaterialHandler>>> &replace);
+    void relight(std::vector<std::unique_ptr<LightSource>> &&light_sources);
+
     // the device scene behind the C ABI (include/pt_hip.h); used by processJob / processItem
     pt_scene *deviceScene() const noexcept { return device_scene; }
     const std::vector<pt_scene *> &deviceScenes() const noexcept { return replicas; }
@@ -316,7 +328,7 @@ class Scene {
     // header keeps working with the library.  What a Scene with mesh instances keeps beyond them -- the instances, their object ranges and
     // the Triangles handed out so far, guarded by a mutex -- lives in the library, looked up by the Scene's address (src/host/scene.cpp).
     const Object *meshObject(uint32_t index) const;
-    void registerEmitters(); // emissive / emissive_cdf from the device scene, as the constructors and pose() fill them
+    void registerEmitters(); // emissive / emissive_cdf from the device scene, as the constructors, pose() and relight() fill them
 };
 
 #endif

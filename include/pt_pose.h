@@ -6,7 +6,8 @@
  * the description (what the caller's arrays held: 36 or 72 bytes per triangle of the description, 16 per sphere, 64 per material).  Behind
  * the first pose it also keeps the assembler's scratch in device memory -- 12 bytes per vertex and 8 per face of all instances, and 20
  * bytes per face corner (60 per face) if any instance is smooth -- and one spare position array and normal array (36 bytes per triangle
- * each), so that a pose of a scene that has been posed before allocates no scratch.  Scenes without instances keep nothing of this.
+ * each), so that a pose of a scene that has been posed before allocates no scratch.  For the relight entry of pt_relight.h it keeps the
+ * depth-first order of its leaves in device memory as well, 4 bytes per object.  Scenes without instances keep nothing of this.
  *
  *   - pt_scene_pose: replaces the matrices of the instances named by `instances` (n indices; NULL = all of them in order, and then n must
  *     be the scene's instance count) with transforms[k][16].  An index that occurs more than once gets the last of its matrices.  All

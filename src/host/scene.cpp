@@ -26,12 +26,8 @@ namespace {
         }
     }
 
-    // index of the pt_material that describes `handler`, appending it on first use
-    uint32_t materialIndex(const MaterialHandler *handler, std::map<const MaterialHandler *, uint32_t> &known, std::vector<pt_material> &materials) {
-        auto found = known.find(handler);
-        if(found != known.end()) {
-            return found->second;
-        }
+    // the pt_material that describes `handler`
+    pt_material describeMaterial(const MaterialHandler *handler) {
         const auto *constant = dynamic_cast<const ConstantMaterialHandler *>(handler);
         if(constant == nullptr) {
             throw std::invalid_argument("PathTrace: only ConstantMaterialHandler can be evaluated on the device");
@@ -60,10 +56,36 @@ namespace {
         else {
             throw std::invalid_argument("PathTrace: only LambertianBRDF, GlassBDF and MirrorBRDF can be evaluated on the device");
         }
+        return m;
+    }
+
+    // index of the pt_material that describes `handler`, appending it on first use
+    uint32_t materialIndex(const MaterialHandler *handler, std::map<const MaterialHandler *, uint32_t> &known, std::vector<pt_material> &materials) {
+        auto found = known.find(handler);
+        if(found != known.end()) {
+            return found->second;
+        }
+        const pt_material m = describeMaterial(handler);
         const uint32_t index = static_cast<uint32_t>(materials.size());
         materials.push_back(m);
         known.emplace(handler, index);
         return index;
+    }
+
+    // position and spectrum of every light as the device takes them
+    void describeLights(const std::vector<std::unique_ptr<LightSource>> &lights, std::vector<float> &light_pos, std::vector<float> &light_spectrum) {
+        for(const auto &light : lights) {
+            const auto *point = dynamic_cast<const PointLightSource *>(light.get());
+            if(point == nullptr) {
+                throw std::invalid_argument("PathTrace: only PointLightSource lights can be rendered on the device");
+            }
+            const vec3<float> anywhere{0.0F, 0.0F, 0.0F};
+            const auto [target, density] = point->importanceSample(anywhere);
+            (void)density;
+            const auto colour = point->getSpectrum(Ray{anywhere, vec3<float>{0.0F, 0.0F, 1.0F}}).getColor();
+            light_pos.insert(light_pos.end(), {target[0], target[1], target[2]});
+            light_spectrum.insert(light_spectrum.end(), {colour[0], colour[1], colour[2], colour[3]});
+        }
     }
 
     // What a Scene with mesh instances keeps beyond its data members (whose layout is fixed, detail/world.h): the instances, their object
@@ -71,6 +93,7 @@ namespace {
     struct MeshState {
         std::vector<MeshInstance> instances;
         std::vector<uint32_t> first, count; // object range of every instance
+        std::vector<const MaterialHandler *> slots; // the handler behind every material index; one handler may hold several (Scene::relight)
         std::mutex mutex;                   // guards `made`
         std::unordered_map<uint32_t, std::unique_ptr<Object>> made; // object index -> Triangle
 
@@ -222,18 +245,7 @@ Scene::Scene(std::vector<std::unique_ptr<Object>> &&objs, std::vector<std::uniqu
         };
         onAllCores(objects.size(), fill);
     }
-    for(const auto &light : light_sources) {
-        const auto *point = dynamic_cast<const PointLightSource *>(light.get());
-        if(point == nullptr) {
-            throw std::invalid_argument("PathTrace: only PointLightSource lights can be rendered on the device");
-        }
-        const vec3<float> anywhere{0.0F, 0.0F, 0.0F};
-        const auto [target, density] = point->importanceSample(anywhere);
-        (void)density;
-        const auto colour = point->getSpectrum(Ray{anywhere, vec3<float>{0.0F, 0.0F, 1.0F}}).getColor();
-        light_pos.insert(light_pos.end(), {target[0], target[1], target[2]});
-        light_spectrum.insert(light_spectrum.end(), {colour[0], colour[1], colour[2], colour[3]});
-    }
+    describeLights(light_sources, light_pos, light_spectrum);
 
     pt_scene_desc desc{};
     desc.n_objects = static_cast<uint32_t>(kinds.size());
@@ -319,6 +331,10 @@ Scene::Scene(std::vector<std::unique_ptr<Object>> &&objs, std::vector<std::uniqu
         state->first.resize(instances.size());
         state->count.resize(instances.size());
         pt_scene_instance_ranges(device_scene, state->first.data(), state->count.data());
+        state->slots.assign(materials.size(), nullptr);
+        for(const auto &[handler, index] : known) {
+            state->slots[index] = handler;
+        }
     }
 
     // (the emitters among the mesh triangles are materialised through the state, which is registered first; nothing below throws)
@@ -404,6 +420,93 @@ void Scene::pose(const std::vector<uint32_t> &instances, const std::vector<mat4<
         pt_scene_instance_ranges(device_scene, state->first.data(), state->count.data());
         state->made.clear(); // (the Triangles handed out so far: their objects are other triangles now, or none)
     }
+    registerEmitters();
+}
+
+void Scene::relight(const std::vector<std::pair<std::shared_ptr<MaterialHandler>, std::shared_ptr<MaterialHandler>>> &replace) {
+    MeshState *state = nullptr;
+    {
+        MeshStates &states = meshStates();
+        std::lock_guard<std::mutex> lock(states.mutex);
+        auto found = states.of.find(this);
+        state = found != states.of.end() ? found->second.get() : nullptr;
+    }
+    if(state == nullptr) {
+        throw std::invalid_argument("PathTrace: Scene::relight on a Scene without mesh instances");
+    }
+    if(replace.empty()) {
+        return;
+    }
+    uint32_t n_materials = 0;
+    if(pt_scene_get_materials(device_scene, nullptr, 0, &n_materials) != PT_OK) {
+        throw std::runtime_error(std::string("PathTrace: cannot read the device scene's materials: ") + pt_last_error());
+    }
+    std::vector<pt_material> materials(n_materials);
+    pt_scene_get_materials(device_scene, materials.data(), n_materials, nullptr);
+    // every replacement takes the slot of the handler it replaces (checked and described before anything changes)
+    std::vector<const MaterialHandler *> slots = state->slots;
+    for(const auto &[from, to] : replace) {
+        if(from == nullptr || to == nullptr || std::find(slots.begin(), slots.end(), from.get()) == slots.end()) {
+            throw std::invalid_argument("PathTrace: Scene::relight replaces a handler the Scene does not use");
+        }
+        const pt_material described = describeMaterial(to.get());
+        // (a handler may hold several slots: it took over those of the handlers it replaced earlier; all of them follow it)
+        for(size_t slot = 0; slot < slots.size() && slot < materials.size(); slot++) {
+            if(slots[slot] == from.get()) {
+                materials[slot] = described;
+                slots[slot] = to.get();
+            }
+        }
+    }
+    pt_relight look{};
+    look.materials = materials.data();
+    look.n_materials = n_materials;
+    for(size_t r = 0; r < replicas.size(); r++) {
+        if(pt_scene_relight(replicas[r], &look, nullptr) != PT_OK) {
+            throw std::runtime_error("PathTrace: cannot relight the device scene (replica " + std::to_string(r) + "): " + pt_last_error());
+        }
+    }
+    {
+        std::lock_guard<std::mutex> lock(state->mutex);
+        for(const auto &[from, to] : replace) {
+            for(auto &object : objects) {
+                if(object->getMaterialHandler() == from.get()) {
+                    object->setMaterialHandler(to);
+                }
+            }
+            for(MeshInstance &instance : state->instances) {
+                if(instance.handler == from) {
+                    instance.handler = to;
+                }
+            }
+        }
+        state->slots = std::move(slots);
+        state->made.clear(); // (the Triangles handed out so far carry the handlers from before)
+    }
+    registerEmitters();
+}
+
+void Scene::relight(std::vector<std::unique_ptr<LightSource>> &&new_light_sources) {
+    {
+        MeshStates &states = meshStates();
+        std::lock_guard<std::mutex> lock(states.mutex);
+        if(states.of.find(this) == states.of.end()) {
+            throw std::invalid_argument("PathTrace: Scene::relight on a Scene without mesh instances");
+        }
+    }
+    std::vector<float> light_pos, light_spectrum;
+    describeLights(new_light_sources, light_pos, light_spectrum);
+    pt_relight look{};
+    look.set_point_lights = 1;
+    look.light_pos = light_pos.data();
+    look.light_spectrum = light_spectrum.data();
+    look.n_point_lights = static_cast<uint32_t>(new_light_sources.size());
+    for(size_t r = 0; r < replicas.size(); r++) {
+        if(pt_scene_relight(replicas[r], &look, nullptr) != PT_OK) {
+            throw std::runtime_error("PathTrace: cannot relight the device scene (replica " + std::to_string(r) + "): " + pt_last_error());
+        }
+    }
+    light_sources = std::move(new_light_sources);
     registerEmitters();
 }
 
