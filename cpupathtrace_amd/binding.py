@@ -63,6 +63,10 @@ POSE_EXPORTS = ["pt_scene_pose", "pt_scene_get_pose", "pt_mesh_assemble_batch"]
 MOTION_EXPORTS = ["pt_motion_table", "pt_render_features_motion", "pt_render_features_motion_device", "pt_temporal_denoise_motion", "pt_temporal_denoise_motion_device"]
 # ... and these in include/pt_relight.h
 RELIGHT_EXPORTS = ["pt_scene_relight", "pt_scene_get_materials", "pt_scene_get_point_lights"]
+# ... and these in include/pt_deform.h
+DEFORM_EXPORTS = ["pt_scene_bind_skin", "pt_scene_deform", "pt_scene_get_mesh_vertices"]
+DEFORM_VERTICES, DEFORM_BONES, DEFORM_REST = 0, 1, 2
+SKIN_MAX_INFLUENCES = 8
 MOTION_STATIC, MOTION_MOVED, MOTION_NONE = 0, 1, 2
 
 
@@ -423,6 +427,22 @@ class PoseInfo(C.Structure):  # pt_pose_info
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class Skin(C.Structure):  # pt_skin
+    _fields_ = [("mesh", C.c_uint32), ("n_bones", C.c_uint32), ("influences", C.c_uint32), ("bone", C.c_void_p), ("weight", C.c_void_p)]
+
+
+class MeshDeform(C.Structure):  # pt_mesh_deform
+    _fields_ = [("mesh", C.c_uint32), ("kind", C.c_uint32), ("data", C.c_void_p), ("count", C.c_uint32)]
+
+
+class DeformInfo(C.Structure):  # pt_deform_info
+    _fields_ = PoseInfo._fields_ + [("n_meshes_deformed", C.c_uint32), ("n_vertices_skinned", C.c_uint32), ("skin_ms", C.c_float), ("vertex_upload_ms", C.c_float),
+                                    ("allocations", C.c_uint32)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class Relight(C.Structure):  # pt_relight
     _fields_ = [("materials", C.c_void_p), ("n_materials", C.c_uint32), ("set_point_lights", C.c_int32), ("light_pos", C.c_void_p), ("light_spectrum", C.c_void_p),
                 ("n_point_lights", C.c_uint32), ("instances", C.c_void_p), ("instance_material", C.c_void_p), ("n_instance_materials", C.c_uint32)]
@@ -682,6 +702,61 @@ class Scene:
         """pt_scene_get_pose: the current matrices of all instances, (n_instances, 4, 4)."""
         out = np.zeros((self.n_instances, 4, 4), np.float32)
         _check(load().pt_scene_get_pose(self._h, _ptr(out)))
+        return out
+
+    def bind_skin(self, mesh, bones, weights, n_bones=None):
+        """pt_scene_bind_skin: a rig for mesh `mesh` of the scene's mesh list: bones (n_vertices, K) indices and weights (n_vertices, K),
+        used as given.  n_bones defaults to the largest index + 1; bones=None unbinds.  Every index is checked on the host."""
+        skin = Skin()
+        skin.mesh = mesh
+        if bones is not None:
+            b = np.ascontiguousarray(bones, dtype=np.uint32)
+            w = np.ascontiguousarray(weights, dtype=np.float32)
+            if b.ndim != 2 or b.shape != w.shape:
+                raise ValueError("bind_skin: bones and weights must both be (n_vertices, K)")
+            skin.n_bones = int(b.max()) + 1 if n_bones is None else int(n_bones)
+            skin.influences, skin.bone, skin.weight = b.shape[1], b.ctypes.data, w.ctypes.data
+        _check(load().pt_scene_bind_skin(self._h, C.byref(skin)))
+
+    def deform(self, vertices=None, bones=None, rest=(), transforms=None, instances=None):
+        """pt_scene_deform: new shapes for meshes, then what pose() does.  vertices: {mesh: (n_vertices, 3)} replaces a mesh's vertices;
+        bones: {mesh: (n_bones, 3, 4) or (n_bones, 4, 4) matrices} skins its rest vertices with the rig of bind_skin on the device (of a
+        4 x 4 matrix rows 0 .. 2 are used); rest: meshes that go back to the vertices they were created with.  A mesh named more than
+        once takes the last of vertices, bones, rest.  transforms / instances: as pose(); None = the pose stays.  All instances of a
+        mesh share its shape.  Returns the pt_deform_info as a dict and updates n_objects."""
+        entries, keep = [], []
+        for mesh, v in (vertices or {}).items():
+            a = np.ascontiguousarray(v, dtype=np.float32).reshape(-1, 3)
+            backing = a if len(a) > 0 else np.zeros((1, 3), np.float32)
+            keep += [a, backing]
+            entries.append(MeshDeform(int(mesh), DEFORM_VERTICES, backing.ctypes.data, len(a)))
+        for mesh, m in (bones or {}).items():
+            a = np.asarray(m, dtype=np.float32)
+            if a.ndim == 3 and a.shape[1:] == (4, 4):
+                a = a[:, :3, :]
+            a = np.ascontiguousarray(a).reshape(-1, 12)
+            backing = a if len(a) > 0 else np.zeros((1, 12), np.float32)
+            keep += [a, backing]
+            entries.append(MeshDeform(int(mesh), DEFORM_BONES, backing.ctypes.data, len(a)))
+        for mesh in rest:
+            entries.append(MeshDeform(int(mesh), DEFORM_REST, None, 0))
+        table = (MeshDeform * max(len(entries), 1))(*entries)
+        m = np.zeros((0, 16), np.float32) if transforms is None else np.ascontiguousarray(transforms, dtype=np.float32).reshape(-1, 16)
+        idx = None if instances is None else np.ascontiguousarray(instances, dtype=np.uint32).reshape(-1)
+        if idx is not None and len(idx) != len(m):
+            raise ValueError("deform: %d instance indices for %d matrices" % (len(idx), len(m)))
+        info = DeformInfo()
+        _check(load().pt_scene_deform(self._h, table, C.c_uint32(len(entries)), _ptr(idx), C.c_uint32(len(m)), _ptr(m) if len(m) > 0 else None, C.byref(info)))
+        del keep
+        self.n_objects = self._n_desc_objects + int(info.n_triangles)
+        return info.as_dict()
+
+    def mesh_vertices(self, mesh):
+        """pt_scene_get_mesh_vertices: the vertices the scene's instances of mesh `mesh` are made of at the moment, (n_vertices, 3)."""
+        n = C.c_uint32()
+        _check(load().pt_scene_get_mesh_vertices(self._h, C.c_uint32(mesh), None, C.byref(n)))
+        out = np.zeros((n.value, 3), np.float32)
+        _check(load().pt_scene_get_mesh_vertices(self._h, C.c_uint32(mesh), _ptr(out), None))
         return out
 
     def relight(self, materials=None, point_lights=None, instance_materials=None):

@@ -1,5 +1,5 @@
 // pt_host.h -- what the host units of libpathtrace_hip.so share: pt_api.cpp (scenes), pt_meshes.cpp (scenes from meshes and instances),
-// pt_pose.cpp (their instances under new matrices, in place),
+// pt_pose.cpp (their instances under new matrices, in place), pt_deform.cpp (their meshes under new vertices, in place),
 // pt_relight.cpp (their materials and lights replaced in place),
 // pt_render.cpp (render calls), pt_frames.cpp and pt_frame_maps.cpp (resumable frames and their maps; pt_frames.h) and pt_image.cpp
 // (post-processing, features, denoising).  Internal:
@@ -29,6 +29,7 @@
 #include "pt_build.h"
 #include "pt_mesh.h"
 #include "pt_mesh_batch.h"
+#include "pt_skin.h"
 #include "pt_bvh.h"
 #include "pt_kernels.h"
 #include "pt_denoise.h"
@@ -200,11 +201,24 @@ struct EventPair {
 
 // ---- what a scene with mesh instances keeps for pt_scene_pose (pt_pose.cpp; include/pt_pose.h has the memory cost) --------------------------
 
+// What pt_scene_deform (pt_deform.cpp; include/pt_deform.h has the memory cost) adds to a mesh: the rig bound to it, and its current
+// vertices with the spare buffer the next deformation is made in.  A mesh that was never bound or deformed has none.
+struct MeshDeform {
+    DevBuf<uint32_t> skin_bone; // [n_vertices][skin_k]
+    DevBuf<float> skin_weight;  // [n_vertices][skin_k]
+    uint32_t skin_bones = 0, skin_k = 0; // skin_bones == 0: no skin
+    DevBuf<float> current, spare;        // [n_vertices][3] each
+};
+
 // One mesh in device memory
 struct KeptMesh {
-    DevBuf<float> vertices;
+    DevBuf<float> vertices; // the rest vertices
     DevBuf<int32_t> faces;
     uint32_t n_vertices = 0, n_faces = 0;
+    // The vertices an assembly reads (assemble_batch, pt_meshes.cpp): the rest vertices, unless pt_scene_deform has pointed it at the
+    // mesh's current ones
+    const float *shape = nullptr;
+    std::unique_ptr<MeshDeform> deform;
     int upload(const pt_mesh_data &m);
 };
 
@@ -226,6 +240,8 @@ struct PoseKeep {
     uint64_t capacity = 0;               // the description's triangles + the faces of all instances, before any is rejected
     PtBatchScratch scratch;              // the assembler's, grown by the first pose (creation has one of its own, freed when it returns)
     DevBuf<float> spare_pos, spare_nrm;  // the arrays the next pose assembles into (the scene keeps the positions it was built from)
+    DevBuf<float> bone_table;            // pt_scene_deform: the bone matrices of a call's skinned meshes, end to end
+    uint64_t deform_allocations = 0;     // ... and its hipMalloc calls for vertex, skin and bone buffers so far
 };
 
 } // namespace pth
@@ -387,6 +403,16 @@ int assemble_mesh_scene(hipStream_t stream, const pt_scene_desc *d, const std::v
 // the description's first, then the instances' ranges).  The scene takes `pos` over (pt_scene_get_triangles); on failure it stays
 // with the caller.  Used by pt_scene_create_meshes and pt_scene_pose.
 int finish_mesh_scene(int device, const pt_scene_desc *d, const MeshAssembly &assembly, DevBuf<float> &pos, pt_scene **out);
+
+// ---- pt_pose.cpp -----------------------------------------------------------------------------------------------------------------------
+
+// What pt_scene_pose and pt_scene_deform share once their arguments are in order (render_mutex held, no live frame, the scene's stream
+// idle or holding only work the assembly may follow): all instances of s->pose under the matrices `posed` through the batched assembler,
+// each mesh read at its `shape`; the scene of these triangles built aside; and, only when that is complete, its content moved into `s`,
+// which keeps its address, stream, lock, pinned words and workspace buffers, with `posed` as its instance table.  A failure leaves `s`
+// as it was.  The stream has been waited for when this returns.  `info` (may be null) receives what a pose reports; t_begin is the
+// call's start, for its wall-clock fields.
+int rebuild_instances(pt_scene *s, std::vector<pt_mesh_instance> &&posed, std::chrono::steady_clock::time_point t_begin, pt_pose_info *info);
 
 // ---- pt_render.cpp: the persistent path kernel (pt_path.hip), one launch per render call ----------------------------------------------
 

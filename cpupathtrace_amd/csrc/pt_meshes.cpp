@@ -18,7 +18,7 @@ int assemble_batch(hipStream_t stream, PtBatchScratch &scratch, const std::vecto
     for(uint32_t i = 0; i < n_instances; i++) {
         const KeptMesh &m = *meshes[instances[i].mesh];
         PtBatchInstance &t = table[i];
-        t.vertices = m.vertices.ptr;
+        t.vertices = m.shape;
         t.faces = m.faces.ptr;
         t.n_vertices = nv[i] = m.n_vertices;
         t.n_faces = nf[i] = m.n_faces;
@@ -75,6 +75,7 @@ int KeptMesh::upload(const pt_mesh_data &m) {
     }
     n_vertices = m.n_vertices;
     n_faces = m.n_faces;
+    shape = vertices.ptr;
     return PT_OK;
 }
 

@@ -2,67 +2,19 @@
 // (DESIGN.md 4.3.2).  The two halves of pt_scene_create_meshes do the work (pt_meshes.cpp): assemble_mesh_scene puts all instances through
 // the batched assembler (pt_mesh_batch.h) into arrays of their own, finish_mesh_scene builds a scene from them aside on the unchanged
 // create_scene path, and only a finished scene's content is moved into the live handle, which keeps its address, stream, lock, pinned
-// words and workspace buffers.
+// words and workspace buffers.  rebuild_instances is that work; pt_scene_deform (pt_deform.cpp) ends with it as well.
 #include "pt_host.h"
 
 using namespace pth;
 
-extern "C" {
+namespace pth {
 
-int pt_scene_get_pose(const pt_scene *scene, float *transforms) {
-    if(scene == nullptr || transforms == nullptr) {
-        return fail(PT_ERR_INVALID, "null argument");
-    }
-    if(scene->pose == nullptr) {
-        return fail(PT_ERR_UNSUPPORTED, "the scene has no instances: it was not made by pt_scene_create_meshes with instances");
-    }
-    std::lock_guard<std::mutex> lock(const_cast<pt_scene *>(scene)->render_mutex);
-    const std::vector<pt_mesh_instance> &instances = scene->pose->instances;
-    for(size_t i = 0; i < instances.size(); i++) {
-        std::copy(instances[i].transform, instances[i].transform + 16, transforms + 16 * i);
-    }
-    return PT_OK;
-}
-
-int pt_scene_pose(pt_scene *s, const uint32_t *instances, uint32_t n, const float *transforms, pt_pose_info *info) {
-    if(info != nullptr) {
-        *info = pt_pose_info{};
-    }
-    if(s == nullptr) {
-        return fail(PT_ERR_INVALID, "null scene");
-    }
-    if(n > 0 && transforms == nullptr) {
-        return fail(PT_ERR_INVALID, "null transforms");
-    }
-    std::lock_guard<std::mutex> lock(s->render_mutex);
-    if(s->pose == nullptr) {
-        return fail(PT_ERR_UNSUPPORTED, "the scene has no instances: it was not made by pt_scene_create_meshes with instances");
-    }
-    PoseKeep &keep = *s->pose;
-    const uint32_t n_instances = static_cast<uint32_t>(keep.instances.size());
-    if(instances == nullptr && n != n_instances) {
-        return fail(PT_ERR_INVALID, "a pose of all instances needs " + std::to_string(n_instances) + " matrices, not " + std::to_string(n));
-    }
-    for(uint32_t k = 0; instances != nullptr && k < n; k++) {
-        if(instances[k] >= n_instances) {
-            return fail(PT_ERR_INVALID, "instance index " + std::to_string(instances[k]) + " out of range: the scene has " + std::to_string(n_instances));
-        }
-    }
-    if(s->live_frames.load() != 0) {
-        return fail(PT_ERR_INVALID, "the scene has a live frame: its parked state belongs to the present geometry (pt_frame_destroy first)");
-    }
-
+int rebuild_instances(pt_scene *s, std::vector<pt_mesh_instance> &&posed, std::chrono::steady_clock::time_point t_begin, pt_pose_info *info) {
     using clock = std::chrono::steady_clock;
     auto ms_since = [](clock::time_point t0) { return std::chrono::duration<float, std::milli>(clock::now() - t0).count(); };
-    const auto t_begin = clock::now();
-    std::vector<pt_mesh_instance> posed = keep.instances; // (adopted with the rest, on success)
-    for(uint32_t k = 0; k < n; k++) {
-        const uint32_t i = instances != nullptr ? instances[k] : k;
-        std::copy(transforms + 16 * static_cast<size_t>(k), transforms + 16 * static_cast<size_t>(k) + 16, posed[i].transform);
-    }
+    PoseKeep &keep = *s->pose;
+    const uint32_t n_instances = static_cast<uint32_t>(keep.instances.size());
     const pt_scene_desc *d = &keep.desc.d;
-    PT_HIP(hipSetDevice(s->device));
-    PT_HIP(hipStreamSynchronize(s->stream));
 
     // ---- the arrays the instances are expanded into, behind the description's own triangles (the meshes are there) ---------------------
     const bool with_normals = keep.any_smooth || (d->n_triangles > 0 && d->tri_nrm != nullptr);
@@ -83,7 +35,11 @@ int pt_scene_pose(pt_scene *s, const uint32_t *instances, uint32_t n, const floa
         PT_HIP(nrm.ensure(9 * static_cast<size_t>(keep.capacity)));
     }
     MeshAssembly assembly;
-    PT_TRY(assemble_mesh_scene(s->stream, d, keep.meshes, posed, keep.scratch, keep.capacity, pos.ptr, with_normals ? nrm.ptr : nullptr, &assembly));
+    const int assembled = assemble_mesh_scene(s->stream, d, keep.meshes, posed, keep.scratch, keep.capacity, pos.ptr, with_normals ? nrm.ptr : nullptr, &assembly);
+    if(assembled != PT_OK) {
+        (void)hipStreamSynchronize(s->stream); // (nothing of the failed call is in flight when its buffers are used again)
+        return assembled;
+    }
     const float upload_ms = std::chrono::duration<float, std::milli>(assembly.front_done - t_begin).count();
 
     // ---- the scene of these arrays, built aside by the path every scene takes -------------------------------------------------------------
@@ -153,9 +109,72 @@ int pt_scene_pose(pt_scene *s, const uint32_t *instances, uint32_t n, const floa
         info->rest_ms = std::max(total_ms - upload_ms - assembly_ms - tree_ms, 0.0F);
         info->total_ms = total_ms;
     }
+    return PT_OK;
+}
+
+} // namespace pth
+
+extern "C" {
+
+int pt_scene_get_pose(const pt_scene *scene, float *transforms) {
+    if(scene == nullptr || transforms == nullptr) {
+        return fail(PT_ERR_INVALID, "null argument");
+    }
+    if(scene->pose == nullptr) {
+        return fail(PT_ERR_UNSUPPORTED, "the scene has no instances: it was not made by pt_scene_create_meshes with instances");
+    }
+    std::lock_guard<std::mutex> lock(const_cast<pt_scene *>(scene)->render_mutex);
+    const std::vector<pt_mesh_instance> &instances = scene->pose->instances;
+    for(size_t i = 0; i < instances.size(); i++) {
+        std::copy(instances[i].transform, instances[i].transform + 16, transforms + 16 * i);
+    }
+    return PT_OK;
+}
+
+int pt_scene_pose(pt_scene *s, const uint32_t *instances, uint32_t n, const float *transforms, pt_pose_info *info) {
+    if(info != nullptr) {
+        *info = pt_pose_info{};
+    }
+    if(s == nullptr) {
+        return fail(PT_ERR_INVALID, "null scene");
+    }
+    if(n > 0 && transforms == nullptr) {
+        return fail(PT_ERR_INVALID, "null transforms");
+    }
+    std::lock_guard<std::mutex> lock(s->render_mutex);
+    if(s->pose == nullptr) {
+        return fail(PT_ERR_UNSUPPORTED, "the scene has no instances: it was not made by pt_scene_create_meshes with instances");
+    }
+    PoseKeep &keep = *s->pose;
+    const uint32_t n_instances = static_cast<uint32_t>(keep.instances.size());
+    if(instances == nullptr && n != n_instances) {
+        return fail(PT_ERR_INVALID, "a pose of all instances needs " + std::to_string(n_instances) + " matrices, not " + std::to_string(n));
+    }
+    for(uint32_t k = 0; instances != nullptr && k < n; k++) {
+        if(instances[k] >= n_instances) {
+            return fail(PT_ERR_INVALID, "instance index " + std::to_string(instances[k]) + " out of range: the scene has " + std::to_string(n_instances));
+        }
+    }
+    if(s->live_frames.load() != 0) {
+        return fail(PT_ERR_INVALID, "the scene has a live frame: its parked state belongs to the present geometry (pt_frame_destroy first)");
+    }
+
+    const auto t_begin = std::chrono::steady_clock::now();
+    std::vector<pt_mesh_instance> posed = keep.instances; // (adopted with the rest, on success)
+    for(uint32_t k = 0; k < n; k++) {
+        const uint32_t i = instances != nullptr ? instances[k] : k;
+        std::copy(transforms + 16 * static_cast<size_t>(k), transforms + 16 * static_cast<size_t>(k) + 16, posed[i].transform);
+    }
+    PT_HIP(hipSetDevice(s->device));
+    PT_HIP(hipStreamSynchronize(s->stream));
+    pt_pose_info done{};
+    PT_TRY(rebuild_instances(s, std::move(posed), t_begin, &done));
+    if(info != nullptr) {
+        *info = done;
+    }
     if(env_int("PT_DEBUG", 0) != 0) {
         std::fprintf(stderr, "[pt] pose: %u instances, %llu triangles kept, %u chunk(s); upload %.1f ms, assembly %.1f ms, tree %.1f ms, total %.1f ms; scratch allocations so far %llu\n",
-                     n_instances, static_cast<unsigned long long>(n_kept), assembly.chunks, upload_ms, assembly_ms, tree_ms, total_ms,
+                     done.n_instances, static_cast<unsigned long long>(done.n_triangles), done.assembly_chunks, done.upload_ms, done.assembly_ms, done.tree_ms, done.total_ms,
                      static_cast<unsigned long long>(keep.scratch.allocations));
     }
     return PT_OK;

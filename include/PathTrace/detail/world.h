@@ -313,6 +313,24 @@ class Scene {
     void relight(const std::vector<std::pair<std::shared_ptr<MaterialHandler>, std::shared_ptr<MaterialHandler>>> &replace);
     void relight(std::vector<std::unique_ptr<LightSource>> &&light_sources);
 
+    // A new shape for a mesh in place (pt_scene_bind_skin, pt_scene_deform, include/pt_deform.h): meshes are named by the MeshData their
+    // MeshInstances share, and ALL instances of a MeshData share its shape -- two characters that bend differently are two MeshData.
+    // bindSkin gives a mesh a rig: per vertex `influences` (1 .. 8) bone indices and as many weights, vertex after vertex; the weights
+    // are used as given.  deform(mesh, vertices) replaces the vertices (one per vertex of the MeshData; the MeshData itself is not
+    // written); deform(mesh, bones) skins the REST vertices on the device with the bound rig, rows 0 .. 2 of every bone's matrix (it never
+    // compounds); restShape goes back to the MeshData's vertices.  The faces never change.  Afterwards the Scene renders, intersects and
+    // samples lights exactly as a Scene constructed from MeshData with the new vertices would; every replica is deformed, one after the
+    // other; a later pose() or relight() works on the new shape.  Object pointers returned earlier for MESH triangles are INVALID
+    // afterwards, as after a pose.  Not to be called while another thread renders, intersects or samples this Scene.  Throws as pose
+    // does: std::invalid_argument for a Scene without mesh instances, a MeshData no instance uses, a wrong count (the rig has as many
+    // bones as its largest index + 1, and deform(mesh, bones) takes exactly that many), influences outside 1 .. 8, bones without a
+    // bound rig; std::runtime_error when the device refuses (a live FrameRender on the scene, no memory); a refused call leaves the
+    // Scene as it was unless a later replica of several failed.  Non-virtual: the class's layout is what it was.
+    void bindSkin(const std::shared_ptr<const io::MeshData> &mesh, const std::vector<uint32_t> &bone_indices, const std::vector<float> &weights, uint32_t influences);
+    void deform(const std::shared_ptr<const io::MeshData> &mesh, const std::vector<vec3<float>> &vertices);
+    void deform(const std::shared_ptr<const io::MeshData> &mesh, const std::vector<mat4<float>> &bones);
+    void restShape(const std::shared_ptr<const io::MeshData> &mesh);
+
     // the device scene behind the C ABI (include/pt_hip.h); used by processJob / processItem
     pt_scene *deviceScene() const noexcept { return device_scene; }
     const std::vector<pt_scene *> &deviceScenes() const noexcept { return replicas; }
@@ -328,7 +346,7 @@ class Scene {
     // header keeps working with the library.  What a Scene with mesh instances keeps beyond them -- the instances, their object ranges and
     // the Triangles handed out so far, guarded by a mutex -- lives in the library, looked up by the Scene's address (src/host/scene.cpp).
     const Object *meshObject(uint32_t index) const;
-    void registerEmitters(); // emissive / emissive_cdf from the device scene, as the constructors, pose() and relight() fill them
+    void registerEmitters(); // emissive / emissive_cdf from the device scene, as the constructors, pose(), relight() and deform() fill them
 };
 
 #endif

@@ -426,6 +426,9 @@ int pt_frame_preview(pt_frame *frame, const float *image, const pt_denoise_param
 /* Re-posing the instances of such a scene in place, and the batched assembler behind it (pt_scene_pose, pt_scene_get_pose,
  * pt_mesh_assemble_batch): the struct and entry points are declared, with their contracts, in: */
 #include "pt_pose.h"
+/* Deforming the meshes of such a scene in place -- new vertices from the caller, or a bound rig skinned on the device -- followed by what
+ * a pose does: the structs and entry points are declared, with their contracts, in: */
+#include "pt_deform.h"
 /* Where the surface a pixel sees was at the previous pose, and the temporal push that reprojects that point (pt_motion_table,
  * pt_render_features_motion, pt_temporal_denoise_motion): the entry points are declared, with their contracts, in: */
 #include "pt_motion.h"

@@ -94,7 +94,8 @@ namespace {
         std::vector<MeshInstance> instances;
         std::vector<uint32_t> first, count; // object range of every instance
         std::vector<const MaterialHandler *> slots; // the handler behind every material index; one handler may hold several (Scene::relight)
-        std::mutex mutex;                   // guards `made`
+        std::map<const io::MeshData *, uint32_t> skin_bones; // the bone count of the rig bound to a mesh (Scene::bindSkin)
+        std::mutex mutex;                   // guards `made` and `skin_bones`
         std::unordered_map<uint32_t, std::unique_ptr<Object>> made; // object index -> Triangle
 
         // The Triangle behind object `index`, made on first use from the arrays the device builder took
@@ -507,6 +508,126 @@ void Scene::relight(std::vector<std::unique_ptr<LightSource>> &&new_light_source
         }
     }
     light_sources = std::move(new_light_sources);
+    registerEmitters();
+}
+
+namespace {
+
+    MeshState *meshStateOf(const Scene *scene, const char *who) {
+        MeshStates &states = meshStates();
+        std::lock_guard<std::mutex> lock(states.mutex);
+        auto found = states.of.find(scene);
+        if(found == states.of.end()) {
+            throw std::invalid_argument(std::string("PathTrace: Scene::") + who + " on a Scene without mesh instances");
+        }
+        return found->second.get();
+    }
+
+    // The index the constructor gave `mesh` in the device scene's mesh list: MeshData are numbered in the order the instances first use them
+    uint32_t meshIndexOf(const MeshState &state, const io::MeshData *mesh, const char *who) {
+        std::map<const io::MeshData *, uint32_t> mesh_of;
+        for(const MeshInstance &instance : state.instances) {
+            mesh_of.emplace(instance.mesh.get(), static_cast<uint32_t>(mesh_of.size()));
+        }
+        auto found = mesh_of.find(mesh);
+        if(mesh == nullptr || found == mesh_of.end()) {
+            throw std::invalid_argument(std::string("PathTrace: Scene::") + who + " names a mesh no instance of the Scene uses");
+        }
+        return found->second;
+    }
+
+    // One pt_mesh_deform on every replica, then what a pose leaves to do on the host side: the ranges, and the Triangles handed out so far
+    void deformReplicas(const std::vector<pt_scene *> &replicas, MeshState &state, const pt_mesh_deform &deform, const char *who) {
+        for(size_t r = 0; r < replicas.size(); r++) {
+            const int rc = pt_scene_deform(replicas[r], &deform, 1, nullptr, 0, nullptr, nullptr);
+            if(rc != PT_OK) {
+                throw std::runtime_error(std::string("PathTrace: Scene::") + who + " cannot deform the device scene (replica " + std::to_string(r) + "): " + pt_last_error());
+            }
+        }
+        std::lock_guard<std::mutex> lock(state.mutex);
+        pt_scene_instance_ranges(replicas[0], state.first.data(), state.count.data());
+        state.made.clear(); // (the Triangles handed out so far: their objects are other triangles now, or none)
+    }
+
+} // namespace
+
+void Scene::bindSkin(const std::shared_ptr<const io::MeshData> &mesh, const std::vector<uint32_t> &bone_indices, const std::vector<float> &weights, uint32_t influences) {
+    MeshState *state = meshStateOf(this, "bindSkin");
+    pt_skin skin{};
+    skin.mesh = meshIndexOf(*state, mesh.get(), "bindSkin");
+    if(influences < 1 || influences > PT_SKIN_MAX_INFLUENCES) {
+        throw std::invalid_argument("PathTrace: Scene::bindSkin takes 1 .. 8 influences per vertex");
+    }
+    if(bone_indices.size() != mesh->vertices.size() * influences || weights.size() != bone_indices.size()) {
+        throw std::invalid_argument("PathTrace: Scene::bindSkin needs `influences` bone indices and weights per vertex of the mesh");
+    }
+    skin.n_bones = bone_indices.empty() ? 1 : *std::max_element(bone_indices.begin(), bone_indices.end()) + 1;
+    skin.influences = influences;
+    const uint32_t no_index = 0;
+    const float no_weight = 0.0F;
+    skin.bone = bone_indices.empty() ? &no_index : bone_indices.data(); // (a mesh without vertices: a null array would unbind)
+    skin.weight = weights.empty() ? &no_weight : weights.data();
+    for(size_t r = 0; r < replicas.size(); r++) {
+        const int rc = pt_scene_bind_skin(replicas[r], &skin);
+        if(rc != PT_OK) {
+            throw std::runtime_error("PathTrace: Scene::bindSkin cannot bind the skin (replica " + std::to_string(r) + "): " + pt_last_error());
+        }
+    }
+    std::lock_guard<std::mutex> lock(state->mutex);
+    state->skin_bones[mesh.get()] = skin.n_bones;
+}
+
+void Scene::deform(const std::shared_ptr<const io::MeshData> &mesh, const std::vector<vec3<float>> &vertices) {
+    static_assert(sizeof(vec3<float>) == 3 * sizeof(float), "vertices are handed over as a flat array");
+    MeshState *state = meshStateOf(this, "deform");
+    pt_mesh_deform deform{};
+    deform.mesh = meshIndexOf(*state, mesh.get(), "deform");
+    deform.kind = PT_DEFORM_VERTICES;
+    if(vertices.size() != mesh->vertices.size()) {
+        throw std::invalid_argument("PathTrace: Scene::deform needs one vertex per vertex of the mesh");
+    }
+    const float none[3] = {0.0F, 0.0F, 0.0F};
+    deform.data = vertices.empty() ? none : reinterpret_cast<const float *>(vertices.data());
+    deform.count = static_cast<uint32_t>(vertices.size());
+    deformReplicas(replicas, *state, deform, "deform");
+    registerEmitters();
+}
+
+void Scene::deform(const std::shared_ptr<const io::MeshData> &mesh, const std::vector<mat4<float>> &bones) {
+    MeshState *state = meshStateOf(this, "deform");
+    pt_mesh_deform deform{};
+    deform.mesh = meshIndexOf(*state, mesh.get(), "deform");
+    deform.kind = PT_DEFORM_BONES;
+    {
+        std::lock_guard<std::mutex> lock(state->mutex);
+        auto bound = state->skin_bones.find(mesh.get());
+        if(bound == state->skin_bones.end()) {
+            throw std::invalid_argument("PathTrace: Scene::deform with bones needs a rig (Scene::bindSkin first)");
+        }
+        if(bones.size() != bound->second) {
+            throw std::invalid_argument("PathTrace: Scene::deform needs one matrix per bone of the rig");
+        }
+    }
+    std::vector<float> rows(12 * std::max<size_t>(bones.size(), 1));
+    for(size_t b = 0; b < bones.size(); b++) {
+        for(int r = 0; r < 3; r++) {
+            for(int c = 0; c < 4; c++) {
+                rows[12 * b + 4 * static_cast<size_t>(r) + static_cast<size_t>(c)] = bones[b].rows[r][c];
+            }
+        }
+    }
+    deform.data = rows.data();
+    deform.count = static_cast<uint32_t>(bones.size());
+    deformReplicas(replicas, *state, deform, "deform");
+    registerEmitters();
+}
+
+void Scene::restShape(const std::shared_ptr<const io::MeshData> &mesh) {
+    MeshState *state = meshStateOf(this, "restShape");
+    pt_mesh_deform deform{};
+    deform.mesh = meshIndexOf(*state, mesh.get(), "restShape");
+    deform.kind = PT_DEFORM_REST;
+    deformReplicas(replicas, *state, deform, "restShape");
     registerEmitters();
 }
 
