@@ -65,6 +65,8 @@ MOTION_EXPORTS = ["pt_motion_table", "pt_render_features_motion", "pt_render_fea
 RELIGHT_EXPORTS = ["pt_scene_relight", "pt_scene_get_materials", "pt_scene_get_point_lights"]
 # ... and these in include/pt_deform.h
 DEFORM_EXPORTS = ["pt_scene_bind_skin", "pt_scene_deform", "pt_scene_get_mesh_vertices"]
+# ... and these in include/pt_morph.h
+MORPH_EXPORTS = ["pt_scene_bind_morphs", "pt_scene_morph", "pt_scene_get_morphs"]
 DEFORM_VERTICES, DEFORM_BONES, DEFORM_REST = 0, 1, 2
 SKIN_MAX_INFLUENCES = 8
 MOTION_STATIC, MOTION_MOVED, MOTION_NONE = 0, 1, 2
@@ -443,6 +445,25 @@ class DeformInfo(C.Structure):  # pt_deform_info
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class MorphTarget(C.Structure):  # pt_morph_target
+    _fields_ = [("n_deltas", C.c_uint32), ("vertex", C.c_void_p), ("delta", C.c_void_p)]
+
+
+class MorphSet(C.Structure):  # pt_morph_set
+    _fields_ = [("mesh", C.c_uint32), ("n_targets", C.c_uint32), ("targets", C.c_void_p)]
+
+
+class MeshMorph(C.Structure):  # pt_mesh_morph
+    _fields_ = [("mesh", C.c_uint32), ("weights", C.c_void_p), ("n_weights", C.c_uint32), ("bones", C.c_void_p), ("n_bones", C.c_uint32)]
+
+
+class MorphInfo(C.Structure):  # pt_morph_info
+    _fields_ = DeformInfo._fields_ + [("n_vertices_morphed", C.c_uint32), ("morph_ms", C.c_float), ("n_entries_read", C.c_uint64)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class Relight(C.Structure):  # pt_relight
     _fields_ = [("materials", C.c_void_p), ("n_materials", C.c_uint32), ("set_point_lights", C.c_int32), ("light_pos", C.c_void_p), ("light_spectrum", C.c_void_p),
                 ("n_point_lights", C.c_uint32), ("instances", C.c_void_p), ("instance_material", C.c_void_p), ("n_instance_materials", C.c_uint32)]
@@ -758,6 +779,70 @@ class Scene:
         out = np.zeros((n.value, 3), np.float32)
         _check(load().pt_scene_get_mesh_vertices(self._h, C.c_uint32(mesh), _ptr(out), None))
         return out
+
+    def bind_morphs(self, mesh, targets):
+        """pt_scene_bind_morphs: a set of morph targets for mesh `mesh`: targets is a list of (indices or None, deltas) -- sparse, with
+        strictly ascending vertex indices and deltas (n, 3), or dense (indices None), with deltas (n_vertices, 3).  None or [] unbinds.
+        Every index is checked on the host; the set is uploaded once, vertex-major."""
+        ms, keep = MorphSet(), []
+        ms.mesh = mesh
+        if targets:
+            table = (MorphTarget * len(targets))()
+            for t, (indices, deltas) in enumerate(targets):
+                d = np.ascontiguousarray(deltas, dtype=np.float32).reshape(-1, 3)
+                backing = d if len(d) > 0 else np.zeros((1, 3), np.float32)
+                keep += [d, backing]
+                table[t].n_deltas, table[t].delta = len(d), backing.ctypes.data
+                if indices is not None:
+                    idx = np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1)
+                    if len(idx) != len(d):
+                        raise ValueError("bind_morphs: target %d has %d indices for %d deltas" % (t, len(idx), len(d)))
+                    backing = idx if len(idx) > 0 else np.zeros(1, np.uint32)
+                    keep += [idx, backing]
+                    table[t].vertex = backing.ctypes.data
+            ms.n_targets, ms.targets = len(targets), C.addressof(table)
+        _check(load().pt_scene_bind_morphs(self._h, C.byref(ms)))
+        del keep
+
+    def morph(self, weights=None, bones=None, transforms=None, instances=None):
+        """pt_scene_morph: weights: {mesh: (n_targets,)} makes a mesh's vertices from its REST vertices and the set of bind_morphs on the
+        device; bones: {mesh: (n_bones, 3, 4) or (n_bones, 4, 4) matrices} sends the morphed vertices of a mesh named in `weights`
+        through the rig of bind_skin in the same launch.  transforms / instances: as pose(); None = the pose stays.  All instances of a
+        mesh share its shape.  Returns the pt_morph_info as a dict and updates n_objects."""
+        entries, keep = [], []
+        bones = dict(bones or {})
+        for mesh, w in (weights or {}).items():
+            a = np.ascontiguousarray(w, dtype=np.float32).reshape(-1)
+            backing = a if len(a) > 0 else np.zeros(1, np.float32)
+            keep += [a, backing]
+            entry = MeshMorph(int(mesh), backing.ctypes.data, len(a), None, 0)
+            if mesh in bones:
+                b = np.asarray(bones.pop(mesh), dtype=np.float32)
+                if b.ndim == 3 and b.shape[1:] == (4, 4):
+                    b = b[:, :3, :]
+                b = np.ascontiguousarray(b).reshape(-1, 12)
+                backing = b if len(b) > 0 else np.zeros((1, 12), np.float32)
+                keep += [b, backing]
+                entry.bones, entry.n_bones = backing.ctypes.data, len(b)
+            entries.append(entry)
+        if bones:
+            raise ValueError("morph: bones for meshes %s without weights" % sorted(bones))
+        table = (MeshMorph * max(len(entries), 1))(*entries)
+        m = np.zeros((0, 16), np.float32) if transforms is None else np.ascontiguousarray(transforms, dtype=np.float32).reshape(-1, 16)
+        idx = None if instances is None else np.ascontiguousarray(instances, dtype=np.uint32).reshape(-1)
+        if idx is not None and len(idx) != len(m):
+            raise ValueError("morph: %d instance indices for %d matrices" % (len(idx), len(m)))
+        info = MorphInfo()
+        _check(load().pt_scene_morph(self._h, table, C.c_uint32(len(entries)), _ptr(idx), C.c_uint32(len(m)), _ptr(m) if len(m) > 0 else None, C.byref(info)))
+        del keep
+        self.n_objects = self._n_desc_objects + int(info.n_triangles)
+        return info.as_dict()
+
+    def morphs(self, mesh):
+        """pt_scene_get_morphs: (targets, listed (vertex, delta) pairs) of the set bound to mesh `mesh`; (0, 0) for none."""
+        n_targets, n_entries = C.c_uint32(), C.c_uint64()
+        _check(load().pt_scene_get_morphs(self._h, C.c_uint32(mesh), C.byref(n_targets), C.byref(n_entries)))
+        return n_targets.value, n_entries.value
 
     def relight(self, materials=None, point_lights=None, instance_materials=None):
         """pt_scene_relight: a new look in place.  materials: the whole new table (MATERIAL_DTYPE), None = it stays; point_lights:

@@ -2,17 +2,17 @@
 // current vertices are made in its spare buffer -- uploaded, or skinned from the rest vertices by pt_skin_launch (pt_deform.hip) on the
 // scene's stream --, the meshes' `shape` pointers are turned to them, and the rest is a pose: rebuild_instances (pt_pose.cpp) assembles
 // all instances behind the skinning launches without a host wait between them and adopts the finished scene.  Only then do spare and
-// current buffers change places; a call that fails turns the pointers back.
+// current buffers change places; a call that fails turns the pointers back.  That back half -- adopt_shapes, with the pose arguments'
+// checks and the vertex buffers beside it -- is shared with pt_scene_morph (pt_morph.cpp), which makes its vertices with another kernel.
 #include "pt_host.h"
 
 using namespace pth;
 
-namespace {
+namespace pth {
 
-const char *const NO_INSTANCES = "the scene has no instances: it was not made by pt_scene_create_meshes with instances";
-const char *const LIVE_FRAME = "the scene has a live frame: its parked state belongs to the present geometry (pt_frame_destroy first)";
+const char *const DEFORM_NO_INSTANCES = "the scene has no instances: it was not made by pt_scene_create_meshes with instances";
+const char *const DEFORM_LIVE_FRAME = "the scene has a live frame: its parked state belongs to the present geometry (pt_frame_destroy first)";
 
-// The mesh `mesh` of the creating call, if an instance uses it
 int used_mesh(PoseKeep &keep, uint32_t mesh, KeptMesh **out) {
     if(mesh >= keep.meshes.size()) {
         return fail(PT_ERR_INVALID, "mesh index " + std::to_string(mesh) + " out of range: the scene was created with " + std::to_string(keep.meshes.size()));
@@ -24,16 +24,38 @@ int used_mesh(PoseKeep &keep, uint32_t mesh, KeptMesh **out) {
     return PT_OK;
 }
 
-// buf.ensure(n), counted when it allocates
-template<typename T>
-int ensure_counted(PoseKeep &keep, DevBuf<T> &buf, size_t n) {
-    const bool allocates = !(n <= buf.count && buf.ptr != nullptr);
-    PT_HIP(buf.ensure(n));
-    if(allocates) {
-        keep.deform_allocations++;
+int check_pose_arguments(const PoseKeep &keep, const uint32_t *instances, uint32_t n) {
+    const uint32_t n_instances = static_cast<uint32_t>(keep.instances.size());
+    if(instances == nullptr && n != 0 && n != n_instances) {
+        return fail(PT_ERR_INVALID, "a pose of all instances needs " + std::to_string(n_instances) + " matrices, not " + std::to_string(n));
+    }
+    for(uint32_t k = 0; instances != nullptr && k < n; k++) {
+        if(instances[k] >= n_instances) {
+            return fail(PT_ERR_INVALID, "instance index " + std::to_string(instances[k]) + " out of range: the scene has " + std::to_string(n_instances));
+        }
     }
     return PT_OK;
 }
+
+std::vector<pt_mesh_instance> posed_instances(const PoseKeep &keep, const uint32_t *instances, uint32_t n, const float *transforms) {
+    std::vector<pt_mesh_instance> posed = keep.instances; // (adopted with the rest, on success)
+    for(uint32_t k = 0; k < n; k++) {
+        const uint32_t i = instances != nullptr ? instances[k] : k;
+        std::copy(transforms + 16 * static_cast<size_t>(k), transforms + 16 * static_cast<size_t>(k) + 16, posed[i].transform);
+    }
+    return posed;
+}
+
+int ensure_vertex_buffers(PoseKeep &keep, KeptMesh &mesh) {
+    if(mesh.deform == nullptr) {
+        mesh.deform.reset(new MeshDeform());
+    }
+    PT_TRY(ensure_counted(keep, mesh.deform->current, 3 * static_cast<size_t>(mesh.n_vertices)));
+    PT_TRY(ensure_counted(keep, mesh.deform->spare, 3 * static_cast<size_t>(mesh.n_vertices)));
+    return PT_OK;
+}
+
+namespace {
 
 template<typename T>
 void exchange(DevBuf<T> &a, DevBuf<T> &b) {
@@ -42,6 +64,36 @@ void exchange(DevBuf<T> &a, DevBuf<T> &b) {
 }
 
 } // namespace
+
+int adopt_shapes(pt_scene *s, const std::vector<const float *> &shape, const std::vector<uint8_t> &in_spare, std::vector<pt_mesh_instance> &&posed,
+                 std::chrono::steady_clock::time_point t_begin, pt_pose_info *info) {
+    PoseKeep &keep = *s->pose;
+    const size_t n_meshes = keep.meshes.size();
+    std::vector<const float *> before(n_meshes, nullptr);
+    for(size_t m = 0; m < n_meshes; m++) {
+        if(shape[m] != nullptr) {
+            before[m] = keep.meshes[m]->shape;
+            keep.meshes[m]->shape = shape[m];
+        }
+    }
+    const int rc = rebuild_instances(s, std::move(posed), t_begin, info);
+    if(rc != PT_OK) {
+        for(size_t m = 0; m < n_meshes; m++) {
+            if(shape[m] != nullptr) {
+                keep.meshes[m]->shape = before[m];
+            }
+        }
+        return rc;
+    }
+    for(size_t m = 0; m < n_meshes; m++) {
+        if(in_spare[m] != 0) {
+            exchange(keep.meshes[m]->deform->current, keep.meshes[m]->deform->spare); // (shape names the buffer that is `current` now)
+        }
+    }
+    return PT_OK;
+}
+
+} // namespace pth
 
 extern "C" {
 
@@ -61,7 +113,7 @@ int pt_scene_bind_skin(pt_scene *s, const pt_skin *skin) {
     }
     std::lock_guard<std::mutex> lock(s->render_mutex);
     if(s->pose == nullptr) {
-        return fail(PT_ERR_UNSUPPORTED, NO_INSTANCES);
+        return fail(PT_ERR_UNSUPPORTED, DEFORM_NO_INSTANCES);
     }
     PoseKeep &keep = *s->pose;
     KeptMesh *mesh = nullptr;
@@ -74,7 +126,7 @@ int pt_scene_bind_skin(pt_scene *s, const pt_skin *skin) {
         }
     }
     if(s->live_frames.load() != 0) {
-        return fail(PT_ERR_INVALID, LIVE_FRAME);
+        return fail(PT_ERR_INVALID, DEFORM_LIVE_FRAME);
     }
     if(mesh->deform == nullptr) {
         if(unbind) {
@@ -124,18 +176,10 @@ int pt_scene_deform(pt_scene *s, const pt_mesh_deform *deforms, uint32_t n_defor
     }
     std::lock_guard<std::mutex> lock(s->render_mutex);
     if(s->pose == nullptr) {
-        return fail(PT_ERR_UNSUPPORTED, NO_INSTANCES);
+        return fail(PT_ERR_UNSUPPORTED, DEFORM_NO_INSTANCES);
     }
     PoseKeep &keep = *s->pose;
-    const uint32_t n_instances = static_cast<uint32_t>(keep.instances.size());
-    if(instances == nullptr && n != 0 && n != n_instances) {
-        return fail(PT_ERR_INVALID, "a pose of all instances needs " + std::to_string(n_instances) + " matrices, not " + std::to_string(n));
-    }
-    for(uint32_t k = 0; instances != nullptr && k < n; k++) {
-        if(instances[k] >= n_instances) {
-            return fail(PT_ERR_INVALID, "instance index " + std::to_string(instances[k]) + " out of range: the scene has " + std::to_string(n_instances));
-        }
-    }
+    PT_TRY(check_pose_arguments(keep, instances, n));
     std::vector<int64_t> entry(keep.meshes.size(), -1); // the last deform that names each mesh
     for(uint32_t e = 0; e < n_deforms; e++) {
         const pt_mesh_deform &de = deforms[e];
@@ -157,22 +201,18 @@ int pt_scene_deform(pt_scene *s, const pt_mesh_deform *deforms, uint32_t n_defor
         entry[de.mesh] = e;
     }
     if(s->live_frames.load() != 0) {
-        return fail(PT_ERR_INVALID, LIVE_FRAME);
+        return fail(PT_ERR_INVALID, DEFORM_LIVE_FRAME);
     }
 
     using clock = std::chrono::steady_clock;
     const auto t_begin = clock::now();
-    std::vector<pt_mesh_instance> posed = keep.instances; // (adopted with the rest, on success)
-    for(uint32_t k = 0; k < n; k++) {
-        const uint32_t i = instances != nullptr ? instances[k] : k;
-        std::copy(transforms + 16 * static_cast<size_t>(k), transforms + 16 * static_cast<size_t>(k) + 16, posed[i].transform);
-    }
+    std::vector<pt_mesh_instance> posed = posed_instances(keep, instances, n, transforms);
     PT_HIP(hipSetDevice(s->device));
     PT_HIP(hipStreamSynchronize(s->stream));
 
     // ---- 1. the new vertices, each mesh's in its spare buffer; the shapes the assembly is to read ---------------------------------------
     const size_t n_meshes = keep.meshes.size();
-    std::vector<const float *> shape(n_meshes, nullptr), before(n_meshes, nullptr);
+    std::vector<const float *> shape(n_meshes, nullptr);
     std::vector<uint8_t> in_spare(n_meshes, 0);
     uint32_t n_deformed = 0, n_skinned_meshes = 0;
     uint64_t n_skinned = 0, total_bones = 0;
@@ -187,12 +227,8 @@ int pt_scene_deform(pt_scene *s, const pt_mesh_deform *deforms, uint32_t n_defor
             shape[m] = mesh.vertices.ptr;
             continue;
         }
-        if(mesh.deform == nullptr) {
-            mesh.deform.reset(new MeshDeform());
-        }
         // (both buffers with the first deformation, so that no later one allocates: they change places after every call)
-        PT_TRY(ensure_counted(keep, mesh.deform->current, 3 * static_cast<size_t>(mesh.n_vertices)));
-        PT_TRY(ensure_counted(keep, mesh.deform->spare, 3 * static_cast<size_t>(mesh.n_vertices)));
+        PT_TRY(ensure_vertex_buffers(keep, mesh));
         shape[m] = mesh.deform->spare.ptr;
         in_spare[m] = 1;
         if(de.kind == PT_DEFORM_BONES) {
@@ -204,15 +240,7 @@ int pt_scene_deform(pt_scene *s, const pt_mesh_deform *deforms, uint32_t n_defor
         PT_TRY(ensure_counted(keep, keep.bone_table, 12 * static_cast<size_t>(total_bones)));
     }
     // (from here on the stream may hold work of this call: whatever happens, it is waited for before the call returns)
-    struct Drain {
-        hipStream_t stream;
-        bool armed = true;
-        ~Drain() {
-            if(armed) {
-                (void)hipStreamSynchronize(stream);
-            }
-        }
-    } drain{s->stream};
+    StreamDrain drain{s->stream};
     const auto t_upload = clock::now();
     size_t bone_at = 0;
     std::vector<size_t> table_at(n_meshes, 0);
@@ -254,28 +282,9 @@ int pt_scene_deform(pt_scene *s, const pt_mesh_deform *deforms, uint32_t n_defor
     }
 
     // ---- 2. and 3. the pose: the assembly reads the new shapes behind the launches above; a failure turns the pointers back -------------
-    for(size_t m = 0; m < n_meshes; m++) {
-        if(entry[m] >= 0) {
-            before[m] = keep.meshes[m]->shape;
-            keep.meshes[m]->shape = shape[m];
-        }
-    }
     pt_pose_info posed_info{};
-    const int rc = rebuild_instances(s, std::move(posed), t_begin, &posed_info);
-    if(rc != PT_OK) {
-        for(size_t m = 0; m < n_meshes; m++) {
-            if(entry[m] >= 0) {
-                keep.meshes[m]->shape = before[m];
-            }
-        }
-        return rc;
-    }
+    PT_TRY(adopt_shapes(s, shape, in_spare, std::move(posed), t_begin, &posed_info));
     drain.armed = false; // (rebuild_instances has waited)
-    for(size_t m = 0; m < n_meshes; m++) {
-        if(in_spare[m] != 0) {
-            exchange(keep.meshes[m]->deform->current, keep.meshes[m]->deform->spare); // (shape names the buffer that is `current` now)
-        }
-    }
     float skin_ms = 0.0F;
     if(n_skinned_meshes > 0) {
         PT_HIP(skin.ms(&skin_ms));
@@ -310,7 +319,7 @@ int pt_scene_get_mesh_vertices(pt_scene *s, uint32_t mesh_index, float *out, uin
     }
     std::lock_guard<std::mutex> lock(s->render_mutex);
     if(s->pose == nullptr) {
-        return fail(PT_ERR_UNSUPPORTED, NO_INSTANCES);
+        return fail(PT_ERR_UNSUPPORTED, DEFORM_NO_INSTANCES);
     }
     KeptMesh *mesh = nullptr;
     PT_TRY(used_mesh(*s->pose, mesh_index, &mesh));

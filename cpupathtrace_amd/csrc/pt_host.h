@@ -1,5 +1,6 @@
 // pt_host.h -- what the host units of libpathtrace_hip.so share: pt_api.cpp (scenes), pt_meshes.cpp (scenes from meshes and instances),
 // pt_pose.cpp (their instances under new matrices, in place), pt_deform.cpp (their meshes under new vertices, in place),
+// pt_morph.cpp (their meshes under blend shapes, in place),
 // pt_relight.cpp (their materials and lights replaced in place),
 // pt_render.cpp (render calls), pt_frames.cpp and pt_frame_maps.cpp (resumable frames and their maps; pt_frames.h) and pt_image.cpp
 // (post-processing, features, denoising).  Internal:
@@ -30,6 +31,7 @@
 #include "pt_mesh.h"
 #include "pt_mesh_batch.h"
 #include "pt_skin.h"
+#include "pt_morph_skin.h"
 #include "pt_bvh.h"
 #include "pt_kernels.h"
 #include "pt_denoise.h"
@@ -208,6 +210,11 @@ struct MeshDeform {
     DevBuf<float> skin_weight;  // [n_vertices][skin_k]
     uint32_t skin_bones = 0, skin_k = 0; // skin_bones == 0: no skin
     DevBuf<float> current, spare;        // [n_vertices][3] each
+    // ... and what pt_scene_bind_morphs (pt_morph.cpp; include/pt_morph.h) binds: the set's entries vertex-major
+    DevBuf<uint32_t> morph_row_start;    // [n_vertices + 1]
+    DevBuf<PtMorphEntry> morph_entries;  // [morph_entry_count], a vertex's in ascending target order
+    uint32_t morph_targets = 0;          // 0: no set
+    uint64_t morph_entry_count = 0;
 };
 
 // One mesh in device memory
@@ -241,6 +248,7 @@ struct PoseKeep {
     PtBatchScratch scratch;              // the assembler's, grown by the first pose (creation has one of its own, freed when it returns)
     DevBuf<float> spare_pos, spare_nrm;  // the arrays the next pose assembles into (the scene keeps the positions it was built from)
     DevBuf<float> bone_table;            // pt_scene_deform: the bone matrices of a call's skinned meshes, end to end
+    DevBuf<float> morph_weights;         // pt_scene_morph: the weights of a call's morphed meshes, end to end
     uint64_t deform_allocations = 0;     // ... and its hipMalloc calls for vertex, skin and bone buffers so far
 };
 
@@ -413,6 +421,48 @@ int finish_mesh_scene(int device, const pt_scene_desc *d, const MeshAssembly &as
 // as it was.  The stream has been waited for when this returns.  `info` (may be null) receives what a pose reports; t_begin is the
 // call's start, for its wall-clock fields.
 int rebuild_instances(pt_scene *s, std::vector<pt_mesh_instance> &&posed, std::chrono::steady_clock::time_point t_begin, pt_pose_info *info);
+
+// ---- pt_deform.cpp ---------------------------------------------------------------------------------------------------------------------
+
+// What pt_scene_deform and pt_scene_morph (pt_morph.cpp) share.  The refusals of both, word for word:
+extern const char *const DEFORM_NO_INSTANCES;
+extern const char *const DEFORM_LIVE_FRAME;
+// The mesh `mesh` of the creating call, if an instance uses it
+int used_mesh(PoseKeep &keep, uint32_t mesh, KeptMesh **out);
+// buf.ensure(n), counted in keep.deform_allocations when it allocates
+template<typename T>
+int ensure_counted(PoseKeep &keep, DevBuf<T> &buf, size_t n) {
+    const bool allocates = !(n <= buf.count && buf.ptr != nullptr);
+    PT_HIP(buf.ensure(n));
+    if(allocates) {
+        keep.deform_allocations++;
+    }
+    return PT_OK;
+}
+// The pose arguments of a deformation, checked as pt_scene_pose checks them (before any device work) ...
+int check_pose_arguments(const PoseKeep &keep, const uint32_t *instances, uint32_t n);
+// ... and the instance table they ask for
+std::vector<pt_mesh_instance> posed_instances(const PoseKeep &keep, const uint32_t *instances, uint32_t n, const float *transforms);
+// Both current and spare vertices of `mesh`, allocated by its first deformation and reused: they change places after every call
+int ensure_vertex_buffers(PoseKeep &keep, KeptMesh &mesh);
+// The back half of a deformation, once every named mesh has its new vertices in the buffer shape[m] names (null: mesh m is not named;
+// in_spare[m]: the buffer is the mesh's spare one), made by work the scene's stream holds: the meshes' `shape` pointers are turned to
+// them, rebuild_instances assembles all instances under `posed` behind that work without a host wait and adopts the finished scene,
+// and only then do spare and current buffers change places; a failure turns the pointers back.  The stream has been waited for when
+// this returns PT_OK.
+int adopt_shapes(pt_scene *s, const std::vector<const float *> &shape, const std::vector<uint8_t> &in_spare, std::vector<pt_mesh_instance> &&posed,
+                 std::chrono::steady_clock::time_point t_begin, pt_pose_info *info);
+// Waits for `stream` when it goes out of scope armed: from its construction on the stream may hold work of a call that must not
+// outlive the call
+struct StreamDrain {
+    hipStream_t stream;
+    bool armed = true;
+    ~StreamDrain() {
+        if(armed) {
+            (void)hipStreamSynchronize(stream);
+        }
+    }
+};
 
 // ---- pt_render.cpp: the persistent path kernel (pt_path.hip), one launch per render call ----------------------------------------------
 

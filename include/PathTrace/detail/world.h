@@ -271,6 +271,13 @@ struct MeshInstance {
     std::shared_ptr<MaterialHandler> handler;
 };
 
+// One blend shape (morph target) of a mesh: for the listed vertices -- strictly ascending indices into the MeshData's vertices -- the
+// offsets a weight of 1 adds.  Empty `vertices` means dense: one delta per vertex of the mesh, in order (Scene::bindMorphs).
+struct MorphTarget {
+    std::vector<uint32_t> vertices;
+    std::vector<vec3<float>> deltas;
+};
+
 class Scene {
   public:
     // takes ownership; builds the hierarchy and the device-resident copy (device = $PATHTRACE_DEVICE, default 0).  With
@@ -330,6 +337,19 @@ class Scene {
     void deform(const std::shared_ptr<const io::MeshData> &mesh, const std::vector<vec3<float>> &vertices);
     void deform(const std::shared_ptr<const io::MeshData> &mesh, const std::vector<mat4<float>> &bones);
     void restShape(const std::shared_ptr<const io::MeshData> &mesh);
+
+    // Blend shapes for a mesh in place (pt_scene_bind_morphs, pt_scene_morph, include/pt_morph.h).  bindMorphs gives a mesh its targets
+    // (an empty list unbinds); morph(mesh, weights) makes its vertices on the device from the MeshData's vertices: every target adds
+    // weight * delta to the vertices it lists, in target order, in float, no target skipped; morph(mesh, weights, bones) sends the
+    // morphed vertices through the rig of bindSkin in the same launch, as deform(mesh, bones) sends the rest vertices.  Nothing compounds:
+    // every call starts from the MeshData's vertices, and a later deform(mesh, bones) skins those, not the morphed ones.  Afterwards the
+    // Scene is what deform() leaves: that of a Scene constructed from MeshData with the new vertices; every replica is morphed.  Throws
+    // as deform does: std::invalid_argument for a Scene without mesh instances, a MeshData no instance uses, indices that do not
+    // ascend or name no vertex, a target whose deltas do not match its indices (or, dense, the mesh), weights that are not one per
+    // bound target, no bound targets, bones without a rig or of another count; std::runtime_error when the device refuses.  Non-virtual.
+    void bindMorphs(const std::shared_ptr<const io::MeshData> &mesh, const std::vector<MorphTarget> &targets);
+    void morph(const std::shared_ptr<const io::MeshData> &mesh, const std::vector<float> &weights);
+    void morph(const std::shared_ptr<const io::MeshData> &mesh, const std::vector<float> &weights, const std::vector<mat4<float>> &bones);
 
     // the device scene behind the C ABI (include/pt_hip.h); used by processJob / processItem
     pt_scene *deviceScene() const noexcept { return device_scene; }

@@ -429,6 +429,9 @@ int pt_frame_preview(pt_frame *frame, const float *image, const pt_denoise_param
 /* Deforming the meshes of such a scene in place -- new vertices from the caller, or a bound rig skinned on the device -- followed by what
  * a pose does: the structs and entry points are declared, with their contracts, in: */
 #include "pt_deform.h"
+/* Blend shapes for the meshes of such a scene -- a bound set of morph targets weighted on the device, alone or in front of the bound rig
+ * in one launch -- followed by what a pose does: the structs and entry points are declared, with their contracts, in: */
+#include "pt_morph.h"
 /* Where the surface a pixel sees was at the previous pose, and the temporal push that reprojects that point (pt_motion_table,
  * pt_render_features_motion, pt_temporal_denoise_motion): the entry points are declared, with their contracts, in: */
 #include "pt_motion.h"

@@ -95,7 +95,8 @@ namespace {
         std::vector<uint32_t> first, count; // object range of every instance
         std::vector<const MaterialHandler *> slots; // the handler behind every material index; one handler may hold several (Scene::relight)
         std::map<const io::MeshData *, uint32_t> skin_bones; // the bone count of the rig bound to a mesh (Scene::bindSkin)
-        std::mutex mutex;                   // guards `made` and `skin_bones`
+        std::map<const io::MeshData *, uint32_t> morph_targets; // ... and the target count of its morph set (Scene::bindMorphs)
+        std::mutex mutex;                   // guards `made`, `skin_bones` and `morph_targets`
         std::unordered_map<uint32_t, std::unique_ptr<Object>> made; // object index -> Triangle
 
         // The Triangle behind object `index`, made on first use from the arrays the device builder took
@@ -628,6 +629,108 @@ void Scene::restShape(const std::shared_ptr<const io::MeshData> &mesh) {
     deform.mesh = meshIndexOf(*state, mesh.get(), "restShape");
     deform.kind = PT_DEFORM_REST;
     deformReplicas(replicas, *state, deform, "restShape");
+    registerEmitters();
+}
+
+void Scene::bindMorphs(const std::shared_ptr<const io::MeshData> &mesh, const std::vector<MorphTarget> &targets) {
+    static_assert(sizeof(vec3<float>) == 3 * sizeof(float), "deltas are handed over as a flat array");
+    MeshState *state = meshStateOf(this, "bindMorphs");
+    pt_morph_set set{};
+    set.mesh = meshIndexOf(*state, mesh.get(), "bindMorphs");
+    const size_t n_vertices = mesh->vertices.size();
+    std::vector<pt_morph_target> table(targets.size());
+    const uint32_t no_index = 0;
+    const float no_delta[3] = {0.0F, 0.0F, 0.0F};
+    for(size_t t = 0; t < targets.size(); t++) {
+        const MorphTarget &target = targets[t];
+        const bool dense = target.vertices.empty();
+        if(dense ? (!target.deltas.empty() && target.deltas.size() != n_vertices) : target.deltas.size() != target.vertices.size()) {
+            throw std::invalid_argument("PathTrace: Scene::bindMorphs needs one delta per listed vertex, or, without indices, per vertex of the mesh");
+        }
+        for(size_t j = 0; j < target.vertices.size(); j++) {
+            if(target.vertices[j] >= n_vertices || (j > 0 && target.vertices[j] <= target.vertices[j - 1])) {
+                throw std::invalid_argument("PathTrace: Scene::bindMorphs needs strictly ascending vertex indices below the mesh's vertex count");
+            }
+        }
+        table[t].n_deltas = static_cast<uint32_t>(target.deltas.size());
+        // (an empty target keeps a non-null index array: without indices it would be a dense one)
+        table[t].vertex = dense ? (target.deltas.empty() ? &no_index : nullptr) : target.vertices.data();
+        table[t].delta = target.deltas.empty() ? no_delta : reinterpret_cast<const float *>(target.deltas.data());
+    }
+    set.n_targets = static_cast<uint32_t>(table.size());
+    set.targets = table.empty() ? nullptr : table.data();
+    for(size_t r = 0; r < replicas.size(); r++) {
+        const int rc = pt_scene_bind_morphs(replicas[r], &set);
+        if(rc != PT_OK) {
+            throw std::runtime_error("PathTrace: Scene::bindMorphs cannot bind the targets (replica " + std::to_string(r) + "): " + pt_last_error());
+        }
+    }
+    std::lock_guard<std::mutex> lock(state->mutex);
+    state->morph_targets[mesh.get()] = set.n_targets;
+}
+
+namespace {
+
+    // One pt_mesh_morph on every replica, then what a deform leaves to do on the host side
+    void morphReplicas(const std::vector<pt_scene *> &replicas, MeshState &state, const io::MeshData *mesh, pt_mesh_morph &morph, const std::vector<float> &weights) {
+        {
+            std::lock_guard<std::mutex> lock(state.mutex);
+            auto bound = state.morph_targets.find(mesh);
+            if(bound == state.morph_targets.end() || bound->second == 0) {
+                throw std::invalid_argument("PathTrace: Scene::morph needs bound targets (Scene::bindMorphs first)");
+            }
+            if(weights.size() != bound->second) {
+                throw std::invalid_argument("PathTrace: Scene::morph needs one weight per bound target");
+            }
+        }
+        morph.weights = weights.data();
+        morph.n_weights = static_cast<uint32_t>(weights.size());
+        for(size_t r = 0; r < replicas.size(); r++) {
+            const int rc = pt_scene_morph(replicas[r], &morph, 1, nullptr, 0, nullptr, nullptr);
+            if(rc != PT_OK) {
+                throw std::runtime_error("PathTrace: Scene::morph cannot morph the device scene (replica " + std::to_string(r) + "): " + pt_last_error());
+            }
+        }
+        std::lock_guard<std::mutex> lock(state.mutex);
+        pt_scene_instance_ranges(replicas[0], state.first.data(), state.count.data());
+        state.made.clear(); // (the Triangles handed out so far: their objects are other triangles now, or none)
+    }
+
+} // namespace
+
+void Scene::morph(const std::shared_ptr<const io::MeshData> &mesh, const std::vector<float> &weights) {
+    MeshState *state = meshStateOf(this, "morph");
+    pt_mesh_morph morph{};
+    morph.mesh = meshIndexOf(*state, mesh.get(), "morph");
+    morphReplicas(replicas, *state, mesh.get(), morph, weights);
+    registerEmitters();
+}
+
+void Scene::morph(const std::shared_ptr<const io::MeshData> &mesh, const std::vector<float> &weights, const std::vector<mat4<float>> &bones) {
+    MeshState *state = meshStateOf(this, "morph");
+    pt_mesh_morph morph{};
+    morph.mesh = meshIndexOf(*state, mesh.get(), "morph");
+    {
+        std::lock_guard<std::mutex> lock(state->mutex);
+        auto bound = state->skin_bones.find(mesh.get());
+        if(bound == state->skin_bones.end()) {
+            throw std::invalid_argument("PathTrace: Scene::morph with bones needs a rig (Scene::bindSkin first)");
+        }
+        if(bones.size() != bound->second) {
+            throw std::invalid_argument("PathTrace: Scene::morph needs one matrix per bone of the rig");
+        }
+    }
+    std::vector<float> rows(12 * std::max<size_t>(bones.size(), 1));
+    for(size_t b = 0; b < bones.size(); b++) {
+        for(int r = 0; r < 3; r++) {
+            for(int c = 0; c < 4; c++) {
+                rows[12 * b + 4 * static_cast<size_t>(r) + static_cast<size_t>(c)] = bones[b].rows[r][c];
+            }
+        }
+    }
+    morph.bones = rows.data();
+    morph.n_bones = static_cast<uint32_t>(bones.size());
+    morphReplicas(replicas, *state, mesh.get(), morph, weights);
     registerEmitters();
 }
 
