@@ -70,6 +70,18 @@ MORPH_EXPORTS = ["pt_scene_bind_morphs", "pt_scene_morph", "pt_scene_get_morphs"
 DEFORM_VERTICES, DEFORM_BONES, DEFORM_REST = 0, 1, 2
 SKIN_MAX_INFLUENCES = 8
 MOTION_STATIC, MOTION_MOVED, MOTION_NONE = 0, 1, 2
+# ... and these in include/pt_motion_shapes.h
+MOTION_SHAPES_EXPORTS = ["pt_scene_motion_mark", "pt_scene_motion_unmark", "pt_scene_get_motion_mark", "pt_scene_get_triangle_faces", "pt_render_features_motion_marked",
+                         "pt_render_features_motion_marked_device"]
+MOTION_DEFORMED = 3
+
+
+class MotionMarkInfo(C.Structure):
+    """pt_motion_mark_info"""
+    _fields_ = [("n_instances", C.c_uint32), ("n_meshes_copied", C.c_uint32), ("bytes_copied", C.c_uint64), ("allocations", C.c_uint32), ("total_ms", C.c_float)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 
@@ -1001,6 +1013,48 @@ class Scene:
         _check(load().pt_render_features_motion_device(self._h, C.byref(cp), C.byref(op), _ptr(prev), C.c_void_p(d_features_ptr), C.c_void_p(d_motion_ptr),
                                                        C.c_void_p(stream_ptr)))
 
+    def mark_motion(self):
+        """pt_scene_motion_mark: the scene as it is now becomes "the previous frame" of render_features_motion_marked: the instance
+        matrices and every mesh's vertices are remembered (a deformed mesh's are copied on the device).  Returns the info as a dict."""
+        info = MotionMarkInfo()
+        _check(load().pt_scene_motion_mark(self._h, C.byref(info)))
+        return info.as_dict()
+
+    def unmark_motion(self):
+        """pt_scene_motion_unmark: forgets the mark and frees what it kept."""
+        _check(load().pt_scene_motion_unmark(self._h))
+
+    def motion_mark(self):
+        """pt_scene_get_motion_mark: (the marked matrices (n_instances, 4, 4), the kind (n_instances,) uint8 every instance has against
+        the mark now: MOTION_STATIC | MOTION_MOVED | MOTION_NONE | MOTION_DEFORMED)."""
+        m, kind = np.zeros((self.n_instances, 4, 4), np.float32), np.zeros(self.n_instances, np.uint8)
+        _check(load().pt_scene_get_motion_mark(self._h, _ptr(m), _ptr(kind)))
+        return m, kind
+
+    def triangle_faces(self):
+        """pt_scene_get_triangle_faces: for every instance triangle, in object order, the scene-wide face it came from (the faces of all
+        instances end to end, before rejection), uint32.  Needs a mark and a pose / deform / morph since the first mark."""
+        n = C.c_uint32()
+        _check(load().pt_scene_get_triangle_faces(self._h, None, C.byref(n)))
+        out = np.zeros(n.value, np.uint32)
+        _check(load().pt_scene_get_triangle_faces(self._h, _ptr(out), None))
+        return out
+
+    def render_features_motion_marked(self, camera, options):
+        """render_features_motion with the scene's mark as the previous frame (pt_render_features_motion_marked): meshes deformed or
+        morphed since the mark are reprojected per vertex.  (features, motion) as render_features_motion."""
+        h, w = options["image_height"], options["image_width"]
+        feat, mot = np.empty((h, w, 3, 4), np.float32), np.empty((h, w, 2, 4), np.float32)
+        cp, op = _camera(camera), _options(options)
+        _check(load().pt_render_features_motion_marked(self._h, C.byref(cp), C.byref(op), _ptr(feat), _ptr(mot)))
+        return feat, mot
+
+    def render_features_motion_marked_device(self, camera, options, d_features_ptr, d_motion_ptr, stream_ptr=0):
+        """render_features_motion_marked into device memory (H*W*12 and H*W*8 floats), ordered on stream_ptr."""
+        cp, op = _camera(camera), _options(options)
+        _check(load().pt_render_features_motion_marked_device(self._h, C.byref(cp), C.byref(op), C.c_void_p(d_features_ptr), C.c_void_p(d_motion_ptr),
+                                                              C.c_void_p(stream_ptr)))
+
     def denoise_sequence(self, frames, cameras, options, params=None, poses=None):
         """Temporal denoising of a sequence of frames of this scene, frames[v] seen through cameras[v] (e.g. process_views' output): a fresh
         TemporalDenoiser pushes every frame with its render_features; returns a (V, H, W, 4) float32 array.  poses: poses[v] are the
@@ -1020,6 +1074,33 @@ class Scene:
                     continue
                 self.pose(poses[v])
                 feat, mot = self.render_features_motion(cam, options, previous=poses[v - 1] if v > 0 else None)
+                out[v], _ = t.denoise(frames[v], feat, cam, motion=mot)
+        return out
+
+    def denoise_sequence_shapes(self, frames, cameras, options, params=None, poses=None, deforms=None, morphs=None):
+        """denoise_sequence for a scene whose meshes change shape between the frames.  poses[v]: as there; deforms[v] / morphs[v]: a dict
+        of deform() / morph() arguments for frame v (None or {}: nothing).  Frame 0 is posed / deformed / morphed and pushed with a motion
+        in which nothing moved; every later frame is: mark_motion(), then pose, deform, morph as given, then
+        render_features_motion_marked and the push with that motion.  The scene is left at the last frame's shape with that frame's
+        predecessor as its mark.  (A method of its own: denoise_sequence keeps its signature and, with poses alone, its route and bits.)"""
+        frames = np.asarray(frames, dtype=np.float32)
+        if len(frames) != len(cameras):
+            raise ValueError("one camera per frame")
+        for name, per_frame in (("pose", poses), ("deform", deforms), ("morph", morphs)):
+            if per_frame is not None and len(per_frame) != len(frames):
+                raise ValueError("one %s per frame" % name)
+        out = np.empty_like(frames)
+        with TemporalDenoiser(options["image_width"], options["image_height"], params=params, device=self.device) as t:
+            for v, cam in enumerate(cameras):
+                if v > 0:
+                    self.mark_motion()
+                if poses is not None:
+                    self.pose(poses[v])
+                if deforms is not None and deforms[v]:
+                    self.deform(**deforms[v])
+                if morphs is not None and morphs[v]:
+                    self.morph(**morphs[v])
+                feat, mot = self.render_features_motion_marked(cam, options) if v > 0 else self.render_features_motion(cam, options)
                 out[v], _ = t.denoise(frames[v], feat, cam, motion=mot)
         return out
 

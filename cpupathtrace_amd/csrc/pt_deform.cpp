@@ -86,6 +86,9 @@ int adopt_shapes(pt_scene *s, const std::vector<const float *> &shape, const std
         return rc;
     }
     for(size_t m = 0; m < n_meshes; m++) {
+        if(shape[m] != nullptr) {
+            keep.meshes[m]->shape_serial++; // (what pt_scene_motion_mark compares: pt_motion_shapes.cpp)
+        }
         if(in_spare[m] != 0) {
             exchange(keep.meshes[m]->deform->current, keep.meshes[m]->deform->spare); // (shape names the buffer that is `current` now)
         }

@@ -1,7 +1,7 @@
 // pt_host.h -- what the host units of libpathtrace_hip.so share: pt_api.cpp (scenes), pt_meshes.cpp (scenes from meshes and instances),
 // pt_pose.cpp (their instances under new matrices, in place), pt_deform.cpp (their meshes under new vertices, in place),
 // pt_morph.cpp (their meshes under blend shapes, in place),
-// pt_relight.cpp (their materials and lights replaced in place),
+// pt_relight.cpp (their materials and lights replaced in place), pt_motion.cpp and pt_motion_shapes.cpp (motion for the temporal denoiser),
 // pt_render.cpp (render calls), pt_frames.cpp and pt_frame_maps.cpp (resumable frames and their maps; pt_frames.h) and pt_image.cpp
 // (post-processing, features, denoising).  Internal:
 // not installed, not part of the C ABI.  Everything but the ABI's own handle types lives in namespace pth, so that no helper can collide
@@ -215,6 +215,9 @@ struct MeshDeform {
     DevBuf<PtMorphEntry> morph_entries;  // [morph_entry_count], a vertex's in ascending target order
     uint32_t morph_targets = 0;          // 0: no set
     uint64_t morph_entry_count = 0;
+    // ... and what pt_scene_motion_mark (pt_motion_shapes.cpp; include/pt_motion_shapes.h) keeps of a deformed mesh: the current vertices
+    // it had at the mark, allocated by the mesh's first such mark and reused
+    DevBuf<float> marked;                // [n_vertices][3]
 };
 
 // One mesh in device memory
@@ -225,6 +228,7 @@ struct KeptMesh {
     // The vertices an assembly reads (assemble_batch, pt_meshes.cpp): the rest vertices, unless pt_scene_deform has pointed it at the
     // mesh's current ones
     const float *shape = nullptr;
+    uint64_t shape_serial = 0; // bumped by adopt_shapes (pt_deform.cpp) for every mesh whose shape a successful call changed
     std::unique_ptr<MeshDeform> deform;
     int upload(const pt_mesh_data &m);
 };
@@ -239,6 +243,19 @@ struct DescCopy {
     void assign(const pt_scene_desc &src);
 };
 
+// What pt_scene_motion_mark (pt_motion_shapes.cpp) records, "the previous frame", and what the scene tracks while there is one: the
+// scene-wide face every instance triangle came from.  A scene that was never marked has none of this.
+struct MotionMark {
+    std::vector<float> transforms;      // [n_instances][16]: the instance matrices at the mark
+    std::vector<const float *> shape;   // per mesh: its vertices at the mark -- the rest array, or the mesh's `marked` buffer; null: unused mesh
+    std::vector<uint64_t> serial;       // per mesh: its shape_serial at the mark
+    // face_of[t] for instance triangle t, written by every successful rebuild since the first mark (has_table); a rebuild makes the
+    // table in `face_of_spare` and they change places at adoption
+    DevBuf<uint32_t> face_of, face_of_spare;
+    bool has_table = false;
+    DevBuf<PtShapeMotionInstance> table; // the instance table of the last marked features call
+};
+
 struct PoseKeep {
     std::vector<std::unique_ptr<KeptMesh>> meshes; // by mesh index of the creating call; null for a mesh no instance uses
     std::vector<pt_mesh_instance> instances;
@@ -250,6 +267,7 @@ struct PoseKeep {
     DevBuf<float> bone_table;            // pt_scene_deform: the bone matrices of a call's skinned meshes, end to end
     DevBuf<float> morph_weights;         // pt_scene_morph: the weights of a call's morphed meshes, end to end
     uint64_t deform_allocations = 0;     // ... and its hipMalloc calls for vertex, skin and bone buffers so far
+    std::unique_ptr<MotionMark> mark;    // pt_scene_motion_mark: null for a scene that is not marked
 };
 
 } // namespace pth
@@ -405,8 +423,10 @@ struct MeshAssembly {
     EventPair chain;                              // the device time of the assembly, once `stream` has been waited for
     std::chrono::steady_clock::time_point front_done; // when the description's triangles had been handed over
 };
+// face_of (device memory, one word per face of all instances; null: not tracked): face_of[t] receives the scene-wide face -- the faces of
+// all instances end to end, before rejection -- that became instance triangle t (pt_face_table_kernel behind every chunk).
 int assemble_mesh_scene(hipStream_t stream, const pt_scene_desc *d, const std::vector<std::unique_ptr<KeptMesh>> &meshes, const std::vector<pt_mesh_instance> &instances,
-                        PtBatchScratch &scratch, uint64_t capacity, float *pos, float *nrm, MeshAssembly *out);
+                        PtBatchScratch &scratch, uint64_t capacity, float *pos, float *nrm, MeshAssembly *out, uint32_t *face_of = nullptr);
 // From the assembled arrays to the finished scene, with either builder: `assembled` names the triangles in `pos` / `nrm` (device memory:
 // the description's first, then the instances' ranges).  The scene takes `pos` over (pt_scene_get_triangles); on failure it stays
 // with the caller.  Used by pt_scene_create_meshes and pt_scene_pose.
@@ -581,6 +601,19 @@ struct StreamOrder {
         return PT_OK;
     }
 };
+
+// ---- pt_motion.cpp ---------------------------------------------------------------------------------------------------------------------
+
+// What pt_render_features_motion and the marked call of pt_motion_shapes.cpp share.  One instance of pt_motion_table: the kind, and for a
+// moved instance back[12] and normal[9]; the identity (static) or zero (none) tables of the other kinds
+uint8_t motion_of(const float *c, const float *p, float back[12], float normal[9]);
+void motion_identity(uint8_t kind, float back[12], float normal[9]);
+// The arguments of the features-with-motion entries, checked without a device
+int motion_check(pt_scene *s, const pt_camera_params *camera, const pt_options *options, const float *out_features, const float *out_motion);
+// The device table of a call (render_mutex held) for the previous matrices `previous` (null: nothing moved); *n_out = 0: no table needed
+int motion_instances(pt_scene *s, const float *previous, uint32_t *n_out);
+// Enqueues pt_motion_kernel on the scene's stream (render_mutex held) with the table motion_instances left
+int motion_launch(pt_scene *s, const pt_camera_params *camera, const pt_options *options, uint32_t n_instances, float4 *d_features, float4 *d_motion);
 
 // ---- pt_image.cpp ----------------------------------------------------------------------------------------------------------------------
 

@@ -250,6 +250,25 @@ struct alignas(16) PtMotionInstance {
 };
 void pt_launch_features_motion(hipStream_t stream, const PtDevScene &scene, const PtDevCamera &camera, int32_t width, int32_t height, float4 *out, float4 *motion,
                                const PtMotionInstance *instances, uint32_t n_instances, const PtPathConfig &cfg);
+// The same for a scene marked by pt_scene_motion_mark whose meshes were deformed since (pt_motion_shapes_kernel;
+// include/pt_motion_shapes.h): an instance of kind PT_MOTION_DEFORMED (3) finds the face its hit triangle came from
+// (face_of[object - first_object]: one word per instance triangle), that face's three vertices as they were at the mark, and the matrix
+// the instance had then.  The other kinds are pt_motion_kernel's, operation for operation.
+struct alignas(16) PtShapeMotionInstance {
+    uint32_t first, count; // as PtMotionInstance's
+    uint32_t kind;         // PT_MOTION_STATIC | PT_MOTION_MOVED | PT_MOTION_NONE | PT_MOTION_DEFORMED
+    uint32_t face_first;   // the scene-wide number of the instance's face 0
+    float back[12];
+    float normal[12];
+    const int32_t *faces;  // device, [n_faces][3]: the instance's mesh
+    const float *marked;   // device, [n_vertices][3]: the mesh's vertices at the mark
+    float m[16];           // rows of the instance's matrix at the mark
+};
+void pt_launch_features_motion_shapes(hipStream_t stream, const PtDevScene &scene, const PtDevCamera &camera, int32_t width, int32_t height, float4 *out, float4 *motion,
+                                      const PtShapeMotionInstance *instances, uint32_t n_instances, const uint32_t *face_of, uint32_t first_object, const PtPathConfig &cfg);
+// face_of[rank[f]] = face_base_scene + f for every face f < n_faces of a chunk with flag[f] != 0 and rank[f] < room (pt_face_table_kernel,
+// pt_motion_shapes_kernels.h): `flag` and `rank` are what pt_mesh_batch_chunk left in its scratch, face_of points at the chunk's first triangle
+hipError_t pt_face_table_launch(hipStream_t stream, const uint32_t *flag, const uint32_t *rank, uint32_t n_faces, uint64_t room, uint32_t *face_of, uint32_t face_base_scene);
 // diagnostic (tools/step_timing.py): stamped walks, `lanes_per_wave` rays per wavefront; out[ray] = (steps, cycles waiting for records, cycles in all, price of a stamp pair)
 void pt_launch_steptime(hipStream_t stream, const PtDevScene &scene, const float *rays6, uint32_t n, uint32_t lanes_per_wave, uint4 *out, uint2 *spill, uint32_t spill_depth, int flags);
 

@@ -10,9 +10,10 @@ namespace {
 
 // All instances through the batched assembler, chunk after chunk, each behind the survivors of the one before: positions and normals at
 // pos / nrm (room for `room` triangles), the per-instance counts to counts[n_instances], their sum to *kept.  One wait per chunk; the
-// last chunk's sort and smoothing are only enqueued when this returns.
+// last chunk's sort and smoothing are only enqueued when this returns.  face_of (null: not tracked): the scene-wide face of every
+// survivor, written behind every chunk from the flags and ranks the chunk left in the scratch (pt_motion_shapes_kernels.h).
 int assemble_batch(hipStream_t stream, PtBatchScratch &scratch, const std::vector<std::unique_ptr<KeptMesh>> &meshes, const pt_mesh_instance *instances, uint32_t n_instances,
-                   uint64_t room, float *pos, float *nrm, uint32_t *counts, uint64_t *kept, uint32_t *chunks) {
+                   uint64_t room, float *pos, float *nrm, uint32_t *counts, uint64_t *kept, uint32_t *chunks, uint32_t *face_of = nullptr) {
     std::vector<PtBatchInstance> table(n_instances);
     std::vector<uint32_t> nv(n_instances), nf(n_instances);
     for(uint32_t i = 0; i < n_instances; i++) {
@@ -30,6 +31,7 @@ int assemble_batch(hipStream_t stream, PtBatchScratch &scratch, const std::vecto
     *kept = 0;
     *chunks = 0;
     const PtBatchLimits limits;
+    uint64_t face_base_scene = 0; // the faces of the chunks before
     for(uint32_t first = 0; first < n_instances;) {
         const uint32_t end = pt_mesh_batch_chunk_end(nv.data(), nf.data(), n_instances, first, limits);
         const size_t at = 9 * static_cast<size_t>(*kept);
@@ -40,6 +42,18 @@ int assemble_batch(hipStream_t stream, PtBatchScratch &scratch, const std::vecto
         if(e != hipSuccess) {
             return fail(PT_ERR_HIP, std::string("batched mesh assembly (") + what + "): " + hipGetErrorString(e));
         }
+        uint64_t chunk_faces = 0;
+        for(uint32_t i = first; i < end; i++) {
+            chunk_faces += nf[i];
+        }
+        if(face_of != nullptr && chunk_faces > 0) { // (a chunk without faces has not touched the scratch)
+            const hipError_t ef = pt_face_table_launch(stream, static_cast<const uint32_t *>(scratch.flag.ptr), static_cast<const uint32_t *>(scratch.rank.ptr),
+                                                       static_cast<uint32_t>(chunk_faces), room - *kept, face_of + *kept, static_cast<uint32_t>(face_base_scene));
+            if(ef != hipSuccess) {
+                return fail(PT_ERR_HIP, std::string("face table kernel: ") + hipGetErrorString(ef));
+            }
+        }
+        face_base_scene += chunk_faces;
         *kept += kept_here;
         (*chunks)++;
         first = end;
@@ -101,7 +115,7 @@ void DescCopy::assign(const pt_scene_desc &src) {
 }
 
 int assemble_mesh_scene(hipStream_t stream, const pt_scene_desc *d, const std::vector<std::unique_ptr<KeptMesh>> &meshes, const std::vector<pt_mesh_instance> &instances,
-                        PtBatchScratch &scratch, uint64_t capacity, float *pos, float *nrm, MeshAssembly *out) {
+                        PtBatchScratch &scratch, uint64_t capacity, float *pos, float *nrm, MeshAssembly *out, uint32_t *face_of) {
     const uint32_t n_instances = static_cast<uint32_t>(instances.size());
     const size_t front = 9 * static_cast<size_t>(d->n_triangles);
     if(d->n_triangles > 0) {
@@ -121,7 +135,7 @@ int assemble_mesh_scene(hipStream_t stream, const pt_scene_desc *d, const std::v
     out->inst_count.assign(n_instances, 0);
     uint64_t kept = 0;
     PT_TRY(assemble_batch(stream, scratch, meshes, instances.data(), n_instances, capacity - d->n_triangles, pos + front, nrm != nullptr ? nrm + front : nullptr,
-                          out->inst_count.data(), &kept, &out->chunks));
+                          out->inst_count.data(), &kept, &out->chunks, face_of));
     PT_HIP(out->chain.end(stream));
 
     DeviceTriangles &t = out->triangles;

@@ -33,6 +33,10 @@ void mul3(const double a[9], const double b[9], double out[9]) {
     }
 }
 
+} // namespace
+
+namespace pth {
+
 // One instance of pt_motion_table: the kind, and for a moved instance back[12] and normal[9]
 uint8_t motion_of(const float *c, const float *p, float back[12], float normal[9]) {
     if(std::memcmp(c, p, 16 * sizeof(float)) == 0) {
@@ -164,7 +168,7 @@ int motion_launch(pt_scene *s, const pt_camera_params *camera, const pt_options 
     return PT_OK;
 }
 
-} // namespace
+} // namespace pth
 
 extern "C" {
 

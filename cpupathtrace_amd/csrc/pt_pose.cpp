@@ -34,8 +34,10 @@ int rebuild_instances(pt_scene *s, std::vector<pt_mesh_instance> &&posed, std::c
     if(with_normals) {
         PT_HIP(nrm.ensure(9 * static_cast<size_t>(keep.capacity)));
     }
+    // (a marked scene also tracks the face of every triangle, made aside like the positions: pt_motion_shapes.cpp)
+    uint32_t *face_of = keep.mark != nullptr ? keep.mark->face_of_spare.ptr : nullptr;
     MeshAssembly assembly;
-    const int assembled = assemble_mesh_scene(s->stream, d, keep.meshes, posed, keep.scratch, keep.capacity, pos.ptr, with_normals ? nrm.ptr : nullptr, &assembly);
+    const int assembled = assemble_mesh_scene(s->stream, d, keep.meshes, posed, keep.scratch, keep.capacity, pos.ptr, with_normals ? nrm.ptr : nullptr, &assembly, face_of);
     if(assembled != PT_OK) {
         (void)hipStreamSynchronize(s->stream); // (nothing of the failed call is in flight when its buffers are used again)
         return assembled;
@@ -86,6 +88,11 @@ int rebuild_instances(pt_scene *s, std::vector<pt_mesh_instance> &&posed, std::c
     take(s->emis_cdf, t->emis_cdf);
     s->dev = t->dev; // (its pointers name the buffers that have just moved)
     keep.instances = std::move(posed);
+    if(keep.mark != nullptr) {
+        std::swap(keep.mark->face_of.ptr, keep.mark->face_of_spare.ptr);
+        std::swap(keep.mark->face_of.count, keep.mark->face_of_spare.count);
+        keep.mark->has_table = true;
+    }
     // What the render workspace was sized from has changed: the configuration derived from the tree (in_lds, wide, stack_lds, lds_bytes,
     // spill_depth) is derived again, and every entry point sizes its buffers from it per call ("the hazard")
     s->path_cfg = PtPathConfig{};

@@ -1,5 +1,5 @@
 // pt_walks.hip -- the kernels that trace ONE walk per lane to its end with the path kernel's traversal machinery (pt_trace.h): closest hits
-// of a ray batch (pt_closest_kernel), the denoiser's first-hit and followed features (pt_feature_kernel, pt_follow_kernel), the first-hit features with motion (pt_motion_kernel) and two
+// of a ray batch (pt_closest_kernel), the denoiser's first-hit and followed features (pt_feature_kernel, pt_follow_kernel), the first-hit features with motion (pt_motion_kernel; pt_motion_shapes_kernel for deformed meshes) and two
 // diagnostics (pt_steptime_kernel, pt_replay_kernel).  They live apart from pt_path.hip so that an edit here neither recompiles nor
 // re-schedules the path kernel.  Written once: the dispatch over the three (stack window, records) routes, the LDS size, and the prologue
 // that binds a lane's Tracer (bind_lane) where it leaves a kernel's instructions as they were: the closest-hit and the step-timing kernel.
@@ -10,6 +10,7 @@
 #include <type_traits>
 
 #include "pt_trace.h"
+#include "pt_motion_shapes_kernels.h" // pt_face_table_kernel and its launch: no walk, but the one unit that holds it
 
 using namespace ptd;
 
@@ -427,6 +428,191 @@ __global__ __launch_bounds__(256) void pt_motion_kernel(PtDevScene sc, PtDevCame
     m[1] = make_float4(mot1.x * q, mot1.y * q, mot1.z * q, mot1.w * q);
 }
 
+// A hit on an instance whose mesh was deformed since the mark (include/pt_motion_shapes.h has the formulas as a contract): the face the
+// hit triangle came from, its three vertices as they were at the mark through the matrix the instance had then -- kb_transform's
+// arithmetic (pt_mesh_batch_kernels.h), so the corners are the marked frame's bit for bit --, the hit's barycentrics as tri_normal
+// computes them, and the previous position and normal from those.  The loads of one level (three indices; nine coordinates and the
+// matrix) are independent and issued together; they happen once per hit ray, after the walk.
+PT_D V3 shape_corner(float4 r0, float4 r1, float4 r2, float4 r3, float x, float y, float z) {
+    float h[4];
+    const float4 rows[4] = {r0, r1, r2, r3};
+    for(int r = 0; r < 4; r++) {
+        float d = 0.0f;
+        d += rows[r].x * x;
+        d += rows[r].y * y;
+        d += rows[r].z * z;
+        d += rows[r].w * 1.0f;
+        h[r] = d;
+    }
+    const float inv = 1.0f / h[3];
+    return v3(h[0] * inv, h[1] * inv, h[2] * inv);
+}
+
+PT_D bool shape_finite(float x) {
+    return __builtin_fabsf(x) < __builtin_huge_valf(); // (false for NaN)
+}
+
+PT_D void shape_motion(const float4 *__restrict__ rec, const PtShapeMotionInstance *__restrict__ mi, uint32_t g, V3 pos, V3 n, float4 &m0, float4 &m1) {
+    const int32_t *fi = mi->faces + 3 * (size_t)(g - mi->face_first);
+    const int32_t ia = fi[0], ib = fi[1], ic = fi[2]; // (a surviving face's indices are in range: the assembler rejected the others)
+    const float *mv = mi->marked;
+    const float *pa = mv + 3 * (size_t)ia, *pb = mv + 3 * (size_t)ib, *pc = mv + 3 * (size_t)ic;
+    const float ax = pa[0], ay = pa[1], az = pa[2], bx = pb[0], by = pb[1], bz = pb[2], cx = pc[0], cy = pc[1], cz = pc[2];
+    const float4 r0 = *reinterpret_cast<const float4 *>(mi->m), r1 = *reinterpret_cast<const float4 *>(mi->m + 4), r2 = *reinterpret_cast<const float4 *>(mi->m + 8),
+                 r3 = *reinterpret_cast<const float4 *>(mi->m + 12);
+    const TriRec t = tri_unpack(rec[0], rec[1], rec[2]);
+    const V3 qa = shape_corner(r0, r1, r2, r3, ax, ay, az), qb = shape_corner(r0, r1, r2, r3, bx, by, bz), qc = shape_corner(r0, r1, r2, r3, cx, cy, cz);
+    // tri_normal's barycentrics
+    const V3 ap = pos - t.a;
+    const float d00 = dot(t.ab, t.ab);
+    const float d01 = dot(t.ab, t.ac);
+    const float d11 = dot(t.ac, t.ac);
+    const float d20 = dot(ap, t.ab);
+    const float d21 = dot(ap, t.ac);
+    const float inv_d = 1.0f / (d00 * d11 - d01 * d01);
+    const float bv = (d11 * d20 - d01 * d21) * inv_d;
+    const float bw = (d00 * d21 - d01 * d20) * inv_d;
+    const float bu = 1.0f - bv - bw;
+    const V3 pp = (qa * bu + qb * bv) + qc * bw;
+    const V3 cp = cross(qb - qa, qc - qa), cc = cross(t.ab, t.ac);
+    const float lp = motion_dot3(cp.x, cp.y, cp.z, cp), lc = motion_dot3(cc.x, cc.y, cc.z, cc);
+    if(!(lp > 0.0f) || !(lc > 0.0f) || !shape_finite(pp.x) || !shape_finite(pp.y) || !shape_finite(pp.z)) { // no previous position
+        m0 = make_float4(0.0f, 0.0f, 0.0f, 1.0f);
+        m1 = make_float4(0.0f, 0.0f, 0.0f, 1.0f);
+        return;
+    }
+    const V3 ngp = cp * (1.0f / sqrtf(lp)), ng = cc * (1.0f / sqrtf(lc));
+    const V3 v = (n - ng) + ngp;
+    const float len2 = motion_dot3(v.x, v.y, v.z, v);
+    const float inv = 1.0f / sqrtf(len2);
+    m0 = make_float4(pp.x, pp.y, pp.z, 1.0f);
+    m1 = make_float4(len2 > 0.0f ? v.x * inv : 0.0f, len2 > 0.0f ? v.y * inv : 0.0f, len2 > 0.0f ? v.z * inv : 0.0f, 0.0f);
+}
+
+// pt_motion_kernel for a scene with a motion mark in which a mesh was deformed (include/pt_motion_shapes.h): its text
+// -- rays, walk, accumulators, stores, the static / moved / none arithmetic operation for operation -- with a fourth kind: an instance
+// whose mesh changed shape since the mark takes a hit's previous position and normal from the marked vertices of the hit triangle's face
+// (shape_motion).  face_of[t] is the scene-wide face of instance triangle t, which is object first_object + t.
+template<int STACK_LDS, bool IN_LDS>
+__global__ __launch_bounds__(256) void pt_motion_shapes_kernel(PtDevScene sc, PtDevCamera cam, int32_t width, int32_t height, float4 *__restrict__ out, uint2 *__restrict__ spill,
+                                                        uint32_t spill_depth, float4 *__restrict__ motion, const PtShapeMotionInstance *__restrict__ inst, uint32_t n_inst,
+                                                               const uint32_t *__restrict__ face_of, uint32_t first_object) {
+    extern __shared__ __align__(16) unsigned char lds_raw[];
+    const int tid = threadIdx.x;
+    lds_u2_ptr stack_l = (lds_u2_ptr)reinterpret_cast<uint2 *>(lds_raw) + tid;
+    float4 *lds_recs = reinterpret_cast<float4 *>(lds_raw + (size_t)STACK_LDS * 256 * sizeof(uint2));
+    if(IN_LDS) {
+        for(uint32_t i = tid; i < 4u * (sc.pair_base + sc.n_pairs); i += 256) {
+            lds_recs[i] = sc.recs[i];
+        }
+        __syncthreads();
+    }
+    Tracer<STACK_LDS, IN_LDS> tr;
+    if(IN_LDS) {
+        tr.recs = (typename RecPtr<IN_LDS>::type)(lds_f4_cptr)lds_recs;
+    }
+    else {
+        tr.recs = (typename RecPtr<IN_LDS>::type)(glb_f4_cptr)sc.recs;
+    }
+    tr.stack_l = stack_l;
+    const size_t gid = (size_t)blockIdx.x * 256 + tid;
+    tr.my_spill = (glb_u2_ptr)(spill + gid * spill_depth);
+    if(gid >= (size_t)width * (size_t)height) {
+        return;
+    }
+    const int32_t px = (int32_t)(gid % (size_t)width);
+    const int32_t py = (int32_t)(gid / (size_t)width);
+    RootBox root;
+    root.ref = sc.root_ref;
+    for(int k = 0; k < 3; k++) {
+        root.lo[k] = sc.root_lo[k];
+        root.hi[k] = sc.root_hi[k];
+    }
+    float4 acc0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), acc1 = acc0, acc2 = acc0, emis = acc0, mot0 = acc0, mot1 = acc0;
+    for(int k = 0; k < 4; k++) {
+        const float dx = (k & 1) ? 0.25f : -0.25f, dy = (k & 2) ? 0.25f : -0.25f;
+        const float one_half = 1.0f / 2.0f;
+        const float x_camera = 2 * (((float)px + one_half + dx) / (float)width - one_half);
+        float y_camera = 2 * (((float)py + one_half + dy) / (float)height - one_half);
+        y_camera = -y_camera;
+        uint64_t rng = 0; // (drawn from, never used: both offsets are +0 and there is no aperture)
+        const Ray ray = camera_shoot(cam, x_camera, y_camera, 0.0f, 0.0f, rng);
+        Walk w;
+        typename Tracer<STACK_LDS, IN_LDS>::Rec rec;
+        rec.r0 = rec.r1 = rec.r2 = rec.r3 = (f4v){0.0f, 0.0f, 0.0f, 0.0f};
+        tr.start(w, rec, root, make_float4(ray.o.x, ray.o.y, ray.o.z, 0.0f), make_float4(ray.d.x, ray.d.y, ray.d.z, __uint_as_float(0u)));
+        uint32_t n_nodes = 0, n_leaves = 0;
+        while(tr.step(w, rec, 1, n_nodes, n_leaves)) {
+        }
+        float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), n4 = a, p4 = a, e4 = a, m0 = a, m1 = a;
+        if(w.best_ref != PT_REF_NONE) {
+            const float t = w.best_t;
+            const V3 pos = ray.o + ray.d * t;
+            uint32_t material_index;
+            const V3 n = object_normal(sc, w.best_ref, pos, material_index);
+            const Material mat = material_load(sc.materials, material_index);
+            const bool lambertian = mat.bsdf == 0; // PT_BSDF_LAMBERTIAN
+            a = make_float4(lambertian ? mat.diffuse.r : mat.specular.r, lambertian ? mat.diffuse.g : mat.specular.g, lambertian ? mat.diffuse.b : mat.specular.b, 1.0f);
+            n4 = make_float4(n.x, n.y, n.z, t);
+            p4 = make_float4(pos.x, pos.y, pos.z, 0.0f);
+            e4 = make_float4(mat.emission.r, mat.emission.g, mat.emission.b, 0.0f);
+            m0 = p4;
+            m1 = make_float4(n.x, n.y, n.z, 0.0f);
+            if(n_inst != 0 && !(w.best_ref & PT_REF_SPHERE)) {
+                const uint32_t obj = __float_as_uint(sc.tri_shade[8 * (size_t)(w.best_ref & PT_REF_INDEX) + 2].z) & 0x7fffffffu;
+                uint32_t lo = 0, hi = n_inst; // the last instance whose first object is <= obj lies in [lo, hi)
+                while(hi - lo > 1) {
+                    const uint32_t mid = lo + (hi - lo) / 2;
+                    if(inst[mid].first <= obj) {
+                        lo = mid;
+                    }
+                    else {
+                        hi = mid;
+                    }
+                }
+                const PtShapeMotionInstance *mi = inst + lo;
+                const uint32_t first = mi->first;
+                if(obj >= first && obj - first < mi->count) {
+                    const uint32_t kind = mi->kind;
+                    if(kind == 2u) { // PT_MOTION_NONE
+                        m0 = make_float4(0.0f, 0.0f, 0.0f, 1.0f);
+                        m1 = make_float4(0.0f, 0.0f, 0.0f, 1.0f);
+                    }
+                    else if(kind == 1u) { // PT_MOTION_MOVED
+                        const float4 b0 = *reinterpret_cast<const float4 *>(mi->back), b1 = *reinterpret_cast<const float4 *>(mi->back + 4),
+                                     b2 = *reinterpret_cast<const float4 *>(mi->back + 8);
+                        const float4 r0 = *reinterpret_cast<const float4 *>(mi->normal), r1 = *reinterpret_cast<const float4 *>(mi->normal + 4),
+                                     r2 = *reinterpret_cast<const float4 *>(mi->normal + 8);
+                        m0 = make_float4(motion_dot3(b0.x, b0.y, b0.z, pos) + b0.w, motion_dot3(b1.x, b1.y, b1.z, pos) + b1.w, motion_dot3(b2.x, b2.y, b2.z, pos) + b2.w, 1.0f);
+                        const V3 v = v3(motion_dot3(r0.x, r0.y, r0.z, n), motion_dot3(r1.x, r1.y, r1.z, n), motion_dot3(r2.x, r2.y, r2.z, n));
+                        const float len2 = motion_dot3(v.x, v.y, v.z, v);
+                        const float inv = 1.0f / sqrtf(len2);
+                        m1 = make_float4(len2 > 0.0f ? v.x * inv : 0.0f, len2 > 0.0f ? v.y * inv : 0.0f, len2 > 0.0f ? v.z * inv : 0.0f, 0.0f);
+                    }
+                    else if(kind == 3u) { // PT_MOTION_DEFORMED
+                        shape_motion(sc.tri_shade + 8 * (size_t)(w.best_ref & PT_REF_INDEX), mi, face_of[obj - first_object], pos, n, m0, m1);
+                    }
+                }
+            }
+        }
+        acc0 = make_float4(acc0.x + a.x, acc0.y + a.y, acc0.z + a.z, acc0.w + a.w);
+        acc1 = make_float4(acc1.x + n4.x, acc1.y + n4.y, acc1.z + n4.z, acc1.w + n4.w);
+        acc2 = make_float4(acc2.x + p4.x, acc2.y + p4.y, acc2.z + p4.z, 0.0f);
+        emis = make_float4(emis.x + e4.x, emis.y + e4.y, emis.z + e4.z, 0.0f);
+        mot0 = make_float4(mot0.x + m0.x, mot0.y + m0.y, mot0.z + m0.z, mot0.w + m0.w);
+        mot1 = make_float4(mot1.x + m1.x, mot1.y + m1.y, mot1.z + m1.z, mot1.w + m1.w);
+    }
+    const float q = 0.25f;
+    const float er = emis.x * q, eg = emis.y * q, eb = emis.z * q;
+    float4 *o = out + 3 * gid;
+    o[0] = make_float4(acc0.x * q, acc0.y * q, acc0.z * q, acc0.w * q);
+    o[1] = make_float4(acc1.x * q, acc1.y * q, acc1.z * q, acc1.w * q);
+    o[2] = make_float4(acc2.x * q, acc2.y * q, acc2.z * q, (0.2126f * er + 0.7152f * eg) + 0.0722f * eb);
+    float4 *m = motion + 2 * gid;
+    m[0] = make_float4(mot0.x * q, mot0.y * q, mot0.z * q, mot0.w * q);
+    m[1] = make_float4(mot1.x * q, mot1.y * q, mot1.z * q, mot1.w * q);
+}
+
 // ---- diagnostic: where the cycles of a traversal step go -------------------------------------------------------------------------------
 // One walk per lane as in pt_closest_kernel, but only the first `lanes_per_wave` lanes of every wavefront get a ray, and every step is
 // stamped (s_memtime): cycles spent waiting for the record that was requested at the end of the previous step, and everything else.
@@ -675,6 +861,18 @@ void pt_launch_features_motion(hipStream_t stream, const PtDevScene &scene, cons
     dispatch_route(cfg, scene, [&](auto window, auto in_lds, size_t lds) {
         hipLaunchKernelGGL((pt_motion_kernel<decltype(window)::value, decltype(in_lds)::value>), grid, dim3(256), lds, stream, scene, camera, width, height, out, cfg.spill,
                            cfg.spill_depth, motion, instances, n_instances);
+    });
+}
+
+void pt_launch_features_motion_shapes(hipStream_t stream, const PtDevScene &scene, const PtDevCamera &camera, int32_t width, int32_t height, float4 *out, float4 *motion,
+                                      const PtShapeMotionInstance *instances, uint32_t n_instances, const uint32_t *face_of, uint32_t first_object, const PtPathConfig &cfg) {
+    if(width <= 0 || height <= 0) {
+        return;
+    }
+    const dim3 grid((unsigned)(((size_t)width * (size_t)height + 255) / 256));
+    dispatch_route(cfg, scene, [&](auto window, auto in_lds, size_t lds) {
+        hipLaunchKernelGGL((pt_motion_shapes_kernel<decltype(window)::value, decltype(in_lds)::value>), grid, dim3(256), lds, stream, scene, camera, width, height, out, cfg.spill,
+                           cfg.spill_depth, motion, instances, n_instances, face_of, first_object);
     });
 }
 

@@ -351,6 +351,16 @@ class Scene {
     void morph(const std::shared_ptr<const io::MeshData> &mesh, const std::vector<float> &weights);
     void morph(const std::shared_ptr<const io::MeshData> &mesh, const std::vector<float> &weights, const std::vector<mat4<float>> &bones);
 
+    // Motion for meshes that change shape between two frames (pt_scene_motion_mark, include/pt_motion_shapes.h): markMotion makes every
+    // replica remember the Scene as it is now -- the instances' matrices and every mesh's vertices -- as "the previous frame" of the
+    // marked feature pass; a later mark replaces it.  A TemporalDenoiser with follow_motion marks the Scene itself after every push
+    // (PathTrace/temporal_denoise.h): call these only to mark by hand or to free what a mark keeps.  While a mark exists every pose(),
+    // deform() and morph() also records the face each mesh triangle came from.  unmarkMotion forgets the mark (nothing to forget is no
+    // error).  They change no geometry and no render, and may be called with a live FrameRender.  Throw std::invalid_argument for a
+    // Scene without mesh instances, std::runtime_error when the device refuses.  Non-virtual.
+    void markMotion();
+    void unmarkMotion();
+
     // the device scene behind the C ABI (include/pt_hip.h); used by processJob / processItem
     pt_scene *deviceScene() const noexcept { return device_scene; }
     const std::vector<pt_scene *> &deviceScenes() const noexcept { return replicas; }

@@ -54,9 +54,10 @@
  *     deformed mesh, the rest ones otherwise.  *n_vertices (may be NULL) receives their number; out == NULL asks for the number alone.
  *     PT_ERR_INVALID: a null scene, a mesh out of range or unused.  PT_ERR_UNSUPPORTED: a scene without instances.
  *
- * OUT OF SCOPE: motion vectors of a deformed mesh.  pt_render_features_motion (pt_motion.h) describes a deformed mesh by its instance
- * matrix alone: where a surface point of a mesh that bent between two frames was before is not known to it, and the temporal denoiser's
- * own position and normal tests decide whether the history there is kept. */
+ * OUT OF SCOPE: motion vectors of a deformed mesh are not made here.  pt_render_features_motion (pt_motion.h) describes a deformed mesh
+ * by its instance matrix alone; pt_scene_motion_mark and pt_render_features_motion_marked (pt_motion_shapes.h) remember the shape every
+ * mesh had at the previous frame and reproject a hit through the vertices of its face.  Every successful pt_scene_deform bumps the shape
+ * serial of the meshes it names, which is how a mark knows that a mesh changed. */
 #ifndef PT_DEFORM_ABI_H
 #define PT_DEFORM_ABI_H
 

@@ -435,6 +435,10 @@ int pt_frame_preview(pt_frame *frame, const float *image, const pt_denoise_param
 /* Where the surface a pixel sees was at the previous pose, and the temporal push that reprojects that point (pt_motion_table,
  * pt_render_features_motion, pt_temporal_denoise_motion): the entry points are declared, with their contracts, in: */
 #include "pt_motion.h"
+/* The same for meshes that were deformed or morphed between two frames: the scene keeps a mark of the previous frame and the feature
+ * pass reprojects per vertex (pt_scene_motion_mark, pt_render_features_motion_marked): the entry points are declared,
+ * with their contracts, in: */
+#include "pt_motion_shapes.h"
 /* A new look for such a scene in place -- materials, point lights, the material of an instance -- with the tree untouched and the emitter
  * registry rebuilt on the device (pt_scene_relight, pt_scene_get_materials, pt_scene_get_point_lights): the structs and
  * entry points are declared, with their contracts, in: */

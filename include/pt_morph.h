@@ -50,7 +50,7 @@
  *   - pt_scene_get_morphs: the target count of the set bound to `mesh` and the (vertex, delta) pairs it lists (0 and 0 for none); either
  *     pointer may be NULL.  PT_ERR_INVALID: a null scene, a mesh out of range or unused.  PT_ERR_UNSUPPORTED: a scene without instances.
  *
- * OUT OF SCOPE: motion vectors of a morphed mesh (as for a deformed one, pt_deform.h); weights per instance; morphed normals as an input
+ * OUT OF SCOPE: motion vectors of a morphed mesh (made, as for a deformed one, by the marked calls of pt_motion_shapes.h); weights per instance; morphed normals as an input
  * of their own (the assembler computes normals from the vertices); building the vertex-major rows on the device. */
 #ifndef PT_MORPH_ABI_H
 #define PT_MORPH_ABI_H

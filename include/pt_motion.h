@@ -39,7 +39,8 @@
  *     pt_temporal_denoise's result bit for bit.
  *
  * Left out: view batches (there is no pt_render_features_motion_views) and followed features (motion describes the FIRST hit; the
- * followed features' virtual positions have no previous pose), motion blur, deforming meshes. */
+ * followed features' virtual positions have no previous pose), motion blur.  Meshes that change shape between two frames are described
+ * by pt_motion_shapes.h, not here: these entry points know an instance by its matrix alone. */
 #ifndef PT_MOTION_ABI_H
 #define PT_MOTION_ABI_H
 

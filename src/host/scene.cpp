@@ -632,6 +632,24 @@ void Scene::restShape(const std::shared_ptr<const io::MeshData> &mesh) {
     registerEmitters();
 }
 
+void Scene::markMotion() {
+    meshStateOf(this, "markMotion");
+    for(size_t r = 0; r < replicas.size(); r++) {
+        if(pt_scene_motion_mark(replicas[r], nullptr) != PT_OK) {
+            throw std::runtime_error("PathTrace: Scene::markMotion cannot mark the device scene (replica " + std::to_string(r) + "): " + pt_last_error());
+        }
+    }
+}
+
+void Scene::unmarkMotion() {
+    meshStateOf(this, "unmarkMotion");
+    for(size_t r = 0; r < replicas.size(); r++) {
+        if(pt_scene_motion_unmark(replicas[r]) != PT_OK) {
+            throw std::runtime_error("PathTrace: Scene::unmarkMotion cannot unmark the device scene (replica " + std::to_string(r) + "): " + pt_last_error());
+        }
+    }
+}
+
 void Scene::bindMorphs(const std::shared_ptr<const io::MeshData> &mesh, const std::vector<MorphTarget> &targets) {
     static_assert(sizeof(vec3<float>) == 3 * sizeof(float), "deltas are handed over as a flat array");
     MeshState *state = meshStateOf(this, "bindMorphs");

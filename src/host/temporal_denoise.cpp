@@ -1,5 +1,5 @@
-// src/host/temporal_denoise.cpp -- TemporalDenoiser and denoiseSequence of PathTrace/temporal_denoise.h on top of pt_render_features and
-// pt_temporal_* (include/pt_hip.h).
+// src/host/temporal_denoise.cpp -- TemporalDenoiser and denoiseSequence of PathTrace/temporal_denoise.h on top of pt_render_features,
+// pt_temporal_* and, with follow_motion, the scene's motion mark (include/pt_hip.h, include/pt_motion_shapes.h).
 #include <PathTrace/temporal_denoise.h>
 
 #include "../../include/pt_hip.h"
@@ -71,19 +71,25 @@ Image<> TemporalDenoiser::push(const Image<> &frame, const Camera &camera) {
     Image<> out(frame.getWidth(), frame.getHeight());
     const size_t n_instances = follow_motion ? sceneInstanceCount(scene) : 0;
     if(n_instances > 0) {
-        // the pose now, and the one this object saw at its last push
-        std::vector<float> pose(16 * n_instances);
-        check(pt_scene_get_pose(replica, pose.data()), "TemporalDenoiser::push (pose)");
-        if(has_pose && last_pose.size() != pose.size()) {
+        // The previous frame is the mark this object left on the scene at the end of its last push (include/pt_motion_shapes.h): the
+        // instances' matrices and the meshes' shapes.  A scene that was only posed since takes pt_render_features_motion's own route
+        // with the marked matrices; one whose meshes were deformed or morphed is reprojected per vertex.  A mark that is gone
+        // (Scene::unmarkMotion) or a scene with another number of instances leaves no previous frame: the history is dropped.
+        if(has_pose && (last_pose.size() != 16 * n_instances || pt_scene_get_motion_mark(replica, nullptr, nullptr) != PT_OK)) {
             reset();
         }
         std::vector<float> motion(pixels * 8);
-        check(pt_render_features_motion(replica, &cam, &opt, has_pose ? last_pose.data() : nullptr, features.data(), motion.data()),
-              "TemporalDenoiser::push (features and motion)");
+        if(has_pose) {
+            check(pt_render_features_motion_marked(replica, &cam, &opt, features.data(), motion.data()), "TemporalDenoiser::push (features and marked motion)");
+        }
+        else {
+            check(pt_render_features_motion(replica, &cam, &opt, nullptr, features.data(), motion.data()), "TemporalDenoiser::push (features and motion)");
+        }
         check(pt_temporal_denoise_motion(handle, reinterpret_cast<const float *>(frame.data()), features.data(), motion.data(), &cam,
                                          reinterpret_cast<float *>(out.data()), nullptr),
               "TemporalDenoiser::push");
-        last_pose = std::move(pose);
+        check(pt_scene_motion_mark(replica, nullptr), "TemporalDenoiser::push (mark)");
+        last_pose.assign(16 * n_instances, 0.0F); // (its size is the instance count of the marked frame)
         has_pose = true;
         return out;
     }
