@@ -74,6 +74,13 @@ MOTION_STATIC, MOTION_MOVED, MOTION_NONE = 0, 1, 2
 MOTION_SHAPES_EXPORTS = ["pt_scene_motion_mark", "pt_scene_motion_unmark", "pt_scene_get_motion_mark", "pt_scene_get_triangle_faces", "pt_render_features_motion_marked",
                          "pt_render_features_motion_marked_device"]
 MOTION_DEFORMED = 3
+# scene queries (include/pt_query.h): hit records for rays, pixels and frames, and occlusion tests
+QUERY_EXPORTS = ["pt_query_rays", "pt_query_rays_device", "pt_query_pixels", "pt_query_pixels_device", "pt_query_frame", "pt_query_frame_device", "pt_occluded_rays",
+                 "pt_occluded_rays_device"]
+QUERY_NO_FACE = 0xFFFFFFFF
+# pt_hit: 64 bytes.  A miss: t -1, object -1, instance -1, face QUERY_NO_FACE, material NO_MATERIAL, every other float 0
+Hit = np.dtype([("t", "<f4"), ("object", "<i4"), ("instance", "<i4"), ("face", "<u4"), ("position", "<f4", 3), ("material", "<u4"), ("normal", "<f4", 3), ("b1", "<f4"),
+                ("geometric_normal", "<f4", 3), ("b2", "<f4")])
 
 
 class MotionMarkInfo(C.Structure):
@@ -946,6 +953,59 @@ class Scene:
         t, obj = np.empty(len(rays), np.float32), np.empty(len(rays), np.int32)
         _check(load().pt_intersect_batch(self._h, _ptr(rays), C.c_size_t(len(rays)), _ptr(t), _ptr(obj)))
         return t, obj
+
+    def query(self, rays):
+        """pt_query_rays: rays (n, 6) -> (n,) records of dtype Hit: what get_intersection reports (t, object, bit for bit) and the hit's
+        instance, mesh face, position, material, shading and geometric normal and barycentrics."""
+        rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
+        out = np.zeros(len(rays), Hit)
+        _check(load().pt_query_rays(self._h, _ptr(rays), C.c_size_t(len(rays)), _ptr(out)))
+        return out
+
+    def query_device(self, d_rays_ptr, n, d_out_ptr, stream_ptr=0):
+        """pt_query_rays_device: n rays (6 floats each) and n records (64 bytes each) in device memory, ordered on stream_ptr."""
+        _check(load().pt_query_rays_device(self._h, C.c_void_p(d_rays_ptr), C.c_size_t(n), C.c_void_p(d_out_ptr), C.c_void_p(stream_ptr)))
+
+    def occluded(self, rays, t_max):
+        """pt_occluded_rays: rays (n, 6) and t_max (n,) or a scalar -> (n,) bool: whether the closest hit of ray i has 0 <= t < t_max[i].
+        The walk ends at the first such hit it meets; +inf asks whether the ray hits anything, a NaN or negative t_max gives False."""
+        rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
+        seg = np.empty((len(rays), 7), np.float32)
+        seg[:, :6], seg[:, 6] = rays, np.asarray(t_max, np.float32)
+        out = np.zeros(len(rays), np.uint8)
+        _check(load().pt_occluded_rays(self._h, _ptr(seg), C.c_size_t(len(seg)), _ptr(out)))
+        return out.astype(bool)
+
+    def occluded_device(self, d_segments_ptr, n, d_out_ptr, stream_ptr=0):
+        """pt_occluded_rays_device: n segments (origin, direction, t_max: 7 floats) and n bytes in device memory, ordered on stream_ptr."""
+        _check(load().pt_occluded_rays_device(self._h, C.c_void_p(d_segments_ptr), C.c_size_t(n), C.c_void_p(d_out_ptr), C.c_void_p(stream_ptr)))
+
+    def pick(self, camera, options, pixels):
+        """pt_query_pixels: pixels (n, 2) of (x, y) -> (n,) records of dtype Hit for the rays through the pixels' centres (no aperture, no
+        jitter: a pure function of camera and pixel).  A pixel outside the frame is refused."""
+        xy = np.ascontiguousarray(pixels, dtype=np.int32).reshape(-1, 2)
+        out = np.zeros(len(xy), Hit)
+        cp, op = _camera(camera), _options(options)
+        _check(load().pt_query_pixels(self._h, C.byref(cp), C.byref(op), _ptr(xy), C.c_size_t(len(xy)), _ptr(out)))
+        return out
+
+    def pick_device(self, camera, options, d_pixels_ptr, n, d_out_ptr, stream_ptr=0):
+        """pt_query_pixels_device: n pixels (two int32 each) and n records in device memory, ordered on stream_ptr."""
+        cp, op = _camera(camera), _options(options)
+        _check(load().pt_query_pixels_device(self._h, C.byref(cp), C.byref(op), C.c_void_p(d_pixels_ptr), C.c_size_t(n), C.c_void_p(d_out_ptr), C.c_void_p(stream_ptr)))
+
+    def id_map(self, camera, options):
+        """pt_query_frame: the record of every pixel's centre ray, an (H, W) array of dtype Hit: the frame's object, instance, face and
+        attribute map."""
+        out = np.zeros((options["image_height"], options["image_width"]), Hit)
+        cp, op = _camera(camera), _options(options)
+        _check(load().pt_query_frame(self._h, C.byref(cp), C.byref(op), _ptr(out)))
+        return out
+
+    def id_map_device(self, camera, options, d_out_ptr, stream_ptr=0):
+        """pt_query_frame_device: H*W records in device memory, ordered on stream_ptr."""
+        cp, op = _camera(camera), _options(options)
+        _check(load().pt_query_frame_device(self._h, C.byref(cp), C.byref(op), C.c_void_p(d_out_ptr), C.c_void_p(stream_ptr)))
 
     def process_item(self, camera, options, streams, image=None, want_stats=False):
         """processItem for many WorkItems at once; streams: array of STREAM_DTYPE (rect + raw engine state)."""

@@ -2,6 +2,7 @@
 // pt_pose.cpp (their instances under new matrices, in place), pt_deform.cpp (their meshes under new vertices, in place),
 // pt_morph.cpp (their meshes under blend shapes, in place),
 // pt_relight.cpp (their materials and lights replaced in place), pt_motion.cpp and pt_motion_shapes.cpp (motion for the temporal denoiser),
+// pt_query.cpp (hit records and occlusion tests),
 // pt_render.cpp (render calls), pt_frames.cpp and pt_frame_maps.cpp (resumable frames and their maps; pt_frames.h) and pt_image.cpp
 // (post-processing, features, denoising).  Internal:
 // not installed, not part of the C ABI.  Everything but the ABI's own handle types lives in namespace pth, so that no helper can collide
@@ -353,6 +354,16 @@ struct pt_scene {
     // pt_render_features_motion (pt_motion.cpp): the host form's motion plane and the instance table of the call
     pth::DevBuf<pth::F4> motion;
     pth::DevBuf<PtMotionInstance> motion_instances;
+    // scene queries (pt_query.cpp; include/pt_query.h): the host forms' queries, records and flags, the walks' spill area, and the
+    // instance table with the object ranges it was made from (it is made again when the scene's ranges differ from them)
+    pth::DevBuf<float> query_in;
+    pth::DevBuf<pt_hit> query_out;
+    pth::DevBuf<uint8_t> query_flags;
+    pth::DevBuf<uint2> query_spill;
+    pth::DevBuf<PtQueryInstance> query_instances;
+    std::vector<uint32_t> query_inst_first, query_inst_count;
+    uint32_t query_n_instances = 0;
+    bool query_table_made = false;
     bool debug_collect_costs = false;                // pt_debug_collect_costs: every launch records them
     std::vector<uint32_t> debug_place;               // pt_debug_set_place: the next launch starts from this table ...
     uint32_t debug_place_waves = 0, debug_place_slots = 0; // ... with this many wavefronts and slots in each

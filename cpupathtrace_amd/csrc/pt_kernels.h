@@ -269,6 +269,29 @@ void pt_launch_features_motion_shapes(hipStream_t stream, const PtDevScene &scen
 // face_of[rank[f]] = face_base_scene + f for every face f < n_faces of a chunk with flag[f] != 0 and rank[f] < room (pt_face_table_kernel,
 // pt_motion_shapes_kernels.h): `flag` and `rank` are what pt_mesh_batch_chunk left in its scratch, face_of points at the chunk's first triangle
 hipError_t pt_face_table_launch(hipStream_t stream, const uint32_t *flag, const uint32_t *rank, uint32_t n_faces, uint64_t room, uint32_t *face_of, uint32_t face_base_scene);
+// Scene queries (pt_query_kernels.h; include/pt_query.h): out[4 * i + k] is the k-th 16 bytes of query i's pt_hit.  The walk
+// and its instantiation are pt_launch_closest's; cfg.spill holds one walk per query.  `tables`: the instances that have objects by
+// ascending first object (device memory; n_inst == 0: none is read), and the scene's face table (null: there is none) with the object
+// its entry 0 belongs to.
+struct alignas(16) PtQueryInstance {
+    uint32_t first, count; // the instance's objects: first .. first + count - 1, count > 0
+    uint32_t face_first;   // the scene-wide number of the instance's face 0
+    uint32_t n_faces;      // faces of its mesh: count == n_faces means every face survived
+    uint32_t instance;     // its index in the scene's instance list
+    uint32_t pad[3];
+};
+struct PtQueryTables {
+    const PtQueryInstance *inst;
+    uint32_t n_inst;
+    uint32_t first_object;
+    const uint32_t *face_of;
+};
+void pt_launch_query_rays(hipStream_t stream, const PtDevScene &scene, const float *rays6, uint32_t n, float4 *out, const PtQueryTables &tables, const PtPathConfig &cfg);
+// the rays through the centres of the pixels xy[n][2] of camera's width x height frame (no aperture), or with xy == nullptr of all n = width * height pixels in row order
+void pt_launch_query_pixels(hipStream_t stream, const PtDevScene &scene, const PtDevCamera &camera, int32_t width, int32_t height, const int32_t *xy, uint32_t n, float4 *out,
+                            const PtQueryTables &tables, const PtPathConfig &cfg);
+// out[i] = 1 iff the closest hit of segment i (origin, direction, t_max: 7 floats) has 0 <= t < t_max: the shadow walk, ended at the first such leaf
+void pt_launch_occluded(hipStream_t stream, const PtDevScene &scene, const float *seg7, uint32_t n, uint8_t *out, const PtPathConfig &cfg);
 // diagnostic (tools/step_timing.py): stamped walks, `lanes_per_wave` rays per wavefront; out[ray] = (steps, cycles waiting for records, cycles in all, price of a stamp pair)
 void pt_launch_steptime(hipStream_t stream, const PtDevScene &scene, const float *rays6, uint32_t n, uint32_t lanes_per_wave, uint4 *out, uint2 *spill, uint32_t spill_depth, int flags);
 

@@ -278,6 +278,10 @@ struct MorphTarget {
     std::vector<vec3<float>> deltas;
 };
 
+class Camera;
+struct RenderOptions;
+struct PickResult; // PathTrace/query.h
+
 class Scene {
   public:
     // takes ownership; builds the hierarchy and the device-resident copy (device = $PATHTRACE_DEVICE, default 0).  With
@@ -360,6 +364,15 @@ class Scene {
     // Scene without mesh instances, std::runtime_error when the device refuses.  Non-virtual.
     void markMotion();
     void unmarkMotion();
+
+    // Scene queries (pt_query_pixels, pt_occluded_rays, include/pt_query.h; PathTrace/query.h has PickResult).  pick: what the ray through
+    // the centre of pixel (x, y) of the frame `options` describes hits -- no aperture, no jitter: a pure function of camera and pixel --
+    // with the object as getIntersection reports it.  occluded: whether the closest hit of `ray` lies in [0, t_max); the walk ends at the
+    // first such hit, so it is cheaper than getIntersection where only the answer matters.  Both may be called with a live FrameRender and
+    // change nothing.  pick throws std::invalid_argument for a pixel outside the frame, both std::runtime_error when the device refuses.
+    // Non-virtual: the class's layout is what it was.
+    PickResult pick(const Camera &camera, const RenderOptions &options, int x, int y) const;
+    bool occluded(const Ray &ray, float t_max) const;
 
     // the device scene behind the C ABI (include/pt_hip.h); used by processJob / processItem
     pt_scene *deviceScene() const noexcept { return device_scene; }

@@ -1,5 +1,6 @@
 // src/host/scene.cpp -- Scene: flattens the caller's object graph into the arrays of include/pt_hip.h and owns the device scene.
 #include <PathTrace/detail/world.h>
+#include <PathTrace/query.h>
 #include <PathTrace/scene/mesh.h>
 
 #include "../../include/pt_hip.h"
@@ -796,6 +797,43 @@ std::tuple<float, const Object *> Scene::getIntersection(const Ray &ray) const n
         return {object != nullptr ? t : -1.0F, object};
     }
     return {t, objects[static_cast<size_t>(index)].get()};
+}
+
+PickResult Scene::pick(const Camera &camera, const RenderOptions &options, int x, int y) const {
+    if(x < 0 || y < 0 || x >= options.image_width || y >= options.image_height) {
+        throw std::invalid_argument("PathTrace: Scene::pick: the pixel lies outside the frame");
+    }
+    const pt_camera_params cam = pathtrace_host::cameraParams(camera);
+    const pt_options opt = pathtrace_host::renderOptions(options);
+    const int32_t xy[2] = {x, y};
+    pt_hit h{};
+    pathtrace_host::check(pt_query_pixels(device_scene, &cam, &opt, xy, 1, &h), "Scene::pick");
+    PickResult out;
+    if(h.object < 0) {
+        return out;
+    }
+    out.object = static_cast<size_t>(h.object) >= objects.size() ? meshObject(static_cast<uint32_t>(h.object)) : objects[static_cast<size_t>(h.object)].get();
+    if(out.object == nullptr) {
+        return out;
+    }
+    out.hit = true;
+    out.t = h.t;
+    out.object_index = h.object;
+    out.instance = h.instance;
+    out.face = h.face;
+    out.position = vec3<float>{h.position[0], h.position[1], h.position[2]};
+    out.normal = vec3<float>{h.normal[0], h.normal[1], h.normal[2]};
+    out.geometric_normal = vec3<float>{h.geometric_normal[0], h.geometric_normal[1], h.geometric_normal[2]};
+    out.b1 = h.b1;
+    out.b2 = h.b2;
+    return out;
+}
+
+bool Scene::occluded(const Ray &ray, float t_max) const {
+    const float segment[7] = {ray.origin[0], ray.origin[1], ray.origin[2], ray.dir[0], ray.dir[1], ray.dir[2], t_max};
+    uint8_t blocked = 0;
+    pathtrace_host::check(pt_occluded_rays(device_scene, segment, 1, &blocked), "Scene::occluded");
+    return blocked != 0;
 }
 
 std::vector<std::tuple<vec3<float>, Spectrum, float>> Scene::sampleLights(vec3<float> pos, vec3<float> /*n*/, RandomEngine &re) const noexcept {
