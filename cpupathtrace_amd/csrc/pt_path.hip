@@ -32,7 +32,9 @@
 // Shadow rays (worker.cpp:84-86) only need "is there a visited leaf with 0 <= t < |to_light| - epsilon"; the walk stops at the first
 // such leaf, which cannot change the answer.
 // One traversal step serves inner nodes and leaves alike: every lane fetches the 64-byte record it stands on (a node's two child
-// boxes, or a triangle) with the same four loads, so leaf tests cost no memory round trip of their own.
+// boxes, or a triangle) with the same four loads, so leaf tests cost no memory round trip of their own.  A step whose rare half (leaves,
+// pops) runs requests records ONCE, behind it, for every lane: the rare half starts with no request of the common half in flight, and
+// such a step waits for one record latency, not two (Tracer::step).
 //
 // gfx950 specifics: 64-wide ballots/popcounts for compaction, typed LDS/global address spaces (a pointer that may be either makes
 // hipcc emit flat_load), per-lane traversal stack in LDS as [entry][lane] (conflict-free ds_read/write_b64) with an HBM spill area

@@ -114,7 +114,8 @@ struct Tracer {
 #endif
 #ifdef PT_PATH_TIMING
     // diagnostic build: what slow_step costs a wavefront (the same values in every lane) -- shader-clock cycles inside it, its invocations, the
-    // lanes it served (leaves + walks that came to pop) and the trips of its pop loop
+    // lanes it served (leaves + walks that came to pop) and the trips of its pop loop.  (No request of this step is in flight while it
+    // runs and it issues none: its cycles are its instructions, its LDS trips and the spill reloads of its pop loop.)
     mutable unsigned long long slow_cycles = 0;
     mutable uint32_t slow_calls = 0, slow_served = 0, slow_trips = 0;
 #endif
@@ -196,7 +197,10 @@ struct Tracer {
     // `deep_mask`: the lanes whose stack has left the window -- for them a push first moves the entry it overwrites to the spill area and
     // a pop brings the entry that left the window last back into the slot that has become free; if there is no such lane (one scalar
     // branch) the far child is simply written ABOVE the top of the stack by every lane: it only becomes an entry where the pointer moves.
-    PT_D void node_step(Walk &w, Rec &R, unsigned long long node_mask, unsigned long long deep_mask) const {
+    // `request_below` (a scalar): the lanes whose new reference is below it request their record here.  PT_REF_POPPING in a step that the
+    // rare step does not follow -- every lane that moved onto a record, AHEAD of the deep-stack reload, whose wait the request shares --
+    // and 0 in one that it follows: step() then requests once, behind the rare step (see there).
+    PT_D void node_step(Walk &w, Rec &R, unsigned long long node_mask, unsigned long long deep_mask, uint32_t request_below) const {
         if(!__builtin_amdgcn_inverse_ballot_w64(node_mask)) {
             return; // (the one exec mask of the step; the caller knows the mask is not empty)
         }
@@ -250,15 +254,15 @@ struct Tracer {
         asm volatile("" ::"v"(w.sp), "v"(w.cur)); // (the walk's new state is complete before the record is requested: nothing is left to do behind the loads)
         PT_STAMP(3); // slab tests, decision, stack
         // the lanes that moved onto a record (not the ones whose walk ended or that go on popping: the two codes at the top)
-        if(next < PT_REF_POPPING) {
+        if(next < request_below) {
             fetch(next, R);
         }
+        PT_STAMP(4); // address and request of the next record (none in a step that the rare step follows, and none for records in LDS: see step())
         if(deep_mask != 0ULL) {
             if(!entered & (sp - 1u >= (uint32_t)STACK_LDS)) {
                 stack_l[((sp - 1u) & (uint32_t)(STACK_LDS - 1)) * 256u] = my_spill[sp - 1u - STACK_LDS]; // the window moves down
             }
         }
-        PT_STAMP(4); // address and request of the next record
     }
 
     // Everything that is not the common step: the leaves in `leaf_mask` (Object::getIntersection) and the walks that must (go on) pop(ping).
@@ -269,6 +273,8 @@ struct Tracer {
     // cur == PT_REF_POPPING, a leaf lane that goes on popping takes that code -- with one test at its bottom and one way out.  (With a
     // flag beside cur and the test on top, every trip copied cur and sp to other registers and back and carried four lane masks
     // through the scalar unit; the early returns of the triangle test and the nested tests behind it were sixteen divergent regions.)
+    // It requests no record: step() does, behind it, and node_step requests none ahead of it, so the leaf block opens without a wait for
+    // other lanes' records.
     PT_D void slow_step(Walk &w, Rec &R, unsigned long long leaf_mask, uint32_t &n_leaves) const {
         uint32_t cur = w.cur;
 #ifdef PT_PATH_TIMING
@@ -324,9 +330,6 @@ struct Tracer {
             w.sp = sp;
         }
         w.cur = cur;
-        if(popper & (cur != PT_REF_NONE)) {
-            fetch(cur, R);
-        }
 #ifdef PT_PATH_TIMING
         slow_cycles += __builtin_amdgcn_s_memtime() - t_slow;
 #endif
@@ -342,19 +345,55 @@ struct Tracer {
             return false;
         }
         PT_STAMP(1); // classification
+        if constexpr(IN_LDS) {
+            // Records in LDS: ONE request at the end of the step, for every lane that either half has moved, kept as a scalar lane mask
+            // (remembering `cur` in a vector register to compare afterwards cost 21 moves and 24 branches in the burst loop).  A node lane
+            // is in `nodes` whether it entered a child, took the top of its stack or was served by the pop loop in this very step; a served
+            // leaf or popping lane is in `slow`; a leaf lane that still waits is in neither and keeps the record it has.  (Why the two
+            // locations of the tree take different forms: the measurements of DESIGN.md 5.8.)
+            unsigned long long moved = 0ULL;
+            if(nodes != 0ULL) {
+                n_nodes += (uint32_t)__popcll(nodes);
+                node_step(w, R, nodes, nodes & __builtin_amdgcn_uicmp(w.sp, (uint32_t)STACK_LDS, 35), 0u);
+                moved = nodes;
+            }
+            PT_STAMP(5); // the deep-stack reload (or the test for it), leaving the common step
+            if(slow != 0ULL && (nodes == 0ULL || __popcll(slow) >= leaf_min)) {
+                slow_step(w, R, slow & __builtin_amdgcn_uicmp(w.cur, PT_REF_POPPING, 36), n_leaves);
+                moved |= slow;
+            }
+            PT_STAMP(6); // the rare step (or the test for it)
+            if(__builtin_amdgcn_inverse_ballot_w64(moved & __builtin_amdgcn_uicmp(w.cur, PT_REF_POPPING, 36))) {
+                fetch(w.cur, R);
+            }
+            return true;
+        }
+        // Records in HBM.  Whether the rare step follows is known before the common one runs (`slow` was taken ahead of it).  Where it follows, node_step
+        // requests nothing and ONE request behind slow_step serves every lane either half has moved: the compiler tracks the record
+        // registers, not lanes, so with node_step's request in flight the leaf block opened with s_waitcnt vmcnt(0) -- the few leaf lanes
+        // waited a full memory latency for records only the node lanes need -- and the poppers' own request at slow_step's end was a second
+        // latency in the same step.  Where it does not follow, the request stays where it was, ahead of the deep-stack reload: moved behind
+        // it, every step with a deep pop paid the reload's latency and the record's one after the other.
+        const bool rare = slow != 0ULL && (nodes == 0ULL || __popcll(slow) >= leaf_min);
         if(nodes != 0ULL) {
             n_nodes += (uint32_t)__popcll(nodes);
-            node_step(w, R, nodes, nodes & __builtin_amdgcn_uicmp(w.sp, (uint32_t)STACK_LDS, 35));
+            node_step(w, R, nodes, nodes & __builtin_amdgcn_uicmp(w.sp, (uint32_t)STACK_LDS, 35), rare ? 0u : PT_REF_POPPING);
         }
-        PT_STAMP(5); // leaving the common step
+        PT_STAMP(5); // the deep-stack reload (or the test for it), leaving the common step
         // The rare step, for the leaves and the walks that have to go on popping: its code is long (a triangle test is 100 instructions,
         // a division among them), so the waiting lanes share it -- not before `leaf_min` of them wait, unless no lane stands on a node any
         // more.  (Serving the popping walks at once instead of letting them wait with the leaves: 422 against 430 Msamples/s.)
-        if(slow != 0ULL && (nodes == 0ULL || __popcll(slow) >= leaf_min)) {
-            // (slow was taken before the common step: a lane that has just reached a leaf is not in it, its record is on its way)
+        if(rare) {
+            // (slow was taken before the common step: a lane that has just reached a leaf is not in it, its record is not requested yet)
             slow_step(w, R, slow & __builtin_amdgcn_uicmp(w.cur, PT_REF_POPPING, 36), n_leaves);
+            // `nodes` and `slow` together are every lane with a walk, and in this step every one of them has moved (a node lane that node_step
+            // sent popping was served by the pop loop just now), so no lane mask is needed: the lanes that stand on a record request it --
+            // not the ones whose walk is over (no lane is left popping: the loop ran until none was)
+            if(w.cur < PT_REF_POPPING) {
+                fetch(w.cur, R);
+            }
         }
-        PT_STAMP(6); // the rare step (or the test for it)
+        PT_STAMP(6); // the rare step with the request behind it (or the test for it)
         return true;
     }
 };

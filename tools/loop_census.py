@@ -12,7 +12,10 @@ instantiation of pt_path_kernel, four regions:
     pop      the loop of slow_step's pops alone: the one loop nested in the burst loop (counted in `burst` as well)
 
 and per region: instructions, VGPR-to-VGPR moves (v_mov_b32 / v_mov_b64 from a vector register), lane reads and writes (v_readlane /
-v_writelane: the reloads and saves of spilled scalars), flat loads, scratch accesses and branches.
+v_writelane: the reloads and saves of spilled scalars), flat loads, scratch accesses, branches and record loads (`record_loads`:
+global_load_dwordx4 -- a 64-byte record is a row of four of them).  Beside the regions, an instantiation's result holds `record_groups`: the
+lengths of the uninterrupted rows of such loads in the burst loop, in text order.  A tree in HBM has two rows of four there (node_step's
+request, and the one behind the rare step: tests/test_step_fetch_census.py); a tree in LDS is read with ds_read and has none.
 
 The regions are found by the loop annotations the compiler writes next to every basic block ("in Loop: Header=BB0_123 Depth=2"), not by
 markers in the source, which would change the code they are meant to measure: the inner loop is the innermost loop whose own blocks hold
@@ -30,7 +33,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 REGIONS = ("ahead", "behind", "burst", "pop")
-COLUMNS = ("instructions", "moves", "lane_reads", "lane_writes", "flat_loads", "scratch", "branches")
+COLUMNS = ("instructions", "moves", "lane_reads", "lane_writes", "flat_loads", "scratch", "branches", "record_loads")
 
 _KERNEL = re.compile(r"^(_Z\w*pt_path_kernelILb([01])ELb([01])ELi(\d+)E\w*):")
 _LABEL = re.compile(r"^\.L(BB\d+_\d+):")
@@ -101,7 +104,21 @@ def _count(instrs):
         c["flat_loads"] += 1 if op.startswith("flat_load") else 0
         c["scratch"] += 1 if op.startswith("scratch_") else 0
         c["branches"] += 1 if op.startswith(("s_cbranch", "s_branch")) else 0
+        c["record_loads"] += 1 if op.startswith("global_load_dwordx4") else 0
     return c
+
+
+def _record_groups(instrs):
+    """Lengths of the uninterrupted rows of global_load_dwordx4 in an instruction list, in text order (the s_nop the compiler puts in
+    front of the load that overwrites its own address registers does not end a row)."""
+    groups, row = [], 0
+    for ins in instrs:
+        if ins.split()[0].startswith("global_load_dwordx4"):
+            row += 1
+        elif row and not ins.startswith("s_nop"):
+            groups.append(row)
+            row = 0
+    return groups + ([row] if row else [])
 
 
 def census_function(lines):
@@ -143,6 +160,7 @@ def census_function(lines):
         elif within(b[1], inner):
             region["ahead" if k < first else "behind" if k > last else "ahead"] += b[2]
     out = {r: _count(region[r]) for r in REGIONS}
+    out["record_groups"] = _record_groups(region["burst"])
     out["loops"] = {"inner": inner, "burst": burst, "pop": pop, "inner_depth": depth(inner)}
     return out
 

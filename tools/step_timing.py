@@ -24,8 +24,10 @@ def rays_through(x0, x1, y0, y1, n):
     return np.ascontiguousarray(np.concatenate([np.tile(np.array([0.0, 0.0, -3.0]), (n, 1)), d], axis=1), dtype=np.float32)
 
 
-SEGMENTS = ["between two steps", "classification", "waiting for the record", "slab tests, decision, stack", "address + request of the next record",
-            "leaving the common step", "the rare step or the test for it", "(two stamps back to back)"]
+# (segment 4: node_step's request -- none in a step that the rare step follows, whose one request falls into segment 6; segment 5: what lies
+# between that request and the end of the common step, i.e. the deep-stack reload with its wait, or the test for it)
+SEGMENTS = ["between two steps", "classification", "waiting for the record", "slab tests, decision, stack", "node_step's address + request of the next record",
+            "deep-stack reload or the test for it", "the rare step with its request, or the test for it", "(two stamps back to back)"]
 
 
 def run(rays, lanes, flags, segments=False):
@@ -49,9 +51,14 @@ for label, win in (("window on the mesh", (-0.05, 0.05, -0.21, -0.11)), ("whole 
             steps = clean[:, 0].reshape(waves, -1).max(axis=1).sum() if lanes > 1 else clean[:, 0].sum()
             total = clean[:, 2].reshape(waves, -1).max(axis=1).sum() if lanes > 1 else clean[:, 2].sum()
             wait = stamped[:, 1].reshape(waves, -1).max(axis=1).sum() if lanes > 1 else stamped[:, 1].sum()
-            if lanes == 1 and pf == 0 and os.environ.get("PT_STEP_STAMPS"):
+            if pf == 0 and os.environ.get("PT_STEP_STAMPS"):
                 seg = run(rays, lanes, pf, segments=True)
                 st = clean[:, 0].sum()
+                if lanes > 1:
+                    # (the stamps are the wavefront's: every lane holds the same sums; per step of the wavefront.  With 64 walks a step has
+                    # leaf lanes beside node lanes, which a lonely walk never shows: the rare step's wait for the node lanes' records)
+                    seg = seg.reshape(waves, -1, 8).max(axis=1)
+                    st = steps
                 price = seg[:, 7].sum() / st
                 print("    stamped build, cycles per step (a stamp's own round trip, %.0f, taken off each): " % price +
                       "; ".join("%s %.0f" % (SEGMENTS[k], seg[:, k].sum() / st - price) for k in range(7)), flush=True)
