@@ -78,6 +78,10 @@ MOTION_DEFORMED = 3
 QUERY_EXPORTS = ["pt_query_rays", "pt_query_rays_device", "pt_query_pixels", "pt_query_pixels_device", "pt_query_frame", "pt_query_frame_device", "pt_occluded_rays",
                  "pt_occluded_rays_device"]
 QUERY_NO_FACE = 0xFFFFFFFF
+# checkpoints of a frame (include/pt_checkpoint.h, which pt_hip.h includes as it includes pt_frame_noise.h)
+CHECKPOINT_EXPORTS = ["pt_checkpoint_inspect", "pt_frame_checkpoint_size", "pt_frame_checkpoint_save", "pt_frame_checkpoint_load"]
+CHECKPOINT_HEADER_BYTES = 352
+CHECKPOINT_FINISHED, CHECKPOINT_UNTOUCHED, CHECKPOINT_RECORD = 0, 1, 2
 # pt_hit: 64 bytes.  A miss: t -1, object -1, instance -1, face QUERY_NO_FACE, material NO_MATERIAL, every other float 0
 Hit = np.dtype([("t", "<f4"), ("object", "<i4"), ("instance", "<i4"), ("face", "<u4"), ("position", "<f4", 3), ("material", "<u4"), ("normal", "<f4", 3), ("b1", "<f4"),
                 ("geometric_normal", "<f4", 3), ("b2", "<f4")])
@@ -578,6 +582,46 @@ class FrameNoise(C.Structure):
         d = {k: getattr(self, k) for k, _ in self._fields_}
         d["histogram"] = np.array(self.histogram, np.uint32)
         return NoiseSummary(d)
+
+
+class CheckpointFingerprint(C.Structure):
+    """pt_checkpoint_fingerprint: what a checkpoint remembers of its scene."""
+    _fields_ = [("triangles", C.c_uint64), ("spheres", C.c_uint64), ("materials", C.c_uint64), ("point_lights", C.c_uint64), ("emitters", C.c_uint64),
+                ("tree_nodes", C.c_uint64), ("root_box", C.c_uint32 * 6)]
+
+
+class CheckpointInfo(C.Structure):
+    """pt_checkpoint_info: what pt_checkpoint_inspect reports of a blob."""
+    _fields_ = [("total_bytes", C.c_uint64), ("n_tiles", C.c_uint64), ("n_streams", C.c_uint64), ("streams_finished", C.c_uint64), ("streams_untouched", C.c_uint64),
+                ("streams_with_record", C.c_uint64), ("streams_with_candidates", C.c_uint64), ("bytes_header", C.c_uint64), ("bytes_tables", C.c_uint64),
+                ("bytes_tiles", C.c_uint64), ("bytes_map", C.c_uint64), ("bytes_pixels", C.c_uint64), ("bytes_records", C.c_uint64), ("samples_lost", C.c_uint64),
+                ("fingerprint", CheckpointFingerprint), ("options", Options), ("version", C.c_uint32), ("n_views", C.c_int32), ("quantum", C.c_int32),
+                ("max_passes_per_call", C.c_int32), ("passes_completed", C.c_int32), ("target", C.c_int32), ("pass_in_progress", C.c_int32),
+                ("noise_target", C.c_float), ("noise_floor", C.c_float), ("noise_fraction", C.c_float), ("follow_features", C.c_int32), ("launches", C.c_int32)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_ if k not in ("fingerprint", "options")}
+        d["options"] = {k: getattr(self.options, k) for k, _ in Options._fields_}
+        d["fingerprint"] = {k: getattr(self.fingerprint, k) for k, _ in CheckpointFingerprint._fields_ if k != "root_box"}
+        d["fingerprint"]["root_box"] = np.array(self.fingerprint.root_box, np.uint32)
+        return d
+
+
+def _blob(blob_or_path):
+    """A checkpoint as a contiguous uint8 array: the bytes of a file, or of anything bytes-like."""
+    if isinstance(blob_or_path, (str, os.PathLike)):
+        return np.fromfile(blob_or_path, np.uint8)
+    return np.ascontiguousarray(np.frombuffer(blob_or_path, np.uint8) if not isinstance(blob_or_path, np.ndarray) else blob_or_path.view(np.uint8).ravel())
+
+
+def checkpoint_inspect(blob):
+    """pt_checkpoint_inspect as a dict: validates a checkpoint (bytes-like, or a path) and says what it holds -- the job's sizes, n_views,
+    the streams of each class, the bytes of each section, the mode, the counters and the scene's fingerprint.  Needs no device; raises
+    PtError (PT_ERR_INVALID, naming the field) for a blob that is not a valid checkpoint."""
+    b = _blob(blob)
+    info = CheckpointInfo()
+    _check(load().pt_checkpoint_inspect(_ptr(b) if len(b) else None, C.c_size_t(len(b)), C.byref(info)))
+    return info.as_dict()
 
 
 def error_bin(error):
@@ -1425,6 +1469,54 @@ class Frame:
         samples = np.empty(self.image.shape[:-1], np.int32)
         _check(load().pt_frame_preview_measured(self._h, _ptr(self.image), _denoise_measured_params(params), _ptr(rgba), _ptr(samples)))
         return rgba, samples
+
+    def checkpoint(self):
+        """The frame as it stands, as a checkpoint (pt_frame_checkpoint_save): a uint8 array that Frame.restore turns back into a frame
+        -- in another process, on another machine, on any number of replicas of the same scene -- which finishes bit-identically.
+        Between two render() calls only; changes nothing the frame will do."""
+        if self._h is None:
+            raise ValueError("frame is closed")
+        need = C.c_size_t()
+        _check(load().pt_frame_checkpoint_size(self._h, C.byref(need)))
+        blob = np.empty(need.value, np.uint8)
+        written = C.c_size_t()
+        _check(load().pt_frame_checkpoint_save(self._h, _ptr(self.image), _ptr(blob), C.c_size_t(len(blob)), C.byref(written)))
+        return blob[:written.value]
+
+    def save(self, path):
+        """checkpoint() into the file `path`: written beside it under a temporary name and moved into place, so that a reader never
+        sees half a checkpoint."""
+        blob = self.checkpoint()
+        tmp = "%s.%d.tmp" % (os.fspath(path), os.getpid())
+        try:
+            with open(tmp, "wb") as fh:
+                fh.write(memoryview(blob))
+            os.replace(tmp, path)
+        finally:
+            if os.path.exists(tmp):
+                os.remove(tmp)
+
+    @classmethod
+    def restore(cls, scenes, blob_or_path):
+        """The frame of a checkpoint (pt_frame_checkpoint_load) on `scenes`: one Scene or several replicas of the scene the frame was
+        made on, however many it had then.  A Frame, or a ViewsFrame when the checkpoint is of a view batch, with .image holding the
+        finished pixels and zeros elsewhere.  Raises PtError (PT_ERR_INVALID) for a damaged blob or another scene."""
+        blob = _blob(blob_or_path)
+        info = checkpoint_inspect(blob)
+        scenes = list(scenes) if isinstance(scenes, (list, tuple)) else [scenes]
+        views = info["n_views"]
+        frame = object.__new__(ViewsFrame if views > 1 else Frame)
+        frame._h = None
+        frame._scenes = scenes
+        at = (CHECKPOINT_HEADER_BYTES + info["bytes_tables"] + 15) // 16 * 16
+        frame.tiles = blob[at:at + info["bytes_tiles"]].copy().view(TILE_DTYPE)
+        h, w = info["options"]["image_height"], info["options"]["image_width"]
+        frame.image = np.zeros((views, h, w, 4) if views > 1 else (h, w, 4), np.float32)
+        handles = (C.c_void_p * len(scenes))(*[sc._h for sc in scenes])
+        handle = C.c_void_p()
+        _check(load().pt_frame_checkpoint_load(handles, C.c_int(len(scenes)), _ptr(blob), C.c_size_t(len(blob)), _ptr(frame.image), C.byref(handle)))
+        frame._h = handle
+        return frame
 
     @property
     def done(self):

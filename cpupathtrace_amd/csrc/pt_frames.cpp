@@ -139,9 +139,12 @@ int frame_launch(pt_frame &f, pt_frame::Replica &r, float *out_image, pt_stats *
     return PT_OK;
 }
 
+} // namespace
+
 // A progressive frame with a noise target, before a pass to `yield_at` samples: the replica's list split again by that sample count and
 // the target as they are now -- streams below the count, streams at it, held streams -- with nothing launched and no record moved.
-int frame_resort(pt_frame &f, pt_frame::Replica &r, int32_t yield_at) {
+// (declared in pt_frames.h: a loaded checkpoint splits the list it rebuilt with it, pt_checkpoint.cpp)
+int pth::frame_resort(pt_frame &f, pt_frame::Replica &r, int32_t yield_at) {
     if(!r.ready || r.n_todo == 0) {
         r.n_held = 0; // (no records yet: nothing is rated)
         return PT_OK;
@@ -163,6 +166,8 @@ int frame_resort(pt_frame &f, pt_frame::Replica &r, int32_t yield_at) {
     r.cur ^= 1;
     return PT_OK;
 }
+
+namespace {
 
 // A failure of a launch or of a work list fails the frame for good: every later call returns this
 int frame_fail(pt_frame *f, int rc) {

@@ -99,4 +99,10 @@ struct pt_frame {
     int check() const { return status != PT_OK ? pth::fail(status, error) : PT_OK; }
 };
 
+namespace pth {
+// A progressive frame's list split again by the sample count `yield_at` and the noise target as they are now, with nothing launched and
+// no record moved (pt_frames.cpp): before a pass of a frame with a noise target, and behind the list a loaded checkpoint rebuilds
+int frame_resort(pt_frame &f, pt_frame::Replica &r, int32_t yield_at);
+} // namespace pth
+
 #endif

@@ -66,8 +66,16 @@ public:
     std::vector<float> variance() const;
     void previewMeasured(Image<> &out, std::vector<std::int32_t> *samples = nullptr, const pt_denoise_measured_params *params = nullptr) const;
     std::uint64_t seed() const noexcept { return seed_; }
+    // A checkpoint (pt_frame_checkpoint_save / _load, include/pt_checkpoint.h): save() puts the frame as it stands between two render()
+    // calls into `blob` (the caller writes it to a file or sends it somewhere); load() makes the frame of such a blob on `scene` -- the
+    // scene the frame was made on, built again in this or another process, on any number of device replicas -- with image() holding its
+    // finished pixels.  The loaded frame goes on as the saved one would have and finishes bit-identically.  Saving changes nothing.
+    // Throw std::runtime_error on failure (a damaged blob, another scene, a view batch's blob: see ViewBatchRender::load).
+    void save(std::vector<std::uint8_t> &blob) const;
+    static FrameRender load(const Scene &scene, const std::vector<std::uint8_t> &blob, int worker_count = 0) { return FrameRender(scene, blob, worker_count); }
 
 private:
+    FrameRender(const Scene &scene, const std::vector<std::uint8_t> &blob, int worker_count);
     Image<> image_;
     std::vector<pt_tile> tiles_;
     pt_frame *frame_ = nullptr;

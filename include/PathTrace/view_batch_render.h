@@ -60,8 +60,13 @@ public:
     void preview(std::vector<Image<>> &out, std::vector<std::int32_t> *samples = nullptr, const pt_denoise_params *denoise = nullptr) const;
     const std::vector<std::uint64_t> &seeds() const noexcept { return seeds_; }
     std::size_t viewCount() const noexcept { return seeds_.size(); }
+    // A checkpoint, as FrameRender::save and FrameRender::load: of the whole batch.  load() throws std::runtime_error for the blob of a
+    // single frame (FrameRender::load takes it).
+    void save(std::vector<std::uint8_t> &blob) const;
+    static ViewBatchRender load(const Scene &scene, const std::vector<std::uint8_t> &blob, int worker_count = 0) { return ViewBatchRender(scene, blob, worker_count); }
 
 private:
+    ViewBatchRender(const Scene &scene, const std::vector<std::uint8_t> &blob, int worker_count);
     std::vector<Image<>> split(const std::vector<float> &stacked) const;
 
     int width_ = 0, height_ = 0;

@@ -420,6 +420,9 @@ int pt_frame_preview(pt_frame *frame, const float *image, const pt_denoise_param
 /* Denoiser features that follow mirrors and glass to the first diffuse hit (pt_render_features_followed*, pt_frame_set_feature_params;
  * DESIGN.md 4.10.2): struct pt_feature_params and those entry points are declared, with their contracts, in: */
 #include "pt_features.h"
+/* Checkpoints of a frame: save it into a blob, load the blob onto any number of replicas, finish bit-identically (pt_checkpoint_inspect,
+ * pt_frame_checkpoint_size / _save / _load): the format, the structs and the entry points are declared in: */
+#include "pt_checkpoint.h"
 /* Scenes from indexed meshes instantiated under transforms, assembled on the device (pt_scene_create_meshes, pt_mesh_assemble,
  * pt_scene_instance_ranges, pt_scene_get_triangles): the structs and entry points are declared, with their contracts, in: */
 #include "pt_mesh.h"

@@ -6,6 +6,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 #include <exception>
 #include <stdexcept>
 #include <vector>
@@ -24,6 +25,39 @@ FrameRender::FrameRender(const FrameRenderJob &job, int worker_count) :
     tiles_ = jobTiles(static_cast<int>(image_.getWidth()), static_cast<int>(image_.getHeight()));
     const std::vector<pt_scene *> &replicas = job.scene.deviceScenes();
     check(pt_frame_create(replicas.data(), replicaCount(replicas, worker_count), &camera, &options, tiles_.data(), tiles_.size(), seed_, &frame_), "FrameRender");
+}
+
+// FrameRender::load
+FrameRender::FrameRender(const Scene &scene, const std::vector<std::uint8_t> &blob, int worker_count) : image_(0, 0) {
+    pt_checkpoint_info info{};
+    check(pt_checkpoint_inspect(blob.data(), blob.size(), &info), "FrameRender::load");
+    if(info.n_views != 1) {
+        throw std::runtime_error("PathTrace: FrameRender::load: the checkpoint is of a view batch (ViewBatchRender::load takes it)");
+    }
+    pt_checkpoint_header header;
+    std::memcpy(&header, blob.data(), sizeof(header));
+    seed_ = header.base_seed;
+    image_ = Image<>(static_cast<size_t>(info.options.image_width), static_cast<size_t>(info.options.image_height));
+    tiles_.resize(static_cast<size_t>(info.n_tiles));
+    if(!tiles_.empty()) {
+        std::memcpy(tiles_.data(), blob.data() + (sizeof(header) + info.bytes_tables + 15) / 16 * 16, tiles_.size() * sizeof(pt_tile));
+    }
+    const std::vector<pt_scene *> &replicas = scene.deviceScenes();
+    check(pt_frame_checkpoint_load(replicas.data(), replicaCount(replicas, worker_count), blob.data(), blob.size(), reinterpret_cast<float *>(image_.data()), &frame_),
+          "FrameRender::load");
+    complete_ = info.streams_finished == info.n_streams;
+}
+
+void FrameRender::save(std::vector<std::uint8_t> &blob) const {
+    blob.clear();
+    if(frame_ == nullptr) {
+        return; // (a frame without pixels has nothing to save)
+    }
+    size_t bytes = 0;
+    check(pt_frame_checkpoint_size(frame_, &bytes), "FrameRender::save");
+    blob.resize(bytes);
+    check(pt_frame_checkpoint_save(frame_, reinterpret_cast<const float *>(image_.data()), blob.data(), blob.size(), &bytes), "FrameRender::save");
+    blob.resize(bytes);
 }
 
 FrameRender::~FrameRender() {

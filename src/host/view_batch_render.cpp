@@ -50,6 +50,39 @@ ViewBatchRender::ViewBatchRender(const Scene &scene, const std::vector<const Cam
           "ViewBatchRender");
 }
 
+// ViewBatchRender::load
+ViewBatchRender::ViewBatchRender(const Scene &scene, const std::vector<std::uint8_t> &blob, int worker_count) {
+    pt_checkpoint_info info{};
+    check(pt_checkpoint_inspect(blob.data(), blob.size(), &info), "ViewBatchRender::load");
+    if(info.n_views < 2) {
+        throw std::runtime_error("PathTrace: ViewBatchRender::load: the checkpoint is of a single frame (FrameRender::load takes it)");
+    }
+    width_ = info.options.image_width;
+    height_ = info.options.image_height;
+    const size_t views = static_cast<size_t>(info.n_views);
+    seeds_.resize(views);
+    const size_t tables = sizeof(pt_checkpoint_header);
+    std::memcpy(seeds_.data(), blob.data() + (tables + views * sizeof(pt_camera_params) + 15) / 16 * 16, views * sizeof(std::uint64_t));
+    tiles_.resize(static_cast<size_t>(info.n_tiles));
+    std::memcpy(tiles_.data(), blob.data() + (tables + info.bytes_tables + 15) / 16 * 16, tiles_.size() * sizeof(pt_tile));
+    stacked_.assign(static_cast<size_t>(width_) * static_cast<size_t>(height_) * 4 * views, 0.0F);
+    const std::vector<pt_scene *> &replicas = scene.deviceScenes();
+    check(pt_frame_checkpoint_load(replicas.data(), replicaCount(replicas, worker_count), blob.data(), blob.size(), stacked_.data(), &frame_), "ViewBatchRender::load");
+    complete_ = info.streams_finished == info.n_streams;
+}
+
+void ViewBatchRender::save(std::vector<std::uint8_t> &blob) const {
+    blob.clear();
+    if(frame_ == nullptr) {
+        return; // (a batch without pixels has nothing to save)
+    }
+    size_t bytes = 0;
+    check(pt_frame_checkpoint_size(frame_, &bytes), "ViewBatchRender::save");
+    blob.resize(bytes);
+    check(pt_frame_checkpoint_save(frame_, stacked_.data(), blob.data(), blob.size(), &bytes), "ViewBatchRender::save");
+    blob.resize(bytes);
+}
+
 ViewBatchRender::~ViewBatchRender() {
     if(frame_ != nullptr) {
         pt_frame_destroy(frame_);
