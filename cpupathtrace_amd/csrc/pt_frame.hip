@@ -350,7 +350,8 @@ __global__ __launch_bounds__(kThreads) void pt_frame_scatter_kernel(const float4
 // One thread per entry of a replica's work list, as the gather kernel: out[i] = (pixel, bits of its error), +inf for an entry without a
 // record or with fewer than two batch means (unrated).  Reads the estimator's fields pixel_error needs, not the record.  The summary is
 // reduced with integer atomics only, per block in LDS and then once per block (PtNoiseWord; errors are never negative, so their bits order as
-// they do).
+// they do; a NaN error, 0 / 0 at floor 0, has the pattern 0xffc00000 here, which is above every number's: it becomes the maximum and
+// lands in bin 63).
 __global__ __launch_bounds__(kThreads) void pt_frame_rate_kernel(const uint2 *__restrict__ todo, uint32_t n, const PtParkRecord *__restrict__ park,
                                                                  const int4 *__restrict__ tiles, const uint32_t *__restrict__ tile_offset, uint32_t n_tiles,
                                                                  int32_t width, PtNoiseRule noise, uint2 *__restrict__ out, uint32_t *__restrict__ summary) {

@@ -193,7 +193,7 @@ enum PtNoiseWord {
     PT_NOISE_RATED = 0,
     PT_NOISE_UNRATED,
     PT_NOISE_HELD,      // rated, and error <= noise.target > 0
-    PT_NOISE_MAX_BITS,  // the bits of the largest error of a rated entry
+    PT_NOISE_MAX_BITS,  // the largest bit pattern of the error of a rated entry, as an unsigned word: the largest error, or a NaN if one rates NaN
     PT_NOISE_FIRST_BIN, // rated entries by pixel_error_bin: 64 bins
     PT_NOISE_SUMMARY_WORDS = PT_NOISE_FIRST_BIN + 64
 };
