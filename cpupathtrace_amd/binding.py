@@ -78,6 +78,9 @@ MOTION_DEFORMED = 3
 QUERY_EXPORTS = ["pt_query_rays", "pt_query_rays_device", "pt_query_pixels", "pt_query_pixels_device", "pt_query_frame", "pt_query_frame_device", "pt_occluded_rays",
                  "pt_occluded_rays_device"]
 QUERY_NO_FACE = 0xFFFFFFFF
+# light gathered at points (include/pt_gather.h): occlusion, direct light, full paths
+GATHER_EXPORTS = ["pt_gather_params_default", "pt_gather_points", "pt_gather_points_device", "pt_gather_frame", "pt_gather_frame_device", "pt_gather_instance"]
+GATHER_OCCLUSION, GATHER_DIRECT, GATHER_PATHS = 0, 1, 2
 # checkpoints of a frame (include/pt_checkpoint.h, which pt_hip.h includes as it includes pt_frame_noise.h)
 CHECKPOINT_EXPORTS = ["pt_checkpoint_inspect", "pt_frame_checkpoint_size", "pt_frame_checkpoint_save", "pt_frame_checkpoint_load"]
 CHECKPOINT_HEADER_BYTES = 352
@@ -85,6 +88,14 @@ CHECKPOINT_FINISHED, CHECKPOINT_UNTOUCHED, CHECKPOINT_RECORD = 0, 1, 2
 # pt_hit: 64 bytes.  A miss: t -1, object -1, instance -1, face QUERY_NO_FACE, material NO_MATERIAL, every other float 0
 Hit = np.dtype([("t", "<f4"), ("object", "<i4"), ("instance", "<i4"), ("face", "<u4"), ("position", "<f4", 3), ("material", "<u4"), ("normal", "<f4", 3), ("b1", "<f4"),
                 ("geometric_normal", "<f4", 3), ("b2", "<f4")])
+
+# pt_gather_result: 32 bytes.  A frame's pixel without a first hit: all zero
+GatherResult = np.dtype([("value", "<f4", 4), ("samples", "<u4"), ("occluded", "<u4"), ("pad", "<u4", 2)])
+
+
+class GatherParams(C.Structure):
+    """pt_gather_params"""
+    _fields_ = [("kind", C.c_int32), ("samples", C.c_int32), ("epsilon", C.c_float), ("distance", C.c_float), ("base_seed", C.c_uint64)]
 
 
 class MotionMarkInfo(C.Structure):
@@ -720,6 +731,25 @@ def _options(opt):
                    float(opt["epsilon"]))
 
 
+def gather_params(kind, samples, epsilon, distance=np.inf, base_seed=0):
+    return GatherParams(int(kind), int(samples), float(epsilon), float(distance), int(base_seed) & 0xFFFFFFFFFFFFFFFF)
+
+
+def gather_params_default():
+    gp = GatherParams()
+    _check(load().pt_gather_params_default(C.byref(gp)))
+    return gp
+
+
+def _gather_points(points, normals):
+    """(n, 6) float32: position, normal"""
+    points = np.asarray(points, np.float32).reshape(-1, 3)
+    normals = np.asarray(normals, np.float32).reshape(-1, 3)
+    if len(points) != len(normals):
+        raise ValueError("as many normals as points")
+    return np.ascontiguousarray(np.concatenate([points, normals], axis=1), dtype=np.float32)
+
+
 class Scene:
     """A scene resident on one MI355X (the reference's Scene: objects + lights + BVH)."""
 
@@ -1050,6 +1080,45 @@ class Scene:
         """pt_query_frame_device: H*W records in device memory, ordered on stream_ptr."""
         cp, op = _camera(camera), _options(options)
         _check(load().pt_query_frame_device(self._h, C.byref(cp), C.byref(op), C.c_void_p(d_out_ptr), C.c_void_p(stream_ptr)))
+
+    def gather(self, points, normals, kind, samples, epsilon, distance=np.inf, base_seed=0):
+        """pt_gather_points: the light that arrives at the points (n, 3) with the unit normals (n, 3), `samples` samples each, as (n,)
+        records of dtype GatherResult.  kind: GATHER_OCCLUSION (the share of cosine-distributed rays that meet nothing within
+        `distance`), GATHER_DIRECT (the light samples of one vertex) or GATHER_PATHS (whole paths from the point)."""
+        pts = _gather_points(points, normals)
+        out = np.zeros(len(pts), GatherResult)
+        gp = gather_params(kind, samples, epsilon, distance, base_seed)
+        _check(load().pt_gather_points(self._h, _ptr(pts), C.c_size_t(len(pts)), C.byref(gp), _ptr(out)))
+        return out
+
+    def gather_device(self, d_points_ptr, n, d_out_ptr, kind, samples, epsilon, distance=np.inf, base_seed=0, stream_ptr=0):
+        """pt_gather_points_device: n points (6 floats each) and n records (32 bytes each) in device memory, ordered on stream_ptr."""
+        gp = gather_params(kind, samples, epsilon, distance, base_seed)
+        _check(load().pt_gather_points_device(self._h, C.c_void_p(d_points_ptr), C.c_size_t(n), C.byref(gp), C.c_void_p(d_out_ptr), C.c_void_p(stream_ptr)))
+
+    def gather_frame(self, camera, options, kind, samples, epsilon, distance=np.inf, base_seed=0):
+        """pt_gather_frame: the gather at the first hit of every pixel's centre ray, the normal turned against the ray: an (H, W) array of
+        dtype GatherResult; all zero where the ray hits nothing."""
+        out = np.zeros((options["image_height"], options["image_width"]), GatherResult)
+        cp, op, gp = _camera(camera), _options(options), gather_params(kind, samples, epsilon, distance, base_seed)
+        _check(load().pt_gather_frame(self._h, C.byref(cp), C.byref(op), C.byref(gp), _ptr(out)))
+        return out
+
+    def gather_frame_device(self, camera, options, d_out_ptr, kind, samples, epsilon, distance=np.inf, base_seed=0, stream_ptr=0):
+        """pt_gather_frame_device: H*W records in device memory, ordered on stream_ptr."""
+        cp, op, gp = _camera(camera), _options(options), gather_params(kind, samples, epsilon, distance, base_seed)
+        _check(load().pt_gather_frame_device(self._h, C.byref(cp), C.byref(op), C.byref(gp), C.c_void_p(d_out_ptr), C.c_void_p(stream_ptr)))
+
+    def bake_instance(self, instance, kind, samples, epsilon, distance=np.inf, base_seed=0):
+        """pt_gather_instance: the gather at the three corners of every surviving triangle of a mesh instance, with the corner normals:
+        an (n, 3) array of dtype GatherResult, n the instance's object count (instance_ranges)."""
+        _, count = self.instance_ranges()
+        if not 0 <= instance < len(count):
+            raise PtError(1, "instance %d out of range: the scene has %d" % (instance, len(count)))
+        out = np.zeros((int(count[instance]), 3), GatherResult)
+        gp = gather_params(kind, samples, epsilon, distance, base_seed)
+        _check(load().pt_gather_instance(self._h, C.c_uint32(instance), C.byref(gp), _ptr(out)))
+        return out
 
     def process_item(self, camera, options, streams, image=None, want_stats=False):
         """processItem for many WorkItems at once; streams: array of STREAM_DTYPE (rect + raw engine state)."""

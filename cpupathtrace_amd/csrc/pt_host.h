@@ -2,7 +2,7 @@
 // pt_pose.cpp (their instances under new matrices, in place), pt_deform.cpp (their meshes under new vertices, in place),
 // pt_morph.cpp (their meshes under blend shapes, in place),
 // pt_relight.cpp (their materials and lights replaced in place), pt_motion.cpp and pt_motion_shapes.cpp (motion for the temporal denoiser),
-// pt_query.cpp (hit records and occlusion tests),
+// pt_query.cpp (hit records and occlusion tests), pt_gather.cpp (light gathered at points),
 // pt_render.cpp (render calls), pt_frames.cpp and pt_frame_maps.cpp (resumable frames and their maps; pt_frames.h) and pt_image.cpp
 // (post-processing, features, denoising).  Internal:
 // not installed, not part of the C ABI.  Everything but the ABI's own handle types lives in namespace pth, so that no helper can collide
@@ -364,6 +364,14 @@ struct pt_scene {
     std::vector<uint32_t> query_inst_first, query_inst_count;
     uint32_t query_n_instances = 0;
     bool query_table_made = false;
+    // light gathered at points (pt_gather.cpp; include/pt_gather.h): the host forms' points and records, the points and the missing
+    // pixels of a frame or an instance, and the workspace of one launch: the samples' plane or bits and the walks' spill area
+    pth::DevBuf<float> gather_points;
+    pth::DevBuf<uint8_t> gather_miss;
+    pth::DevBuf<pt_gather_result> gather_out;
+    pth::DevBuf<pth::F4> gather_plane;
+    pth::DevBuf<unsigned long long> gather_bits;
+    pth::DevBuf<uint2> gather_spill;
     bool debug_collect_costs = false;                // pt_debug_collect_costs: every launch records them
     std::vector<uint32_t> debug_place;               // pt_debug_set_place: the next launch starts from this table ...
     uint32_t debug_place_waves = 0, debug_place_slots = 0; // ... with this many wavefronts and slots in each

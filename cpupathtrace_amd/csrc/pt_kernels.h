@@ -292,6 +292,17 @@ void pt_launch_query_pixels(hipStream_t stream, const PtDevScene &scene, const P
                             const PtQueryTables &tables, const PtPathConfig &cfg);
 // out[i] = 1 iff the closest hit of segment i (origin, direction, t_max: 7 floats) has 0 <= t < t_max: the shadow walk, ended at the first such leaf
 void pt_launch_occluded(hipStream_t stream, const PtDevScene &scene, const float *seg7, uint32_t n, uint8_t *out, const PtPathConfig &cfg);
+// Light gathered at points (pt_gather_kernels.h; include/pt_gather.h): the samples of the points first .. first + n_points - 1
+// of points6 (position, normal; `miss`, if not null, marks the points that are not there) into the chunk's workspace -- plane[n_points *
+// samples] for kinds 1 and 2, bits[ceil(n_points * samples / 64)] for kind 0 --, then their records out[2 * point], out[2 * point + 1] by the
+// ordered reduce.  n_points * samples <= 0x7fffffff; cfg.spill holds one walk per pair of the chunk.
+void pt_launch_gather(hipStream_t stream, const PtDevScene &scene, int kind, const float *points6, const uint8_t *miss, uint32_t first, uint32_t n_points, uint32_t samples,
+                      float epsilon, float distance, uint64_t base_seed, float4 *plane, unsigned long long *bits, float4 *out, const PtPathConfig &cfg);
+// the points of a frame's first hits (pt_query_frame's rays; the normal turned against the ray) and which pixels have none; cfg.spill holds one walk per pixel
+void pt_launch_gather_frame_points(hipStream_t stream, const PtDevScene &scene, const PtDevCamera &camera, int32_t width, int32_t height, float *points6, uint8_t *miss,
+                                   const PtPathConfig &cfg);
+// the corners of the triangles first_tri .. first_tri + n_tris - 1 with their normals: 3 points per triangle
+void pt_launch_gather_corner_points(hipStream_t stream, const float *pos, const float4 *shade, uint32_t first_tri, uint32_t n_tris, float *points6);
 // diagnostic (tools/step_timing.py): stamped walks, `lanes_per_wave` rays per wavefront; out[ray] = (steps, cycles waiting for records, cycles in all, price of a stamp pair)
 void pt_launch_steptime(hipStream_t stream, const PtDevScene &scene, const float *rays6, uint32_t n, uint32_t lanes_per_wave, uint4 *out, uint2 *spill, uint32_t spill_depth, int flags);
 

@@ -281,6 +281,9 @@ struct MorphTarget {
 class Camera;
 struct RenderOptions;
 struct PickResult; // PathTrace/query.h
+struct GatherOptions; // PathTrace/gather.h
+struct GatherPoint;
+struct GatherResult;
 
 class Scene {
   public:
@@ -373,6 +376,18 @@ class Scene {
     // Non-virtual: the class's layout is what it was.
     PickResult pick(const Camera &camera, const RenderOptions &options, int x, int y) const;
     bool occluded(const Ray &ray, float t_max) const;
+
+    // Light gathered at surface points (pt_gather_points, pt_gather_frame, pt_gather_instance, include/pt_gather.h; PathTrace/gather.h has
+    // the types).  gather: the light that arrives at each point -- the unoccluded share, the direct light or whole paths, as the options
+    // say -- for a white Lambertian receiver, one result per point.  gatherFrame: the same at the first hit of the ray through the centre
+    // of every pixel of the frame `options` describes, the normal turned against the ray: image_width * image_height results in row
+    // order, samples = 0 where the ray hits nothing.  bakeInstance: the same at the three corners of every surviving triangle of mesh
+    // instance `instance`, with the corner normals; the corners are made on the device.  All three may be called with a live FrameRender
+    // and change nothing.  They throw std::invalid_argument for options the device would refuse (samples < 1, a negative epsilon, an
+    // occlusion distance that is not positive, an instance out of range), std::runtime_error when the device refuses.  Non-virtual.
+    std::vector<GatherResult> gather(const std::vector<GatherPoint> &points, const GatherOptions &gather_options) const;
+    std::vector<GatherResult> gatherFrame(const Camera &camera, const RenderOptions &options, const GatherOptions &gather_options) const;
+    std::vector<std::array<GatherResult, 3>> bakeInstance(size_t instance, const GatherOptions &gather_options) const;
 
     // the device scene behind the C ABI (include/pt_hip.h); used by processJob / processItem
     pt_scene *deviceScene() const noexcept { return device_scene; }

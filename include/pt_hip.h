@@ -490,6 +490,11 @@ int pt_temporal_denoise_device(pt_temporal *t, const float *d_rgba, const float 
 int pt_temporal_reset(pt_temporal *t);
 int pt_temporal_destroy(pt_temporal *t);
 
+/* Light gathered at surface points -- ambient occlusion, direct light, full paths -- for points, for a frame's first hits and for the
+ * corners of a mesh instance's triangles (pt_gather_points, pt_gather_frame, pt_gather_instance): declared, with their
+ * contracts, in: */
+#include "pt_gather.h"
+
 /* Scene queries: the hit record of a ray, of a pixel or of every pixel of a frame -- object, instance, face, position, normals,
  * barycentrics -- and occlusion tests of segments (pt_query_rays, pt_query_pixels, pt_query_frame, pt_occluded_rays): the
  * record and the entry points are declared, with their contracts, in: */

@@ -1,5 +1,6 @@
 // src/host/scene.cpp -- Scene: flattens the caller's object graph into the arrays of include/pt_hip.h and owns the device scene.
 #include <PathTrace/detail/world.h>
+#include <PathTrace/gather.h>
 #include <PathTrace/query.h>
 #include <PathTrace/scene/mesh.h>
 
@@ -834,6 +835,82 @@ bool Scene::occluded(const Ray &ray, float t_max) const {
     uint8_t blocked = 0;
     pathtrace_host::check(pt_occluded_rays(device_scene, segment, 1, &blocked), "Scene::occluded");
     return blocked != 0;
+}
+
+namespace {
+
+    // The parameters of the C ABI; what it would refuse is refused here, as an argument error
+    pt_gather_params gatherParams(const GatherOptions &o, const char *what) {
+        if(o.samples < 1 || !(o.epsilon >= 0.0F) || (o.kind == GatherKind::occlusion && !(o.distance > 0.0F)) ||
+           (o.kind != GatherKind::occlusion && o.kind != GatherKind::direct && o.kind != GatherKind::paths)) {
+            throw std::invalid_argument(std::string("PathTrace: ") + what + ": samples must be at least 1, epsilon not negative, an occlusion distance positive and the kind known");
+        }
+        pt_gather_params p{};
+        p.kind = static_cast<int32_t>(o.kind);
+        p.samples = o.samples;
+        p.epsilon = o.epsilon;
+        p.distance = o.distance;
+        p.base_seed = o.base_seed;
+        return p;
+    }
+
+    GatherResult gatherResult(const pt_gather_result &r) {
+        GatherResult out;
+        out.value = Color<float>{r.value[0], r.value[1], r.value[2], r.value[3]};
+        out.samples = r.samples;
+        out.occluded = r.occluded;
+        return out;
+    }
+
+} // namespace
+
+std::vector<GatherResult> Scene::gather(const std::vector<GatherPoint> &points, const GatherOptions &gather_options) const {
+    const pt_gather_params params = gatherParams(gather_options, "Scene::gather");
+    std::vector<float> packed(6 * points.size());
+    for(size_t i = 0; i < points.size(); i++) {
+        for(size_t k = 0; k < 3; k++) {
+            packed[6 * i + k] = points[i].position[k];
+            packed[6 * i + 3 + k] = points[i].normal[k];
+        }
+    }
+    std::vector<pt_gather_result> raw(points.size());
+    pathtrace_host::check(pt_gather_points(device_scene, packed.data(), points.size(), &params, raw.data()), "Scene::gather");
+    std::vector<GatherResult> out(points.size());
+    std::transform(raw.begin(), raw.end(), out.begin(), gatherResult);
+    return out;
+}
+
+std::vector<GatherResult> Scene::gatherFrame(const Camera &camera, const RenderOptions &options, const GatherOptions &gather_options) const {
+    const pt_gather_params params = gatherParams(gather_options, "Scene::gatherFrame");
+    if(options.image_width <= 0 || options.image_height <= 0) {
+        throw std::invalid_argument("PathTrace: Scene::gatherFrame: the image size must be positive");
+    }
+    const pt_camera_params cam = pathtrace_host::cameraParams(camera);
+    const pt_options opt = pathtrace_host::renderOptions(options);
+    std::vector<pt_gather_result> raw(static_cast<size_t>(options.image_width) * static_cast<size_t>(options.image_height));
+    pathtrace_host::check(pt_gather_frame(device_scene, &cam, &opt, &params, raw.data()), "Scene::gatherFrame");
+    std::vector<GatherResult> out(raw.size());
+    std::transform(raw.begin(), raw.end(), out.begin(), gatherResult);
+    return out;
+}
+
+std::vector<std::array<GatherResult, 3>> Scene::bakeInstance(size_t instance, const GatherOptions &gather_options) const {
+    const pt_gather_params params = gatherParams(gather_options, "Scene::bakeInstance");
+    const size_t n_instances = pathtrace_host::sceneInstanceCount(*this);
+    if(instance >= n_instances) {
+        throw std::invalid_argument("PathTrace: Scene::bakeInstance: instance out of range");
+    }
+    std::vector<uint32_t> first(n_instances), count(n_instances);
+    pathtrace_host::check(pt_scene_instance_ranges(device_scene, first.data(), count.data()), "Scene::bakeInstance");
+    std::vector<pt_gather_result> raw(3 * static_cast<size_t>(count[instance]) + 1); // (+ 1: never empty)
+    pathtrace_host::check(pt_gather_instance(device_scene, static_cast<uint32_t>(instance), &params, raw.data()), "Scene::bakeInstance");
+    std::vector<std::array<GatherResult, 3>> out(count[instance]);
+    for(size_t t = 0; t < out.size(); t++) {
+        for(size_t c = 0; c < 3; c++) {
+            out[t][c] = gatherResult(raw[3 * t + c]);
+        }
+    }
+    return out;
 }
 
 std::vector<std::tuple<vec3<float>, Spectrum, float>> Scene::sampleLights(vec3<float> pos, vec3<float> /*n*/, RandomEngine &re) const noexcept {
