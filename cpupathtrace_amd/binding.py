@@ -81,6 +81,9 @@ QUERY_NO_FACE = 0xFFFFFFFF
 # light gathered at points (include/pt_gather.h): occlusion, direct light, full paths
 GATHER_EXPORTS = ["pt_gather_params_default", "pt_gather_points", "pt_gather_points_device", "pt_gather_frame", "pt_gather_frame_device", "pt_gather_instance"]
 GATHER_OCCLUSION, GATHER_DIRECT, GATHER_PATHS = 0, 1, 2
+# light probes (include/pt_light_probes.h): SH radiance at free points, probe grids, the lookup that shades points from a grid
+LIGHT_PROBE_EXPORTS = ["pt_light_probe_params_default", "pt_light_probes_points", "pt_light_probes_points_device", "pt_light_probes_grid", "pt_light_probes_shade",
+                       "pt_light_probes_shade_device"]
 # checkpoints of a frame (include/pt_checkpoint.h, which pt_hip.h includes as it includes pt_frame_noise.h)
 CHECKPOINT_EXPORTS = ["pt_checkpoint_inspect", "pt_frame_checkpoint_size", "pt_frame_checkpoint_save", "pt_frame_checkpoint_load"]
 CHECKPOINT_HEADER_BYTES = 352
@@ -91,6 +94,15 @@ Hit = np.dtype([("t", "<f4"), ("object", "<i4"), ("instance", "<i4"), ("face", "
 
 # pt_gather_result: 32 bytes.  A frame's pixel without a first hit: all zero
 GatherResult = np.dtype([("value", "<f4", 4), ("samples", "<u4"), ("occluded", "<u4"), ("pad", "<u4", 2)])
+
+# pt_light_probe: 128 bytes; sh[k][c]: coefficient k (bands 0..2) of colour channel c.  pt_light_probe_grid: 36 bytes
+LightProbe = np.dtype([("sh", "<f4", (9, 3)), ("samples", "<u4"), ("missed", "<u4"), ("backfacing", "<u4"), ("pad", "<u4", 2)])
+LightProbeGrid = np.dtype([("origin", "<f4", 3), ("step", "<f4", 3), ("count", "<u4", 3)])
+
+
+class LightProbeParams(C.Structure):
+    """pt_light_probe_params"""
+    _fields_ = [("samples", C.c_int32), ("epsilon", C.c_float), ("base_seed", C.c_uint64), ("max_backfacing", C.c_float), ("pad", C.c_uint32)]
 
 
 class GatherParams(C.Structure):
@@ -741,6 +753,25 @@ def gather_params_default():
     return gp
 
 
+def light_probe_params(samples, epsilon, base_seed=0, max_backfacing=0.25):
+    return LightProbeParams(int(samples), float(epsilon), int(base_seed) & 0xFFFFFFFFFFFFFFFF, float(max_backfacing), 0)
+
+
+def light_probe_params_default():
+    lp = LightProbeParams()
+    _check(load().pt_light_probe_params_default(C.byref(lp)))
+    return lp
+
+
+def light_probe_grid(origin, step, count):
+    """A pt_light_probe_grid as a 0-d array of dtype LightProbeGrid; a grid made by this function passes through unchanged."""
+    if isinstance(origin, np.ndarray) and origin.dtype == LightProbeGrid:
+        return np.ascontiguousarray(origin).reshape(())
+    g = np.zeros((), LightProbeGrid)
+    g["origin"], g["step"], g["count"] = np.asarray(origin, np.float32), np.asarray(step, np.float32), np.asarray(count, np.int64)
+    return g
+
+
 def _gather_points(points, normals):
     """(n, 6) float32: position, normal"""
     points = np.asarray(points, np.float32).reshape(-1, 3)
@@ -1119,6 +1150,50 @@ class Scene:
         gp = gather_params(kind, samples, epsilon, distance, base_seed)
         _check(load().pt_gather_instance(self._h, C.c_uint32(instance), C.byref(gp), _ptr(out)))
         return out
+
+    def light_probes(self, positions, samples, epsilon, base_seed=0):
+        """pt_light_probes_points: the radiance that arrives at the free points (n, 3) from every direction, `samples` samples each,
+        projected onto SH bands 0..2: (n,) records of dtype LightProbe."""
+        pos = np.ascontiguousarray(np.asarray(positions, np.float32).reshape(-1, 3))
+        out = np.zeros(len(pos), LightProbe)
+        lp = light_probe_params(samples, epsilon, base_seed)
+        _check(load().pt_light_probes_points(self._h, _ptr(pos), C.c_size_t(len(pos)), C.byref(lp), _ptr(out)))
+        return out
+
+    def light_probes_device(self, d_positions_ptr, n, d_out_ptr, samples, epsilon, base_seed=0, stream_ptr=0):
+        """pt_light_probes_points_device: n positions (3 floats each) and n records (128 bytes each) in device memory, ordered on stream_ptr."""
+        lp = light_probe_params(samples, epsilon, base_seed)
+        _check(load().pt_light_probes_points_device(self._h, C.c_void_p(d_positions_ptr), C.c_size_t(n), C.byref(lp), C.c_void_p(d_out_ptr), C.c_void_p(stream_ptr)))
+
+    def light_probe_grid(self, origin, step, count, samples=256, epsilon=1e-3, base_seed=0):
+        """pt_light_probes_grid: the light probes at origin + i * step, count = (nx, ny, nz): (grid, records (nz, ny, nx) of dtype
+        LightProbe); the grid is what shade_with_light_probes takes.  The positions are made on the device."""
+        grid = light_probe_grid(origin, step, count)
+        nx, ny, nz = (int(c) for c in grid["count"])
+        out = np.zeros((nz, ny, nx), LightProbe)
+        lp = light_probe_params(samples, epsilon, base_seed)
+        _check(load().pt_light_probes_grid(self._h, _ptr(grid), C.byref(lp), _ptr(out)))
+        return grid, out
+
+    def shade_with_light_probes(self, grid, probes, points, normals, max_backfacing=0.25):
+        """pt_light_probes_shade: what a white Lambertian receiver at each point (n, 3) that faces its normal (n, 3) sends out under the
+        grid's probes, blended from the eight probes around it: (n, 4) float32, rgb and the sum of the blend weights (0: no probe counted)."""
+        grid = light_probe_grid(grid, None, None)
+        probes = np.ascontiguousarray(probes, dtype=LightProbe).reshape(-1)
+        if len(probes) != int(np.prod(grid["count"].astype(np.int64))):
+            raise ValueError("as many probes as the grid has nodes")
+        pts = _gather_points(points, normals)
+        out = np.zeros((len(pts), 4), np.float32)
+        lp = light_probe_params(1, 0.0, 0, max_backfacing)
+        _check(load().pt_light_probes_shade(self._h, _ptr(grid), _ptr(probes), C.byref(lp), _ptr(pts), C.c_size_t(len(pts)), _ptr(out)))
+        return out
+
+    def shade_with_light_probes_device(self, grid, d_probes_ptr, d_points_ptr, n, d_out_ptr, max_backfacing=0.25, stream_ptr=0):
+        """pt_light_probes_shade_device: the grid's records, n points (6 floats each) and n results (4 floats each) in device memory."""
+        grid = light_probe_grid(grid, None, None)
+        lp = light_probe_params(1, 0.0, 0, max_backfacing)
+        _check(load().pt_light_probes_shade_device(self._h, _ptr(grid), C.c_void_p(d_probes_ptr), C.byref(lp), C.c_void_p(d_points_ptr), C.c_size_t(n), C.c_void_p(d_out_ptr),
+                                                   C.c_void_p(stream_ptr)))
 
     def process_item(self, camera, options, streams, image=None, want_stats=False):
         """processItem for many WorkItems at once; streams: array of STREAM_DTYPE (rect + raw engine state)."""

@@ -303,6 +303,19 @@ void pt_launch_gather_frame_points(hipStream_t stream, const PtDevScene &scene, 
                                    const PtPathConfig &cfg);
 // the corners of the triangles first_tri .. first_tri + n_tris - 1 with their normals: 3 points per triangle
 void pt_launch_gather_corner_points(hipStream_t stream, const float *pos, const float4 *shade, uint32_t first_tri, uint32_t n_tris, float *points6);
+// Light probes (pt_light_probe_kernels.h; include/pt_light_probes.h).  A grid as the kernels take it: pt_light_probe_grid's fields
+struct PtLightProbeGrid {
+    float origin[3];
+    float step[3];
+    uint32_t count[3];
+};
+// The samples of the probes first .. first + n_probes - 1 -- at positions[3 * probe], or, with positions == null, at the grid's nodes -- into
+// the chunk's workspace plane[2 * n_probes * samples] (radiance; direction and flags), then their 128-byte records out[8 * probe ..] by the
+// projection, one wavefront per probe.  n_probes * samples <= 0x7fffffff; cfg.spill holds one walk per pair of the chunk.
+void pt_launch_light_probes(hipStream_t stream, const PtDevScene &scene, const float *positions, const PtLightProbeGrid &grid, uint32_t first, uint32_t n_probes, uint32_t samples,
+                            float epsilon, uint64_t base_seed, float4 *plane, float4 *out, const PtPathConfig &cfg);
+// out[i] = the blend of the grid's records (8 float4 each) around point i (position, normal), evaluated towards its normal, and the sum of the weights
+void pt_launch_light_probe_shade(hipStream_t stream, const PtLightProbeGrid &grid, const float4 *probes, float max_backfacing, const float *points6, uint32_t n, float4 *out);
 // diagnostic (tools/step_timing.py): stamped walks, `lanes_per_wave` rays per wavefront; out[ray] = (steps, cycles waiting for records, cycles in all, price of a stamp pair)
 void pt_launch_steptime(hipStream_t stream, const PtDevScene &scene, const float *rays6, uint32_t n, uint32_t lanes_per_wave, uint4 *out, uint2 *spill, uint32_t spill_depth, int flags);
 

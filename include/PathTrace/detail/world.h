@@ -284,6 +284,9 @@ struct PickResult; // PathTrace/query.h
 struct GatherOptions; // PathTrace/gather.h
 struct GatherPoint;
 struct GatherResult;
+struct LightProbeOptions; // PathTrace/light_probes.h
+struct LightProbe;
+struct LightProbeGrid;
 
 class Scene {
   public:
@@ -388,6 +391,20 @@ class Scene {
     std::vector<GatherResult> gather(const std::vector<GatherPoint> &points, const GatherOptions &gather_options) const;
     std::vector<GatherResult> gatherFrame(const Camera &camera, const RenderOptions &options, const GatherOptions &gather_options) const;
     std::vector<std::array<GatherResult, 3>> bakeInstance(size_t instance, const GatherOptions &gather_options) const;
+
+    // Light probes (pt_light_probes_points, pt_light_probes_grid, pt_light_probes_shade, include/pt_light_probes.h; PathTrace/light_probes.h
+    // has the types).  lightProbes: the radiance that arrives at each free position from every direction, as SH of bands 0..2 per colour
+    // channel, one record per position.  lightProbeGrid: the same at the nodes of a grid, x fastest; the positions are made on the
+    // device.  shadeWithLightProbes: what a white Lambertian receiver at each point, facing its normal, sends out under a grid's probes,
+    // blended from the eight probes around it -- rgb, and in alpha the sum of the blend weights (0: no probe counted); of the options it
+    // reads max_backfacing alone.  All three may be called with a live
+    // FrameRender and change nothing.  They throw std::invalid_argument for arguments the device would refuse (samples < 1, a negative
+    // epsilon or max_backfacing, a grid with a zero count or a step that is zero or not finite, a number of probes other than the grid's number of nodes),
+    // std::runtime_error when the device refuses.  Non-virtual.
+    std::vector<LightProbe> lightProbes(const std::vector<vec3<float>> &positions, const LightProbeOptions &probe_options) const;
+    std::vector<LightProbe> lightProbeGrid(const LightProbeGrid &grid, const LightProbeOptions &probe_options) const;
+    std::vector<Color<float>> shadeWithLightProbes(const LightProbeGrid &grid, const std::vector<LightProbe> &probes, const std::vector<GatherPoint> &points,
+                                                   const LightProbeOptions &probe_options) const;
 
     // the device scene behind the C ABI (include/pt_hip.h); used by processJob / processItem
     pt_scene *deviceScene() const noexcept { return device_scene; }

@@ -495,6 +495,11 @@ int pt_temporal_destroy(pt_temporal *t);
  * contracts, in: */
 #include "pt_gather.h"
 
+/* Light probes -- the radiance that arrives at free points projected onto spherical harmonics, grids of such probes and the lookup that
+ * shades a point with a normal from a grid (pt_light_probes_points, pt_light_probes_grid, pt_light_probes_shade):
+ * declared, with their contracts, in: */
+#include "pt_light_probes.h"
+
 /* Scene queries: the hit record of a ray, of a pixel or of every pixel of a frame -- object, instance, face, position, normals,
  * barycentrics -- and occlusion tests of segments (pt_query_rays, pt_query_pixels, pt_query_frame, pt_occluded_rays): the
  * record and the entry points are declared, with their contracts, in: */

@@ -1,6 +1,7 @@
 // src/host/scene.cpp -- Scene: flattens the caller's object graph into the arrays of include/pt_hip.h and owns the device scene.
 #include <PathTrace/detail/world.h>
 #include <PathTrace/gather.h>
+#include <PathTrace/light_probes.h>
 #include <PathTrace/query.h>
 #include <PathTrace/scene/mesh.h>
 
@@ -909,6 +910,113 @@ std::vector<std::array<GatherResult, 3>> Scene::bakeInstance(size_t instance, co
         for(size_t c = 0; c < 3; c++) {
             out[t][c] = gatherResult(raw[3 * t + c]);
         }
+    }
+    return out;
+}
+
+namespace {
+
+    // The parameters and the grid of the C ABI; what it would refuse is refused here, as an argument error
+    pt_light_probe_params lightProbeParams(const LightProbeOptions &o, const char *what) {
+        if(o.samples < 1 || !(o.epsilon >= 0.0F) || !(o.max_backfacing >= 0.0F)) {
+            throw std::invalid_argument(std::string("PathTrace: ") + what + ": samples must be at least 1, epsilon and max_backfacing not negative");
+        }
+        pt_light_probe_params p{};
+        p.samples = o.samples;
+        p.epsilon = o.epsilon;
+        p.base_seed = o.base_seed;
+        p.max_backfacing = o.max_backfacing;
+        return p;
+    }
+
+    pt_light_probe_grid lightProbeGridParams(const LightProbeGrid &g, const char *what, size_t *n_probes) {
+        pt_light_probe_grid out{};
+        uint64_t n = 1;
+        for(size_t a = 0; a < 3; a++) {
+            if(g.count[a] == 0 || !std::isfinite(g.step[a]) || g.step[a] == 0.0F || (n *= g.count[a]) > 0x7fffffffULL) {
+                throw std::invalid_argument(std::string("PathTrace: ") + what + ": a grid needs counts of at least 1, at most 0x7fffffff probes, and finite steps that are not zero");
+            }
+            out.origin[a] = g.origin[a];
+            out.step[a] = g.step[a];
+            out.count[a] = g.count[a];
+        }
+        *n_probes = static_cast<size_t>(n);
+        return out;
+    }
+
+    LightProbe lightProbe(const pt_light_probe &r) {
+        LightProbe out;
+        for(size_t k = 0; k < 9; k++) {
+            for(size_t c = 0; c < 3; c++) {
+                out.sh[k][c] = r.sh[k][c];
+            }
+        }
+        out.samples = r.samples;
+        out.missed = r.missed;
+        out.backfacing = r.backfacing;
+        return out;
+    }
+
+} // namespace
+
+std::vector<LightProbe> Scene::lightProbes(const std::vector<vec3<float>> &positions, const LightProbeOptions &probe_options) const {
+    const pt_light_probe_params params = lightProbeParams(probe_options, "Scene::lightProbes");
+    std::vector<float> packed(3 * positions.size());
+    for(size_t i = 0; i < positions.size(); i++) {
+        for(size_t k = 0; k < 3; k++) {
+            packed[3 * i + k] = positions[i][k];
+        }
+    }
+    std::vector<pt_light_probe> raw(positions.size());
+    pathtrace_host::check(pt_light_probes_points(device_scene, packed.data(), positions.size(), &params, raw.data()), "Scene::lightProbes");
+    std::vector<LightProbe> out(raw.size());
+    std::transform(raw.begin(), raw.end(), out.begin(), lightProbe);
+    return out;
+}
+
+std::vector<LightProbe> Scene::lightProbeGrid(const LightProbeGrid &grid, const LightProbeOptions &probe_options) const {
+    const pt_light_probe_params params = lightProbeParams(probe_options, "Scene::lightProbeGrid");
+    size_t n = 0;
+    const pt_light_probe_grid g = lightProbeGridParams(grid, "Scene::lightProbeGrid", &n);
+    std::vector<pt_light_probe> raw(n);
+    pathtrace_host::check(pt_light_probes_grid(device_scene, &g, &params, raw.data()), "Scene::lightProbeGrid");
+    std::vector<LightProbe> out(raw.size());
+    std::transform(raw.begin(), raw.end(), out.begin(), lightProbe);
+    return out;
+}
+
+std::vector<Color<float>> Scene::shadeWithLightProbes(const LightProbeGrid &grid, const std::vector<LightProbe> &probes, const std::vector<GatherPoint> &points,
+                                                      const LightProbeOptions &probe_options) const {
+    pt_light_probe_params params = lightProbeParams(LightProbeOptions{1, 0.0F, 0, probe_options.max_backfacing}, "Scene::shadeWithLightProbes");
+    size_t n = 0;
+    const pt_light_probe_grid g = lightProbeGridParams(grid, "Scene::shadeWithLightProbes", &n);
+    if(probes.size() != n) {
+        throw std::invalid_argument("PathTrace: Scene::shadeWithLightProbes: as many probes as the grid has nodes");
+    }
+    std::vector<pt_light_probe> raw(n);
+    for(size_t i = 0; i < n; i++) {
+        for(size_t k = 0; k < 9; k++) {
+            for(size_t c = 0; c < 3; c++) {
+                raw[i].sh[k][c] = probes[i].sh[k][c];
+            }
+        }
+        raw[i].samples = probes[i].samples;
+        raw[i].missed = probes[i].missed;
+        raw[i].backfacing = probes[i].backfacing;
+        raw[i].pad[0] = raw[i].pad[1] = 0;
+    }
+    std::vector<float> packed(6 * points.size());
+    for(size_t i = 0; i < points.size(); i++) {
+        for(size_t k = 0; k < 3; k++) {
+            packed[6 * i + k] = points[i].position[k];
+            packed[6 * i + 3 + k] = points[i].normal[k];
+        }
+    }
+    std::vector<float> values(4 * points.size());
+    pathtrace_host::check(pt_light_probes_shade(device_scene, &g, raw.data(), &params, packed.data(), points.size(), values.data()), "Scene::shadeWithLightProbes");
+    std::vector<Color<float>> out(points.size());
+    for(size_t i = 0; i < out.size(); i++) {
+        out[i] = Color<float>{values[4 * i], values[4 * i + 1], values[4 * i + 2], values[4 * i + 3]};
     }
     return out;
 }
