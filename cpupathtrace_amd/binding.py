@@ -84,6 +84,9 @@ GATHER_OCCLUSION, GATHER_DIRECT, GATHER_PATHS = 0, 1, 2
 # light probes (include/pt_light_probes.h): SH radiance at free points, probe grids, the lookup that shades points from a grid
 LIGHT_PROBE_EXPORTS = ["pt_light_probe_params_default", "pt_light_probes_points", "pt_light_probes_points_device", "pt_light_probes_grid", "pt_light_probes_shade",
                        "pt_light_probes_shade_device"]
+# radiance along free rays and captures (include/pt_radiance.h): per-ray means, and images made by four camera models on the device
+RADIANCE_EXPORTS = ["pt_radiance_params_default", "pt_radiance_rays", "pt_radiance_rays_device", "pt_radiance_capture", "pt_radiance_capture_device"]
+CAPTURE_EQUIRECT, CAPTURE_CUBE, CAPTURE_FISHEYE, CAPTURE_ORTHO = 0, 1, 2, 3
 # checkpoints of a frame (include/pt_checkpoint.h, which pt_hip.h includes as it includes pt_frame_noise.h)
 CHECKPOINT_EXPORTS = ["pt_checkpoint_inspect", "pt_frame_checkpoint_size", "pt_frame_checkpoint_save", "pt_frame_checkpoint_load"]
 CHECKPOINT_HEADER_BYTES = 352
@@ -103,6 +106,20 @@ LightProbeGrid = np.dtype([("origin", "<f4", 3), ("step", "<f4", 3), ("count", "
 class LightProbeParams(C.Structure):
     """pt_light_probe_params"""
     _fields_ = [("samples", C.c_int32), ("epsilon", C.c_float), ("base_seed", C.c_uint64), ("max_backfacing", C.c_float), ("pad", C.c_uint32)]
+
+# pt_radiance_result: 32 bytes; value: the mean radiance and its alpha
+RadianceResult = np.dtype([("value", "<f4", 4), ("samples", "<u4"), ("missed", "<u4"), ("outside", "<u4"), ("pad", "<u4")])
+
+
+class RadianceParams(C.Structure):
+    """pt_radiance_params"""
+    _fields_ = [("samples", C.c_int32), ("epsilon", C.c_float), ("base_seed", C.c_uint64)]
+
+
+class CaptureDesc(C.Structure):
+    """pt_capture_desc"""
+    _fields_ = [("model", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("jitter", C.c_int32), ("origin", C.c_float * 3), ("right", C.c_float * 3), ("up", C.c_float * 3),
+                ("forward", C.c_float * 3), ("fov", C.c_float), ("extent", C.c_float * 2), ("pad", C.c_uint32)]
 
 
 class GatherParams(C.Structure):
@@ -772,6 +789,37 @@ def light_probe_grid(origin, step, count):
     return g
 
 
+def radiance_params(samples, epsilon, base_seed=0):
+    return RadianceParams(int(samples), float(epsilon), int(base_seed) & 0xFFFFFFFFFFFFFFFF)
+
+
+def radiance_params_default():
+    rp = RadianceParams()
+    _check(load().pt_radiance_params_default(C.byref(rp)))
+    return rp
+
+
+def capture_desc(model, width, height, origin, look_at, up, fov=np.pi, extent=(1.0, 1.0), jitter=True):
+    """A pt_capture_desc that looks from origin at look_at: the basis is made in numpy float32, forward = normalize(look_at - origin),
+    right = normalize(cross(forward, up)), and up re-made as cross(right, forward).  fov: FISHEYE's full angle, radians; extent: ORTHO's
+    half width and half height."""
+    f32 = np.float32
+
+    def normalize(v):  # (vec3::normalize's arithmetic: the C++ Capture::lookAt makes the same basis, bit for bit)
+        total = f32(0.0)
+        for x in v:
+            total = f32(total + f32(x * x))
+        return (v * f32(f32(1.0) / np.sqrt(total))).astype(f32)
+
+    origin = np.asarray(origin, f32).reshape(3)
+    forward = normalize((np.asarray(look_at, f32).reshape(3) - origin).astype(f32))
+    right = normalize(np.cross(forward, np.asarray(up, f32).reshape(3)).astype(f32))
+    true_up = np.cross(right, forward).astype(f32)
+    extent = np.asarray(extent, f32).reshape(2)
+    return CaptureDesc(int(model), int(width), int(height), int(bool(jitter)), (C.c_float * 3)(*origin), (C.c_float * 3)(*right), (C.c_float * 3)(*true_up), (C.c_float * 3)(*forward),
+                       float(f32(fov)), (C.c_float * 2)(*extent), 0)
+
+
 def _gather_points(points, normals):
     """(n, 6) float32: position, normal"""
     points = np.asarray(points, np.float32).reshape(-1, 3)
@@ -1194,6 +1242,33 @@ class Scene:
         lp = light_probe_params(1, 0.0, 0, max_backfacing)
         _check(load().pt_light_probes_shade_device(self._h, _ptr(grid), C.c_void_p(d_probes_ptr), C.byref(lp), C.c_void_p(d_points_ptr), C.c_size_t(n), C.c_void_p(d_out_ptr),
                                                    C.c_void_p(stream_ptr)))
+
+    def radiance(self, rays, samples=64, epsilon=1e-3, base_seed=0):
+        """pt_radiance_rays: the radiance that arrives along each ray (n, 6) -- origin, direction as given --, the mean of `samples`
+        paths: (n,) records of dtype RadianceResult."""
+        rays = np.ascontiguousarray(np.asarray(rays, np.float32).reshape(-1, 6))
+        out = np.zeros(len(rays), RadianceResult)
+        rp = radiance_params(samples, epsilon, base_seed)
+        _check(load().pt_radiance_rays(self._h, _ptr(rays), C.c_size_t(len(rays)), C.byref(rp), _ptr(out)))
+        return out
+
+    def radiance_device(self, d_rays_ptr, n, d_out_ptr, samples=64, epsilon=1e-3, base_seed=0, stream_ptr=0):
+        """pt_radiance_rays_device: n rays (6 floats each) and n records (32 bytes each) in device memory, ordered on stream_ptr."""
+        rp = radiance_params(samples, epsilon, base_seed)
+        _check(load().pt_radiance_rays_device(self._h, C.c_void_p(d_rays_ptr), C.c_size_t(n), C.byref(rp), C.c_void_p(d_out_ptr), C.c_void_p(stream_ptr)))
+
+    def capture(self, desc, samples=64, epsilon=1e-3, base_seed=0):
+        """pt_radiance_capture: the image of a CaptureDesc (capture_desc makes one), rays made on the device: (height, width) records of
+        dtype RadianceResult."""
+        out = np.zeros((max(int(desc.height), 0), max(int(desc.width), 0)), RadianceResult)
+        rp = radiance_params(samples, epsilon, base_seed)
+        _check(load().pt_radiance_capture(self._h, C.byref(desc), C.byref(rp), _ptr(out)))
+        return out
+
+    def capture_device(self, desc, d_out_ptr, samples=64, epsilon=1e-3, base_seed=0, stream_ptr=0):
+        """pt_radiance_capture_device: height * width records (32 bytes each) in device memory, ordered on stream_ptr."""
+        rp = radiance_params(samples, epsilon, base_seed)
+        _check(load().pt_radiance_capture_device(self._h, C.byref(desc), C.byref(rp), C.c_void_p(d_out_ptr), C.c_void_p(stream_ptr)))
 
     def process_item(self, camera, options, streams, image=None, want_stats=False):
         """processItem for many WorkItems at once; streams: array of STREAM_DTYPE (rect + raw engine state)."""

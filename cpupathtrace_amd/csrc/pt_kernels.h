@@ -316,6 +316,23 @@ void pt_launch_light_probes(hipStream_t stream, const PtDevScene &scene, const f
                             float epsilon, uint64_t base_seed, float4 *plane, float4 *out, const PtPathConfig &cfg);
 // out[i] = the blend of the grid's records (8 float4 each) around point i (position, normal), evaluated towards its normal, and the sum of the weights
 void pt_launch_light_probe_shade(hipStream_t stream, const PtLightProbeGrid &grid, const float4 *probes, float max_backfacing, const float *points6, uint32_t n, float4 *out);
+// Radiance along free rays and captures (pt_radiance_kernels.h; include/pt_radiance.h).  A capture as the kernels take it:
+// pt_capture_desc's fields, the model one of PT_CAPTURE_*
+#define PT_CAPTURE_MODEL_EQUIRECT 0
+#define PT_CAPTURE_MODEL_CUBE 1
+#define PT_CAPTURE_MODEL_FISHEYE 2
+#define PT_CAPTURE_MODEL_ORTHO 3
+struct PtCaptureParams {
+    int32_t model, width, height, jitter;
+    float origin[3], right[3], up[3], forward[3];
+    float fov;
+    float extent[2];
+};
+// The samples of the rays (rays[6 * i], origin and direction) or, with rays == null, of the capture's pixels first .. first + n - 1 into the
+// chunk's workspace plane[n * samples] (radiance and flags), then their 32-byte records out[2 * i ..] by the reduction, one wavefront
+// each.  n * samples <= 0x7fffffff; cfg.spill holds one walk per pair of the chunk.
+void pt_launch_radiance(hipStream_t stream, const PtDevScene &scene, const float *rays, const PtCaptureParams &capture, uint32_t first, uint32_t n, uint32_t samples, float epsilon,
+                        uint64_t base_seed, float4 *plane, float4 *out, const PtPathConfig &cfg);
 // diagnostic (tools/step_timing.py): stamped walks, `lanes_per_wave` rays per wavefront; out[ray] = (steps, cycles waiting for records, cycles in all, price of a stamp pair)
 void pt_launch_steptime(hipStream_t stream, const PtDevScene &scene, const float *rays6, uint32_t n, uint32_t lanes_per_wave, uint4 *out, uint2 *spill, uint32_t spill_depth, int flags);
 

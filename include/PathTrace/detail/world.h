@@ -287,6 +287,11 @@ struct GatherResult;
 struct LightProbeOptions; // PathTrace/light_probes.h
 struct LightProbe;
 struct LightProbeGrid;
+struct RadianceOptions; // PathTrace/radiance.h
+struct RadianceResult;
+struct Capture;
+template<typename T>
+class Image; // PathTrace/image/image.h
 
 class Scene {
   public:
@@ -405,6 +410,16 @@ class Scene {
     std::vector<LightProbe> lightProbeGrid(const LightProbeGrid &grid, const LightProbeOptions &probe_options) const;
     std::vector<Color<float>> shadeWithLightProbes(const LightProbeGrid &grid, const std::vector<LightProbe> &probes, const std::vector<GatherPoint> &points,
                                                    const LightProbeOptions &probe_options) const;
+
+    // Radiance along free rays and captures (pt_radiance_rays, pt_radiance_capture, include/pt_radiance.h; PathTrace/radiance.h has the
+    // types).  radiance: the mean of `samples` paths behind each ray -- origin and direction as given, the direction is not normalised --,
+    // one record per ray.  capture: the image of a Capture, its rays made on the device by one of four camera models; the values of the
+    // records, row-major, alpha the share of samples that hit something.  Both may be called with a live FrameRender and change nothing.
+    // They throw std::invalid_argument for arguments the device would refuse (samples < 1, a negative epsilon, a size below 1, a cube that
+    // is not 6 : 1, a fisheye that is not square or whose fov is outside (0, 2 pi], an orthographic extent that is not finite and positive,
+    // an origin or basis that is not finite), std::runtime_error when the device refuses.  Non-virtual.
+    std::vector<RadianceResult> radiance(const std::vector<Ray> &rays, const RadianceOptions &radiance_options) const;
+    Image<Color<float>> capture(const Capture &capture, const RadianceOptions &radiance_options) const;
 
     // the device scene behind the C ABI (include/pt_hip.h); used by processJob / processItem
     pt_scene *deviceScene() const noexcept { return device_scene; }

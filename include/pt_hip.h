@@ -495,6 +495,10 @@ int pt_temporal_destroy(pt_temporal *t);
  * contracts, in: */
 #include "pt_gather.h"
 
+/* Radiance along rays the caller chooses, and captures -- images of such rays made on the device by an equirectangular, cube-map, fisheye
+ * or orthographic camera model (pt_radiance_rays, pt_radiance_capture): declared, with their contracts, in: */
+#include "pt_radiance.h"
+
 /* Light probes -- the radiance that arrives at free points projected onto spherical harmonics, grids of such probes and the lookup that
  * shades a point with a normal from a grid (pt_light_probes_points, pt_light_probes_grid, pt_light_probes_shade):
  * declared, with their contracts, in: */

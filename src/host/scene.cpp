@@ -3,6 +3,7 @@
 #include <PathTrace/gather.h>
 #include <PathTrace/light_probes.h>
 #include <PathTrace/query.h>
+#include <PathTrace/radiance.h>
 #include <PathTrace/scene/mesh.h>
 
 #include "../../include/pt_hip.h"
@@ -1019,6 +1020,86 @@ std::vector<Color<float>> Scene::shadeWithLightProbes(const LightProbeGrid &grid
         out[i] = Color<float>{values[4 * i], values[4 * i + 1], values[4 * i + 2], values[4 * i + 3]};
     }
     return out;
+}
+
+namespace {
+
+    // The parameters and the capture of the C ABI; what it would refuse is refused here, as an argument error
+    pt_radiance_params radianceParams(const RadianceOptions &o, const char *what) {
+        if(o.samples < 1 || !(o.epsilon >= 0.0F)) {
+            throw std::invalid_argument(std::string("PathTrace: ") + what + ": samples must be at least 1, epsilon not negative");
+        }
+        pt_radiance_params p{};
+        p.samples = o.samples;
+        p.epsilon = o.epsilon;
+        p.base_seed = o.base_seed;
+        return p;
+    }
+
+    pt_capture_desc captureDesc(const Capture &c, const char *what) {
+        const int model = static_cast<int>(c.model);
+        bool ok = model >= PT_CAPTURE_EQUIRECT && model <= PT_CAPTURE_ORTHO && c.width >= 1 && c.height >= 1;
+        ok = ok && (model != PT_CAPTURE_CUBE || static_cast<int64_t>(c.width) == 6 * static_cast<int64_t>(c.height));
+        ok = ok && (model != PT_CAPTURE_FISHEYE || (c.width == c.height && c.fov > 0.0F && c.fov <= 2.0F * 3.14159274101257324219F));
+        ok = ok && (model != PT_CAPTURE_ORTHO || (std::isfinite(c.extent_x) && std::isfinite(c.extent_y) && c.extent_x > 0.0F && c.extent_y > 0.0F));
+        for(size_t k = 0; k < 3; k++) {
+            ok = ok && std::isfinite(c.origin[k]) && std::isfinite(c.right[k]) && std::isfinite(c.up[k]) && std::isfinite(c.forward[k]);
+        }
+        if(!ok) {
+            throw std::invalid_argument(std::string("PathTrace: ") + what +
+                                        ": a capture needs a known model, a size of at least 1 (cube: 6 : 1, fisheye: square with a fov in (0, 2 pi]), "
+                                        "for ortho finite positive extents, and a finite origin and basis");
+        }
+        pt_capture_desc d{};
+        d.model = model;
+        d.width = c.width;
+        d.height = c.height;
+        d.jitter = c.jitter ? 1 : 0;
+        for(size_t k = 0; k < 3; k++) {
+            d.origin[k] = c.origin[k];
+            d.right[k] = c.right[k];
+            d.up[k] = c.up[k];
+            d.forward[k] = c.forward[k];
+        }
+        d.fov = c.fov;
+        d.extent[0] = c.extent_x;
+        d.extent[1] = c.extent_y;
+        return d;
+    }
+
+} // namespace
+
+std::vector<RadianceResult> Scene::radiance(const std::vector<Ray> &rays, const RadianceOptions &radiance_options) const {
+    const pt_radiance_params params = radianceParams(radiance_options, "Scene::radiance");
+    std::vector<float> packed(6 * rays.size());
+    for(size_t i = 0; i < rays.size(); i++) {
+        for(size_t k = 0; k < 3; k++) {
+            packed[6 * i + k] = rays[i].origin[k];
+            packed[6 * i + 3 + k] = rays[i].dir[k];
+        }
+    }
+    std::vector<pt_radiance_result> raw(rays.size());
+    pathtrace_host::check(pt_radiance_rays(device_scene, packed.data(), rays.size(), &params, raw.data()), "Scene::radiance");
+    std::vector<RadianceResult> out(raw.size());
+    for(size_t i = 0; i < raw.size(); i++) {
+        out[i].value = Color<float>{raw[i].value[0], raw[i].value[1], raw[i].value[2], raw[i].value[3]};
+        out[i].samples = raw[i].samples;
+        out[i].missed = raw[i].missed;
+        out[i].outside = raw[i].outside;
+    }
+    return out;
+}
+
+Image<Color<float>> Scene::capture(const Capture &capture, const RadianceOptions &radiance_options) const {
+    const pt_radiance_params params = radianceParams(radiance_options, "Scene::capture");
+    const pt_capture_desc desc = captureDesc(capture, "Scene::capture");
+    std::vector<pt_radiance_result> raw(static_cast<size_t>(capture.width) * static_cast<size_t>(capture.height));
+    pathtrace_host::check(pt_radiance_capture(device_scene, &desc, &params, raw.data()), "Scene::capture");
+    Image<Color<float>> image(capture.width, capture.height);
+    for(size_t i = 0; i < raw.size(); i++) {
+        image.data()[i] = Color<float>{raw[i].value[0], raw[i].value[1], raw[i].value[2], raw[i].value[3]};
+    }
+    return image;
 }
 
 std::vector<std::tuple<vec3<float>, Spectrum, float>> Scene::sampleLights(vec3<float> pos, vec3<float> /*n*/, RandomEngine &re) const noexcept {
