@@ -87,6 +87,11 @@ LIGHT_PROBE_EXPORTS = ["pt_light_probe_params_default", "pt_light_probes_points"
 # radiance along free rays and captures (include/pt_radiance.h): per-ray means, and images made by four camera models on the device
 RADIANCE_EXPORTS = ["pt_radiance_params_default", "pt_radiance_rays", "pt_radiance_rays_device", "pt_radiance_capture", "pt_radiance_capture_device"]
 CAPTURE_EQUIRECT, CAPTURE_CUBE, CAPTURE_FISHEYE, CAPTURE_ORTHO = 0, 1, 2, 3
+# light-group passes (include/pt_light_passes.h): the same samples split by emitter group and bounce depth, and the mix of such passes
+LIGHT_PASSES_EXPORTS = ["pt_light_passes_count", "pt_light_passes_rays", "pt_light_passes_rays_device", "pt_light_passes_capture", "pt_light_passes_capture_device",
+                        "pt_light_passes_mix", "pt_light_passes_mix_device"]
+LIGHT_GROUPS_MAX = 8
+PASS_EMITTED, PASS_DIRECT, PASS_INDIRECT = 0, 1, 2
 # checkpoints of a frame (include/pt_checkpoint.h, which pt_hip.h includes as it includes pt_frame_noise.h)
 CHECKPOINT_EXPORTS = ["pt_checkpoint_inspect", "pt_frame_checkpoint_size", "pt_frame_checkpoint_save", "pt_frame_checkpoint_load"]
 CHECKPOINT_HEADER_BYTES = 352
@@ -120,6 +125,23 @@ class CaptureDesc(C.Structure):
     """pt_capture_desc"""
     _fields_ = [("model", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("jitter", C.c_int32), ("origin", C.c_float * 3), ("right", C.c_float * 3), ("up", C.c_float * 3),
                 ("forward", C.c_float * 3), ("fov", C.c_float), ("extent", C.c_float * 2), ("pad", C.c_uint32)]
+
+
+# pt_light_pass: 16 bytes; value: the rgb of one pass
+LightPass = np.dtype([("value", "<f4", 3), ("pad", "<u4")])
+
+
+class LightGroups(C.Structure):
+    """pt_light_groups (light_groups makes one and keeps its tables alive)"""
+    _fields_ = [("n_groups", C.c_uint32), ("split", C.c_int32), ("material_group", C.c_void_p), ("n_materials", C.c_uint32), ("point_light_group", C.c_void_p),
+                ("n_point_lights", C.c_uint32)]
+
+    @property
+    def n_passes(self):
+        """P = n_groups * (split ? 3 : 1), by pt_light_passes_count"""
+        n = C.c_uint32(0)
+        _check(load().pt_light_passes_count(C.byref(self), C.byref(n)))
+        return int(n.value)
 
 
 class GatherParams(C.Structure):
@@ -820,6 +842,32 @@ def capture_desc(model, width, height, origin, look_at, up, fov=np.pi, extent=(1
                        float(f32(fov)), (C.c_float * 2)(*extent), 0)
 
 
+def light_groups(n_groups, material_group, point_light_group, split=False):
+    """A pt_light_groups: the group (0 .. n_groups - 1) of every material of the scene's table and of every point light; split: three
+    passes per group (emitted, direct, indirect) instead of one."""
+    materials = np.ascontiguousarray(np.asarray(material_group, np.uint8).reshape(-1))
+    lights = np.ascontiguousarray(np.asarray(point_light_group, np.uint8).reshape(-1))
+    g = LightGroups(int(n_groups), int(split), materials.ctypes.data if len(materials) else None, len(materials), lights.ctypes.data if len(lights) else None, len(lights))
+    g._tables = (materials, lights)  # (the struct points into them)
+    return g
+
+
+def mix_light_passes(passes, gains, total=None):
+    """pt_light_passes_mix, on the host: passes (..., P) records of dtype LightPass, gains (P, 3), total (...) records of dtype
+    RadianceResult or None -> (..., 4) float32: the passes weighed by the gains and added in order; alpha from total, or 0."""
+    passes = np.ascontiguousarray(passes, LightPass)
+    shape, n_passes = passes.shape[:-1], passes.shape[-1]
+    gains = np.ascontiguousarray(np.asarray(gains, np.float32).reshape(n_passes, 3))
+    n = int(np.prod(shape, dtype=np.int64))
+    if total is not None:
+        total = np.ascontiguousarray(total, RadianceResult)
+        if total.shape != shape:
+            raise ValueError("total must have one record per ray or pixel")
+    out = np.zeros(shape + (4,), np.float32)
+    _check(load().pt_light_passes_mix(_ptr(passes), C.c_size_t(n), C.c_uint32(n_passes), _ptr(gains), _ptr(total), _ptr(out)))
+    return out
+
+
 def _gather_points(points, normals):
     """(n, 6) float32: position, normal"""
     points = np.asarray(points, np.float32).reshape(-1, 3)
@@ -1269,6 +1317,44 @@ class Scene:
         """pt_radiance_capture_device: height * width records (32 bytes each) in device memory, ordered on stream_ptr."""
         rp = radiance_params(samples, epsilon, base_seed)
         _check(load().pt_radiance_capture_device(self._h, C.byref(desc), C.byref(rp), C.c_void_p(d_out_ptr), C.c_void_p(stream_ptr)))
+
+    def light_passes(self, rays, groups, samples=64, epsilon=1e-3, base_seed=0, want_total=True):
+        """pt_light_passes_rays: radiance()'s samples split by emitter group and bounce depth (groups: light_groups makes one):
+        (passes (n, P) records of dtype LightPass, total (n,) records of dtype RadianceResult -- radiance()'s own, bit for bit -- or None)."""
+        rays = np.ascontiguousarray(np.asarray(rays, np.float32).reshape(-1, 6))
+        passes = np.zeros((len(rays), groups.n_passes), LightPass)
+        total = np.zeros(len(rays), RadianceResult) if want_total else None
+        rp = radiance_params(samples, epsilon, base_seed)
+        _check(load().pt_light_passes_rays(self._h, _ptr(rays), C.c_size_t(len(rays)), C.byref(groups), C.byref(rp), _ptr(passes), _ptr(total)))
+        return passes, total
+
+    def light_passes_device(self, d_rays_ptr, n, groups, d_passes_ptr, d_total_ptr=0, samples=64, epsilon=1e-3, base_seed=0, stream_ptr=0):
+        """pt_light_passes_rays_device: n rays, n * P pass records (16 bytes each) and, unless d_total_ptr is 0, n records (32 bytes each)
+        in device memory, ordered on stream_ptr."""
+        rp = radiance_params(samples, epsilon, base_seed)
+        _check(load().pt_light_passes_rays_device(self._h, C.c_void_p(d_rays_ptr), C.c_size_t(n), C.byref(groups), C.byref(rp), C.c_void_p(d_passes_ptr), C.c_void_p(d_total_ptr),
+                                                  C.c_void_p(stream_ptr)))
+
+    def capture_light_passes(self, desc, groups, samples=64, epsilon=1e-3, base_seed=0, want_total=True):
+        """pt_light_passes_capture: capture()'s samples split the same way: (passes (height, width, P), total (height, width) or None)."""
+        shape = (max(int(desc.height), 0), max(int(desc.width), 0))
+        passes = np.zeros(shape + (groups.n_passes,), LightPass)
+        total = np.zeros(shape, RadianceResult) if want_total else None
+        rp = radiance_params(samples, epsilon, base_seed)
+        _check(load().pt_light_passes_capture(self._h, C.byref(desc), C.byref(groups), C.byref(rp), _ptr(passes), _ptr(total)))
+        return passes, total
+
+    def capture_light_passes_device(self, desc, groups, d_passes_ptr, d_total_ptr=0, samples=64, epsilon=1e-3, base_seed=0, stream_ptr=0):
+        """pt_light_passes_capture_device: height * width * P pass records and, unless d_total_ptr is 0, height * width records in device
+        memory, ordered on stream_ptr."""
+        rp = radiance_params(samples, epsilon, base_seed)
+        _check(load().pt_light_passes_capture_device(self._h, C.byref(desc), C.byref(groups), C.byref(rp), C.c_void_p(d_passes_ptr), C.c_void_p(d_total_ptr), C.c_void_p(stream_ptr)))
+
+    def mix_light_passes_device(self, d_passes_ptr, n, n_passes, d_gains_ptr, d_out_ptr, d_total_ptr=0, stream_ptr=0):
+        """pt_light_passes_mix_device: n * n_passes pass records, n_passes * 3 gains, n * 4 floats out and, unless d_total_ptr is 0, n
+        records in device memory, one thread per ray or pixel on this scene's device, ordered on stream_ptr."""
+        _check(load().pt_light_passes_mix_device(self._h, C.c_void_p(d_passes_ptr), C.c_size_t(n), C.c_uint32(n_passes), C.c_void_p(d_gains_ptr), C.c_void_p(d_total_ptr),
+                                                 C.c_void_p(d_out_ptr), C.c_void_p(stream_ptr)))
 
     def process_item(self, camera, options, streams, image=None, want_stats=False):
         """processItem for many WorkItems at once; streams: array of STREAM_DTYPE (rect + raw engine state)."""

@@ -634,6 +634,16 @@ int motion_instances(pt_scene *s, const float *previous, uint32_t *n_out);
 // Enqueues pt_motion_kernel on the scene's stream (render_mutex held) with the table motion_instances left
 int motion_launch(pt_scene *s, const pt_camera_params *camera, const pt_options *options, uint32_t n_instances, float4 *d_features, float4 *d_motion);
 
+// ---- pt_radiance.cpp -------------------------------------------------------------------------------------------------------------------
+
+// The refusals of include/pt_radiance.h, made without a device, for pt_light_passes.cpp as well: `out` is the array the call fills
+// (needed where n > 0); *n_out = the capture's pixels
+int radiance_check_params(const pt_radiance_params *p, uint64_t n);
+int radiance_check_rays(pt_scene *s, const float *rays, size_t n, const pt_radiance_params *params, const void *out);
+int radiance_check_capture(pt_scene *s, const pt_capture_desc *c, const pt_radiance_params *params, const void *out, uint64_t *n_out);
+// A capture as the kernels take it (null: a 1 x 1 capture that no kernel reads)
+PtCaptureParams radiance_device_capture(const pt_capture_desc *c);
+
 // ---- pt_image.cpp ----------------------------------------------------------------------------------------------------------------------
 
 // Enqueues the feature pass for the stacked frames of n_views cameras on the scene's stream (render_mutex held), in one launch: into

@@ -333,6 +333,16 @@ struct PtCaptureParams {
 // each.  n * samples <= 0x7fffffff; cfg.spill holds one walk per pair of the chunk.
 void pt_launch_radiance(hipStream_t stream, const PtDevScene &scene, const float *rays, const PtCaptureParams &capture, uint32_t first, uint32_t n, uint32_t samples, float epsilon,
                         uint64_t base_seed, float4 *plane, float4 *out, const PtPathConfig &cfg);
+// Light-group passes (pt_light_pass_kernels.h; include/pt_light_passes.h).  The samples of pt_launch_radiance's rays or
+// pixels into plane[n * samples] as there and into the pass accumulators passes[n_passes * n * samples] (pass-major), then the 16-byte pass
+// records out_passes[(first + i) * n_passes + p] by a reduction of one wavefront each and, with out_total, the 32-byte records
+// out_total[2 * (first + i) ..] by pt_launch_radiance's own reduction.  groups: the group of every material, then of every point light
+// (scene.n_materials + scene.n_lights bytes); n_passes = groups * (split ? 3 : 1) <= 24; n * samples * n_passes <= 0x7fffffff.
+void pt_launch_light_passes(hipStream_t stream, const PtDevScene &scene, const float *rays, const PtCaptureParams &capture, uint32_t first, uint32_t n, uint32_t samples, float epsilon,
+                            uint64_t base_seed, const uint8_t *groups, uint32_t n_passes, uint32_t split, float4 *plane, float4 *passes, float4 *out_passes, float4 *out_total,
+                            const PtPathConfig &cfg);
+// out[i] = the mix of passes[i * n_passes ..] under gains[n_passes][3], one thread each; alpha = total[2 * i].w, or 0 without total
+void pt_launch_light_pass_mix(hipStream_t stream, const float4 *passes, size_t n, uint32_t n_passes, const float *gains, const float4 *total, float4 *out);
 // diagnostic (tools/step_timing.py): stamped walks, `lanes_per_wave` rays per wavefront; out[ray] = (steps, cycles waiting for records, cycles in all, price of a stamp pair)
 void pt_launch_steptime(hipStream_t stream, const PtDevScene &scene, const float *rays6, uint32_t n, uint32_t lanes_per_wave, uint4 *out, uint2 *spill, uint32_t spill_depth, int flags);
 

@@ -51,7 +51,12 @@ int settle(RadianceWorkspace &ws) {
     return PT_OK;
 }
 
-int check_params(const pt_radiance_params *p, uint64_t n) {
+} // namespace
+
+// The argument checks and the capture as the kernels take it, shared with pt_light_passes.cpp (declared in pt_host.h)
+namespace pth {
+
+int radiance_check_params(const pt_radiance_params *p, uint64_t n) {
     if(p->samples < 1) {
         return fail(PT_ERR_INVALID, "samples must be at least 1");
     }
@@ -64,15 +69,15 @@ int check_params(const pt_radiance_params *p, uint64_t n) {
     return PT_OK;
 }
 
-int check_rays(pt_scene *s, const float *rays, size_t n, const pt_radiance_params *params, const pt_radiance_result *out) {
+int radiance_check_rays(pt_scene *s, const float *rays, size_t n, const pt_radiance_params *params, const void *out) {
     if(s == nullptr || params == nullptr || (n > 0 && (rays == nullptr || out == nullptr))) {
         return fail(PT_ERR_INVALID, "null argument");
     }
-    return check_params(params, n);
+    return radiance_check_params(params, n);
 }
 
 // *n_out = the capture's pixels
-int check_capture(pt_scene *s, const pt_capture_desc *c, const pt_radiance_params *params, const pt_radiance_result *out, uint64_t *n_out) {
+int radiance_check_capture(pt_scene *s, const pt_capture_desc *c, const pt_radiance_params *params, const void *out, uint64_t *n_out) {
     if(s == nullptr || c == nullptr || params == nullptr || out == nullptr) {
         return fail(PT_ERR_INVALID, "null argument");
     }
@@ -110,10 +115,10 @@ int check_capture(pt_scene *s, const pt_capture_desc *c, const pt_radiance_param
         }
     }
     *n_out = static_cast<uint64_t>(c->width) * static_cast<uint64_t>(c->height);
-    return check_params(params, *n_out);
+    return radiance_check_params(params, *n_out);
 }
 
-PtCaptureParams device_capture(const pt_capture_desc *c) {
+PtCaptureParams radiance_device_capture(const pt_capture_desc *c) {
     PtCaptureParams out{};
     if(c == nullptr) {
         out.width = out.height = 1;
@@ -134,6 +139,10 @@ PtCaptureParams device_capture(const pt_capture_desc *c) {
     out.extent[1] = c->extent[1];
     return out;
 }
+
+} // namespace pth
+
+namespace {
 
 // Rays or pixels per launch: whole ones, PT_RADIANCE_CHUNK pairs at the most, one where one alone has more
 size_t chunk_items(const pt_radiance_params *p) {
@@ -203,7 +212,7 @@ int run(pt_scene *s, const float *rays, const float *d_rays, const pt_capture_de
     const size_t step = chunk_items(params);
     PtPathConfig cfg;
     PT_TRY(prepare(s, ws, n, step, params, &cfg));
-    const PtCaptureParams cap = device_capture(capture);
+    const PtCaptureParams cap = radiance_device_capture(capture);
     if(d_out != nullptr) {
         return run_device(s, ws, stream, [&] { enqueue(s, ws, cfg, params, step, d_rays, cap, n, d_out); });
     }
@@ -230,7 +239,7 @@ int pt_radiance_params_default(pt_radiance_params *out) {
 }
 
 int pt_radiance_rays(pt_scene *s, const float *rays, size_t n, const pt_radiance_params *params, pt_radiance_result *out) {
-    PT_TRY(check_rays(s, rays, n, params, out));
+    PT_TRY(radiance_check_rays(s, rays, n, params, out));
     if(n == 0) {
         return PT_OK;
     }
@@ -238,7 +247,7 @@ int pt_radiance_rays(pt_scene *s, const float *rays, size_t n, const pt_radiance
 }
 
 int pt_radiance_rays_device(pt_scene *s, const float *d_rays, size_t n, const pt_radiance_params *params, pt_radiance_result *d_out, void *stream) {
-    PT_TRY(check_rays(s, d_rays, n, params, d_out));
+    PT_TRY(radiance_check_rays(s, d_rays, n, params, d_out));
     if(n == 0) {
         return PT_OK;
     }
@@ -247,13 +256,13 @@ int pt_radiance_rays_device(pt_scene *s, const float *d_rays, size_t n, const pt
 
 int pt_radiance_capture(pt_scene *s, const pt_capture_desc *capture, const pt_radiance_params *params, pt_radiance_result *out) {
     uint64_t n = 0;
-    PT_TRY(check_capture(s, capture, params, out, &n));
+    PT_TRY(radiance_check_capture(s, capture, params, out, &n));
     return run(s, nullptr, nullptr, capture, static_cast<size_t>(n), params, out, nullptr, nullptr);
 }
 
 int pt_radiance_capture_device(pt_scene *s, const pt_capture_desc *capture, const pt_radiance_params *params, pt_radiance_result *d_out, void *stream) {
     uint64_t n = 0;
-    PT_TRY(check_capture(s, capture, params, d_out, &n));
+    PT_TRY(radiance_check_capture(s, capture, params, d_out, &n));
     return run(s, nullptr, nullptr, capture, static_cast<size_t>(n), params, nullptr, d_out, stream);
 }
 

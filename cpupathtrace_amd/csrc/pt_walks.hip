@@ -1,6 +1,6 @@
 // pt_walks.hip -- the kernels that trace ONE walk per lane to its end with the path kernel's traversal machinery (pt_trace.h): closest hits
 // of a ray batch (pt_closest_kernel), the denoiser's first-hit and followed features (pt_feature_kernel, pt_follow_kernel), the first-hit features with motion (pt_motion_kernel; pt_motion_shapes_kernel for deformed meshes), the scene
-// queries (pt_query_kernels.h: pt_query_kernel, pt_query_pixels_kernel, pt_occluded_kernel), the light gathered at points (pt_gather_kernels.h), the light probes (pt_light_probe_kernels.h), radiance along free rays and captures (pt_radiance_kernels.h) and two
+// queries (pt_query_kernels.h: pt_query_kernel, pt_query_pixels_kernel, pt_occluded_kernel), the light gathered at points (pt_gather_kernels.h), the light probes (pt_light_probe_kernels.h), radiance along free rays and captures (pt_radiance_kernels.h), light-group passes (pt_light_pass_kernels.h) and two
 // diagnostics (pt_steptime_kernel, pt_replay_kernel).  They live apart from pt_path.hip so that an edit here neither recompiles nor
 // re-schedules the path kernel.  Written once: the dispatch over the three (stack window, records) routes, the LDS size, and the prologue
 // that binds a lane's Tracer (bind_lane) where it leaves a kernel's instructions as they were: the closest-hit and the step-timing kernel.
@@ -819,6 +819,7 @@ void dispatch_route(const PtPathConfig &cfg, const PtDevScene &scene, Launch lau
 #include "pt_gather_kernels.h" // pt_gather_kernel, its reduce and the two kernels that make points, with their launches (behind the same two)
 #include "pt_light_probe_kernels.h" // the light probes: sampling, projection and lookup kernels with their launches (behind pt_gather_kernels.h)
 #include "pt_radiance_kernels.h" // radiance along free rays and captures: the sampling kernel and its reduction with their launch (behind pt_light_probe_kernels.h)
+#include "pt_light_pass_kernels.h" // light-group passes: the sampling kernel with an accumulator per pass, its reduction and the mix (behind pt_radiance_kernels.h)
 
 void pt_launch_closest(hipStream_t stream, const PtDevScene &scene, const float *rays6, uint32_t n, uint2 *out, const PtPathConfig &cfg) {
     if(n == 0) {

@@ -290,6 +290,8 @@ struct LightProbeGrid;
 struct RadianceOptions; // PathTrace/radiance.h
 struct RadianceResult;
 struct Capture;
+struct LightGroups; // PathTrace/light_passes.h
+struct LightPasses;
 template<typename T>
 class Image; // PathTrace/image/image.h
 
@@ -420,6 +422,14 @@ class Scene {
     // an origin or basis that is not finite), std::runtime_error when the device refuses.  Non-virtual.
     std::vector<RadianceResult> radiance(const std::vector<Ray> &rays, const RadianceOptions &radiance_options) const;
     Image<Color<float>> capture(const Capture &capture, const RadianceOptions &radiance_options) const;
+
+    // Light-group passes (pt_light_passes_rays, pt_light_passes_capture, include/pt_light_passes.h; PathTrace/light_passes.h has the
+    // types and mixLightPasses).  The samples of radiance / capture, every term also added to the pass of its emitter group -- and, with
+    // groups.split, of its bounce depth --; with want_total the records of radiance / capture themselves, bit for bit.  They throw
+    // std::invalid_argument for what radiance / capture refuse and for a group count outside 1..8 or a table entry not below it,
+    // std::runtime_error when the device refuses -- as it does when the tables' lengths are not the scene's counts.  Non-virtual.
+    LightPasses lightPasses(const std::vector<Ray> &rays, const LightGroups &groups, const RadianceOptions &radiance_options, bool want_total = true) const;
+    LightPasses captureLightPasses(const Capture &capture, const LightGroups &groups, const RadianceOptions &radiance_options, bool want_total = true) const;
 
     // the device scene behind the C ABI (include/pt_hip.h); used by processJob / processItem
     pt_scene *deviceScene() const noexcept { return device_scene; }

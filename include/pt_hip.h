@@ -496,7 +496,9 @@ int pt_temporal_destroy(pt_temporal *t);
 #include "pt_gather.h"
 
 /* Radiance along rays the caller chooses, and captures -- images of such rays made on the device by an equirectangular, cube-map, fisheye
- * or orthographic camera model (pt_radiance_rays, pt_radiance_capture): declared, with their contracts, in: */
+ * or orthographic camera model (pt_radiance_rays, pt_radiance_capture): declared, with their contracts, in the file below.
+ * Its last line includes pt_light_passes.h: the same samples split into passes by emitter group and bounce depth, and the mix of such
+ * passes (pt_light_passes_rays, pt_light_passes_capture, pt_light_passes_mix). */
 #include "pt_radiance.h"
 
 /* Light probes -- the radiance that arrives at free points projected onto spherical harmonics, grids of such probes and the lookup that

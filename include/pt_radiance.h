@@ -88,4 +88,8 @@ int pt_radiance_capture_device(pt_scene *scene, const pt_capture_desc *capture, 
 }
 #endif
 
+/* The same samples split by emitter group and bounce depth, and the mix of such passes (pt_light_passes_rays, pt_light_passes_capture,
+ * pt_light_passes_mix): they take this file's parameters, capture and record, and are declared, with their contracts, in: */
+#include "pt_light_passes.h"
+
 #endif

@@ -1,6 +1,7 @@
 // src/host/scene.cpp -- Scene: flattens the caller's object graph into the arrays of include/pt_hip.h and owns the device scene.
 #include <PathTrace/detail/world.h>
 #include <PathTrace/gather.h>
+#include <PathTrace/light_passes.h>
 #include <PathTrace/light_probes.h>
 #include <PathTrace/query.h>
 #include <PathTrace/radiance.h>
@@ -1100,6 +1101,110 @@ Image<Color<float>> Scene::capture(const Capture &capture, const RadianceOptions
         image.data()[i] = Color<float>{raw[i].value[0], raw[i].value[1], raw[i].value[2], raw[i].value[3]};
     }
     return image;
+}
+
+namespace {
+
+    // The groups of the C ABI (pointing into `g`); what it would refuse without a scene is refused here, as an argument error
+    pt_light_groups lightGroups(const LightGroups &g, const char *what) {
+        bool ok = g.n_groups >= 1 && g.n_groups <= PT_LIGHT_GROUPS_MAX;
+        for(const uint8_t group : g.material_group) {
+            ok = ok && group < g.n_groups;
+        }
+        for(const uint8_t group : g.point_light_group) {
+            ok = ok && group < g.n_groups;
+        }
+        if(!ok) {
+            throw std::invalid_argument(std::string("PathTrace: ") + what + ": light groups need 1..8 groups and every table entry below that count");
+        }
+        pt_light_groups out{};
+        out.n_groups = g.n_groups;
+        out.split = g.split ? 1 : 0;
+        out.material_group = g.material_group.empty() ? nullptr : g.material_group.data();
+        out.n_materials = static_cast<uint32_t>(g.material_group.size());
+        out.point_light_group = g.point_light_group.empty() ? nullptr : g.point_light_group.data();
+        out.n_point_lights = static_cast<uint32_t>(g.point_light_group.size());
+        return out;
+    }
+
+    LightPasses lightPassesOut(size_t n, size_t n_passes, const std::vector<pt_light_pass> &raw, const std::vector<pt_radiance_result> &total) {
+        LightPasses out;
+        out.n_passes = n_passes;
+        out.value.resize(n * n_passes);
+        for(size_t i = 0; i < raw.size(); i++) {
+            out.value[i] = {raw[i].value[0], raw[i].value[1], raw[i].value[2]};
+        }
+        out.total.resize(total.size());
+        for(size_t i = 0; i < total.size(); i++) {
+            out.total[i].value = Color<float>{total[i].value[0], total[i].value[1], total[i].value[2], total[i].value[3]};
+            out.total[i].samples = total[i].samples;
+            out.total[i].missed = total[i].missed;
+            out.total[i].outside = total[i].outside;
+        }
+        return out;
+    }
+
+} // namespace
+
+LightPasses Scene::lightPasses(const std::vector<Ray> &rays, const LightGroups &groups, const RadianceOptions &radiance_options, bool want_total) const {
+    const pt_radiance_params params = radianceParams(radiance_options, "Scene::lightPasses");
+    const pt_light_groups table = lightGroups(groups, "Scene::lightPasses");
+    std::vector<float> packed(6 * rays.size());
+    for(size_t i = 0; i < rays.size(); i++) {
+        for(size_t k = 0; k < 3; k++) {
+            packed[6 * i + k] = rays[i].origin[k];
+            packed[6 * i + 3 + k] = rays[i].dir[k];
+        }
+    }
+    std::vector<pt_light_pass> raw(rays.size() * groups.passes());
+    std::vector<pt_radiance_result> total(want_total ? rays.size() : 0);
+    pathtrace_host::check(pt_light_passes_rays(device_scene, packed.data(), rays.size(), &table, &params, raw.data(), want_total ? total.data() : nullptr), "Scene::lightPasses");
+    return lightPassesOut(rays.size(), groups.passes(), raw, total);
+}
+
+LightPasses Scene::captureLightPasses(const Capture &capture, const LightGroups &groups, const RadianceOptions &radiance_options, bool want_total) const {
+    const pt_radiance_params params = radianceParams(radiance_options, "Scene::captureLightPasses");
+    const pt_capture_desc desc = captureDesc(capture, "Scene::captureLightPasses");
+    const pt_light_groups table = lightGroups(groups, "Scene::captureLightPasses");
+    const size_t n = static_cast<size_t>(capture.width) * static_cast<size_t>(capture.height);
+    std::vector<pt_light_pass> raw(n * groups.passes());
+    std::vector<pt_radiance_result> total(want_total ? n : 0);
+    pathtrace_host::check(pt_light_passes_capture(device_scene, &desc, &table, &params, raw.data(), want_total ? total.data() : nullptr), "Scene::captureLightPasses");
+    LightPasses out = lightPassesOut(n, groups.passes(), raw, total);
+    out.width = capture.width;
+    out.height = capture.height;
+    return out;
+}
+
+std::vector<Color<float>> mixLightPasses(const LightPasses &passes, const std::vector<std::array<float, 3>> &gains) {
+    const size_t n = passes.size();
+    if(passes.n_passes < 1 || passes.n_passes > 3 * PT_LIGHT_GROUPS_MAX || gains.size() != passes.n_passes || passes.value.size() != n * passes.n_passes ||
+       (!passes.total.empty() && passes.total.size() != n)) {
+        throw std::invalid_argument("PathTrace: mixLightPasses: 1..24 passes, one gain per pass, and a total per ray or pixel or none");
+    }
+    std::vector<pt_light_pass> raw(passes.value.size());
+    for(size_t i = 0; i < raw.size(); i++) {
+        raw[i] = pt_light_pass{{passes.value[i][0], passes.value[i][1], passes.value[i][2]}, 0};
+    }
+    std::vector<pt_radiance_result> total(passes.total.size());
+    for(size_t i = 0; i < total.size(); i++) {
+        total[i] = pt_radiance_result{};
+        total[i].value[3] = passes.total[i].value[3];
+    }
+    std::vector<float> flat_gains(3 * gains.size());
+    for(size_t p = 0; p < gains.size(); p++) {
+        for(size_t c = 0; c < 3; c++) {
+            flat_gains[3 * p + c] = gains[p][c];
+        }
+    }
+    std::vector<float> mixed(4 * n);
+    pathtrace_host::check(pt_light_passes_mix(raw.data(), n, static_cast<uint32_t>(passes.n_passes), flat_gains.data(), total.empty() ? nullptr : total.data(), mixed.data()),
+                          "mixLightPasses");
+    std::vector<Color<float>> out(n);
+    for(size_t i = 0; i < n; i++) {
+        out[i] = Color<float>{mixed[4 * i], mixed[4 * i + 1], mixed[4 * i + 2], mixed[4 * i + 3]};
+    }
+    return out;
 }
 
 std::vector<std::tuple<vec3<float>, Spectrum, float>> Scene::sampleLights(vec3<float> pos, vec3<float> /*n*/, RandomEngine &re) const noexcept {
