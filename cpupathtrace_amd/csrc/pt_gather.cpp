@@ -3,7 +3,7 @@
 // workspace on the scene (grown on demand, freed with it) and cuts a call into launches of whole points: at most PT_GATHER_CHUNK (point,
 // sample) pairs each, read per call.  A sample's engine is seeded with its point's index in the call, so the cut changes no bit.
 // Nothing here changes the scene, so every call is allowed with a live pt_frame and with or without a motion mark.
-#include "pt_host.h"
+#include "pt_sample_host.h"
 
 #include <limits>
 
@@ -12,7 +12,6 @@ using namespace pth;
 namespace {
 
 const uint64_t GATHER_MAX = 0x7fffffffULL;
-const int GATHER_CHUNK_DEFAULT = 4 << 20;
 
 int check_params(const pt_gather_params *p, uint64_t n) {
     if(p->kind != PT_GATHER_OCCLUSION && p->kind != PT_GATHER_DIRECT && p->kind != PT_GATHER_PATHS) {
@@ -51,61 +50,34 @@ int check_frame(pt_scene *s, const pt_camera_params *camera, const pt_options *o
     return check_params(params, static_cast<uint64_t>(options->image_width) * static_cast<uint64_t>(options->image_height));
 }
 
-// Points per launch: whole points, PT_GATHER_CHUNK pairs at the most, one point where a point alone has more
+// Points per launch (PT_GATHER_CHUNK)
 size_t chunk_points(const pt_gather_params *p) {
-    const int pairs = std::max(env_int("PT_GATHER_CHUNK", GATHER_CHUNK_DEFAULT), 1);
-    return std::max<size_t>(static_cast<size_t>(pairs) / static_cast<size_t>(p->samples), 1);
+    return chunk_items("PT_GATHER_CHUNK", GATHER_CHUNK_DEFAULT, p->samples, 1);
 }
 
 // The launch configuration and the workspace of a call of n points (render_mutex held, the device set); `walks`: walks of a launch
-// that makes the points, which shares the spill area
+// that makes the points, which shares the spill area.  The buffers live on the scene and are ordered by its stream.
 int prepare(pt_scene *s, size_t n, const pt_gather_params *p, size_t walks, PtPathConfig *cfg) {
-    PT_TRY(setup_path(s));
-    *cfg = s->path_cfg;
     const size_t pairs = std::min(n, chunk_points(p)) * static_cast<size_t>(p->samples);
-    PT_HIP(s->gather_spill.ensure(((std::max(pairs, walks) + 255) / 256) * 256 * cfg->spill_depth));
-    cfg->spill = s->gather_spill.ptr;
-    if(p->kind == PT_GATHER_OCCLUSION) {
+    const bool bits = p->kind == PT_GATHER_OCCLUSION;
+    PT_TRY(size_launch(s, s->gather_spill, std::max(pairs, walks), bits ? nullptr : &s->gather_plane, pairs, cfg));
+    if(bits) {
         PT_HIP(s->gather_bits.ensure((pairs + 63) / 64));
-    }
-    else {
-        PT_HIP(s->gather_plane.ensure(pairs));
     }
     return PT_OK;
 }
 
-// Enqueues the launches of n points on the scene's stream
-void enqueue(pt_scene *s, const PtPathConfig &cfg, const pt_gather_params *p, const float *d_points, const uint8_t *d_miss, size_t n, pt_gather_result *d_out) {
+// Enqueues the launches of n points on the scene's stream and, host form (out != null), the n records' way to `out`
+int enqueue(pt_scene *s, const PtPathConfig &cfg, const pt_gather_params *p, const float *d_points, const uint8_t *d_miss, size_t n, pt_gather_result *d_out,
+            pt_gather_result *out = nullptr) {
     const size_t step = chunk_points(p);
     for(size_t first = 0; first < n; first += step) {
         pt_launch_gather(s->stream, s->dev, p->kind, d_points, d_miss, static_cast<uint32_t>(first), static_cast<uint32_t>(std::min(step, n - first)),
                          static_cast<uint32_t>(p->samples), p->epsilon, p->distance, p->base_seed, reinterpret_cast<float4 *>(s->gather_plane.ptr), s->gather_bits.ptr,
                          reinterpret_cast<float4 *>(d_out), cfg);
     }
-}
-
-// Host form: what `enqueue_all` puts on the scene's stream, then the n records into `out`.  Device form: the same between the two halves
-// of a StreamOrder (pt_query.cpp's arrangement).
-template<typename Enqueue>
-int run_host(pt_scene *s, pt_gather_result *out, size_t n, Enqueue enqueue_all) {
-    StreamDrain drain{s->stream};
-    enqueue_all();
-    PT_HIP(hipGetLastError());
-    PT_HIP(hipMemcpyAsync(out, s->gather_out.ptr, n * sizeof(pt_gather_result), hipMemcpyDeviceToHost, s->stream));
-    drain.armed = false;
-    PT_HIP(hipStreamSynchronize(s->stream));
-    return PT_OK;
-}
-
-template<typename Enqueue>
-int run_device(pt_scene *s, void *stream, Enqueue enqueue_all) {
-    StreamOrder order;
-    PT_TRY(order.begin(stream, s->stream));
-    enqueue_all();
-    PT_HIP(hipGetLastError());
-    PT_TRY(order.end());
-    if(order.caller == nullptr) {
-        PT_HIP(hipStreamSynchronize(s->stream));
+    if(out != nullptr) {
+        PT_HIP(hipMemcpyAsync(out, d_out, n * sizeof(pt_gather_result), hipMemcpyDeviceToHost, s->stream));
     }
     return PT_OK;
 }
@@ -143,8 +115,10 @@ int pt_gather_points(pt_scene *s, const float *points, size_t n, const pt_gather
     PT_TRY(prepare(s, n, params, 0, &cfg));
     PT_HIP(s->gather_points.ensure(6 * n));
     PT_HIP(s->gather_out.ensure(n));
-    PT_HIP(hipMemcpyAsync(s->gather_points.ptr, points, 6 * n * sizeof(float), hipMemcpyHostToDevice, s->stream));
-    return run_host(s, out, n, [&] { enqueue(s, cfg, params, s->gather_points.ptr, nullptr, n, s->gather_out.ptr); });
+    return run_host(s, [&]() -> int {
+        PT_HIP(hipMemcpyAsync(s->gather_points.ptr, points, 6 * n * sizeof(float), hipMemcpyHostToDevice, s->stream));
+        return enqueue(s, cfg, params, s->gather_points.ptr, nullptr, n, s->gather_out.ptr, out);
+    });
 }
 
 int pt_gather_points_device(pt_scene *s, const float *d_points, size_t n, const pt_gather_params *params, pt_gather_result *d_out, void *stream) {
@@ -156,7 +130,7 @@ int pt_gather_points_device(pt_scene *s, const float *d_points, size_t n, const 
     PT_HIP(hipSetDevice(s->device));
     PtPathConfig cfg;
     PT_TRY(prepare(s, n, params, 0, &cfg));
-    return run_device(s, stream, [&] { enqueue(s, cfg, params, d_points, nullptr, n, d_out); });
+    return run_device(s, nullptr, stream, [&]() -> int { return enqueue(s, cfg, params, d_points, nullptr, n, d_out); });
 }
 
 int pt_gather_frame(pt_scene *s, const pt_camera_params *camera, const pt_options *options, const pt_gather_params *params, pt_gather_result *out) {
@@ -170,9 +144,9 @@ int pt_gather_frame(pt_scene *s, const pt_camera_params *camera, const pt_option
     PT_HIP(s->gather_miss.ensure(n));
     PT_HIP(s->gather_out.ensure(n));
     const PtDevCamera cam = pixel_camera(camera);
-    return run_host(s, out, n, [&] {
+    return run_host(s, [&]() -> int {
         pt_launch_gather_frame_points(s->stream, s->dev, cam, options->image_width, options->image_height, s->gather_points.ptr, s->gather_miss.ptr, cfg);
-        enqueue(s, cfg, params, s->gather_points.ptr, s->gather_miss.ptr, n, s->gather_out.ptr);
+        return enqueue(s, cfg, params, s->gather_points.ptr, s->gather_miss.ptr, n, s->gather_out.ptr, out);
     });
 }
 
@@ -186,9 +160,9 @@ int pt_gather_frame_device(pt_scene *s, const pt_camera_params *camera, const pt
     PT_HIP(s->gather_points.ensure(6 * n));
     PT_HIP(s->gather_miss.ensure(n));
     const PtDevCamera cam = pixel_camera(camera);
-    return run_device(s, stream, [&] {
+    return run_device(s, nullptr, stream, [&]() -> int {
         pt_launch_gather_frame_points(s->stream, s->dev, cam, options->image_width, options->image_height, s->gather_points.ptr, s->gather_miss.ptr, cfg);
-        enqueue(s, cfg, params, s->gather_points.ptr, s->gather_miss.ptr, n, d_out);
+        return enqueue(s, cfg, params, s->gather_points.ptr, s->gather_miss.ptr, n, d_out);
     });
 }
 
@@ -215,9 +189,9 @@ int pt_gather_instance(pt_scene *s, uint32_t instance, const pt_gather_params *p
     PT_HIP(s->gather_points.ensure(6 * n));
     PT_HIP(s->gather_out.ensure(n));
     const uint32_t first_tri = s->n_desc_tris + (s->inst_first[instance] - s->n_desc_objects); // (pt_scene_get_triangles' triangle of an instance's object)
-    return run_host(s, out, n, [&] {
+    return run_host(s, [&]() -> int {
         pt_launch_gather_corner_points(s->stream, s->tri_pos_kept.ptr, reinterpret_cast<const float4 *>(s->tri_shade.ptr), first_tri, n_tris, s->gather_points.ptr);
-        enqueue(s, cfg, params, s->gather_points.ptr, nullptr, n, s->gather_out.ptr);
+        return enqueue(s, cfg, params, s->gather_points.ptr, nullptr, n, s->gather_out.ptr, out);
     });
 }
 

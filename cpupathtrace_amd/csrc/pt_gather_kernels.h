@@ -1,16 +1,14 @@
 // pt_gather_kernels.h -- light gathered at surface points (include/pt_gather.h): the kernel that traces the samples of a
 // chunk of points, the ordered reduce that makes their records, and the two kernels that make points from a frame's first hits and from
-// an instance's triangle records.  Included by exactly one translation unit, pt_walks.hip, behind bind_lane and dispatch_route (and behind
-// pt_query_kernels.h, whose walk and record the frame's points are made with).
+// an instance's triangle records.  Included by exactly one translation unit, pt_walks.hip, behind bind_lane and dispatch_route, behind
+// pt_query_kernels.h, whose walk and record the frame's points are made with, and behind pt_sample_walk.h.
 //
 // One lane per (point, sample) pair, sample-fastest: lane g of a chunk that starts at point p0 is sample g % samples of point p0 +
 // g / samples, with the engine RandomEngine(pt_pixel_seed(base_seed, sample, point)) -- the POINT's index in the call, not in the chunk,
-// so a value does not depend on how the call is cut.  A lane runs its sample's walks one after another on its Tracer through ONE
-// tr.start / tr.step site (pt_follow_kernel's arrangement): a turn of the loop advances the lane's vertex -- light sample by light sample,
-// then the bounce -- until it has a ray to trace, and traces it; lanes on a shadow walk and lanes on a closest walk step together, the
-// destination word tells them apart.  The vertex is the path kernel's (pt_path.hip, worker.cpp:55-138), operation for operation: the
-// emission term and the two double-precision weights are formed as there, a light sample whose weight is +-0 in all three channels or
-// whose threshold is not positive needs no ray, and a shadow walk is Tracer::begin's with the threshold in the origin's w.
+// so a value does not depend on how the call is cut.  The direct light and the full paths are the shared loop's (sample_walk,
+// pt_sample_walk.h); what this kernel adds to it is the entry: a sample starts at a vertex that is already there, the point with its
+// normal and no material, and the direct kind never bounces.  It sets no flag and keeps no term apart, so its sink is the empty one.
+// The occlusion kind is not a path sample: one bsdf_propagate at the receiver and one shadow walk of its own.
 #ifndef PT_GATHER_KERNELS_H
 #define PT_GATHER_KERNELS_H
 
@@ -21,11 +19,6 @@
 namespace {
 
 using namespace ptd;
-
-// RandomEngine(seed), base.h:26
-PT_D uint64_t gather_engine(uint64_t seed) {
-    return seed ^ (~seed << 32);
-}
 
 // The samples of the points first .. first + n_pairs / samples - 1.  KIND 0 (PT_GATHER_OCCLUSION): bits[g / 64] bit g % 64 = sample g is
 // occluded (one 8-byte store per wavefront; the grid's last wavefront writes zeros for the lanes past n_pairs).  KIND 1, 2: plane[g] = the
@@ -59,12 +52,12 @@ __global__ __launch_bounds__(256) void pt_gather_kernel(PtDevScene sc, const flo
         pos = v3(pt[0], pt[1], pt[2]);
         n = v3(pt[3], pt[4], pt[5]);
     }
-    V3 rd = neg(n);
-    uint32_t material_index = 0xFFFFFFFFu; // PT_NO_MATERIAL: the receiver
 
     if constexpr(KIND == 0) {
         bool occluded = false;
         if(there) {
+            const V3 rd = neg(n);
+            const uint32_t material_index = 0xFFFFFFFFu; // PT_NO_MATERIAL: the receiver
             const Material mat = material_load(sc.materials, material_index);
             float ray_factor, ray_pd;
             const Ray next = bsdf_propagate(mat, rd, pos, n, epsilon, rng, ray_factor, ray_pd);
@@ -84,135 +77,8 @@ __global__ __launch_bounds__(256) void pt_gather_kernel(PtDevScene sc, const flo
         return;
     }
     else {
-        const uint32_t n_light_samples = sc.n_lights + sc.n_object_samples;
-        // getSample's state (worker.cpp:37-43) at a first vertex that is already there
-        float contribution_unweighted = 1.0f;
-        double divisor = 1.0, bounce_pd = 1.0;
-        C4 spectrum = c4(1.0f, 1.0f, 1.0f, 1.0f);
-        C4 out = c4(0.0f, 0.0f, 0.0f, 0.0f);
-        int path_length = 1;
-        // worker.cpp:64 adds 0 at the receiver; :67-70
-        float bounce_probability = 1.0f;
-        bool do_bounce = false;
-        if constexpr(KIND == 2) {
-            do_bounce = rng_uniform01(rng) < bounce_probability;
-        }
-        uint32_t j = 0;
-        bool alive = there;
-        C4 pending = c4(0.0f, 0.0f, 0.0f, 0.0f);
-        while(alive) {
-            // ---- advance the vertex until it has a ray to trace ---------------------------------------------------------------------------------
-            bool need = false;
-            float4 ro = make_float4(0.0f, 0.0f, 0.0f, 0.0f), rdv = ro;
-            while(alive && !need) {
-                if(j < n_light_samples) {
-                    // worker.cpp:76-103, light sample j
-                    V3 light_pos;
-                    C4 light_spectrum;
-                    float lpd;
-                    bool valid;
-                    if(j < sc.n_lights) {
-                        const float4 lp = sc.lights[2 * j];
-                        light_pos = v3(lp.x, lp.y, lp.z);
-                        light_spectrum = c4(sc.lights[2 * j + 1]);
-                        lpd = 1.0f;
-                        valid = true;
-                    }
-                    else {
-                        valid = sample_emissive(sc, EmisGlobal{sc}, pos, rng, light_pos, light_spectrum, lpd);
-                    }
-                    j += 1;
-                    if(valid) {
-                        const Material mat = material_load(sc.materials, material_index);
-                        const V3 to_light = light_pos - pos;
-                        const V3 light_dir = normalize(to_light);
-                        float shading_factor, shadow_ray_pd;
-                        const C4 base_spectrum = bsdf_spectrum(mat, rd, light_dir, n, light_spectrum, true, shading_factor, shadow_ray_pd);
-                        if(shadow_ray_pd > 0.0f) {
-                            const C4 combined = (base_spectrum * shading_factor) * spectrum;
-                            const C4 weighed = combined / (float)(divisor * bounce_pd * lpd * shadow_ray_pd);
-                            // adding +-0 never changes out_spectrum (which is never -0), so such a sample needs no ray
-                            if(!(weighed.r == 0.0f && weighed.g == 0.0f && weighed.b == 0.0f)) {
-                                const float threshold = len(to_light) - epsilon;
-                                if(threshold <= 0.0f) {
-                                    out = out + weighed; // light_t < 0 || light_t >= threshold holds for every light_t
-                                }
-                                else {
-                                    need = true;
-                                    pending = weighed;
-                                    const V3 o2 = pos + light_dir * epsilon;
-                                    ro = make_float4(o2.x, o2.y, o2.z, threshold);
-                                    rdv = make_float4(light_dir.x, light_dir.y, light_dir.z, __uint_as_float(PT_DEST_SHADOW));
-                                }
-                            }
-                        }
-                    }
-                }
-                else if(KIND == 1 || !do_bounce) {
-                    alive = false; // worker.cpp:106-109 (the direct light of one vertex ends here as well)
-                }
-                else {
-                    // worker.cpp:110-138
-                    bounce_pd *= bounce_probability;
-                    if(bounce_pd <= 1E-20) {
-                        alive = false;
-                    }
-                    else {
-                        const Material mat = material_load(sc.materials, material_index);
-                        float ray_factor, ray_pd;
-                        const Ray next_ray = bsdf_propagate(mat, rd, pos, n, epsilon, rng, ray_factor, ray_pd);
-                        divisor *= ray_pd;
-                        divisor /= ray_factor;
-                        contribution_unweighted *= ray_factor;
-                        float shading_factor, shading_pd;
-                        const C4 shaded = bsdf_spectrum(mat, rd, next_ray.d, n, spectrum, false, shading_factor, shading_pd);
-                        divisor *= shading_pd;
-                        divisor /= shading_factor;
-                        contribution_unweighted *= shading_factor;
-                        spectrum = shaded;
-                        if(divisor <= 1E-20) {
-                            alive = false;
-                        }
-                        else {
-                            need = true;
-                            ro = make_float4(next_ray.o.x, next_ray.o.y, next_ray.o.z, 0.0f);
-                            rdv = make_float4(next_ray.d.x, next_ray.d.y, next_ray.d.z, __uint_as_float(0u));
-                        }
-                    }
-                }
-            }
-            if(!alive) {
-                break;
-            }
-            // ---- the walk: a shadow ray's or the bounce's -----------------------------------------------------------------------------------------
-            Walk w;
-            typename Tracer<STACK_LDS, IN_LDS>::Rec rec;
-            rec.r0 = rec.r1 = rec.r2 = rec.r3 = (f4v){0.0f, 0.0f, 0.0f, 0.0f};
-            tr.start(w, rec, root, ro, rdv);
-            uint32_t n_nodes = 0, n_leaves = 0;
-            while(tr.step(w, rec, 1, n_nodes, n_leaves)) {
-            }
-            if(w.dest & PT_DEST_SHADOW) {
-                if(!w.occluded) {
-                    out = out + pending; // worker.cpp:100
-                }
-            }
-            else if(w.best_ref == PT_REF_NONE) {
-                alive = false; // worker.cpp:47-49
-            }
-            else {
-                // the next vertex, up to the roulette draw (worker.cpp:50-70)
-                path_length++;
-                rd = v3(rdv.x, rdv.y, rdv.z);
-                pos = v3(ro.x, ro.y, ro.z) + rd * w.best_t;
-                n = object_normal(sc, w.best_ref, pos, material_index);
-                const Material mat = material_load(sc.materials, material_index);
-                out = out + (spectrum * mat.emission) / (float)(divisor * bounce_pd);
-                bounce_probability = path_length <= 4 ? 1.0f : 0.1f + 0.1f * fmin_std(contribution_unweighted * get_contribution(spectrum), 1.0f);
-                do_bounce = rng_uniform01(rng) < bounce_probability;
-                j = 0;
-            }
-        }
+        SampleSink sink;
+        const C4 out = sample_walk<true, KIND == 2>(tr, sc, root, epsilon, rng, there, pos, n, sink);
         plane[gid] = there ? make_float4(out.r, out.g, out.b, 1.0f) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     }
 }

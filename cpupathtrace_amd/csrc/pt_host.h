@@ -2,7 +2,8 @@
 // pt_pose.cpp (their instances under new matrices, in place), pt_deform.cpp (their meshes under new vertices, in place),
 // pt_morph.cpp (their meshes under blend shapes, in place),
 // pt_relight.cpp (their materials and lights replaced in place), pt_motion.cpp and pt_motion_shapes.cpp (motion for the temporal denoiser),
-// pt_query.cpp (hit records and occlusion tests), pt_gather.cpp (light gathered at points),
+// pt_query.cpp (hit records and occlusion tests), pt_gather.cpp (light gathered at points; with pt_light_probes.cpp, pt_radiance.cpp and
+// pt_light_passes.cpp it takes its launch frame from pt_sample_host.h, which sits on top of this header),
 // pt_render.cpp (render calls), pt_frames.cpp and pt_frame_maps.cpp (resumable frames and their maps; pt_frames.h) and pt_image.cpp
 // (post-processing, features, denoising).  Internal:
 // not installed, not part of the C ABI.  Everything but the ABI's own handle types lives in namespace pth, so that no helper can collide

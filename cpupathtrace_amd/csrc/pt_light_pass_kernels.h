@@ -1,14 +1,14 @@
 // pt_light_pass_kernels.h -- light-group passes (include/pt_light_passes.h): the kernel that traces the samples of a chunk
 // of rays or pixels and keeps an accumulator per pass beside the ordinary one, the reduction that makes the pass records, and the mix.
-// Included by exactly one translation unit, pt_walks.hip, behind pt_radiance_kernels.h, and so behind capture_ray, gather_engine,
-// bind_lane and dispatch_route.
+// Included by exactly one translation unit, pt_walks.hip, behind pt_sample_walk.h and pt_radiance_kernels.h, and so behind capture_ray,
+// RadianceSink, bind_lane and dispatch_route.
 //
-// The loop is pt_radiance_sample_kernel's, copied so that no existing kernel changes (4.20 and 4.21 copied theirs for the same reason),
-// with one more thing at each of its three addition sites: the term also goes to the lane's cell of one pass.  The accumulators live in
-// the chunk's workspace, pass-major -- passes[p * n_pairs + pair], 16 bytes each --, not in registers: 24 passes would be 72 VGPRs on top
-// of a loop that already carries the tracer.  The 64 lanes of a wavefront touch 64 neighbouring cells; a lane reads, adds and writes only
-// its own cell with plain vector loads and stores, so no atomics are needed, and it zeroes its P cells before its loop.  ONE tr.start /
-// tr.step site, as there.
+// The sample is the shared loop's (sample_walk, pt_sample_walk.h) behind pt_radiance_sample_kernel's first ray; what this kernel adds to it
+// is a sink that asks for every term's emitter and sends the term, at each of the loop's three addition sites, to the lane's cell of one
+// pass as well.  The accumulators live in the chunk's workspace, pass-major -- passes[p * n_pairs + pair], 16 bytes each --, not in
+// registers: 24 passes would be 72 VGPRs on top of a loop that already carries the tracer.  The 64 lanes of a wavefront touch 64
+// neighbouring cells; a lane reads, adds and writes only its own cell with plain vector loads and stores, so no atomics are needed, and
+// it zeroes its P cells before its loop.
 #ifndef PT_LIGHT_PASS_KERNELS_H
 #define PT_LIGHT_PASS_KERNELS_H
 
@@ -19,28 +19,6 @@
 namespace {
 
 using namespace ptd;
-
-// sample_emissive (pt_shading.h) that also hands out the registry index it chose.  The selection -- the first of the sample's three
-// numbers, std::lower_bound over the CDF -- is replayed on a COPY of the engine; the sample itself is then sample_emissive's, untouched:
-// every draw and every number are its own by construction.
-template<typename Tables>
-PT_D bool sample_emissive_indexed(const PtDevScene &sc, const Tables &tb, V3 pos, uint64_t &rng, V3 &light_pos, C4 &spectrum, float &pd, uint32_t &object_index) {
-    uint64_t peek = rng;
-    const float r = rng_uniform01(peek);
-    int lo = 0, n = (int)sc.n_emis;
-    while(n > 0) {
-        const int half = n >> 1;
-        if(tb.cdf(lo + half) < r) {
-            lo = lo + half + 1;
-            n = n - half - 1;
-        }
-        else {
-            n = half;
-        }
-    }
-    object_index = (uint32_t)lo;
-    return sample_emissive(sc, tb, pos, rng, light_pos, spectrum, pd);
-}
 
 // groups[material] (PT_NO_MATERIAL: group 0); the table holds the materials' groups, then the point lights'
 PT_D uint32_t material_group(const uint8_t *__restrict__ groups, uint32_t material) {
@@ -59,6 +37,24 @@ PT_D void pass_add(float4 *__restrict__ cell, const C4 &term) {
     v.z = v.z + term.b;
     *cell = v;
 }
+
+// The radiance sink that also splits: an emitter is kept as its group, and a term goes to the cell of pass group * per_group + depth,
+// depth = min(scatterings before the term, 2) where the call splits by depth
+struct LightPassSink : RadianceSink {
+    static constexpr bool kEmitters = true;
+    typedef uint32_t Emitter;
+    const uint8_t *__restrict__ groups;
+    uint32_t n_materials, per_group, split;
+    float4 *__restrict__ mine; // pass p: mine[p * n_pairs]
+    uint32_t n_pairs;
+    PT_D Emitter point_light(uint32_t j) const { return (uint32_t)groups[n_materials + j]; }
+    PT_D Emitter material(uint32_t m) const { return material_group(groups, m); }
+    PT_D void add(const C4 &term, uint32_t group, int scatterings) {
+        pass_add(mine + (size_t)(group * per_group + (split != 0u ? (uint32_t)(scatterings < 2 ? scatterings : 2) : 0u)) * n_pairs, term);
+    }
+    PT_D void direct(const C4 &term, Emitter group, int path_length) { add(term, group, path_length); }
+    PT_D void emitted(const C4 &term, Emitter group, int path_length) { add(term, group, path_length - 1); }
+};
 
 // The samples of the rays or pixels first .. first + n_pairs / samples - 1: plane[g] as pt_radiance_sample_kernel leaves it, and
 // passes[p * n_pairs + g] = (the pass's rgb, 0) for p < n_groups * (split ? 3 : 1).  groups: the materials' groups, then, from
@@ -80,13 +76,8 @@ __global__ __launch_bounds__(256) void pt_light_pass_sample_kernel(PtDevScene sc
     for(uint32_t p = 0; p < n_passes; p++) {
         mine[(size_t)p * n_pairs] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     }
-    const uint32_t per_group = split != 0u ? 3u : 1u;
     RootBox root;
-    root.ref = sc.root_ref;
-    for(int k = 0; k < 3; k++) {
-        root.lo[k] = sc.root_lo[k];
-        root.hi[k] = sc.root_hi[k];
-    }
+    scene_root(sc, root);
     uint64_t rng = gather_engine(pixel_seed(base_seed, (int32_t)sample, (int32_t)index));
     // the first ray: the caller's as it is -- nothing is drawn --, or the capture's
     V3 pos, d0;
@@ -99,152 +90,10 @@ __global__ __launch_bounds__(256) void pt_light_pass_sample_kernel(PtDevScene sc
     else {
         alive = capture_ray(cap, index, rng, pos, d0);
     }
-    uint32_t flags = alive ? 0u : PT_RADIANCE_OUTSIDE;
-
-    const uint32_t n_light_samples = sc.n_lights + sc.n_object_samples;
-    // getSample's state at its top (worker.cpp:37-43)
-    float contribution_unweighted = 1.0f;
-    double divisor = 1.0, bounce_pd = 1.0;
-    C4 spectrum = c4(1.0f, 1.0f, 1.0f, 1.0f);
-    C4 out = c4(0.0f, 0.0f, 0.0f, 0.0f);
-    int path_length = 0;
-    float bounce_probability = 1.0f;
-    bool do_bounce = false;
-    uint32_t j = 0;
-    uint32_t material_index = 0xFFFFFFFFu;
-    V3 n = v3(0.0f, 1.0f, 0.0f), rd = d0;
-    bool need = true; // the first ray is there
-    float4 ro = make_float4(pos.x, pos.y, pos.z, 0.0f), rdv = make_float4(d0.x, d0.y, d0.z, __uint_as_float(0u));
-    C4 pending = c4(0.0f, 0.0f, 0.0f, 0.0f);
-    uint32_t pending_pass = 0; // the pass of `pending`
-    while(alive) {
-        // ---- advance the vertex until it has a ray to trace -------------------------------------------------------------------------------------
-        while(alive && !need) {
-            if(j < n_light_samples) {
-                // worker.cpp:76-103, light sample j
-                V3 light_pos;
-                C4 light_spectrum;
-                float lpd;
-                bool valid;
-                uint32_t group;
-                if(j < sc.n_lights) {
-                    const float4 lp = sc.lights[2 * j];
-                    light_pos = v3(lp.x, lp.y, lp.z);
-                    light_spectrum = c4(sc.lights[2 * j + 1]);
-                    lpd = 1.0f;
-                    valid = true;
-                    group = (uint32_t)groups[n_materials + j];
-                }
-                else {
-                    uint32_t object_index;
-                    valid = sample_emissive_indexed(sc, EmisGlobal{sc}, pos, rng, light_pos, light_spectrum, lpd, object_index);
-                    group = valid ? material_group(groups, __float_as_uint(sc.emis[4 * (size_t)object_index + 2].w)) : 0u;
-                }
-                j += 1;
-                if(valid) {
-                    const Material mat = material_load(sc.materials, material_index);
-                    const V3 to_light = light_pos - pos;
-                    const V3 light_dir = normalize(to_light);
-                    float shading_factor, shadow_ray_pd;
-                    const C4 base_spectrum = bsdf_spectrum(mat, rd, light_dir, n, light_spectrum, true, shading_factor, shadow_ray_pd);
-                    if(shadow_ray_pd > 0.0f) {
-                        const C4 combined = (base_spectrum * shading_factor) * spectrum;
-                        const C4 weighed = combined / (float)(divisor * bounce_pd * lpd * shadow_ray_pd);
-                        // adding +-0 never changes out_spectrum (which is never -0), so such a sample needs no ray
-                        if(!(weighed.r == 0.0f && weighed.g == 0.0f && weighed.b == 0.0f)) {
-                            // k = path_length scatterings lie before a light sample
-                            const uint32_t pass = group * per_group + (split != 0u ? (uint32_t)(path_length < 2 ? path_length : 2) : 0u);
-                            const float threshold = len(to_light) - epsilon;
-                            if(threshold <= 0.0f) {
-                                out = out + weighed; // light_t < 0 || light_t >= threshold holds for every light_t
-                                pass_add(mine + (size_t)pass * n_pairs, weighed);
-                            }
-                            else {
-                                need = true;
-                                pending = weighed;
-                                pending_pass = pass;
-                                const V3 o2 = pos + light_dir * epsilon;
-                                ro = make_float4(o2.x, o2.y, o2.z, threshold);
-                                rdv = make_float4(light_dir.x, light_dir.y, light_dir.z, __uint_as_float(PT_DEST_SHADOW));
-                            }
-                        }
-                    }
-                }
-            }
-            else if(!do_bounce) {
-                alive = false; // worker.cpp:106-109
-            }
-            else {
-                // worker.cpp:110-138
-                bounce_pd *= bounce_probability;
-                if(bounce_pd <= 1E-20) {
-                    alive = false;
-                }
-                else {
-                    const Material mat = material_load(sc.materials, material_index);
-                    float ray_factor, ray_pd;
-                    const Ray next_ray = bsdf_propagate(mat, rd, pos, n, epsilon, rng, ray_factor, ray_pd);
-                    divisor *= ray_pd;
-                    divisor /= ray_factor;
-                    contribution_unweighted *= ray_factor;
-                    float shading_factor, shading_pd;
-                    const C4 shaded = bsdf_spectrum(mat, rd, next_ray.d, n, spectrum, false, shading_factor, shading_pd);
-                    divisor *= shading_pd;
-                    divisor /= shading_factor;
-                    contribution_unweighted *= shading_factor;
-                    spectrum = shaded;
-                    if(divisor <= 1E-20) {
-                        alive = false;
-                    }
-                    else {
-                        need = true;
-                        ro = make_float4(next_ray.o.x, next_ray.o.y, next_ray.o.z, 0.0f);
-                        rdv = make_float4(next_ray.d.x, next_ray.d.y, next_ray.d.z, __uint_as_float(0u));
-                    }
-                }
-            }
-        }
-        if(!alive) {
-            break;
-        }
-        // ---- the walk: the first ray's, a shadow ray's or a bounce's --------------------------------------------------------------------------
-        Walk w;
-        typename Tracer<STACK_LDS, IN_LDS>::Rec rec;
-        rec.r0 = rec.r1 = rec.r2 = rec.r3 = (f4v){0.0f, 0.0f, 0.0f, 0.0f};
-        tr.start(w, rec, root, ro, rdv);
-        uint32_t n_nodes = 0, n_leaves = 0;
-        while(tr.step(w, rec, 1, n_nodes, n_leaves)) {
-        }
-        need = false;
-        if(w.dest & PT_DEST_SHADOW) {
-            if(!w.occluded) {
-                out = out + pending; // worker.cpp:100
-                pass_add(mine + (size_t)pending_pass * n_pairs, pending);
-            }
-        }
-        else if(w.best_ref == PT_REF_NONE) {
-            alive = false; // worker.cpp:47-49
-            if(path_length == 0) {
-                flags = PT_RADIANCE_MISSED;
-            }
-        }
-        else {
-            // the next vertex, up to the roulette draw (worker.cpp:50-70)
-            path_length++;
-            rd = v3(rdv.x, rdv.y, rdv.z);
-            pos = v3(ro.x, ro.y, ro.z) + rd * w.best_t;
-            n = object_normal(sc, w.best_ref, pos, material_index);
-            const Material mat = material_load(sc.materials, material_index);
-            const C4 emitted = (spectrum * mat.emission) / (float)(divisor * bounce_pd);
-            out = out + emitted;
-            // k = path_length - 1 scatterings lie before the emission of this vertex
-            pass_add(mine + (size_t)(material_group(groups, material_index) * per_group + (split != 0u ? (uint32_t)(path_length < 3 ? path_length - 1 : 2) : 0u)) * n_pairs, emitted);
-            bounce_probability = path_length <= 4 ? 1.0f : 0.1f + 0.1f * fmin_std(contribution_unweighted * get_contribution(spectrum), 1.0f);
-            do_bounce = rng_uniform01(rng) < bounce_probability;
-            j = 0;
-        }
-    }
-    plane[gid] = make_float4(out.r, out.g, out.b, __uint_as_float(flags));
+    LightPassSink sink{{}, groups, n_materials, split != 0u ? 3u : 1u, split, mine, n_pairs};
+    sink.flags = alive ? 0u : PT_RADIANCE_OUTSIDE;
+    const C4 out = sample_walk<false, true>(tr, sc, root, epsilon, rng, alive, pos, d0, sink);
+    plane[gid] = make_float4(out.r, out.g, out.b, __uint_as_float(sink.flags));
 }
 
 // The pass records of the rays or pixels first .. first + n - 1 from the chunk's workspace: one wavefront per (ray or pixel, pass), four

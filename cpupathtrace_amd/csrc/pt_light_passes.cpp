@@ -1,57 +1,28 @@
 // pt_light_passes.cpp -- the entry points of include/pt_light_passes.h: the radiance of pt_radiance.h's rays and captures
 // split into passes by emitter group and bounce depth, and the mix of such passes.  The kernels are pt_light_pass_kernels.h's (in
 // pt_walks.hip); this unit checks the arguments -- pt_radiance.cpp's checks first, then its own --, keeps the workspace -- one per device,
-// grown on demand, as pt_radiance.cpp keeps its own -- and cuts a call into launches of whole rays or pixels: at most PT_RADIANCE_CHUNK / P
+// grown on demand, from pt_sample_host.h's table and launch frame -- and cuts a call into launches of whole rays or pixels: at most PT_RADIANCE_CHUNK / P
 // (ray or pixel, sample) pairs each, so that the P + 1 planes of a launch hold about as many cells as a radiance launch's one.  The group
 // tables travel per call.  The host mix is plain fp32 on the host (this file is compiled without contraction, like the rest).  Nothing
 // here changes the scene, so every call is allowed with a live pt_frame and with or without a motion mark.
-#include "pt_host.h"
+#include "pt_sample_host.h"
 
 using namespace pth;
 
 namespace {
 
 const uint64_t PASSES_MAX = 0x7fffffffULL;
-const int RADIANCE_CHUNK_DEFAULT = 2 << 20; // pt_radiance.cpp's
 
-// The buffers of the calls on one device: the host forms' rays and records, the group tables of the latest call, and the workspace of
-// one launch -- the total's plane, the passes' planes and the walks' spill area.  One call at a time per device (`mutex`, taken behind
-// the scene's render lock); `last` marks the end of the latest device-form call, whose work may still run when the next call comes: that
-// call waits for it before it touches a buffer.  Lives as long as the process (pt_radiance.cpp's arrangement).
-struct PassWorkspace {
-    std::mutex mutex;
+// The buffers of the calls on one device beside the workspace of one launch (the total's plane): the host forms' rays and records, the
+// group tables of the latest call, and the passes' planes
+struct PassWorkspace : SampleWorkspace {
     DevBuf<float> rays;
     DevBuf<pt_light_pass> out_passes;
     DevBuf<pt_radiance_result> out_total;
     DevBuf<uint8_t> groups;
     std::vector<uint8_t> table; // ... as they are uploaded from: the materials' groups, then the point lights'
-    DevBuf<F4> plane, passes;
-    DevBuf<uint2> spill;
-    hipEvent_t last = nullptr;
-    bool pending = false;
+    DevBuf<F4> passes;
 };
-
-PassWorkspace &workspace(int device) {
-    static std::mutex table_mutex;
-    static std::vector<PassWorkspace *> table;
-    std::lock_guard<std::mutex> lock(table_mutex);
-    if(static_cast<size_t>(device) >= table.size()) {
-        table.resize(static_cast<size_t>(device) + 1, nullptr);
-    }
-    if(table[static_cast<size_t>(device)] == nullptr) {
-        table[static_cast<size_t>(device)] = new PassWorkspace();
-    }
-    return *table[static_cast<size_t>(device)];
-}
-
-// ws.mutex held: what the latest device-form call left running has ended
-int settle(PassWorkspace &ws) {
-    if(ws.pending) {
-        PT_HIP(hipEventSynchronize(ws.last));
-        ws.pending = false;
-    }
-    return PT_OK;
-}
 
 int check_shape(const pt_light_groups *g) {
     if(g->n_groups < 1 || g->n_groups > PT_LIGHT_GROUPS_MAX) {
@@ -93,43 +64,6 @@ int check_groups(const pt_light_groups *g, const void *passes, uint64_t n, const
     return PT_OK;
 }
 
-// Rays or pixels per launch: whole ones, PT_RADIANCE_CHUNK / P pairs at the most, one where one alone has more
-size_t chunk_items(const pt_radiance_params *p, uint32_t n_passes) {
-    const int pairs = std::max(env_int("PT_RADIANCE_CHUNK", RADIANCE_CHUNK_DEFAULT), 1);
-    return std::max<size_t>(static_cast<size_t>(pairs) / n_passes / static_cast<size_t>(p->samples), 1);
-}
-
-template<typename Enqueue>
-int run_host(pt_scene *s, Enqueue enqueue_all) {
-    StreamDrain drain{s->stream};
-    PT_TRY(enqueue_all());
-    PT_HIP(hipGetLastError());
-    drain.armed = false;
-    PT_HIP(hipStreamSynchronize(s->stream));
-    return PT_OK;
-}
-
-// The same between the two halves of a StreamOrder; `last` (null: none is kept) marks the end of the work for the next call
-template<typename Enqueue>
-int run_device(pt_scene *s, hipEvent_t *last, bool *pending, void *stream, Enqueue enqueue_all) {
-    StreamOrder order;
-    PT_TRY(order.begin(stream, s->stream));
-    PT_TRY(enqueue_all());
-    PT_HIP(hipGetLastError());
-    if(last != nullptr) {
-        if(*last == nullptr) {
-            PT_HIP(hipEventCreateWithFlags(last, hipEventDisableTiming));
-        }
-        PT_HIP(hipEventRecord(*last, s->stream));
-        *pending = true;
-    }
-    PT_TRY(order.end());
-    if(order.caller == nullptr) {
-        PT_HIP(hipStreamSynchronize(s->stream));
-    }
-    return PT_OK;
-}
-
 // A call of n rays (d_rays or, host form, rays) or of the capture's n pixels (both null); host form: d_passes == null, the records go to
 // `passes` and `total`
 int run(pt_scene *s, const float *rays, const float *d_rays, const pt_capture_desc *capture, size_t n, const pt_light_groups *g, const pt_radiance_params *params,
@@ -140,17 +74,15 @@ int run(pt_scene *s, const float *rays, const float *d_rays, const pt_capture_de
                                         " point lights");
     }
     PT_HIP(hipSetDevice(s->device));
-    PassWorkspace &ws = workspace(s->device);
+    PassWorkspace &ws = sample_workspace<PassWorkspace>(s->device);
     std::lock_guard<std::mutex> ws_lock(ws.mutex);
     const uint32_t n_passes = passes_of(g);
-    const size_t step = chunk_items(params, n_passes);
+    // PT_RADIANCE_CHUNK / P pairs a launch, so that its P + 1 planes hold about as many cells as a radiance launch's one
+    const size_t step = chunk_items("PT_RADIANCE_CHUNK", RADIANCE_CHUNK_DEFAULT, params->samples, n_passes);
     PT_TRY(settle(ws));
-    PT_TRY(setup_path(s));
-    PtPathConfig cfg = s->path_cfg;
     const size_t pairs = std::min(n, step) * static_cast<size_t>(params->samples);
-    PT_HIP(ws.spill.ensure(((pairs + 255) / 256) * 256 * cfg.spill_depth));
-    cfg.spill = ws.spill.ptr;
-    PT_HIP(ws.plane.ensure(pairs));
+    PtPathConfig cfg;
+    PT_TRY(size_launch(s, ws.spill, pairs, &ws.plane, pairs, &cfg));
     PT_HIP(ws.passes.ensure(pairs * n_passes));
     const size_t n_table = static_cast<size_t>(g->n_materials) + g->n_point_lights;
     // (kept in the workspace: a device-form call returns while its copy may still read it; settle() has ended the call before)
@@ -196,7 +128,7 @@ int run(pt_scene *s, const float *rays, const float *d_rays, const pt_capture_de
     if(host) {
         return run_host(s, enqueue_all);
     }
-    return run_device(s, &ws.last, &ws.pending, stream, enqueue_all);
+    return run_device(s, &ws, stream, enqueue_all);
 }
 
 } // namespace
@@ -283,7 +215,7 @@ int pt_light_passes_mix_device(pt_scene *s, const pt_light_pass *d_passes, size_
     }
     std::lock_guard<std::mutex> lock(s->render_mutex);
     PT_HIP(hipSetDevice(s->device));
-    return run_device(s, nullptr, nullptr, stream, [&]() -> int {
+    return run_device(s, nullptr, stream, [&]() -> int {
         pt_launch_light_pass_mix(s->stream, reinterpret_cast<const float4 *>(d_passes), n, n_passes, d_gains, reinterpret_cast<const float4 *>(d_total),
                                  reinterpret_cast<float4 *>(d_out));
         return PT_OK;

@@ -1,10 +1,10 @@
 // pt_radiance.cpp -- the entry points of include/pt_radiance.h: the radiance along rays the caller chooses, and captures --
 // images of such rays made on the device by one of four camera models.  The kernels are pt_radiance_kernels.h's (in pt_walks.hip); this
-// unit checks the arguments, keeps the workspace -- one per device, grown on demand, as pt_light_probes.cpp keeps its own; pt_scene is as
-// it was -- and cuts a call into launches of whole rays or pixels: at most PT_RADIANCE_CHUNK (ray or pixel, sample) pairs each, read per
+// unit checks the arguments, keeps the workspace -- one per device, grown on demand, from pt_sample_host.h's table and launch frame;
+// pt_scene is as it was -- and cuts a call into launches of whole rays or pixels: at most PT_RADIANCE_CHUNK (ray or pixel, sample) pairs each, read per
 // call.  A sample's engine is seeded with its ray's or pixel's index in the call, and a record is reduced in an order of its own, so the
 // cut changes no bit.  Nothing here changes the scene, so every call is allowed with a live pt_frame and with or without a motion mark.
-#include "pt_host.h"
+#include "pt_sample_host.h"
 
 #include <cmath>
 
@@ -13,43 +13,13 @@ using namespace pth;
 namespace {
 
 const uint64_t RADIANCE_MAX = 0x7fffffffULL;
-const int RADIANCE_CHUNK_DEFAULT = 2 << 20;
 
-// The buffers of the calls on one device: the host forms' rays and records, and the workspace of one launch -- one float4 per pair and
-// the walks' spill area.  One call at a time per device (`mutex`, taken behind the scene's render lock); `last` marks the end of the
-// latest device-form call, whose work may still run when the next call comes: that call waits for it before it touches a buffer.  Lives
-// as long as the process (never freed: a static destructor would run after the HIP runtime has gone).
-struct RadianceWorkspace {
-    std::mutex mutex;
+// The buffers of the calls on one device beside the workspace of one launch (one float4 per pair in the plane): the host forms' rays
+// and records
+struct RadianceWorkspace : SampleWorkspace {
     DevBuf<float> rays;
     DevBuf<pt_radiance_result> out;
-    DevBuf<F4> plane;
-    DevBuf<uint2> spill;
-    hipEvent_t last = nullptr;
-    bool pending = false;
 };
-
-RadianceWorkspace &workspace(int device) {
-    static std::mutex table_mutex;
-    static std::vector<RadianceWorkspace *> table;
-    std::lock_guard<std::mutex> lock(table_mutex);
-    if(static_cast<size_t>(device) >= table.size()) {
-        table.resize(static_cast<size_t>(device) + 1, nullptr);
-    }
-    if(table[static_cast<size_t>(device)] == nullptr) {
-        table[static_cast<size_t>(device)] = new RadianceWorkspace();
-    }
-    return *table[static_cast<size_t>(device)];
-}
-
-// ws.mutex held: what the latest device-form call left running has ended
-int settle(RadianceWorkspace &ws) {
-    if(ws.pending) {
-        PT_HIP(hipEventSynchronize(ws.last));
-        ws.pending = false;
-    }
-    return PT_OK;
-}
 
 } // namespace
 
@@ -144,84 +114,46 @@ PtCaptureParams radiance_device_capture(const pt_capture_desc *c) {
 
 namespace {
 
-// Rays or pixels per launch: whole ones, PT_RADIANCE_CHUNK pairs at the most, one where one alone has more
-size_t chunk_items(const pt_radiance_params *p) {
-    const int pairs = std::max(env_int("PT_RADIANCE_CHUNK", RADIANCE_CHUNK_DEFAULT), 1);
-    return std::max<size_t>(static_cast<size_t>(pairs) / static_cast<size_t>(p->samples), 1);
-}
-
-// The launch configuration and the workspace of a call of n rays or pixels cut by `step` (render_mutex held, the device set)
-int prepare(pt_scene *s, RadianceWorkspace &ws, size_t n, size_t step, const pt_radiance_params *p, PtPathConfig *cfg) {
-    PT_TRY(settle(ws));
-    PT_TRY(setup_path(s));
-    *cfg = s->path_cfg;
-    const size_t pairs = std::min(n, step) * static_cast<size_t>(p->samples);
-    PT_HIP(ws.spill.ensure(((pairs + 255) / 256) * 256 * cfg->spill_depth));
-    cfg->spill = ws.spill.ptr;
-    PT_HIP(ws.plane.ensure(pairs));
-    return PT_OK;
-}
-
-// Enqueues the launches of n rays or pixels on the scene's stream; d_rays == null: the capture's pixels
-void enqueue(pt_scene *s, RadianceWorkspace &ws, const PtPathConfig &cfg, const pt_radiance_params *p, size_t step, const float *d_rays, const PtCaptureParams &capture, size_t n,
-             pt_radiance_result *d_out) {
-    for(size_t first = 0; first < n; first += step) {
-        pt_launch_radiance(s->stream, s->dev, d_rays, capture, static_cast<uint32_t>(first), static_cast<uint32_t>(std::min(step, n - first)), static_cast<uint32_t>(p->samples),
-                           p->epsilon, p->base_seed, reinterpret_cast<float4 *>(ws.plane.ptr), reinterpret_cast<float4 *>(d_out), cfg);
-    }
-}
-
-// Host form: what `enqueue_all` puts on the scene's stream, then `bytes` from `from` into `out`.  Device form: the same between the two
-// halves of a StreamOrder (pt_gather.cpp's arrangement).
-template<typename Enqueue>
-int run_host(pt_scene *s, void *out, const void *from, size_t bytes, Enqueue enqueue_all) {
-    StreamDrain drain{s->stream};
-    enqueue_all();
-    PT_HIP(hipGetLastError());
-    PT_HIP(hipMemcpyAsync(out, from, bytes, hipMemcpyDeviceToHost, s->stream));
-    drain.armed = false;
-    PT_HIP(hipStreamSynchronize(s->stream));
-    return PT_OK;
-}
-
-template<typename Enqueue>
-int run_device(pt_scene *s, RadianceWorkspace &ws, void *stream, Enqueue enqueue_all) {
-    StreamOrder order;
-    PT_TRY(order.begin(stream, s->stream));
-    enqueue_all();
-    PT_HIP(hipGetLastError());
-    if(ws.last == nullptr) {
-        PT_HIP(hipEventCreateWithFlags(&ws.last, hipEventDisableTiming));
-    }
-    PT_HIP(hipEventRecord(ws.last, s->stream));
-    ws.pending = true;
-    PT_TRY(order.end());
-    if(order.caller == nullptr) {
-        PT_HIP(hipStreamSynchronize(s->stream));
-    }
-    return PT_OK;
-}
-
 // A call of n rays (d_rays or, host form, rays) or of the capture's n pixels (both null); host form: d_out == null, the records go to `out`
 int run(pt_scene *s, const float *rays, const float *d_rays, const pt_capture_desc *capture, size_t n, const pt_radiance_params *params, pt_radiance_result *out,
         pt_radiance_result *d_out, void *stream) {
     std::lock_guard<std::mutex> lock(s->render_mutex);
     PT_HIP(hipSetDevice(s->device));
-    RadianceWorkspace &ws = workspace(s->device);
+    RadianceWorkspace &ws = sample_workspace<RadianceWorkspace>(s->device);
     std::lock_guard<std::mutex> ws_lock(ws.mutex);
-    const size_t step = chunk_items(params);
+    const size_t step = chunk_items("PT_RADIANCE_CHUNK", RADIANCE_CHUNK_DEFAULT, params->samples, 1);
+    PT_TRY(settle(ws));
+    const size_t pairs = std::min(n, step) * static_cast<size_t>(params->samples);
     PtPathConfig cfg;
-    PT_TRY(prepare(s, ws, n, step, params, &cfg));
+    PT_TRY(size_launch(s, ws.spill, pairs, &ws.plane, pairs, &cfg));
+    const bool host = d_out == nullptr;
+    if(host) {
+        PT_HIP(ws.out.ensure(n));
+        if(rays != nullptr) {
+            PT_HIP(ws.rays.ensure(6 * n));
+        }
+    }
     const PtCaptureParams cap = radiance_device_capture(capture);
-    if(d_out != nullptr) {
-        return run_device(s, ws, stream, [&] { enqueue(s, ws, cfg, params, step, d_rays, cap, n, d_out); });
+    const float *use_rays = host ? (rays != nullptr ? ws.rays.ptr : nullptr) : d_rays;
+    pt_radiance_result *records = host ? ws.out.ptr : d_out;
+    auto enqueue_all = [&]() -> int {
+        if(host && rays != nullptr) {
+            PT_HIP(hipMemcpyAsync(ws.rays.ptr, rays, 6 * n * sizeof(float), hipMemcpyHostToDevice, s->stream));
+        }
+        for(size_t first = 0; first < n; first += step) {
+            pt_launch_radiance(s->stream, s->dev, use_rays, cap, static_cast<uint32_t>(first), static_cast<uint32_t>(std::min(step, n - first)),
+                               static_cast<uint32_t>(params->samples), params->epsilon, params->base_seed, reinterpret_cast<float4 *>(ws.plane.ptr),
+                               reinterpret_cast<float4 *>(records), cfg);
+        }
+        if(host) {
+            PT_HIP(hipMemcpyAsync(out, ws.out.ptr, n * sizeof(pt_radiance_result), hipMemcpyDeviceToHost, s->stream));
+        }
+        return PT_OK;
+    };
+    if(host) {
+        return run_host(s, enqueue_all);
     }
-    PT_HIP(ws.out.ensure(n));
-    if(rays != nullptr) {
-        PT_HIP(ws.rays.ensure(6 * n));
-        PT_HIP(hipMemcpyAsync(ws.rays.ptr, rays, 6 * n * sizeof(float), hipMemcpyHostToDevice, s->stream));
-    }
-    return run_host(s, out, ws.out.ptr, n * sizeof(pt_radiance_result), [&] { enqueue(s, ws, cfg, params, step, rays != nullptr ? ws.rays.ptr : nullptr, cap, n, ws.out.ptr); });
+    return run_device(s, &ws, stream, enqueue_all);
 }
 
 } // namespace

@@ -1,12 +1,11 @@
 // pt_radiance_kernels.h -- radiance along free rays and captures (include/pt_radiance.h): the kernel that traces the samples
 // of a chunk of rays or pixels and the reduction that makes their records.  Included by exactly one translation unit, pt_walks.hip, behind
-// pt_light_probe_kernels.h, and so behind gather_engine, bind_lane and dispatch_route.
+// pt_sample_walk.h and pt_light_probe_kernels.h, and so behind bind_lane and dispatch_route.
 //
 // One lane per (ray or pixel, sample) pair, sample-fastest, with the engine RandomEngine(pt_pixel_seed(base_seed, sample, index)) -- the
-// ray's index in the call, or py * width + px.  The loop is pt_light_probe_sample_kernel's, copied so that no existing kernel changes (4.20
-// copied pt_gather_kernel's for the same reason), with another entry and another exit: the first ray is the caller's, or the capture
-// generator's, and the lane leaves L_s with its alpha's flags in one float4.  ONE tr.start / tr.step site serves the first ray, the
-// shadow rays and the bounces; a sample without a ray (FISHEYE outside the image circle) never reaches it.
+// ray's index in the call, or py * width + px.  The sample is the shared loop's (sample_walk, pt_sample_walk.h); what this kernel adds to
+// it is the first ray -- the caller's, or the capture generator's -- and a sink that keeps the flags of the sample's alpha, which leave
+// the lane with L_s in one float4.  A sample without a ray (FISHEYE outside the image circle) starts dead and never reaches a walk.
 #ifndef PT_RADIANCE_KERNELS_H
 #define PT_RADIANCE_KERNELS_H
 
@@ -90,6 +89,12 @@ PT_D bool capture_ray(const PtCaptureParams &cap, uint32_t pixel, uint64_t &rng,
     return true;
 }
 
+// The flags of a sample's alpha: 0 the first walk hit, PT_RADIANCE_MISSED, or PT_RADIANCE_OUTSIDE, which the kernel sets where there is no ray
+struct RadianceSink : SampleSink {
+    uint32_t flags = 0;
+    PT_D void first_miss() { flags = PT_RADIANCE_MISSED; }
+};
+
 // The samples of the rays or pixels first .. first + n_pairs / samples - 1: plane[g] = (L_s rgb, flags: 0 the first walk hit -- alpha 1 --,
 // PT_RADIANCE_MISSED, PT_RADIANCE_OUTSIDE -- alpha 0).  rays == null: the rays are the capture's.
 template<int STACK_LDS, bool IN_LDS>
@@ -104,11 +109,7 @@ __global__ __launch_bounds__(256) void pt_radiance_sample_kernel(PtDevScene sc, 
     const uint32_t sample = (uint32_t)gid - local * samples;
     const uint32_t index = first + local;
     RootBox root;
-    root.ref = sc.root_ref;
-    for(int k = 0; k < 3; k++) {
-        root.lo[k] = sc.root_lo[k];
-        root.hi[k] = sc.root_hi[k];
-    }
+    scene_root(sc, root);
     uint64_t rng = gather_engine(pixel_seed(base_seed, (int32_t)sample, (int32_t)index));
     // the first ray: the caller's as it is -- nothing is drawn --, or the capture's
     V3 pos, d0;
@@ -121,139 +122,10 @@ __global__ __launch_bounds__(256) void pt_radiance_sample_kernel(PtDevScene sc, 
     else {
         alive = capture_ray(cap, index, rng, pos, d0);
     }
-    uint32_t flags = alive ? 0u : PT_RADIANCE_OUTSIDE;
-
-    const uint32_t n_light_samples = sc.n_lights + sc.n_object_samples;
-    // getSample's state at its top (worker.cpp:37-43)
-    float contribution_unweighted = 1.0f;
-    double divisor = 1.0, bounce_pd = 1.0;
-    C4 spectrum = c4(1.0f, 1.0f, 1.0f, 1.0f);
-    C4 out = c4(0.0f, 0.0f, 0.0f, 0.0f);
-    int path_length = 0;
-    float bounce_probability = 1.0f;
-    bool do_bounce = false;
-    uint32_t j = 0;
-    uint32_t material_index = 0xFFFFFFFFu;
-    V3 n = v3(0.0f, 1.0f, 0.0f), rd = d0;
-    bool need = true; // the first ray is there
-    float4 ro = make_float4(pos.x, pos.y, pos.z, 0.0f), rdv = make_float4(d0.x, d0.y, d0.z, __uint_as_float(0u));
-    C4 pending = c4(0.0f, 0.0f, 0.0f, 0.0f);
-    while(alive) {
-        // ---- advance the vertex until it has a ray to trace -------------------------------------------------------------------------------------
-        while(alive && !need) {
-            if(j < n_light_samples) {
-                // worker.cpp:76-103, light sample j
-                V3 light_pos;
-                C4 light_spectrum;
-                float lpd;
-                bool valid;
-                if(j < sc.n_lights) {
-                    const float4 lp = sc.lights[2 * j];
-                    light_pos = v3(lp.x, lp.y, lp.z);
-                    light_spectrum = c4(sc.lights[2 * j + 1]);
-                    lpd = 1.0f;
-                    valid = true;
-                }
-                else {
-                    valid = sample_emissive(sc, EmisGlobal{sc}, pos, rng, light_pos, light_spectrum, lpd);
-                }
-                j += 1;
-                if(valid) {
-                    const Material mat = material_load(sc.materials, material_index);
-                    const V3 to_light = light_pos - pos;
-                    const V3 light_dir = normalize(to_light);
-                    float shading_factor, shadow_ray_pd;
-                    const C4 base_spectrum = bsdf_spectrum(mat, rd, light_dir, n, light_spectrum, true, shading_factor, shadow_ray_pd);
-                    if(shadow_ray_pd > 0.0f) {
-                        const C4 combined = (base_spectrum * shading_factor) * spectrum;
-                        const C4 weighed = combined / (float)(divisor * bounce_pd * lpd * shadow_ray_pd);
-                        // adding +-0 never changes out_spectrum (which is never -0), so such a sample needs no ray
-                        if(!(weighed.r == 0.0f && weighed.g == 0.0f && weighed.b == 0.0f)) {
-                            const float threshold = len(to_light) - epsilon;
-                            if(threshold <= 0.0f) {
-                                out = out + weighed; // light_t < 0 || light_t >= threshold holds for every light_t
-                            }
-                            else {
-                                need = true;
-                                pending = weighed;
-                                const V3 o2 = pos + light_dir * epsilon;
-                                ro = make_float4(o2.x, o2.y, o2.z, threshold);
-                                rdv = make_float4(light_dir.x, light_dir.y, light_dir.z, __uint_as_float(PT_DEST_SHADOW));
-                            }
-                        }
-                    }
-                }
-            }
-            else if(!do_bounce) {
-                alive = false; // worker.cpp:106-109
-            }
-            else {
-                // worker.cpp:110-138
-                bounce_pd *= bounce_probability;
-                if(bounce_pd <= 1E-20) {
-                    alive = false;
-                }
-                else {
-                    const Material mat = material_load(sc.materials, material_index);
-                    float ray_factor, ray_pd;
-                    const Ray next_ray = bsdf_propagate(mat, rd, pos, n, epsilon, rng, ray_factor, ray_pd);
-                    divisor *= ray_pd;
-                    divisor /= ray_factor;
-                    contribution_unweighted *= ray_factor;
-                    float shading_factor, shading_pd;
-                    const C4 shaded = bsdf_spectrum(mat, rd, next_ray.d, n, spectrum, false, shading_factor, shading_pd);
-                    divisor *= shading_pd;
-                    divisor /= shading_factor;
-                    contribution_unweighted *= shading_factor;
-                    spectrum = shaded;
-                    if(divisor <= 1E-20) {
-                        alive = false;
-                    }
-                    else {
-                        need = true;
-                        ro = make_float4(next_ray.o.x, next_ray.o.y, next_ray.o.z, 0.0f);
-                        rdv = make_float4(next_ray.d.x, next_ray.d.y, next_ray.d.z, __uint_as_float(0u));
-                    }
-                }
-            }
-        }
-        if(!alive) {
-            break;
-        }
-        // ---- the walk: the first ray's, a shadow ray's or a bounce's --------------------------------------------------------------------------
-        Walk w;
-        typename Tracer<STACK_LDS, IN_LDS>::Rec rec;
-        rec.r0 = rec.r1 = rec.r2 = rec.r3 = (f4v){0.0f, 0.0f, 0.0f, 0.0f};
-        tr.start(w, rec, root, ro, rdv);
-        uint32_t n_nodes = 0, n_leaves = 0;
-        while(tr.step(w, rec, 1, n_nodes, n_leaves)) {
-        }
-        need = false;
-        if(w.dest & PT_DEST_SHADOW) {
-            if(!w.occluded) {
-                out = out + pending; // worker.cpp:100
-            }
-        }
-        else if(w.best_ref == PT_REF_NONE) {
-            alive = false; // worker.cpp:47-49
-            if(path_length == 0) {
-                flags = PT_RADIANCE_MISSED;
-            }
-        }
-        else {
-            // the next vertex, up to the roulette draw (worker.cpp:50-70)
-            path_length++;
-            rd = v3(rdv.x, rdv.y, rdv.z);
-            pos = v3(ro.x, ro.y, ro.z) + rd * w.best_t;
-            n = object_normal(sc, w.best_ref, pos, material_index);
-            const Material mat = material_load(sc.materials, material_index);
-            out = out + (spectrum * mat.emission) / (float)(divisor * bounce_pd);
-            bounce_probability = path_length <= 4 ? 1.0f : 0.1f + 0.1f * fmin_std(contribution_unweighted * get_contribution(spectrum), 1.0f);
-            do_bounce = rng_uniform01(rng) < bounce_probability;
-            j = 0;
-        }
-    }
-    plane[gid] = make_float4(out.r, out.g, out.b, __uint_as_float(flags));
+    RadianceSink sink;
+    sink.flags = alive ? 0u : PT_RADIANCE_OUTSIDE;
+    const C4 out = sample_walk<false, true>(tr, sc, root, epsilon, rng, alive, pos, d0, sink);
+    plane[gid] = make_float4(out.r, out.g, out.b, __uint_as_float(sink.flags));
 }
 
 // The records of the rays or pixels first .. first + n - 1 from the chunk's workspace: one wavefront each, four to a workgroup.  Lane j

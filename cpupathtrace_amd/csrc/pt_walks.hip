@@ -4,7 +4,8 @@
 // diagnostics (pt_steptime_kernel, pt_replay_kernel).  They live apart from pt_path.hip so that an edit here neither recompiles nor
 // re-schedules the path kernel.  Written once: the dispatch over the three (stack window, records) routes, the LDS size, and the prologue
 // that binds a lane's Tracer (bind_lane) where it leaves a kernel's instructions as they were: the closest-hit and the step-timing kernel.
-// The bodies are deliberately NOT folded further.  Helpers for the root box, the walk to its end and the feature kernels' pixel and sums
+// The path-sample loop of the gather, probe, radiance and light-pass kernels is written once as well (pt_sample_walk.h).
+// The other bodies are deliberately NOT folded further.  Helpers for the root box, the walk to its end and the feature kernels' pixel and sums
 // were built and measured ("The split"): every one of them, and bind_lane in the feature kernels, changed the compiler's
 // schedule, and the feature passes then exceeded the measurement's tolerance on three rows.  As it stands the instruction text of every
 // kernel here is the one it had in pt_path.hip, but for one commutative operand swap in the kViews instantiations (tools/kernel_diff.py).
@@ -816,6 +817,7 @@ void dispatch_route(const PtPathConfig &cfg, const PtDevScene &scene, Launch lau
 } // namespace
 
 #include "pt_query_kernels.h" // pt_query_kernel, pt_query_pixels_kernel, pt_occluded_kernel and their launches (behind bind_lane and dispatch_route, which they use)
+#include "pt_sample_walk.h" // sample_walk: the one path-sample loop of the four files below, with gather_engine and scene_root
 #include "pt_gather_kernels.h" // pt_gather_kernel, its reduce and the two kernels that make points, with their launches (behind the same two)
 #include "pt_light_probe_kernels.h" // the light probes: sampling, projection and lookup kernels with their launches (behind pt_gather_kernels.h)
 #include "pt_radiance_kernels.h" // radiance along free rays and captures: the sampling kernel and its reduction with their launch (behind pt_light_probe_kernels.h)

@@ -2,7 +2,8 @@
 against the yardstick tests/light_probe_ref.py on the oracle, coefficients and counts bit for bit, on scenes S (tree in LDS), L
 (device-built, records in HBM, walks that outgrow the stack's LDS window) and G (glass, both emitter kinds, point lights, a one-way mirror)
 with the probes of tests/light_probe_cases.py; every chunk size gives the same bits; the device forms equal the host forms; a grid's
-records equal the probes at its nodes; the lookup equals its restatement bit for bit; after a relight the scene answers as a fresh one; a
+records equal the probes at its nodes; a probe's sample is the radiance call's along the same direction, bit for bit; the
+lookup equals its restatement bit for bit; after a relight the scene answers as a fresh one; a
 live frame is left alone; and in a furnace the record and the lookup return the emission."""
 import math
 import os
@@ -13,7 +14,7 @@ import numpy as np
 import pytest
 
 from cpupathtrace_amd import binding, scenes
-from tests import light_probe_cases as cases, light_probe_ref as ref, pose_probe, query_cases
+from tests import gather_ref, light_probe_cases as cases, light_probe_ref as ref, pose_probe, query_cases
 from tests.util import assert_bits_equal
 
 pytestmark = pytest.mark.gpu
@@ -97,6 +98,49 @@ def test_chunks_change_no_bit(case):
             del os.environ["PT_LIGHT_PROBE_CHUNK"]
         else:
             os.environ["PT_LIGHT_PROBE_CHUNK"] = before
+
+
+def _base_seed_for_state(state, x=0, y=0):
+    """The base_seed whose engine RandomEngine(pt_pixel_seed(base_seed, x, y)) has `state`: both maps are bijections of 64-bit words
+    (seed ^ (~seed << 32) keeps the low half; splitmix64's finaliser is xor-shifts and odd multiplications), undone step by step."""
+    M = (1 << 64) - 1
+
+    def unshift(v, s):  # the z of v = z ^ (z >> s)
+        z = v
+        for _ in range(64 // s + 1):
+            z = v ^ (z >> s)
+        return z
+
+    lo = state & 0xFFFFFFFF
+    seed = ((((state >> 32) ^ ~lo) & 0xFFFFFFFF) << 32) | lo
+    z = unshift(seed, 31)
+    z = unshift((z * pow(0x94D049BB133111EB, -1, 1 << 64)) & M, 27)
+    z = unshift((z * pow(0xBF58476D1CE4E5B9, -1, 1 << 64)) & M, 30)
+    base_seed = (z - 0x9E3779B97F4A7C15 * (1 + (y << 32) + x)) & M
+    assert binding.seed_to_state(binding.pixel_seed(base_seed, x, y)) == state
+    return base_seed
+
+
+def test_a_probe_sample_is_the_radiance_along_its_direction(case):
+    """The light-probe kernel against the radiance kernel, sample for sample: the yardstick's direction of a probe's one sample, a radiance
+    ray from the probe along it whose engine starts where the probe's stands behind its two draws (a base_seed made for that), and the
+    ray's traced rgb is that sample's L_s -- the yardstick's, and the one in the probe's record, through the yardstick's projection."""
+    g, n = case["g"], 3
+    pos = case["pos"][:n]
+    d, states = ref.directions(gather_ref.sample_states(cases.SEED, n, 1).reshape(-1))
+    assert_bits_equal(d, case["samples"][0][:n, 0], "the directions")
+    L = np.zeros((n, 1, 4), F)
+    missed = np.zeros((n, 1), bool)
+    for i in range(n):
+        ray = np.concatenate([pos[i], d[i]]).astype(F)
+        rec = g.radiance(ray, 1, EPSILON, _base_seed_for_state(int(states[i])))[0]
+        L[i, 0], missed[i, 0] = rec["value"], rec["missed"] == 1
+        assert rec["samples"] == 1 and rec["outside"] == 0
+    _, want_L, want_missed, backfacing = (v[:n, :1] for v in case["samples"])
+    assert (missed == want_missed).all()
+    ref.assert_floats_equal(L[:, :, :3], want_L[:, :, :3], "%s: a ray's rgb against the probe sample's L_s" % case["name"])
+    got = g.light_probes(pos, 1, EPSILON, cases.SEED)
+    ref.assert_probes_equal(got, ref.project(d.reshape(n, 1, 3), L, missed, backfacing), "%s: the probes' records from the rays' rgb" % case["name"])
 
 
 def _grid_records(case, count, samples=64):
