@@ -78,6 +78,9 @@ MOTION_DEFORMED = 3
 QUERY_EXPORTS = ["pt_query_rays", "pt_query_rays_device", "pt_query_pixels", "pt_query_pixels_device", "pt_query_frame", "pt_query_frame_device", "pt_occluded_rays",
                  "pt_occluded_rays_device"]
 QUERY_NO_FACE = 0xFFFFFFFF
+# nearest-surface queries (include/pt_nearest.h): the closest point of the scene to free points, and distance grids
+NEAREST_EXPORTS = ["pt_nearest_points", "pt_nearest_points_device", "pt_distance_grid_fill", "pt_distance_grid_fill_device"]
+NEAREST_FACE, NEAREST_EDGE_AB, NEAREST_EDGE_BC, NEAREST_EDGE_CA, NEAREST_VERTEX_A, NEAREST_VERTEX_B, NEAREST_VERTEX_C, NEAREST_SPHERE = range(8)
 # light gathered at points (include/pt_gather.h): occlusion, direct light, full paths
 GATHER_EXPORTS = ["pt_gather_params_default", "pt_gather_points", "pt_gather_points_device", "pt_gather_frame", "pt_gather_frame_device", "pt_gather_instance"]
 GATHER_OCCLUSION, GATHER_DIRECT, GATHER_PATHS = 0, 1, 2
@@ -99,6 +102,12 @@ CHECKPOINT_FINISHED, CHECKPOINT_UNTOUCHED, CHECKPOINT_RECORD = 0, 1, 2
 # pt_hit: 64 bytes.  A miss: t -1, object -1, instance -1, face QUERY_NO_FACE, material NO_MATERIAL, every other float 0
 Hit = np.dtype([("t", "<f4"), ("object", "<i4"), ("instance", "<i4"), ("face", "<u4"), ("position", "<f4", 3), ("material", "<u4"), ("normal", "<f4", 3), ("b1", "<f4"),
                 ("geometric_normal", "<f4", 3), ("b2", "<f4")])
+
+# pt_nearest: 64 bytes.  A miss: distance and squared_distance +inf, object -1, instance -1, face QUERY_NO_FACE, material NO_MATERIAL,
+# every other word 0.  pt_distance_grid: 36 bytes
+Nearest = np.dtype([("distance", "<f4"), ("object", "<i4"), ("instance", "<i4"), ("face", "<u4"), ("position", "<f4", 3), ("material", "<u4"),
+                    ("geometric_normal", "<f4", 3), ("b1", "<f4"), ("squared_distance", "<f4"), ("feature", "<u4"), ("side", "<i4"), ("b2", "<f4")])
+DistanceGrid = np.dtype([("origin", "<f4", 3), ("step", "<f4", 3), ("count", "<u4", 3)])
 
 # pt_gather_result: 32 bytes.  A frame's pixel without a first hit: all zero
 GatherResult = np.dtype([("value", "<f4", 4), ("samples", "<u4"), ("occluded", "<u4"), ("pad", "<u4", 2)])
@@ -811,6 +820,15 @@ def light_probe_grid(origin, step, count):
     return g
 
 
+def distance_grid(origin, step, count):
+    """A pt_distance_grid as a 0-d array of dtype DistanceGrid; a grid made by this function passes through unchanged."""
+    if isinstance(origin, np.ndarray) and origin.dtype == DistanceGrid:
+        return np.ascontiguousarray(origin).reshape(())
+    g = np.zeros((), DistanceGrid)
+    g["origin"], g["step"], g["count"] = np.asarray(origin, np.float32), np.asarray(step, np.float32), np.asarray(count, np.int64)
+    return g
+
+
 def radiance_params(samples, epsilon, base_seed=0):
     return RadianceParams(int(samples), float(epsilon), int(base_seed) & 0xFFFFFFFFFFFFFFFF)
 
@@ -1207,6 +1225,39 @@ class Scene:
         """pt_query_frame_device: H*W records in device memory, ordered on stream_ptr."""
         cp, op = _camera(camera), _options(options)
         _check(load().pt_query_frame_device(self._h, C.byref(cp), C.byref(op), C.c_void_p(d_out_ptr), C.c_void_p(stream_ptr)))
+
+    def nearest(self, points, max_distance=np.inf):
+        """pt_nearest_points: the closest point of the scene's surfaces to each point (n, 3) within max_distance (a scalar or (n,)):
+        (n,) records of dtype Nearest -- distance, object, instance, face, position, barycentrics, the feature (NEAREST_*) and the side
+        of that primitive.  A miss has distance +inf and object -1."""
+        pts = np.asarray(points, np.float32).reshape(-1, 3)
+        q = np.empty((len(pts), 4), np.float32)
+        q[:, :3], q[:, 3] = pts, np.asarray(max_distance, np.float32)
+        out = np.zeros(len(q), Nearest)
+        _check(load().pt_nearest_points(self._h, _ptr(q), C.c_size_t(len(q)), _ptr(out)))
+        return out
+
+    def nearest_device(self, d_points_ptr, n, d_out_ptr, stream_ptr=0):
+        """pt_nearest_points_device: n queries (xyz, max_distance: 4 floats each) and n records (64 bytes each) in device memory,
+        ordered on stream_ptr."""
+        _check(load().pt_nearest_points_device(self._h, C.c_void_p(d_points_ptr), C.c_size_t(n), C.c_void_p(d_out_ptr), C.c_void_p(stream_ptr)))
+
+    def distance_grid(self, origin, step, count, max_distance=np.inf, want_object=True):
+        """pt_distance_grid_fill: the unsigned distance to the nearest surface at origin + i * step, count = (nx, ny, nz): (distance
+        (nz, ny, nx) float32, +inf where nothing lies within max_distance; object (nz, ny, nx) int32, -1 there -- None without
+        want_object).  The positions are made on the device."""
+        grid = distance_grid(origin, step, count)
+        nx, ny, nz = (int(c) for c in grid["count"])
+        distance = np.zeros((nz, ny, nx), np.float32)
+        obj = np.zeros((nz, ny, nx), np.int32) if want_object else None
+        _check(load().pt_distance_grid_fill(self._h, _ptr(grid), C.c_float(max_distance), _ptr(distance), _ptr(obj)))
+        return distance, obj
+
+    def distance_grid_device(self, grid, d_distance_ptr, d_object_ptr=0, max_distance=np.inf, stream_ptr=0):
+        """pt_distance_grid_fill_device: nx * ny * nz floats and (d_object_ptr not 0) as many int32 in device memory, ordered on stream_ptr."""
+        grid = distance_grid(grid, None, None)
+        _check(load().pt_distance_grid_fill_device(self._h, _ptr(grid), C.c_float(max_distance), C.c_void_p(d_distance_ptr), C.c_void_p(d_object_ptr or None),
+                                                   C.c_void_p(stream_ptr)))
 
     def gather(self, points, normals, kind, samples, epsilon, distance=np.inf, base_seed=0):
         """pt_gather_points: the light that arrives at the points (n, 3) with the unit normals (n, 3), `samples` samples each, as (n,)

@@ -2,7 +2,7 @@
 // pt_pose.cpp (their instances under new matrices, in place), pt_deform.cpp (their meshes under new vertices, in place),
 // pt_morph.cpp (their meshes under blend shapes, in place),
 // pt_relight.cpp (their materials and lights replaced in place), pt_motion.cpp and pt_motion_shapes.cpp (motion for the temporal denoiser),
-// pt_query.cpp (hit records and occlusion tests), pt_gather.cpp (light gathered at points; with pt_light_probes.cpp, pt_radiance.cpp and
+// pt_query.cpp (hit records and occlusion tests), pt_nearest.cpp (the nearest surface to free points, distance grids), pt_gather.cpp (light gathered at points; with pt_light_probes.cpp, pt_radiance.cpp and
 // pt_light_passes.cpp it takes its launch frame from pt_sample_host.h, which sits on top of this header),
 // pt_render.cpp (render calls), pt_frames.cpp and pt_frame_maps.cpp (resumable frames and their maps; pt_frames.h) and pt_image.cpp
 // (post-processing, features, denoising).  Internal:
@@ -365,6 +365,11 @@ struct pt_scene {
     std::vector<uint32_t> query_inst_first, query_inst_count;
     uint32_t query_n_instances = 0;
     bool query_table_made = false;
+    // nearest-surface queries (pt_nearest.cpp; include/pt_nearest.h): the host forms' points, records and grid planes; the walks spill
+    // into query_spill, ordered by the scene's stream like the queries above
+    pth::DevBuf<float> nearest_in, nearest_distance;
+    pth::DevBuf<pt_nearest> nearest_out;
+    pth::DevBuf<int32_t> nearest_object;
     // light gathered at points (pt_gather.cpp; include/pt_gather.h): the host forms' points and records, the points and the missing
     // pixels of a frame or an instance, and the workspace of one launch: the samples' plane or bits and the walks' spill area
     pth::DevBuf<float> gather_points;
@@ -634,6 +639,12 @@ int motion_check(pt_scene *s, const pt_camera_params *camera, const pt_options *
 int motion_instances(pt_scene *s, const float *previous, uint32_t *n_out);
 // Enqueues pt_motion_kernel on the scene's stream (render_mutex held) with the table motion_instances left
 int motion_launch(pt_scene *s, const pt_camera_params *camera, const pt_options *options, uint32_t n_instances, float4 *d_features, float4 *d_motion);
+
+// ---- pt_query.cpp ----------------------------------------------------------------------------------------------------------------------
+
+// The tables a record's instance and face are looked up in (render_mutex held, the device set), for pt_nearest.cpp as well: the
+// instance table is made again only when the scene's ranges differ from the ones it was made from
+int query_record_tables(pt_scene *s, PtQueryTables *out);
 
 // ---- pt_radiance.cpp -------------------------------------------------------------------------------------------------------------------
 

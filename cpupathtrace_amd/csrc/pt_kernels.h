@@ -343,6 +343,22 @@ void pt_launch_light_passes(hipStream_t stream, const PtDevScene &scene, const f
                             const PtPathConfig &cfg);
 // out[i] = the mix of passes[i * n_passes ..] under gains[n_passes][3], one thread each; alpha = total[2 * i].w, or 0 without total
 void pt_launch_light_pass_mix(hipStream_t stream, const float4 *passes, size_t n, uint32_t n_passes, const float *gains, const float4 *total, float4 *out);
+// Nearest-surface queries (pt_nearest_kernels.h, pt_nearest.hip; include/pt_nearest.h).  A grid as the kernel takes it:
+// pt_distance_grid's fields
+struct PtDistanceGrid {
+    float origin[3];
+    float step[3];
+    uint32_t count[3];
+};
+// out[4 * (first + i) + k], i < n: the k-th 16 bytes of the pt_nearest of query first + i of points4 (xyz, max_distance).  spill holds
+// spill_depth entries for each of the launch's ((n + 255) / 256) * 256 lanes.  counts (diagnostic; null in the product's calls): the
+// pair and the leaf records the launch fetched are added to counts[0] and counts[1].
+void pt_launch_nearest_points(hipStream_t stream, const PtDevScene &scene, const float *points4, uint32_t first, uint32_t n, float4 *out, const PtQueryTables &tables, uint2 *spill,
+                              uint32_t spill_depth, unsigned long long *counts);
+// out_distance[first + i] and (out_object not null) out_object[first + i], i < n: distance and object of the query at cell first + i of
+// the grid with max_distance; the spill area as above
+void pt_launch_nearest_grid(hipStream_t stream, const PtDevScene &scene, const PtDistanceGrid &grid, float max_distance, uint32_t first, uint32_t n, float *out_distance,
+                            int32_t *out_object, uint2 *spill, uint32_t spill_depth);
 // diagnostic (tools/step_timing.py): stamped walks, `lanes_per_wave` rays per wavefront; out[ray] = (steps, cycles waiting for records, cycles in all, price of a stamp pair)
 void pt_launch_steptime(hipStream_t stream, const PtDevScene &scene, const float *rays6, uint32_t n, uint32_t lanes_per_wave, uint4 *out, uint2 *spill, uint32_t spill_depth, int flags);
 

@@ -123,6 +123,10 @@ int run_device(pt_scene *s, void *stream, Enqueue enqueue) {
 
 } // namespace
 
+int pth::query_record_tables(pt_scene *s, PtQueryTables *out) {
+    return query_tables(s, out);
+}
+
 extern "C" {
 
 int pt_query_rays(pt_scene *s, const float *rays, size_t n, pt_hit *out) {

@@ -15,6 +15,36 @@
 
 namespace ptd {
 
+// The instance and the face of object `obj`.  The instance: the last one whose first object is not above obj, if its range holds obj
+// (pt_motion_kernel's search); the face: the triangle's index inside an instance that kept every face, else the face table's word, else
+// none.  Both stay 0xffffffff where there is none.  (Shared with pt_nearest_kernels.h: one search, two records.)
+PT_D void query_instance_face(const PtQueryTables &qt, uint32_t obj, uint32_t &instance, uint32_t &face) {
+    instance = 0xffffffffu;
+    face = 0xffffffffu;
+    if(qt.n_inst != 0) {
+        uint32_t lo = 0, hi = qt.n_inst;
+        while(hi - lo > 1) {
+            const uint32_t mid = lo + (hi - lo) / 2;
+            if(qt.inst[mid].first <= obj) {
+                lo = mid;
+            }
+            else {
+                hi = mid;
+            }
+        }
+        const PtQueryInstance qi = qt.inst[lo];
+        if(obj >= qi.first && obj - qi.first < qi.count) {
+            instance = qi.instance;
+            if(qi.count == qi.n_faces) {
+                face = obj - qi.first;
+            }
+            else if(qt.face_of != nullptr) {
+                face = qt.face_of[obj - qt.first_object] - qi.face_first;
+            }
+        }
+    }
+}
+
 // The record of one walk: (best_ref, best_t) of the ray (o, d) in scene `sc`, with the instance table and the face table of `qt`.
 // r[k] is the record's k-th 16 bytes (include/pt_query.h: pt_hit).  The loads of a triangle are object_normal's own (one 128-byte line).
 PT_D void query_record(const PtDevScene &sc, const PtQueryTables &qt, uint32_t best_ref, float best_t, V3 o, V3 d, float4 r[4]) {
@@ -55,31 +85,8 @@ PT_D void query_record(const PtDevScene &sc, const PtQueryTables &qt, uint32_t b
     const float inv_l = 1.0f / __builtin_sqrtf(l);
     const bool flat = !(l > 0.0f);
     const V3 g = v3(flat ? 0.0f : c.x * inv_l, flat ? 0.0f : c.y * inv_l, flat ? 0.0f : c.z * inv_l);
-    // the instance: the last one whose first object is not above obj, if its range holds obj (pt_motion_kernel's search); the face: the
-    // triangle's index inside an instance that kept every face, else the face table's word, else none
-    uint32_t instance = 0xffffffffu, face = 0xffffffffu;
-    if(qt.n_inst != 0) {
-        uint32_t lo = 0, hi = qt.n_inst;
-        while(hi - lo > 1) {
-            const uint32_t mid = lo + (hi - lo) / 2;
-            if(qt.inst[mid].first <= obj) {
-                lo = mid;
-            }
-            else {
-                hi = mid;
-            }
-        }
-        const PtQueryInstance qi = qt.inst[lo];
-        if(obj >= qi.first && obj - qi.first < qi.count) {
-            instance = qi.instance;
-            if(qi.count == qi.n_faces) {
-                face = obj - qi.first;
-            }
-            else if(qt.face_of != nullptr) {
-                face = qt.face_of[obj - qt.first_object] - qi.face_first;
-            }
-        }
-    }
+    uint32_t instance, face;
+    query_instance_face(qt, obj, instance, face);
     r[0] = make_float4(t, __uint_as_float(obj), __uint_as_float(instance), __uint_as_float(face));
     r[1] = make_float4(pos.x, pos.y, pos.z, __uint_as_float(material));
     r[2] = make_float4(n.x, n.y, n.z, b1);

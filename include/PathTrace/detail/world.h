@@ -18,6 +18,7 @@
 
 #include <array>
 #include <cstdint>
+#include <limits>
 #include <memory>
 #include <tuple>
 #include <utility>
@@ -287,6 +288,9 @@ struct GatherResult;
 struct LightProbeOptions; // PathTrace/light_probes.h
 struct LightProbe;
 struct LightProbeGrid;
+struct NearestResult; // PathTrace/nearest.h
+struct DistanceGrid;
+struct DistanceField;
 struct RadianceOptions; // PathTrace/radiance.h
 struct RadianceResult;
 struct Capture;
@@ -430,6 +434,15 @@ class Scene {
     // std::runtime_error when the device refuses -- as it does when the tables' lengths are not the scene's counts.  Non-virtual.
     LightPasses lightPasses(const std::vector<Ray> &rays, const LightGroups &groups, const RadianceOptions &radiance_options, bool want_total = true) const;
     LightPasses captureLightPasses(const Capture &capture, const LightGroups &groups, const RadianceOptions &radiance_options, bool want_total = true) const;
+
+    // Nearest-surface queries (pt_nearest_points, pt_distance_grid_fill, include/pt_nearest.h; PathTrace/nearest.h has the types).
+    // nearest: for each point the closest point of the scene's surfaces within max_distance (+inf: unbounded) -- a minimum over all
+    // objects, defined in the C header --, one result per point.  distanceGrid: the distance and the object of the same query at the
+    // nodes of a grid, x fastest; the positions are made on the device.  Both may be called with a live FrameRender and change nothing.
+    // They throw std::invalid_argument for a grid with a zero count or more than 0x7fffffff cells, std::runtime_error when the device
+    // refuses.  Non-virtual.
+    std::vector<NearestResult> nearest(const std::vector<vec3<float>> &points, float max_distance = std::numeric_limits<float>::infinity()) const;
+    DistanceField distanceGrid(const DistanceGrid &grid, float max_distance = std::numeric_limits<float>::infinity()) const;
 
     // the device scene behind the C ABI (include/pt_hip.h); used by processJob / processItem
     pt_scene *deviceScene() const noexcept { return device_scene; }

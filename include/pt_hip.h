@@ -508,7 +508,9 @@ int pt_temporal_destroy(pt_temporal *t);
 
 /* Scene queries: the hit record of a ray, of a pixel or of every pixel of a frame -- object, instance, face, position, normals,
  * barycentrics -- and occlusion tests of segments (pt_query_rays, pt_query_pixels, pt_query_frame, pt_occluded_rays): the
- * record and the entry points are declared, with their contracts, in: */
+ * record and the entry points are declared, with their contracts, in the file below.  Its last line includes pt_nearest.h: the question
+ * that follows no ray -- the closest point of the scene's surfaces to a free point, with distance, object, instance, face, barycentrics
+ * and the feature it lies on, and unsigned distance grids (pt_nearest_points, pt_distance_grid_fill). */
 #include "pt_query.h"
 
 #ifdef __cplusplus

@@ -74,4 +74,8 @@ int pt_occluded_rays_device(pt_scene *scene, const float *d_segments, size_t n, 
 }
 #endif
 
+/* The nearest surface to a free point and distance grids (pt_nearest_points, pt_distance_grid_fill): they report
+ * instance and face by this file's rules, and are declared, with their contracts, in: */
+#include "pt_nearest.h"
+
 #endif
